@@ -16,6 +16,16 @@ its own 1M-sample shard; no sample ever crosses ranks.
 Scaling modes (--scaling): "weak" (default; every rank holds its own --batch samples) and "strong" (--batch is the
 whole job, split contiguously over the ranks by vcnf_amd.shard_bounds).
 
+A plain run sets up, runs --warmup untimed and --steps timed steps, writes the last timed step's outputs when
+--dump-outputs DIR is given, and prints the line: metric, value, unit, ms_per_step, dtype, config and the roofline of
+the timed region.  Everything else (other_matrix_path, the two directions on their own, the split spline kernel,
+extra_configs, cpu_baseline) is measured with --full only.
+
+--dump-outputs DIR (rank 0, config C3): what the last timed step returned, as float32 / float64 .npy files -
+log_prob.npy, sample_z.npy and sample_log_q.npy on DUMP_ROWS rows drawn with a fixed seed (all rows when the batch
+is smaller; sorted row order), and log_prob_sum_count.npy, the all-reduced [sum log_prob, count].  Inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
+
 The JSON line also carries
   roofline     - the dominant HIP kernel of the timed region.  Fused layers (default): one kernel per layer does
                  conditioner + splines; its work is the conditioner's algorithmic flop per launch (339 968 per
@@ -24,6 +34,7 @@ The JSON line also carries
                  matrix instructions per product) or the fp32 matrix peak (--precision fp32).  --split: the
                  HBM-bound spline kernel, 3464 algorithmic bytes per sample-layer against 8 TB/s (and against
                  the measured 6.3 TB/s copy rate, frac_of_measured_copy_bw);
+and, with --full,
   other_matrix_path - the fused kernel's other matrix arithmetic on the same workload, timed exactly like the
                  headline: the same --warmup untimed steps, the same --steps timed steps, fenced by barrier +
                  synchronize on both sides, max over ranks;
@@ -31,7 +42,7 @@ The JSON line also carries
                  training step, 1 warm-up + 2 timed steps each, each with its own ms_per_step, dtype and roofline;
   cpu_baseline - the CPU oracle (op-order-faithful PyTorch-CPU restatement of the reference path) timed on this
                  box's host cores on a bounded sample of the same workload: 1 warm-up + 3 timed runs, median
-                 (rank 0, N=1 only).  Reported, not a target.
+                 (rank 0, N=1 only, unless --no-cpu-baseline).  Reported, not a target.
 """
 import argparse
 import json
@@ -60,6 +71,21 @@ BYTES_PER_SAMPLE_LAYER = 4 * D + 4 * (D // 2) * P + 4 * D + 8     # 3464, SURVEY
 # conditioner flop per sample-layer (339 968): 2 * (48*128 + 4*128*128 + 2*16*128 + 128*736)
 FLOP_PER_SAMPLE_LAYER = 2 * ((D // 2 + CTX) * HIDDEN + 2 * BLOCKS * HIDDEN * HIDDEN +
                              BLOCKS * CTX * HIDDEN + HIDDEN * (D // 2) * P)
+DUMP_ROWS, DUMP_SEED = 131072, 0                    # --dump-outputs: 131072 x (64 + 2) fp32 = 34.6 MB
+
+
+def dump_outputs(out_dir, lp, stats, z, lq):
+    """The last timed step's outputs as .npy files (module docstring): the per-sample arrays on a fixed, seeded
+    sample of DUMP_ROWS rows, the all-reduced [sum log_prob, count] whole."""
+    import numpy as np
+    b = lp.shape[0]
+    if b > DUMP_ROWS:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        rows = torch.randperm(b, generator=g)[:DUMP_ROWS].sort().values.to(lp.device)
+        lp, z, lq = lp[rows], z[rows], lq[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("log_prob", lp), ("sample_z", z), ("sample_log_q", lq), ("log_prob_sum_count", stats)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy())
 
 
 def build_model(device, seed=0):
@@ -481,15 +507,24 @@ def main():
                          "C4 (3x32x32 multiscale Glow, 16384 images per GPU) and C5 (D=1024, 24 RQS couplings, 16 bins, the per-GPU shard 524288) are BASELINE.json's other "
                          "GPU configurations, reported with their own roofline; C3-train: Adam steps on forward_kld of the C3 model "
                          "at 131072 samples per GPU (training path, samples/s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs legs (C2 / C4 / C5 / C3-train) of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="config C3: also time the other matrix path, the two directions on their own and the split "
+                         "spline kernel, the extra_configs legs and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="config C3: write the last timed step's outputs (a seeded row sample) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (of --full, and of --config C2)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs legs (C2 / C4 / C5 / C3-train)")
     ap.add_argument("--split", action="store_true",
                     help="three-step layers (gather kernel, torch GEMMs, spline kernel) instead of the fused kernel")
     ap.add_argument("--precision", choices=["fp16x3", "fp32"], default="fp16x3",
                     help="matrix path of the fused layer kernel whose figure is `value`: fp16 split-half operands with "
                          "fp32 accumulation and device-side fp32 re-evaluation of out-of-range tiles (default), or exact "
-                         "fp32 matrix instructions; the other one is timed the same way and reported as other_matrix_path")
+                         "fp32 matrix instructions; with --full the other one is timed the same way and reported as other_matrix_path")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "C3":
+        ap.error("--dump-outputs writes the headline configuration's (C3) outputs only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -546,7 +581,7 @@ def main():
         lp = model.log_prob(x, ctx)
         stats = evaluator.reduce_stats(lp)                   # the one collective: [sum log_prob, count]
         z, lq = model.sample_from(eps, ctx)
-        return stats, z, lq
+        return lp, stats, z, lq
 
     def fence():
         torch.cuda.synchronize()
@@ -556,7 +591,8 @@ def main():
 
     def timed_region(split, precision):
         """--warmup untimed steps, then exactly --steps steps between two fences; whole-job time = max over ranks.
-        Returns (seconds, per-launch HIP-event durations of the layer kernel inside the region)."""
+        Returns (seconds, per-launch HIP-event durations of the layer kernel inside the region, the outputs of the
+        last timed step: log_prob, [sum log_prob, count], z, log_q)."""
         route(split, precision)
         with torch.no_grad():
             for _ in range(args.warmup):
@@ -566,29 +602,33 @@ def main():
             fence()
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                stats, z, lq = step()
+                outs = step()
             fence()
             dt = time.perf_counter() - t0
             _lib.EVENT_SINK = None
         nf.check_discriminant(device)
-        assert torch.isfinite(stats).all() and torch.isfinite(lq).all()
-        return max_over_ranks(dt, device), [a.elapsed_time(b) * 1e-3 for a, b, _ in events]
+        assert torch.isfinite(outs[1]).all() and torch.isfinite(outs[3]).all()
+        return max_over_ranks(dt, device), [a.elapsed_time(b) * 1e-3 for a, b, _ in events], outs
 
     head = "split" if args.split else args.precision
-    dt, durs = timed_region(args.split, args.precision)
+    dt, durs, outs = timed_region(args.split, args.precision)
     redone = nf.range_redo_count(device)                     # tiles the split-half kernel handed to the exact fp32 path
-    with torch.no_grad():
-        # the two directions on their own (outside the timed region): rates + harmonic combination, SURVEY 8d
-        def timed(fn, n=2):
-            fn()
-            fence()
-            t1 = time.perf_counter()
-            for _ in range(n):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *outs)
+    del outs
+    if args.full:
+        with torch.no_grad():
+            # the two directions on their own (outside the timed region): rates + harmonic combination, SURVEY 8d
+            def timed(fn, n=2):
                 fn()
-            fence()
-            return (time.perf_counter() - t1) / n
-        dt_lp = max_over_ranks(timed(lambda: evaluator.reduce_stats(model.log_prob(x, ctx))), device)
-        dt_sm = max_over_ranks(timed(lambda: model.sample_from(eps, ctx)), device)
+                fence()
+                t1 = time.perf_counter()
+                for _ in range(n):
+                    fn()
+                fence()
+                return (time.perf_counter() - t1) / n
+            dt_lp = max_over_ranks(timed(lambda: evaluator.reduce_stats(model.log_prob(x, ctx))), device)
+            dt_sm = max_over_ranks(timed(lambda: model.sample_from(eps, ctx)), device)
 
     total = torch.tensor([float(B)], dtype=torch.float64, device=device)     # samples of the whole job
     if dist.is_initialized():
@@ -622,9 +662,9 @@ def main():
 
     # the other matrix path of the fused kernel: same workload, same warm-up, same steps, same fences
     other = None
-    if not args.split:
+    if args.full and not args.split:
         alt = "fp32" if args.precision == "fp16x3" else "fp16x3"
-        dt_alt, durs_alt = timed_region(False, alt)
+        dt_alt, durs_alt, _ = timed_region(False, alt)
         redone += nf.range_redo_count(device)
         other = {"matrix_path": alt, "dtype": DTYPE[alt], "value": round(2.0 * total * args.steps / dt_alt, 1),
                  "unit": "transforms/s", "ms_per_step": round(1e3 * dt_alt / args.steps, 3), "steps": args.steps,
@@ -634,7 +674,7 @@ def main():
     # the HBM-bound spline kernel on its own (outside the timed region): one layer evaluated
     # through the three-step path with the conditioner output materialised, spline launch timed
     hbm_side = None
-    if rank == 0 and not args.split:
+    if args.full and rank == 0 and not args.split:
         lay = model.flows[0].prqct
         with torch.no_grad():
             params = lay._params(x, ctx, False)
@@ -668,8 +708,6 @@ def main():
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": DTYPE[head],
             "data": "synthetic",
-            "log_prob_rate": round(total / dt_lp, 1), "sample_rate": round(total / dt_sm, 1),
-            "harmonic_rate": round(2.0 * total / (dt_lp + dt_sm), 1),
             "frac_of_hbm_roofline_end_to_end": round(2 * LAYERS * BYTES_PER_SAMPLE_LAYER * B / HBM_PEAK / (dt / args.steps), 4),
             "config": {"workload": "C3: conditional D=64 (cond_dim=16), 12 RQ-spline coupling layers "
                                    "(8 bins), batch=%d per GPU, log_prob + sample per step" % B,
@@ -682,17 +720,20 @@ def main():
                                        ("%d samples in total" % int(total)), world)},
             "roofline": roofline_of(head, durs),
         }
+        if args.full:
+            out.update({"log_prob_rate": round(total / dt_lp, 1), "sample_rate": round(total / dt_sm, 1),
+                        "harmonic_rate": round(2.0 * total / (dt_lp + dt_sm), 1)})
         if hbm_side is not None:
             out["roofline_hbm_spline_kernel"] = hbm_side
         if other is not None:
             out["other_matrix_path"] = other
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(model)
     del model, x, ctx, eps, evaluator
     torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             out["extra_configs"] = extra_configs(args, device)
         if cpu is not None:
             out["cpu_baseline"] = cpu
