@@ -574,6 +574,12 @@ int vcnf_rqs_elementwise_f64(const double* x, const double* uw, const double* uh
                              int64_t ld_w, int64_t ld_h, int64_t ld_d,
                              double* y, double* logabsdet, int64_t n,
                              const vcnf_rqs_cfg_f64* cfg, int inverse, int32_t* bad_disc, void* stream);
+/* VJP of vcnf_rqs_elementwise_f64: the contract of vcnf_rqs_elementwise_bwd_f32 in double (dense gradient rows). */
+int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                 int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                 const double* g_y, const double* g_logabsdet,
+                                 double* g_x, double* g_uw, double* g_uh, double* g_ud, int64_t n,
+                                 const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream);
 int vcnf_affine_coupling_f64(const double* z, const double* param, double* out, double* logdet,
                              int64_t batch, int32_t channels, int32_t inner,
                              int32_t t_off, int32_t d_t, int scale_map, int inverse,

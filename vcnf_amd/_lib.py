@@ -135,6 +135,8 @@ PROTOTYPES = {
     "vcnf_linear_probe_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _P, _P], _INT),
     "vcnf_rqs_elementwise_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64,
                                   ctypes.POINTER(RqsCfg64), _INT, _P, _P], _INT),
+    "vcnf_rqs_elementwise_bwd_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64,
+                                      ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
     "vcnf_affine_coupling_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT, _INT, _INT, _F64, _P], _INT),
     "vcnf_masked_affine_f64": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F64, _P], _INT),
     "vcnf_affine_const_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _P], _INT),
@@ -484,8 +486,11 @@ def rqs_shared_bwd(x, uw, uh, ud, gy, glad, cfg, inverse):
 
 
 def rqs_elementwise_bwd(x, uw, uh, ud, gy, glad, cfg, inverse):
-    """VJP of rqs_elementwise: returns (g_x, g_uw, g_uh, g_ud), shapes of the inputs."""
-    dev = require_device(x, uw, uh, ud, gy, glad, allow_grad=True)
+    """VJP of rqs_elementwise: returns (g_x, g_uw, g_uh, g_ud), shapes of the inputs.  fp32 or fp64 (every tensor)."""
+    f64 = x.dtype == torch.float64
+    dev = require_device(x, uw, uh, ud, gy, glad, allow_grad=True, f64=f64)
+    if f64 and not all(t.dtype == torch.float64 for t in (uw, uh, ud, gy, glad)):
+        raise VcnfError("fp64 spline VJP: inputs, logits and upstream gradients must all be fp64")
     k = cfg.num_bins
     nd = n_derivatives(cfg)
     shape = x.shape
@@ -498,10 +503,11 @@ def rqs_elementwise_bwd(x, uw, uh, ud, gy, glad, cfg, inverse):
     gx = torch.empty_like(xf)
     gw, gh, gd = torch.empty_like(w2), torch.empty_like(h2), torch.empty_like(d2)
     with torch.cuda.device(dev):
-        st = lib().vcnf_rqs_elementwise_bwd_f32(_ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), k, k, nd,
-                                               _ptr(gyf), _ptr(glf), _ptr(gx), _ptr(gw), _ptr(gh), _ptr(gd),
-                                               xf.numel(), ctypes.byref(cfg), int(bool(inverse)), _stream())
-    _check(st, "vcnf_rqs_elementwise_bwd_f32")
+        fn = lib().vcnf_rqs_elementwise_bwd_f64 if f64 else lib().vcnf_rqs_elementwise_bwd_f32
+        st = fn(_ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), k, k, nd,
+                _ptr(gyf), _ptr(glf), _ptr(gx), _ptr(gw), _ptr(gh), _ptr(gd),
+                xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)), _stream())
+    _check(st, "vcnf_rqs_elementwise_bwd" + _sfx(xf))
     return gx.view(shape), gw.view(shape + (k,)), gh.view(shape + (k,)), gd.view(shape + (nd,))
 
 

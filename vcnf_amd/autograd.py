@@ -1,5 +1,5 @@
-"""Differentiable spline op: forward = vcnf_rqs_elementwise_f32, backward =
-vcnf_rqs_elementwise_bwd_f32 (csrc/rqs_backward.hip).  This is the training path of the
+"""Differentiable spline op: forward = vcnf_rqs_elementwise_f32 / _f64, backward =
+vcnf_rqs_elementwise_bwd_f32 (csrc/rqs_backward.hip) / _f64 (csrc/rqs_f64.hip).  This is the training path of the
 RQS couplings: when gradients are required the coupling layer composes
 gather / conditioner / scatter in PyTorch (all differentiable) around this op, exactly the
 structure of the reference (flows/neural_spline/coupling.py:70-125), with the spline
@@ -97,8 +97,9 @@ class RqsSharedFn(torch.autograd.Function):
 
 
 def rqs_shared(x, uw, uh, ud, cfg, inverse=False):
-    """(y, logabsdet[B]) of the batch-shared spline, differentiable."""
-    if cfg.num_bins in _lib.SHARED_BWD_BINS:
+    """(y, logabsdet[B]) of the batch-shared spline, differentiable.  fp64 takes the dense path (there is no fp64
+    batch-shared reduction kernel; autograd of the expansion sums the logit gradient over the batch)."""
+    if cfg.num_bins in _lib.SHARED_BWD_BINS and x.dtype != torch.float64:
         return RqsSharedFn.apply(x, uw, uh, ud, cfg, inverse)
     y, lad = rqs_spline(x, uw, uh, ud, cfg, inverse)           # any K: dense expansion
     return y, lad.reshape(lad.shape[0], -1).sum(1)

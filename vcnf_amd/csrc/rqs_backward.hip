@@ -13,6 +13,7 @@
 
 #include "../../include/vcnf_hip.h"
 #include "rqs_math.hpp"
+#include "rqs_vjp.hpp"
 
 namespace vcnf {
 
@@ -41,67 +42,10 @@ __device__ __forceinline__ float softplus_grad(float v) {
   return v > 20.f ? 1.f : div_nr(1.f, 1.f + hw_exp2(-v * kLog2e));
 }
 
-// Reverse pass through rqs_bin_eval's forward branch: inputs the bin (xl, w, yl, h, d0, d1),
-// the point x and upstream (gy, gl); outputs gradients w.r.t. all seven.
-struct BinGrad {
-  float gx, gxl, gw, gyl, gh, gd0, gd1;
-};
+// Reverse pass through rqs_bin_eval: the bin adjoints of rqs_vjp.hpp in fp32.
+using BinGrad = BinGradT<float>;
 
-// Adjoint of the bin-coordinate map  (t, s, h, d0, d1) -> (y - yl, lad):
-//   y - yl = h (s t^2 + d0 t(1-t)) / Q,   Q = s + (d0 + d1 - 2 s) t(1-t)
-//   lad    = log(s^2 (d1 t^2 + 2 s t(1-t) + d0 (1-t)^2)) - 2 log Q          (splines.py:179-191)
-// gh is the direct dependence on h (through the numerator), not the one through s = h / w.
-struct CoreGrad {
-  float gt, gs, gh, gd0, gd1;
-};
-
-__device__ __forceinline__ CoreGrad bin_core_vjp(float t, float s, float h, float d0, float d1, float gy, float gl) {
-  const float omt = 1.f - t;
-  const float a = t * omt;
-  const float e = d0 + d1 - 2.f * s;
-  const float inner = s * t * t + d0 * a;
-  const float N = h * inner;
-  const float Q = s + e * a;
-  const float M = d1 * t * t + 2.f * s * a + d0 * omt * omt;
-  const float rQ = 1.f / Q;
-  const float g_dn = gl / (s * s * M);
-  const float g_Q = -2.f * gl * rQ - gy * N * rQ * rQ;
-  const float g_N = gy * rQ;
-  const float g_M = s * s * g_dn;
-  const float g_in = h * g_N;
-  const float g_e = a * g_Q;
-  const float g_a = 2.f * s * g_M + e * g_Q + d0 * g_in;
-  const float g_omt = 2.f * d0 * omt * g_M + t * g_a;
-  CoreGrad r;
-  r.gs = 2.f * s * M * g_dn + 2.f * a * g_M + g_Q + t * t * g_in - 2.f * g_e;
-  r.gt = 2.f * d1 * t * g_M + 2.f * s * t * g_in + omt * g_a - g_omt;
-  r.gh = inner * g_N;
-  r.gd0 = omt * omt * g_M + a * g_in + g_e;
-  r.gd1 = t * t * g_M + g_e;
-  return r;
-}
-
-// Density direction: y = F(x), lad = log F'(x), with t = (x - xl) / w and s = h / w.
-__device__ __forceinline__ BinGrad bin_forward_vjp(float x, const RqsBin& b, float gy, float gl) {
-  const float rw = 1.f / b.w;
-  const float s = b.h * rw;
-  const float t = (x - b.xl) * rw;
-  const CoreGrad c = bin_core_vjp(t, s, b.h, b.d0, b.d1, gy, gl);
-  BinGrad r;
-  r.gx = c.gt * rw;
-  r.gxl = -r.gx;
-  r.gw = -(c.gt * t + c.gs * s) * rw;
-  r.gh = c.gh + c.gs * rw;
-  r.gyl = gy;
-  r.gd0 = c.gd0;
-  r.gd1 = c.gd1;
-  return r;
-}
-
-// Sampling direction: v = xl + w r with r the root of  h phi(r; s, d0, d1) = u - yl,  lad = -log F'(v).
-// The root is differentiated implicitly IN BIN COORDINATES (dr/du = 1 / (h phi_r), dr/ds = -phi_s / phi_r,
-// ...): written per unit x the width gradient is a difference of two terms of size L_t / w that
-// agree to several digits in narrow bins; in r they never appear.  ``x`` is u.
+// Sampling direction: v = xl + w r with r the root of  h phi(r; s, d0, d1) = u - yl  (rqs_vjp.hpp).  ``x`` is u.
 __device__ __forceinline__ BinGrad bin_inverse_vjp(float u, float v0, const RqsBin& b, float gy, float gl) {
   const float rw = 1.f / b.w;
   const float s = b.h * rw;
@@ -118,20 +62,7 @@ __device__ __forceinline__ BinGrad bin_inverse_vjp(float u, float v0, const RqsB
     const float fr = b.h * s * (b.d1 * r * r + 2.f * s * a + b.d0 * omr * omr) / (Q * Q);
     r = fminf(fmaxf(r - (f - target) / fr, 0.f), 1.f);
   }
-  const CoreGrad F = bin_core_vjp(r, s, b.h, b.d0, b.d1, 1.f, 0.f);
-  const CoreGrad L = bin_core_vjp(r, s, b.h, b.d0, b.d1, 0.f, 1.f);
-  const float gr = gy * b.w - gl * L.gt;
-  const float gu = gr / F.gt;
-  const float gs = -gu * F.gs - gl * L.gs;
-  BinGrad o;
-  o.gx = gu;
-  o.gyl = -gu;
-  o.gxl = gy;
-  o.gw = gy * r - gs * s * rw;
-  o.gh = -gu * F.gh + gs * rw;
-  o.gd0 = -gu * F.gd0 - gl * L.gd0;
-  o.gd1 = -gu * F.gd1 - gl * L.gd1;
-  return o;
+  return bin_inverse_vjp_at_root<float>(r, rw, s, b, gy, gl);
 }
 
 // PACKED: logits and their gradients are rows of P contiguous floats in the same layout (conditioner
@@ -216,7 +147,7 @@ __global__ __launch_bounds__(kBwdBlock) void rqs_elementwise_bwd_kernel(const Bw
 
     BinGrad g;
     if (!INV) {
-      g = bin_forward_vjp(x, b, gy, gl);
+      g = bin_forward_vjp<float>(x, b, gy, gl);
     } else {
       // v = F^-1(u): solve as the forward kernel does, then differentiate the root
       float v, lad_inv;
@@ -352,7 +283,7 @@ __global__ __launch_bounds__(kBwdBlock) void rqs_shared_bwd_kernel(const SharedB
     b.h = yr - b.yl;
     BinGrad g;
     if (!INV) {
-      g = bin_forward_vjp(x, b, gy, gl);
+      g = bin_forward_vjp<float>(x, b, gy, gl);
     } else {
       float v, lad_inv;
       bool bad = false;

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/vcnf_hip.h"
+#include "rqs_vjp.hpp"
 
 namespace vcnf {
 
@@ -25,9 +26,17 @@ struct Rqs64Args {
   int32_t* bad;
 };
 
-// knots of one side: cum[0..K] from K logits (splines.py:109-119 / :123-133)
-__device__ __forceinline__ void partition64(const double* lg, int K, double scale, double lo, double hi, double floor_,
-                                            double* cum) {
+// Knot construction, bin search and derivative-logit padding are shared by the forward kernel and the VJP kernel
+// below, so that both select the same bin for every element.  KT > 0: compile-time bin count (the VJP kernel's
+// templated instances keep every array in registers); KT == 0: runtime K (the forward kernel, and the VJP kernel's
+// generic instance).
+
+// knots of one side: cum[0..K] from K logits (splines.py:109-119 / :123-133); ``prob`` (optional) receives the
+// softmax probabilities
+template <int KT>
+__device__ __forceinline__ void partition64(const double* lg, int Kr, double scale, double lo, double hi,
+                                            double floor_, double* cum, double* prob = nullptr) {
+  const int K = KT > 0 ? KT : Kr;
   double m = -INFINITY;
   for (int k = 0; k < K; ++k) m = fmax(m, lg[k] * scale);
   double s = 0.0;
@@ -35,11 +44,29 @@ __device__ __forceinline__ void partition64(const double* lg, int K, double scal
   double run = 0.0;
   cum[0] = lo;
   for (int k = 0; k < K; ++k) {
+    if (prob) prob[k] = exp(lg[k] * scale - m) / s;
     const double p = floor_ + (1.0 - floor_ * K) * (exp(lg[k] * scale - m) / s);
     run += p;
     cum[k + 1] = (hi - lo) * run + lo;
   }
   cum[K] = hi;
+}
+
+// bin: number of knots <= value, last knot bumped by eps (splines.py:12-17), clamped to [0, K-1]
+template <int KT>
+__device__ __forceinline__ int bin64(const double* kn, int Kr, double x) {
+  const int K = KT > 0 ? KT : Kr;
+  int bin = -1;
+  for (int k = 0; k <= K; ++k) bin += (x >= (k == K ? kn[k] + 1e-6 : kn[k])) ? 1 : 0;
+  return bin < 0 ? 0 : (bin > K - 1 ? K - 1 : bin);
+}
+
+// derivative logit of knot k (padding per tails mode, splines.py:36-49): its column in the ud row, or -1 for the
+// constant boundary logit of linear tails
+__device__ __forceinline__ int dlogit_col64(int k, int K, int tails) {
+  if (tails == VCNF_TAILS_LINEAR) return (k == 0 || k == K) ? -1 : k - 1;
+  if (tails == VCNF_TAILS_CIRCULAR) return k == K ? 0 : k;
+  return k;
 }
 
 __device__ __forceinline__ double softplus64(double v) { return v > 20.0 ? v : log1p(exp(v)); }   // F.softplus (threshold 20)
@@ -54,19 +81,13 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
     }
     const int K = a.K;
     double xk[kMaxBins64 + 1], yk[kMaxBins64 + 1];
-    partition64(a.uw + i * a.ld_w, K, a.wh_scale, a.left, a.right, a.min_w, xk);
-    partition64(a.uh + i * a.ld_h, K, a.wh_scale, a.bottom, a.top, a.min_h, yk);
-    // bin: number of knots <= value, last knot bumped by eps (splines.py:12-17)
-    const double* kn = a.inverse ? yk : xk;
-    int bin = -1;
-    for (int k = 0; k <= K; ++k) bin += (x >= (k == K ? kn[k] + 1e-6 : kn[k])) ? 1 : 0;
-    bin = bin < 0 ? 0 : (bin > K - 1 ? K - 1 : bin);
-    // derivative logits of the bin's two knots (padding per tails mode, splines.py:36-49)
+    partition64<0>(a.uw + i * a.ld_w, K, a.wh_scale, a.left, a.right, a.min_w, xk);
+    partition64<0>(a.uh + i * a.ld_h, K, a.wh_scale, a.bottom, a.top, a.min_h, yk);
+    const int bin = bin64<0>(a.inverse ? yk : xk, K, x);
     const double* ud = a.ud + i * a.ld_d;
     auto dlogit = [&](int k) -> double {
-      if (a.tails == VCNF_TAILS_LINEAR) return (k == 0 || k == K) ? a.edge : ud[k - 1];
-      if (a.tails == VCNF_TAILS_CIRCULAR) return k == K ? ud[0] : ud[k];
-      return ud[k];
+      const int j = dlogit_col64(k, K, a.tails);
+      return j < 0 ? a.edge : ud[j];
     };
     const double d0 = a.min_d + softplus64(dlogit(bin));           // :121
     const double d1 = a.min_d + softplus64(dlogit(bin + 1));
@@ -102,6 +123,117 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
   }
 }
 
+
+// ------------------------------------------------------------------ VJP (training path of .double() models)
+// The adjoint of rqs_elementwise_f64_kernel, as rqs_backward.hip does it in fp32: the element is re-evaluated with
+// the forward kernel's own knot / bin / padding functions, then walked backwards - bin map (rqs_vjp.hpp) -> knots ->
+// cumulative widths (end knots are constants) -> the floor's (1 - min K) factor -> softmax -> wh_scale; the two knot
+// derivatives through softplus.  The sampling direction differentiates the closed-form root implicitly in bin
+// coordinates; in fp64 that root is exact enough that the fp32 kernel's Newton refinement is not needed.
+struct Rqs64BwdArgs {
+  Rqs64Args f;                     // forward operands (y, lad, bad unused)
+  const double *gy, *glad;
+  double *gx, *guw, *guh, *gud;    // dense gradient rows: K, K, nd
+  int nd;
+};
+
+struct RqsBin64 {
+  double xl, w, yl, h, d0, d1;
+};
+
+// KT > 0: the K probabilities and K+1 knots of each side live in registers (loops of constant trip count, fully
+// unrolled by the compiler: compile-time indices;
+// the bin's values are picked by comparison, never by a runtime index).  KT == 0 (any other K up to 64): the same
+// code with runtime-indexed arrays, which go to scratch.
+template <int KT, bool INV>
+__global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs64BwdArgs g) {
+  const Rqs64Args& a = g.f;
+  constexpr int KA = KT > 0 ? KT : kMaxBins64;
+  const int K = KT > 0 ? KT : a.K;
+  const int nd = g.nd;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long long)gridDim.x * blockDim.x) {
+    const double x = a.x[i];
+    const double gy = g.gy[i], gl = g.glad[i];
+    double* guw = g.guw + i * K;
+    double* guh = g.guh + i * K;
+    double* gud = g.gud + i * nd;
+    if (a.tails != VCNF_TAILS_NONE && !(x >= a.left && x <= a.right)) {   // identity outside: dy/dx = 1
+      g.gx[i] = gy;
+      for (int k = 0; k < K; ++k) { guw[k] = 0.0; guh[k] = 0.0; }
+      for (int k = 0; k < nd; ++k) gud[k] = 0.0;
+      continue;
+    }
+    double xk[KA + 1], yk[KA + 1], pw[KA], ph[KA];
+    partition64<KT>(a.uw + i * a.ld_w, K, a.wh_scale, a.left, a.right, a.min_w, xk, pw);
+    partition64<KT>(a.uh + i * a.ld_h, K, a.wh_scale, a.bottom, a.top, a.min_h, yk, ph);
+    const int bin = bin64<KT>(INV ? yk : xk, K, x);
+    RqsBin64 b;
+    double xr, yr;
+    if (KT > 0) {
+      b.xl = xk[0]; xr = xk[1]; b.yl = yk[0]; yr = yk[1];
+      for (int k = 1; k < K; ++k)
+        if (bin == k) { b.xl = xk[k]; xr = xk[k + 1]; b.yl = yk[k]; yr = yk[k + 1]; }
+    } else {
+      b.xl = xk[bin]; xr = xk[bin + 1]; b.yl = yk[bin]; yr = yk[bin + 1];
+    }
+    b.w = xr - b.xl;
+    b.h = yr - b.yl;
+    const double* ud = a.ud + i * a.ld_d;
+    const int j0 = dlogit_col64(bin, K, a.tails), j1 = dlogit_col64(bin + 1, K, a.tails);
+    const double l0 = j0 < 0 ? a.edge : ud[j0], l1 = j1 < 0 ? a.edge : ud[j1];
+    b.d0 = a.min_d + softplus64(l0);
+    b.d1 = a.min_d + softplus64(l1);
+    BinGradT<double> bg;
+    if (!INV) {
+      bg = bin_forward_vjp<double>(x, b, gy, gl);
+    } else {
+      // the forward kernel's root (splines.py:153-166), in bin coordinates
+      const double rw = 1.0 / b.w;
+      const double s = b.h * rw;
+      const double dy = x - b.yl;
+      const double e = b.d0 + b.d1 - 2.0 * s;
+      const double qa = dy * e + b.h * (s - b.d0);
+      const double qb = b.h * b.d0 - dy * e;
+      const double qc = -s * dy;
+      const double r = (2.0 * qc) / (-qb - sqrt(qb * qb - 4.0 * qa * qc));
+      bg = bin_inverse_vjp_at_root<double>(r, rw, s, b, gy, gl);
+    }
+    g.gx[i] = bg.gx;
+    // knots -> cumulative widths -> softmax -> logits.  X_bin carries (gxl - gw), X_bin+1 carries gw; the end knots
+    // are constants.  dX_k / dW_j = span (1 - min K) for j < k.
+    const double gXl = bin >= 1 ? bg.gxl - bg.gw : 0.0, gXr = bin + 1 <= K - 1 ? bg.gw : 0.0;
+    const double gYl = bin >= 1 ? bg.gyl - bg.gh : 0.0, gYr = bin + 1 <= K - 1 ? bg.gh : 0.0;
+    const double cx = (a.right - a.left) * (1.0 - a.min_w * K), cy = (a.top - a.bottom) * (1.0 - a.min_h * K);
+    double dotw = 0.0, doth = 0.0;
+    for (int k = 0; k < K; ++k) {
+      dotw += pw[k] * (cx * ((k < bin ? gXl : 0.0) + (k < bin + 1 ? gXr : 0.0)));
+      doth += ph[k] * (cy * ((k < bin ? gYl : 0.0) + (k < bin + 1 ? gYr : 0.0)));
+    }
+    for (int k = 0; k < K; ++k) {
+      const double gWk = cx * ((k < bin ? gXl : 0.0) + (k < bin + 1 ? gXr : 0.0));
+      const double gHk = cy * ((k < bin ? gYl : 0.0) + (k < bin + 1 ? gYr : 0.0));
+      guw[k] = a.wh_scale * pw[k] * (gWk - dotw);
+      guh[k] = a.wh_scale * ph[k] * (gHk - doth);
+    }
+    // derivative logits: d softplus / dv = sigmoid(v) (1 above the threshold 20); circular with one bin: both knots
+    // share logit 0 and the two contributions add
+    double gd0 = j0 < 0 ? 0.0 : bg.gd0 * (l0 > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-l0)));
+    double gd1 = j1 < 0 ? 0.0 : bg.gd1 * (l1 > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-l1)));
+    if (j0 == j1) { gd0 += gd1; gd1 = 0.0; }
+    for (int k = 0; k < nd; ++k) gud[k] = k == j0 ? gd0 : (k == j1 ? gd1 : 0.0);
+  }
+}
+
+template <bool INV>
+static void launch_bwd64(const Rqs64BwdArgs& g, dim3 grid, hipStream_t st) {
+  switch (g.f.K) {
+    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<8, INV>), grid, dim3(256), 0, st, g); break;
+    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<10, INV>), grid, dim3(256), 0, st, g); break;
+    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<16, INV>), grid, dim3(256), 0, st, g); break;
+    default: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<0, INV>), grid, dim3(256), 0, st, g); break;
+  }
+}
+
 }  // namespace vcnf
 
 using namespace vcnf;
@@ -128,5 +260,40 @@ extern "C" int vcnf_rqs_elementwise_f64(const double* x, const double* uw, const
   long long blocks = (n + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
   hipLaunchKernelGGL(rqs_elementwise_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+}
+
+
+extern "C" int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                            int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                            const double* g_y, const double* g_logabsdet,
+                                            double* g_x, double* g_uw, double* g_uh, double* g_ud, int64_t n,
+                                            const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream) {
+  // validation as bwd_common / vcnf_rqs_elementwise_bwd_f32 (rqs_backward.hip)
+  if (!cfg) return VCNF_ERR_NULL;
+  const int K = cfg->num_bins;
+  if (K < 1 || K > kMaxBins64) return VCNF_ERR_SHAPE;
+  if (cfg->tails != VCNF_TAILS_NONE && cfg->tails != VCNF_TAILS_LINEAR && cfg->tails != VCNF_TAILS_CIRCULAR)
+    return VCNF_ERR_UNSUPPORTED;
+  if (cfg->tails == VCNF_TAILS_LINEAR && K < 2) return VCNF_ERR_SHAPE;
+  if (cfg->min_bin_width * K > 1.0 || cfg->min_bin_height * K > 1.0) return VCNF_ERR_VALUE;
+  if (n < 0 || ld_w < 0 || ld_h < 0 || ld_d < 0) return VCNF_ERR_SHAPE;
+  if (n == 0) return VCNF_OK;
+  if (!x || !uw || !uh || !ud || !g_y || !g_logabsdet || !g_x || !g_uw || !g_uh || !g_ud) return VCNF_ERR_NULL;
+  Rqs64BwdArgs g;
+  Rqs64Args& a = g.f;
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
+  a.y = nullptr; a.lad = nullptr; a.n = n; a.K = K; a.tails = cfg->tails; a.inverse = inverse ? 1 : 0;
+  a.left = cfg->left; a.right = cfg->right; a.bottom = cfg->bottom; a.top = cfg->top;
+  a.min_w = cfg->min_bin_width; a.min_h = cfg->min_bin_height; a.min_d = cfg->min_derivative;
+  a.wh_scale = cfg->wh_scale;
+  a.edge = log(exp(1.0 - cfg->min_derivative) - 1.0);
+  a.bad = nullptr;
+  g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x; g.guw = g_uw; g.guh = g_uh; g.gud = g_ud;
+  g.nd = cfg->tails == VCNF_TAILS_LINEAR ? K - 1 : cfg->tails == VCNF_TAILS_CIRCULAR ? K : K + 1;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  if (inverse) launch_bwd64<true>(g, dim3((unsigned)blocks), (hipStream_t)stream);
+  else launch_bwd64<false>(g, dim3((unsigned)blocks), (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
 }

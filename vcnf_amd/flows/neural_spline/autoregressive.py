@@ -79,6 +79,16 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Flow):
         cfg = _lib.make_cfg(k, self.tails, tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,
                             min_bin_height=self.min_bin_height, min_derivative=self.min_derivative,
                             wh_scale=self._logit_scale())
+        if inputs.dtype == torch.float64:
+            # fp64 (.double() models): the elementwise fp64 spline on the three slices of the MADE output viewed as
+            # [B, D, P] (row stride P, read in place), or its VJP kernel when a gradient is needed
+            p = params.view(inputs.shape[0], self.features, -1)
+            args = (inputs, p[..., :k], p[..., k:2 * k], p[..., 2 * k:], cfg)
+            if autograd.needs_grad(inputs, params):
+                out, lad = autograd.rqs_spline(*args, inverse=inverse)
+            else:
+                out, lad = _lib.rqs_elementwise(*args, inverse)
+            return out, lad.sum(1)
         if autograd.needs_grad(inputs, params):
             return autograd.rqs_packed(inputs.contiguous(), params, cfg, inverse=inverse)
         out, lad = _lib.rqs_elementwise_image(inputs, params, cfg, inverse)

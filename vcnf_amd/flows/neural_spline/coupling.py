@@ -104,9 +104,13 @@ class PiecewiseRationalQuadraticCDF(Flow):
         splines._check_bins(self.num_bins, self.min_bin_width, self.min_bin_height)
         if inputs.dtype == torch.float64:
             # fp64 models (the reference's drivers call .double()): the elementwise fp64 spline on the logit rows
-            # expanded over the batch (no gradient path in fp64; csrc/rqs_f64.hip)
+            # expanded over the batch (csrc/rqs_f64.hip); with a gradient, its VJP kernel, and autograd of the
+            # expansion sums the logit gradient over the batch
             uw, uh, ud = (t.unsqueeze(0).expand((inputs.shape[0],) + tuple(t.shape)) for t in self.logits())
-            out, lad = _lib.rqs_elementwise(inputs, uw, uh, ud, self._cfg(), inverse)
+            if autograd.needs_grad(inputs, *self.logits()):
+                out, lad = autograd.rqs_spline(inputs, uw, uh, ud, self._cfg(), inverse=inverse)
+            else:
+                out, lad = _lib.rqs_elementwise(inputs, uw, uh, ud, self._cfg(), inverse)
         elif autograd.needs_grad(inputs, *self.logits()):
             return autograd.rqs_shared(inputs, *self.logits(), self._cfg(), inverse=inverse)
         else:

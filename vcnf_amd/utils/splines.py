@@ -1,6 +1,7 @@
 """Functional spline API of the reference (normflow/utils/splines.py) on HIP.
 
-Same names, argument meaning and error behaviour; tensors must live on the GPU.
+Same names, argument meaning and error behaviour; tensors must live on the GPU.  Differentiable in fp32 and fp64
+(the spline VJP kernels, through vcnf_amd.autograd) when an input or a logit tensor requires grad.
 Per-feature tail lists and tensor tail bounds (splines.py:50-66) are evaluated group by group:
 features sharing (kind, bound) go through one uniform kernel call.
 """
@@ -68,6 +69,15 @@ def _per_feature_spline(inputs, uw, uh, ud, inverse, tails, tail_bound, min_bin_
     return out, lad
 
 
+def _spline(inputs, uw, uh, ud, cfg, inverse):
+    """One uniform spline call: through the VJP kernel when a gradient is needed (fp32 and fp64), else the plain
+    kernel."""
+    from .. import autograd
+    if autograd.needs_grad(inputs, uw, uh, ud):
+        return autograd.rqs_spline(inputs, uw, uh, ud, cfg, inverse=inverse)
+    return _lib.rqs_elementwise(inputs, uw, uh, ud, cfg, inverse)
+
+
 def _check_bins(num_bins, min_bin_width, min_bin_height):
     # splines.py:104-107
     if min_bin_width * num_bins > 1.0:
@@ -92,8 +102,7 @@ def rational_quadratic_spline(inputs, unnormalized_widths, unnormalized_heights,
     cfg = _lib.make_cfg(num_bins, None, left=left, right=right, bottom=bottom, top=top,
                         min_bin_width=min_bin_width, min_bin_height=min_bin_height,
                         min_derivative=min_derivative)
-    return _lib.rqs_elementwise(inputs, unnormalized_widths, unnormalized_heights,
-                                unnormalized_derivatives, cfg, inverse)
+    return _spline(inputs, unnormalized_widths, unnormalized_heights, unnormalized_derivatives, cfg, inverse)
 
 
 def unconstrained_rational_quadratic_spline(inputs, unnormalized_widths, unnormalized_heights,
@@ -114,5 +123,4 @@ def unconstrained_rational_quadratic_spline(inputs, unnormalized_widths, unnorma
     _check_bins(num_bins, min_bin_width, min_bin_height)
     cfg = _lib.make_cfg(num_bins, tails, tail_bound=tail_bound, min_bin_width=min_bin_width,
                         min_bin_height=min_bin_height, min_derivative=min_derivative)
-    return _lib.rqs_elementwise(inputs, unnormalized_widths, unnormalized_heights,
-                                unnormalized_derivatives, cfg, inverse)
+    return _spline(inputs, unnormalized_widths, unnormalized_heights, unnormalized_derivatives, cfg, inverse)
