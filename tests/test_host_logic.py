@@ -343,3 +343,31 @@ def test_refresh_packed_invalidates_every_cache():
     assert glow.__dict__['_mix_cache'][True]['key'] is None and glow.__dict__['_mix_cache'][True]['out'] is keep
     assert glow.__dict__['_mix_cache']['norm_ready'] is False
     assert glow.flows[0].flows[1].param_map.__dict__['_fused_conv_pack']['key'] is None
+
+
+def test_memo_plan_reuses_a_plan_while_the_modules_it_has_seen_are_unchanged():
+    """The plan memo shared by the RQS and masked stack families (vcnf_amd.fused.memo_plan)."""
+    import types
+    from vcnf_amd.fused import memo_plan
+    owner, made = types.SimpleNamespace(), []
+    order = [types.SimpleNamespace(tag=i) for i in range(6)]
+
+    def memo(end, seen=None):
+        def make():
+            made.append(end)
+            return None if end is None else (end, "run")
+        return memo_plan(owner, "_plans", ("k",), order, 1, make, lambda f: f.tag, seen)
+
+    assert memo(4) == (4, "run") and made == [4]           # seen: the run order[1:4] and the flow that ended it
+    order[5] = types.SimpleNamespace(tag=5)
+    assert memo(5) == (4, "run") and made == [4]           # a module the plan did not see: reused
+    order[4].tag = 9
+    assert memo(3) == (3, "run") and made == [4, 3]        # the stamp of the flow that ended the run changed
+    order[2] = types.SimpleNamespace(tag=2)
+    assert memo(None) is None and made == [4, 3, None]     # a module of the run replaced
+    order[2] = types.SimpleNamespace(tag=2)
+    assert memo(5) is None and made == [4, 3, None]        # no run: only order[1] was seen
+    owner._plans.clear()
+    assert memo(3, seen=lambda mods: mods[:1]) == (3, "run")
+    order[2] = types.SimpleNamespace(tag=2)
+    assert memo(5) == (3, "run") and made == [4, 3, None, 3]   # ``seen`` narrowed the watched modules to order[1]

@@ -24,6 +24,15 @@ SCALE_EXP, SCALE_SIGMOID, SCALE_SIGMOID_INV, SCALE_NONE = 0, 1, 2, 3
 SCALE_MAPS = {"exp": SCALE_EXP, "sigmoid": SCALE_SIGMOID, "sigmoid_inv": SCALE_SIGMOID_INV}
 
 
+def scale_code(scale, scale_map):
+    """Kernel code of an affine coupling's ``scale`` / ``scale_map`` settings."""
+    if not scale:
+        return SCALE_NONE
+    if scale_map not in SCALE_MAPS:
+        raise NotImplementedError('This scale map is not implemented.')
+    return SCALE_MAPS[scale_map]
+
+
 class RqsCfg(ctypes.Structure):
     """struct vcnf_rqs_cfg"""
     _fields_ = [("num_bins", _I32), ("tails", _I32), ("left", _F32), ("right", _F32),

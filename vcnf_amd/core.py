@@ -16,11 +16,17 @@ the AttributeError the reference has at this HEAD.
 import torch
 from torch import nn
 
-from .flows.affine.coupling import AffineCouplingBlock, MaskedAffineFlow, AffineConstFlow, _scale_code
+from .flows.affine.coupling import AffineCouplingBlock, MaskedAffineFlow, AffineConstFlow
 from . import fused_affine, fused, fused_masked
 from .flows.mixing import Permute
 from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
 from .fused import refresh_packed
+
+# The single-launch families, tried in this order at every position of a pass: (the model's switch, the flow types a
+# run can start with, the family's planner: None or (end, launch) with launch(z, log_q, sign) -> (z, log_q))
+_STACKS = (('fuse_affine_stacks', (Permute, AffineCouplingBlock), fused_affine.stack_run),
+           ('fuse_masked_stacks', (MaskedAffineFlow, AffineConstFlow), fused_masked.stack_run),
+           ('fuse_rqs_stacks', (CoupledRationalQuadraticSpline,), fused.stack_run))
 
 
 class _PackedWeightsMixin:
@@ -53,56 +59,69 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         self.fuse_rqs_stacks = True              # runs of one-kernel RQS layers in a single launch at small batches (fused.run_stack)
         self.fuse_masked_stacks = True           # runs of MaskedAffineFlow (+ MLP conditioners) / ActNorm layers in a single launch
 
+    def _walk(self, z, log_q, context, density):
+        """(z, log_q) after one pass over the flows: last to first through their inverses with the log-dets added
+        (``density``), or first to last with the log-dets subtracted (sampling).  At each position the first of these
+        takes the layers it covers: a single-launch run of one family (_STACKS, in order), a one-kernel affine layer
+        and the Permute after it in model order, the layer's accumulating form (inverse_into / forward_into), the
+        plain (z, log_det) contract."""
+        order = list(reversed(self.flows)) if density else list(self.flows)
+        sign = 1.0 if density else -1.0
+        n = len(order)
+        i = 0
+        while i < n:
+            flow = order[i]
+            run = None
+            for switch, starts, stack_run in _STACKS:
+                if isinstance(flow, starts) and getattr(self, switch):
+                    run = stack_run(self, order, i, z, context, density)
+                    if run is not None:
+                        break
+            if run is not None:
+                i, launch = run
+                z, log_q = launch(z, log_q, sign)
+                continue
+            # the Permute becomes the affine kernel's load index in the density pass, its store index when sampling
+            if i + 1 < n:
+                block, perm = (order[i + 1], flow) if density else (flow, order[i + 1])
+                if isinstance(block, AffineCouplingBlock) and isinstance(perm, Permute) and z.dim() == 2 \
+                        and block.fusable(z):
+                    gather = perm._idx32(density, z.device)
+                    z = block.run_with_permute(z, density, log_q, sign, in_gather=gather if density else None,
+                                               out_gather=None if density else gather)
+                    i += 2
+                    continue
+            ctx = {'context': context} if (context is not None and getattr(flow, 'takes_context', False)) else {}
+            into = getattr(flow, 'inverse_into' if density else 'forward_into', None)
+            if into is not None:
+                z = into(z, log_q, **ctx)
+            elif density:
+                z, log_det = flow.inverse(z, **ctx)
+                log_q += log_det
+            else:
+                z, log_det = flow(z, **ctx)
+                log_q -= log_det
+            i += 1
+        return z, log_q
+
+    def _plain_walk(self, z, log_q, context, density, trace=None):
+        """The pass of ``_walk`` through every flow's plain ``(z, log_det)`` contract, log-dets summed out of place;
+        ``trace``: two lists that receive each layer's output and log-det as numpy arrays (the reference's
+        ``extended`` lists)."""
+        for flow in (reversed(self.flows) if density else self.flows):
+            ctx = {'context': context} if (context is not None and getattr(flow, 'takes_context', False)) else {}
+            z, log_det = flow.inverse(z, **ctx) if density else flow(z, **ctx)
+            if trace is not None:
+                trace[0].append(z.detach().cpu().numpy())
+                trace[1].append(torch.as_tensor(log_det).detach().cpu().numpy())
+            log_q = log_q + log_det if density else log_q - log_det
+        return z, log_q
+
     # ------------------------------------------------------------ density
     def log_prob(self, x, context=None):
         """log q(x) [B]: flows inverted last to first, log-dets added, base
         log-density at the end (core.py:176-183)."""
-        log_q = torch.zeros(len(x), dtype=x.dtype, device=x.device)
-        z = x
-        order = list(reversed(self.flows))
-        skip = False
-        resume = 0                               # flows before this position were executed by a stack launch
-        for i, flow in enumerate(order):
-            if i < resume:
-                continue
-            if skip:
-                skip = False
-                continue
-            ctx = {'context': context} if (context is not None and getattr(flow, 'takes_context', False)) else {}
-            # a run of one-kernel affine layers (and the Permutes between them) is ONE launch
-            if i >= resume and isinstance(flow, (Permute, AffineCouplingBlock)) and self.fuse_affine_stacks:
-                plan = fused_affine.cached_plan(self, order, i, z, True)
-                if plan is not None:
-                    resume, steps, trailing = plan
-                    core_ = steps[0][0].flows[1]
-                    z = fused_affine.run_stack(steps, trailing, z, _scale_code(core_.scale, core_.scale_map), True,
-                                               log_q, 1.0)[0]
-                    continue
-            # a run of MaskedAffineFlow layers with MLP conditioners / per-feature affine layers is ONE launch
-            if self.fuse_masked_stacks and isinstance(flow, (MaskedAffineFlow, AffineConstFlow)):
-                plan = fused_masked.cached_plan(self, order, i, z)
-                if plan is not None:
-                    resume, steps = plan
-                    z, log_q = fused_masked.run(steps, z, True, log_q, 1.0)       # (a new log_q when autograd records)
-                    continue
-            # a run of one-kernel RQS coupling layers at a small batch is ONE launch (the tile stays in LDS)
-            if self.fuse_rqs_stacks and type(flow) is CoupledRationalQuadraticSpline:
-                plan = fused.cached_plan_stack(self, order, i, z, context)
-                if plan is not None:
-                    resume, run, sig = plan
-                    z = fused.run_stack(run, sig, z, context, False, log_q, 1.0)[0]
-                    continue
-            # a Permute undone right before a one-kernel affine layer becomes that kernel's load index
-            if (isinstance(flow, Permute) and i + 1 < len(order) and z.dim() == 2
-                    and isinstance(order[i + 1], AffineCouplingBlock) and order[i + 1].fusable(z)):
-                z = order[i + 1].run_with_permute(z, True, log_q, 1.0, in_gather=flow._idx32(True, z.device))
-                skip = True
-                continue
-            if hasattr(flow, 'inverse_into'):
-                z = flow.inverse_into(z, log_q, **ctx)
-            else:
-                z, log_det = flow.inverse(z, **ctx)
-                log_q += log_det
+        z, log_q = self._walk(x, torch.zeros(len(x), dtype=x.dtype, device=x.device), context, True)
         if hasattr(self.q0, 'from_noise'):
             self.q0.log_prob(z, out=log_q)
         else:
@@ -113,69 +132,19 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
     def sample(self, num_samples=1, context=None):
         """(z, log q(z)) for fresh base draws (core.py:150-155, :168)."""
         z, log_q = self.q0(num_samples)
-        return self._push(z, log_q, context)
+        return self._walk(z, log_q, context, False)
 
     def sample_from(self, eps, context=None):
         """Same as ``sample`` with the standard-normal base draw given."""
         z, log_q = self.q0.from_noise(eps)
-        return self._push(z, log_q, context)
-
-    def _push(self, z, log_q, context):
-        order = list(self.flows)
-        skip = False
-        resume = 0
-        for i, flow in enumerate(order):
-            if i < resume:
-                continue
-            if skip:
-                skip = False
-                continue
-            ctx = {'context': context} if (context is not None and getattr(flow, 'takes_context', False)) else {}
-            if i >= resume and isinstance(flow, (Permute, AffineCouplingBlock)) and self.fuse_affine_stacks:
-                plan = fused_affine.cached_plan(self, order, i, z, False)
-                if plan is not None:
-                    resume, steps, trailing = plan
-                    core_ = steps[0][0].flows[1]
-                    z = fused_affine.run_stack(steps, trailing, z, _scale_code(core_.scale, core_.scale_map), False,
-                                               log_q, -1.0)[0]
-                    continue
-            if self.fuse_masked_stacks and isinstance(flow, (MaskedAffineFlow, AffineConstFlow)):
-                plan = fused_masked.cached_plan(self, order, i, z)
-                if plan is not None:
-                    resume, steps = plan
-                    z, log_q = fused_masked.run(steps, z, False, log_q, -1.0)
-                    continue
-            if self.fuse_rqs_stacks and type(flow) is CoupledRationalQuadraticSpline:
-                plan = fused.cached_plan_stack(self, order, i, z, context)
-                if plan is not None:
-                    resume, run, sig = plan
-                    z = fused.run_stack(run, sig, z, context, True, log_q, -1.0)[0]
-                    continue
-            # a Permute applied right after a one-kernel affine layer becomes that kernel's store index
-            if (isinstance(flow, AffineCouplingBlock) and i + 1 < len(order) and isinstance(order[i + 1], Permute)
-                    and z.dim() == 2 and flow.fusable(z)):
-                z = flow.run_with_permute(z, False, log_q, -1.0, out_gather=order[i + 1]._idx32(False, z.device))
-                skip = True
-                continue
-            if hasattr(flow, 'forward_into'):
-                z = flow.forward_into(z, log_q, **ctx)
-            else:
-                z, log_det = flow(z, **ctx)
-                log_q -= log_det
-        return z, log_q
+        return self._walk(z, log_q, context, False)
 
     # ------------------------------------------------------------ objectives
     def _pull(self, z, context=None, trace=None):
         """log q of given points through the plain ``(z, log_det)`` contract, optionally
         recording each layer's output and log-det (the reference's ``extended`` lists)."""
         log_q = torch.zeros(len(z), dtype=z.dtype, device=z.device)
-        for flow in reversed(self.flows):
-            ctx = {'context': context} if (context is not None and getattr(flow, 'takes_context', False)) else {}
-            z, log_det = flow.inverse(z, **ctx)
-            if trace is not None:
-                trace[0].append(z.detach().cpu().numpy())
-                trace[1].append(torch.as_tensor(log_det).detach().cpu().numpy())
-            log_q = log_q + log_det
+        z, log_q = self._plain_walk(z, log_q, context, True, trace)
         return log_q + self.q0.log_prob(z)
 
     def forward_kld(self, x, extended=False, context=None):
@@ -203,13 +172,7 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         """mean log q(z) - beta * mean log p(z), z ~ q (core.py:67-100)."""
         z, log_q = self.q0(num_samples)
         trace = ([], []) if extended else None
-        for flow in self.flows:
-            ctx = {'context': context} if (context is not None and getattr(flow, 'takes_context', False)) else {}
-            z, log_det = flow(z, **ctx)
-            if trace is not None:
-                trace[0].append(z.detach().cpu().numpy())
-                trace[1].append(torch.as_tensor(log_det).detach().cpu().numpy())
-            log_q = log_q - log_det
+        z, log_q = self._plain_walk(z, log_q, context, False, trace)
         if not score_fn:
             log_q = self._frozen_log_q(z, context)
         log_p = self.p.log_prob(z)

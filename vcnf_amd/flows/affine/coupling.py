@@ -6,17 +6,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from ..base import Flow
+from ..base import Flow, fold_log_det
 from ..reshape import Split, Merge
 from ... import _lib, autograd, fused_affine
-
-
-def _scale_code(scale, scale_map):
-    if not scale:
-        return _lib.SCALE_NONE
-    if scale_map not in _lib.SCALE_MAPS:
-        raise NotImplementedError('This scale map is not implemented.')
-    return _lib.SCALE_MAPS[scale_map]
 
 
 class AffineConstFlow(Flow):
@@ -74,7 +66,7 @@ class AffineCoupling(Flow):
 
     def _run(self, z, inverse):
         z1, z2 = z
-        code = _scale_code(self.scale, self.scale_map)
+        code = _lib.scale_code(self.scale, self.scale_map)
         param = self.param_map(z1)
         if autograd.needs_grad(z2, param):
             out, log_det = autograd.AffineCouplingFn.apply(z2, param, 0, z2.shape[1], code, inverse)
@@ -158,7 +150,7 @@ class AffineCouplingBlock(Flow):
     def run_with_permute(self, z, inverse, log_q, sign, in_gather=None, out_gather=None):
         """One-kernel layer with a neighbouring Permute folded into its load / store indexing."""
         core = self.flows[1]
-        return fused_affine.run(self, z, _scale_code(core.scale, core.scale_map), inverse, log_q, sign,
+        return fused_affine.run(self, z, _lib.scale_code(core.scale, core.scale_map), inverse, log_q, sign,
                                 in_gather, out_gather)[0]
 
     def _run(self, z, inverse, log_q=None, sign=1.0):
@@ -169,11 +161,9 @@ class AffineCouplingBlock(Flow):
             out, _ = (self.flows[2].forward(pair) if not inverse else self.flows[0].inverse(pair))
             if not torch.is_tensor(ld):
                 ld = torch.zeros(z.shape[0], dtype=z.dtype, device=z.device)
-            if log_q is not None:
-                return out, log_q.add_(ld, alpha=sign)
-            return out, (ld if sign == 1.0 else sign * ld)
+            return fold_log_det(out, ld, log_q, sign)
         core = self.flows[1]
-        code = _scale_code(core.scale, core.scale_map)
+        code = _lib.scale_code(core.scale, core.scale_map)
         if (self.fused and not (torch.is_grad_enabled() and autograd.needs_grad(z, log_q, *core.param_map.parameters()))
                 and fused_affine.eligible(self, z)):
             # conditioner + affine map + log|det| in one kernel (csrc/fused_affine.hip)
@@ -189,9 +179,7 @@ class AffineCouplingBlock(Flow):
         param = core.param_map(cond_in)
         if autograd.needs_grad(z, param, log_q):
             out, ld = autograd.AffineCouplingFn.apply(z, param, t_off, d_t, code, inverse)
-            if log_q is not None:
-                return out, log_q.add_(ld, alpha=sign)
-            return out, (ld if sign == 1.0 else sign * ld)
+            return fold_log_det(out, ld, log_q, sign)
         ld = log_q
         if ld is None:
             ld = torch.zeros(z.shape[0], dtype=z.dtype, device=z.device)   # coupling.py:248

@@ -6,6 +6,14 @@ import torch
 from torch import nn
 
 
+def fold_log_det(out, log_det, log_q, sign):
+    """(out, log_q + sign * log_det) with the sum taken in place in ``log_q``, or (out, sign * log_det) without one:
+    the epilogue of the layers' accumulating forms (``_run(..., log_q, sign)``)."""
+    if log_q is not None:
+        return out, log_q.add_(log_det, alpha=sign)
+    return out, (log_det if sign == 1.0 else sign * log_det)
+
+
 class Flow(nn.Module):
     # layers that accept ``context=`` in forward/inverse set this
     takes_context = False

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ..base import Flow
+from ..base import Flow, fold_log_det
 from ... import _lib, fused, fused_final, autograd
 from ...utils import splines
 
@@ -349,20 +349,11 @@ class PiecewiseRationalQuadraticCoupling(Flow):
         self._check(inputs)
         if self.per_feature or (inputs.dtype == torch.float64 and inputs.dim() == 2):
             # fp64: the plain structure of coupling.py:70-125 over the fp64 elementwise spline (csrc/rqs_f64.hip)
-            out, lad = self._run_per_feature(inputs, context, sampling)
-            if log_q is not None:
-                return out, log_q.add_(lad, alpha=sign)
-            return out, (lad if sign == 1.0 else sign * lad)
+            return fold_log_det(*self._run_per_feature(inputs, context, sampling), log_q, sign)
         if inputs.dim() == 4:
-            out, lad = self._run_image(inputs, context, sampling)
-            if log_q is not None:
-                return out, log_q.add_(lad, alpha=sign)
-            return out, (lad if sign == 1.0 else sign * lad)
+            return fold_log_det(*self._run_image(inputs, context, sampling), log_q, sign)
         if self._needs_grad(inputs, context):
-            out, lad = self._run_differentiable(inputs, context, sampling)
-            if log_q is not None:
-                return out, log_q.add_(lad, alpha=sign)
-            return out, (lad if sign == 1.0 else sign * lad)
+            return fold_log_det(*self._run_differentiable(inputs, context, sampling), log_q, sign)
         if self.fused and fused.eligible(self, context):
             # conditioner + splines in one kernel (csrc/fused_layer.hip)
             return fused.run(self, inputs, context, sampling, log_q, sign)

@@ -315,9 +315,37 @@ def plan_stack(order, start, z, context):
     return start + len(run), run, sig
 
 
-def _stack_stamp(cp):
+def memo_plan(owner, attr, key, order, start, make, stamp, seen=None):
+    """``make()`` - a run plan (end, ...) or None - memoised in the dict ``owner.<attr>`` under ``key``.  An entry is
+    reused while the modules the plan has seen - the run and the flow that ended it, narrowed by ``seen`` - are the
+    same objects at the same positions of ``order`` with the same ``stamp``."""
+    plans = owner.__dict__.setdefault(attr, {})
+    hit = plans.get(key)
+    if hit is not None:
+        plan, mods, stamps = hit
+        if all(a is b for a, b in zip(order[start:start + len(mods)], mods)) and stamps == tuple(map(stamp, mods)):
+            return plan
+    plan = make()
+    mods = order[start:(start if plan is None else plan[0]) + 1]
+    if seen is not None:
+        mods = seen(mods)
+    if len(plans) > 64:
+        plans.clear()
+    plans[key] = (plan, mods, tuple(map(stamp, mods)))
+    return plan
+
+
+def _stack_stamp(flow):
+    cp = flow.prqct
     return (cp.fused, cp.fused_precision, getattr(cp, 'range_safe', True), cp.tails, cp.num_bins, cp.per_feature,
             cp.unconditional_transform is None, id(cp.transform_net), cp.tail_bound if not torch.is_tensor(cp.tail_bound) else id(cp.tail_bound))
+
+
+def _stack_seen(mods):
+    # plan_stack reads at most the kernel's layer limit and stops at the first flow of another type
+    from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
+    lim = int(_lib.lib().vcnf_rqs_stack_fused_max_layers())
+    return [f for f in mods[:lim] if type(f) is CoupledRationalQuadraticSpline]
 
 
 def cached_plan_stack(owner, order, start, z, context):
@@ -332,23 +360,17 @@ def cached_plan_stack(owner, order, start, z, context):
     small = z.shape[0] <= _lib.small_batch_rows()
     key = (start, len(order), id(order[start]), z.shape[1], small, None if context is None else tuple(context.shape[1:]),
            DEFAULT_PRECISION)
-    plans = owner.__dict__.setdefault('_rqs_stack_plans', {})
-    hit = plans.get(key)
-    if hit is not None:
-        plan, mods, stamp = hit
-        if all(a is b for a, b in zip(order[start:start + len(mods)], mods)) and \
-                stamp == tuple(_stack_stamp(f.prqct) for f in mods if hasattr(f, 'prqct')):
-            return plan
-    plan = plan_stack(order, start, z, context)
-    from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
-    lim = int(_lib.lib().vcnf_rqs_stack_fused_max_layers())
-    # what the plan looked at: the run and the flow that ended it
-    n = (plan[0] - start if plan is not None else 0) + 1
-    mods = [f for f in order[start:start + min(n, lim)] if type(f) is CoupledRationalQuadraticSpline]
-    if len(plans) > 64:
-        plans.clear()
-    plans[key] = (plan, mods, tuple(_stack_stamp(f.prqct) for f in mods))
-    return plan
+    return memo_plan(owner, '_rqs_stack_plans', key, order, start, lambda: plan_stack(order, start, z, context),
+                     _stack_stamp, _stack_seen)
+
+
+def stack_run(owner, order, start, z, context, density):
+    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS)."""
+    plan = cached_plan_stack(owner, order, start, z, context)
+    if plan is None:
+        return None
+    end, run, sig = plan
+    return end, lambda z, log_q, sign: (run_stack(run, sig, z, context, not density, log_q, sign)[0], log_q)
 
 
 def run_stack(run, sig, z, context, sampling, log_q, sign):

@@ -238,6 +238,17 @@ def cached_plan(owner, order, start, z, inverse):
     return plans[key]
 
 
+def stack_run(owner, order, start, z, context, density):
+    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS)."""
+    plan = cached_plan(owner, order, start, z, density)
+    if plan is None:
+        return None
+    end, steps, trailing = plan
+    core = steps[0][0].flows[1]
+    code = _lib.scale_code(core.scale, core.scale_map)
+    return end, lambda z, log_q, sign: (run_stack(steps, trailing, z, code, density, log_q, sign)[0], log_q)
+
+
 def run_stack(steps, trailing, z, code, inverse, log_q, sign):
     """Execute a planned run (see plan_stack) in one launch."""
     first = steps[0][0]

@@ -11,6 +11,7 @@ scale and the log2(e) factors of the spline's exponentials (see pack).
 import torch
 
 from . import _lib
+from .flows.base import fold_log_det
 from .fused import _split_halves, _as_floats
 
 
@@ -182,6 +183,4 @@ def run(coupling, inputs, context, sampling, log_q=None, sign=1.0):
     lad = partial.sum(0) if partial.shape[0] > 1 else partial[0]
     if lad_i is not None:
         lad = lad + lad_i
-    if log_q is not None:
-        return out, log_q.add_(lad, alpha=sign)
-    return out, (lad if sign == 1.0 else sign * lad)
+    return fold_log_det(out, lad, log_q, sign)

@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .fused import memo_plan
 
 MAX_LAYERS = 4096
 
@@ -118,19 +119,17 @@ def cached_plan(owner, order, start, z):
     if z.dim() != 2:
         return None
     key = (start, len(order), id(order[start]), z.shape[1], z.dtype, str(z.device))
-    plans = owner.__dict__.setdefault('_masked_stack_plans', {})
-    hit = plans.get(key)
-    if hit is not None:
-        p, mods, stamp = hit
-        if all(a is b for a, b in zip(order[start:start + len(mods)], mods)) and stamp == tuple(_stamp(f) for f in mods):
-            return p
-    p = plan(order, start, z)
-    n = (p[0] - start if p is not None else 0) + 1              # the run and the flow that ended it
-    mods = list(order[start:start + n])
-    if len(plans) > 64:
-        plans.clear()
-    plans[key] = (p, mods, tuple(_stamp(f) for f in mods))
-    return p
+    return memo_plan(owner, '_masked_stack_plans', key, order, start, lambda: plan(order, start, z), _stamp)
+
+
+def stack_run(owner, order, start, z, context, density):
+    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS); the launch returns a
+    new log_q when autograd records the run."""
+    p = cached_plan(owner, order, start, z)
+    if p is None:
+        return None
+    end, steps = p
+    return end, lambda z, log_q, sign: run(steps, z, density, log_q, sign)
 
 
 def run(steps, z, inverse, log_q, sign):
