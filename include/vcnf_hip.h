@@ -580,6 +580,23 @@ int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, const double
                                  const double* g_y, const double* g_logabsdet,
                                  double* g_x, double* g_uw, double* g_uh, double* g_ud, int64_t n,
                                  const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream);
+/* vcnf_rqs_elementwise_strided_f32 in double (image-shaped couplings: the conditioner output [B, C*P, H, W] read in
+ * place).  Per element the same bin and the same arithmetic as vcnf_rqs_elementwise_f64. */
+int vcnf_rqs_elementwise_strided_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                     int64_t row_w, int64_t row_h, int64_t row_d, int64_t inner,
+                                     int64_t k_stride, int64_t period,
+                                     double* y, double* logabsdet, int64_t n,
+                                     const vcnf_rqs_cfg_f64* cfg, int inverse, int32_t* bad_discriminant,
+                                     void* stream);
+/* VJP of vcnf_rqs_elementwise_strided_f64 on the conditioner layout: the contract of vcnf_rqs_packed_bwd_f32 in
+ * double (g_params written in the layout of params). */
+int vcnf_rqs_packed_bwd_f64(const double* x, const double* params, int64_t inner, int64_t lad_div,
+                            const double* g_y, const double* g_logabsdet,
+                            double* g_x, double* g_params, int64_t n,
+                            const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream);
+/* vcnf_maf_affine_f32 in double; params must be 16-byte aligned (one double2 load per feature). */
+int vcnf_maf_affine_f64(const double* x, const double* params, double* out, double* logdet, int64_t batch,
+                        int32_t features, int inverse, int ld_mode, double ld_sign, void* stream);
 int vcnf_affine_coupling_f64(const double* z, const double* param, double* out, double* logdet,
                              int64_t batch, int32_t channels, int32_t inner,
                              int32_t t_off, int32_t d_t, int scale_map, int inverse,

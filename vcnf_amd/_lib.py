@@ -146,6 +146,10 @@ PROTOTYPES = {
                                   ctypes.POINTER(RqsCfg64), _INT, _P, _P], _INT),
     "vcnf_rqs_elementwise_bwd_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64,
                                       ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
+    "vcnf_rqs_elementwise_strided_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64,
+                                          ctypes.POINTER(RqsCfg64), _INT, _P, _P], _INT),
+    "vcnf_rqs_packed_bwd_f64": ([_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
+    "vcnf_maf_affine_f64": ([_P, _P, _P, _P, _I64, _I32, _INT, _INT, _F64, _P], _INT),
     "vcnf_affine_coupling_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT, _INT, _INT, _F64, _P], _INT),
     "vcnf_masked_affine_f64": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F64, _P], _INT),
     "vcnf_affine_const_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _P], _INT),
@@ -412,8 +416,10 @@ def rqs_elementwise(x, uw, uh, ud, cfg, inverse, allow_grad=False):
 
 def rqs_elementwise_image(x, params, cfg, inverse, allow_grad=False):
     """x [B, C, *inner] with the conditioner output params [B, C*P, *inner] read in place
-    (the reference reshapes/permutes it to [B, C, *inner, P]; coupling.py:148-151)."""
-    dev = require_device(x, params, allow_grad=allow_grad)
+    (the reference reshapes/permutes it to [B, C, *inner, P]; coupling.py:148-151).  fp32 or fp64 (both tensors)."""
+    dev = require_device(x, params, allow_grad=allow_grad, f64=True)
+    if params.dtype != x.dtype:
+        raise VcnfError("rqs_elementwise_image: mixed dtypes (%s inputs, %s logits)" % (x.dtype, params.dtype))
     k, nd = cfg.num_bins, n_derivatives(cfg)
     p = 2 * k + nd
     b, c = x.shape[0], x.shape[1]
@@ -424,13 +430,14 @@ def rqs_elementwise_image(x, params, cfg, inverse, allow_grad=False):
     x = x.contiguous()
     params = params.contiguous()
     y, lad = torch.empty_like(x), torch.empty_like(x)
-    base = params.data_ptr()
+    base, es = params.data_ptr(), params.element_size()
+    f64 = x.dtype == torch.float64
     with torch.cuda.device(dev):
-        st = lib().vcnf_rqs_elementwise_strided_f32(
-            _ptr(x), base, base + 4 * k * inner, base + 8 * k * inner, p * inner, p * inner, p * inner,
-            inner, inner, 0, _ptr(y), _ptr(lad), x.numel(), ctypes.byref(cfg), int(bool(inverse)),
+        st = getattr(lib(), "vcnf_rqs_elementwise_strided" + _sfx(x))(
+            _ptr(x), base, base + es * k * inner, base + 2 * es * k * inner, p * inner, p * inner, p * inner,
+            inner, inner, 0, _ptr(y), _ptr(lad), x.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)),
             _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-    _check(st, "vcnf_rqs_elementwise_strided_f32")
+    _check(st, "vcnf_rqs_elementwise_strided" + _sfx(x))
     return y, lad
 
 
@@ -458,17 +465,21 @@ def rqs_elementwise_shared(x, uw, uh, ud, cfg, inverse, allow_grad=False):
 
 def rqs_packed_bwd(x, params, gy, glad, cfg, inverse):
     """VJP of rqs_elementwise_image: x, gy [B, C, *inner]; params [B, C*P, *inner]; glad [B]
-    (gradient of the per-sample log-det).  Returns (g_x, g_params) in the layouts of x / params."""
-    dev = require_device(x, params, gy, glad, allow_grad=True)
+    (gradient of the per-sample log-det).  Returns (g_x, g_params) in the layouts of x / params.  fp32 or fp64
+    (every tensor)."""
+    dev = require_device(x, params, gy, glad, allow_grad=True, f64=True)
+    if any(t.dtype != x.dtype for t in (params, gy, glad)):
+        raise VcnfError("rqs_packed_bwd: inputs, logits and upstream gradients must share one dtype")
     x, params = x.detach().contiguous(), params.detach().contiguous()
     gy, glad = gy.detach().contiguous(), glad.detach().contiguous()
     inner = int(x[0, 0].numel())
     gx, gp = torch.empty_like(x), torch.empty_like(params)
+    f64 = x.dtype == torch.float64
     with torch.cuda.device(dev):
-        st = lib().vcnf_rqs_packed_bwd_f32(_ptr(x), _ptr(params), inner, int(x[0].numel()), _ptr(gy), _ptr(glad),
-                                           _ptr(gx), _ptr(gp), x.numel(), ctypes.byref(cfg),
-                                           int(bool(inverse)), _stream())
-    _check(st, "vcnf_rqs_packed_bwd_f32")
+        st = getattr(lib(), "vcnf_rqs_packed_bwd" + _sfx(x))(
+            _ptr(x), _ptr(params), inner, int(x[0].numel()), _ptr(gy), _ptr(glad), _ptr(gx), _ptr(gp), x.numel(),
+            ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)), _stream())
+    _check(st, "vcnf_rqs_packed_bwd" + _sfx(x))
     return gx, gp
 
 
@@ -858,18 +869,20 @@ def masked_affine(z, s, t, bmask, inverse, logdet=None, sign=1.0):
 
 def maf_affine(x, params, inverse):
     """Masked-affine-autoregressive elementwise map on a MADE output [B, D * 2] (csrc/affine_kernels.hip::
-    maf_affine_kernel): returns (y, log_det[B])."""
-    dev = require_device(x, params)
+    maf_affine_kernel): returns (y, log_det[B]) in the dtype of the inputs (fp32 or fp64)."""
+    dev = require_device(x, params, f64=True)
+    if params.dtype != x.dtype:
+        raise VcnfError("maf_affine: mixed dtypes (%s inputs, %s params)" % (x.dtype, params.dtype))
     x, params = x.contiguous(), params.contiguous()
     b, d = x.shape
     if params.shape[0] != b or params[0].numel() != 2 * d:
         raise VcnfError("maf_affine: params %s do not match inputs %s" % (tuple(params.shape), tuple(x.shape)))
     out = torch.empty_like(x)
-    ld = torch.empty(b, dtype=torch.float32, device=dev)
+    ld = torch.empty(b, dtype=x.dtype, device=dev)
     with torch.cuda.device(dev):
-        st = lib().vcnf_maf_affine_f32(_ptr(x), _ptr(params), _ptr(out), _ptr(ld), b, d, int(bool(inverse)), LD_STORE, 1.0,
-                                       _stream())
-    _check(st, "vcnf_maf_affine_f32")
+        st = getattr(lib(), "vcnf_maf_affine" + _sfx(x))(_ptr(x), _ptr(params), _ptr(out), _ptr(ld), b, d,
+                                                          int(bool(inverse)), LD_STORE, 1.0, _stream())
+    _check(st, "vcnf_maf_affine" + _sfx(x))
     return out, ld
 
 

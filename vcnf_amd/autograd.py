@@ -60,10 +60,11 @@ class RqsPackedFn(torch.autograd.Function):
         ctx.save_for_backward(x, params)
         ctx.cfg, ctx.inverse = cfg, inverse
         with torch.no_grad():
-            if x.dim() == 2 and params.dim() == 2 and cfg.tails == _lib.TAILS_LINEAR:
+            if x.dim() == 2 and params.dim() == 2 and cfg.tails == _lib.TAILS_LINEAR and x.dtype == torch.float32:
                 # [B, C] inputs: the coupling kernel of the inference path with all C features transformed and no
                 # identity half - rows staged through LDS with 16-byte transfers (88 us at 131 072 x 32 against 186 us for
-                # the generally-addressed elementwise kernel); it returns the per-sample sum of the log-derivatives
+                # the generally-addressed elementwise kernel); it returns the per-sample sum of the log-derivatives.
+                # fp32 only: fp64 takes the strided elementwise kernel below (csrc/rqs_f64.hip)
                 idx = _arange32(x.shape[1], x.device)
                 return _lib.rqs_coupling(x.detach(), params.detach(), idx, idx[:0], None, cfg, inverse)
             y, lad = _lib.rqs_elementwise_image(x, params, cfg, inverse, allow_grad=True)

@@ -116,29 +116,38 @@ __global__ __launch_bounds__(kBlock) void affine_coupling_kernel(const AffineArg
 // flows/affine/autoregressive.py:75-103: params [B, D, 2] = (unconstrained scale, shift) per feature from a MADE pass,
 // scale = sigmoid(u + 2) + 1e-3; density direction y = scale x + shift, log|det| = sum log scale; the other direction
 // y = (x - shift) / scale, log|det| = -sum log scale (called D times by the sampling loop, :29-36).
-struct MafArgs {
-  const float* x;
-  const float* param;
-  float* out;
-  float* logdet;
+template <typename T>
+struct MafArgsT {
+  const T* x;
+  const T* param;
+  T* out;
+  T* logdet;
   long long B;
   int D, inverse, G, ld_mode;
-  float ld_sign;
+  T ld_sign;
 };
+using MafArgs = MafArgsT<float>;
 
-__global__ __launch_bounds__(kBlock) void maf_affine_kernel(const MafArgs a) {
+// one (scale logit, shift) pair per 8 / 16-byte load
+template <typename T> struct Pair;
+template <> struct Pair<float> { using type = float2; };
+template <> struct Pair<double> { using type = double2; };
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void maf_affine_kernel(const MafArgsT<T> a) {
+  using P2 = typename Pair<T>::type;
   const int g = threadIdx.x & (a.G - 1);
   const int per_block = kBlock / a.G;
   for (long long b = (long long)blockIdx.x * per_block + threadIdx.x / a.G; b < a.B;
        b += (long long)gridDim.x * per_block) {
-    const float2* pr = reinterpret_cast<const float2*>(a.param) + b * a.D;
-    float acc = 0.f;
+    const P2* pr = reinterpret_cast<const P2*>(a.param) + b * a.D;
+    T acc = 0;
     for (int j = g; j < a.D; j += a.G) {
-      const float2 p = pr[j];
-      const float scale = sigmoid_f(p.x + 2.f) + 1e-3f;
-      const float v = a.x[b * a.D + j];
+      const P2 p = pr[j];
+      const T scale = sigmoid_f(p.x + T(2)) + T(1e-3);
+      const T v = a.x[b * a.D + j];
       a.out[b * a.D + j] = a.inverse ? (v - p.y) / scale : scale * v + p.y;
-      acc += logf(scale);
+      acc += log_(scale);
     }
     acc = group_sum(acc, a.G);
     if (g == 0) put_ld(a.logdet, b, a.ld_sign * (a.inverse ? -acc : acc), a.ld_mode);
@@ -444,7 +453,7 @@ extern "C" int vcnf_maf_affine_f32(const float* x, const float* params, float* o
   if (!x || !params || !out || !logdet) return VCNF_ERR_NULL;
   if (reinterpret_cast<uintptr_t>(params) & 7) return VCNF_ERR_ALIGN;
   MafArgs a{x, params, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
-  hipLaunchKernelGGL(maf_affine_kernel, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(maf_affine_kernel<float>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
   return launched();
 }
 
@@ -570,6 +579,18 @@ extern "C" int vcnf_affine_coupling_f64(const double* z, const double* param, do
   AffineArgsT<double> a{z, param, out, logdet, batch, channels, inner, t_off, d_t, scale_map, inverse ? 1 : 0,
                         pick_lanes((long long)channels * inner), ld_mode, ld_sign};
   hipLaunchKernelGGL(affine_coupling_kernel<double>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
+  return launched();
+}
+
+extern "C" int vcnf_maf_affine_f64(const double* x, const double* params, double* out, double* logdet, int64_t batch,
+                                   int32_t features, int inverse, int ld_mode, double ld_sign, void* stream) {
+  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
+  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
+  if (batch == 0) return VCNF_OK;
+  if (!x || !params || !out || !logdet) return VCNF_ERR_NULL;
+  if (reinterpret_cast<uintptr_t>(params) & 15) return VCNF_ERR_ALIGN;       // double2 loads
+  MafArgsT<double> a{x, params, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
+  hipLaunchKernelGGL(maf_affine_kernel<double>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
   return launched();
 }
 

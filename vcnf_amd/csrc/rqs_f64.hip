@@ -1,4 +1,5 @@
-// Rational-quadratic spline in double precision: the elementwise spline of vcnf_rqs_elementwise_f32 for models
+// Rational-quadratic spline in double precision: the elementwise spline of vcnf_rqs_elementwise_f32 (and, with strided
+// logit rows, of vcnf_rqs_elementwise_strided_f32 / vcnf_rqs_packed_bwd_f32 for image couplings) for models
 // converted with .double() (the reference's drivers do: /root/reference run.py:114, runadultvdeq.py:183; its Flow
 // contract is dtype-agnostic).  One thread per element, the reference's operation order as written in
 // normflow/utils/splines.py:20-85 (tails) and :88-193 (spline): softmax -> floor -> cumsum -> affine map -> exact end
@@ -24,28 +25,43 @@ struct Rqs64Args {
   int K, tails, inverse;
   double left, right, bottom, top, min_w, min_h, min_d, wh_scale, edge;
   int32_t* bad;
+  long long inner, ks, period;     // strided addressing only (see rows64)
 };
 
-// Knot construction, bin search and derivative-logit padding are shared by the forward kernel and the VJP kernel
-// below, so that both select the same bin for every element.  KT > 0: compile-time bin count (the VJP kernel's
-// templated instances keep every array in registers); KT == 0: runtime K (the forward kernel, and the VJP kernel's
-// generic instance).
+// Offsets of element i's logit rows.  Dense (vcnf_rqs_elementwise_f64): row i at i * ld, logit k at + k.  Strided
+// (vcnf_rqs_elementwise_strided_f64, as vcnf_rqs_elementwise_strided_f32): r = period > 0 ? i % period : i,
+// outer = r / inner, s = r % inner; row at outer * ld + s, logit k at + k * ks (ld_* are the per-row strides).
+struct Rows64 {
+  long long w, h, d, ks;
+};
 
-// knots of one side: cum[0..K] from K logits (splines.py:109-119 / :123-133); ``prob`` (optional) receives the
-// softmax probabilities
+template <bool STRIDED>
+__device__ __forceinline__ Rows64 rows64(const Rqs64Args& a, long long i) {
+  if (!STRIDED) return Rows64{i * a.ld_w, i * a.ld_h, i * a.ld_d, 1};
+  const long long r = a.period > 0 ? i % a.period : i;
+  const long long outer = a.inner == 1 ? r : r / a.inner, s = r - outer * a.inner;
+  return Rows64{outer * a.ld_w + s, outer * a.ld_h + s, outer * a.ld_d + s, a.ks};
+}
+
+// Knot construction, bin search and derivative-logit padding are shared by the forward kernel and the VJP kernel
+// below, so that both select the same bin for every element.  KT > 0: compile-time bin count (the templated instances
+// of both kernels keep every array in registers); KT == 0: runtime K (their generic instances).
+
+// knots of one side: cum[0..K] from K logits lg[k * ks] (splines.py:109-119 / :123-133); ``prob`` (optional) receives
+// the softmax probabilities
 template <int KT>
-__device__ __forceinline__ void partition64(const double* lg, int Kr, double scale, double lo, double hi,
+__device__ __forceinline__ void partition64(const double* lg, long long ks, int Kr, double scale, double lo, double hi,
                                             double floor_, double* cum, double* prob = nullptr) {
   const int K = KT > 0 ? KT : Kr;
   double m = -INFINITY;
-  for (int k = 0; k < K; ++k) m = fmax(m, lg[k] * scale);
+  for (int k = 0; k < K; ++k) m = fmax(m, lg[k * ks] * scale);
   double s = 0.0;
-  for (int k = 0; k < K; ++k) s += exp(lg[k] * scale - m);
+  for (int k = 0; k < K; ++k) s += exp(lg[k * ks] * scale - m);
   double run = 0.0;
   cum[0] = lo;
   for (int k = 0; k < K; ++k) {
-    if (prob) prob[k] = exp(lg[k] * scale - m) / s;
-    const double p = floor_ + (1.0 - floor_ * K) * (exp(lg[k] * scale - m) / s);
+    if (prob) prob[k] = exp(lg[k * ks] * scale - m) / s;
+    const double p = floor_ + (1.0 - floor_ * K) * (exp(lg[k * ks] * scale - m) / s);
     run += p;
     cum[k + 1] = (hi - lo) * run + lo;
   }
@@ -71,7 +87,25 @@ __device__ __forceinline__ int dlogit_col64(int k, int K, int tails) {
 
 __device__ __forceinline__ double softplus64(double v) { return v > 20.0 ? v : log1p(exp(v)); }   // F.softplus (threshold 20)
 
+// the knots bounding bin ``bin`` on both sides.  KT > 0: picked by comparison, so that the knot arrays stay in
+// registers; KT == 0: indexed.
+template <int KT>
+__device__ __forceinline__ void pick_bin64(const double* xk, const double* yk, int bin, int K, double& xl, double& xr,
+                                           double& yl, double& yr) {
+  if (KT > 0) {
+    xl = xk[0]; xr = xk[1]; yl = yk[0]; yr = yk[1];
+    for (int k = 1; k < K; ++k)
+      if (bin == k) { xl = xk[k]; xr = xk[k + 1]; yl = yk[k]; yr = yk[k + 1]; }
+  } else {
+    xl = xk[bin]; xr = xk[bin + 1]; yl = yk[bin]; yr = yk[bin + 1];
+  }
+}
+
+// KT > 0: compile-time bin count, every array in registers (K = 8, 10, 16); KT == 0: any K up to 64 (runtime-indexed
+// arrays in scratch).  Both instances evaluate the same expressions in the same order.
+template <int KT, bool STRIDED>
 __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Args a) {
+  constexpr int KA = KT > 0 ? KT : kMaxBins64;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long long)gridDim.x * blockDim.x) {
     const double x = a.x[i];
     if (a.tails != VCNF_TAILS_NONE && !(x >= a.left && x <= a.right)) {   // splines.py:30-49: identity outside
@@ -79,20 +113,23 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
       a.lad[i] = 0.0;
       continue;
     }
-    const int K = a.K;
-    double xk[kMaxBins64 + 1], yk[kMaxBins64 + 1];
-    partition64<0>(a.uw + i * a.ld_w, K, a.wh_scale, a.left, a.right, a.min_w, xk);
-    partition64<0>(a.uh + i * a.ld_h, K, a.wh_scale, a.bottom, a.top, a.min_h, yk);
-    const int bin = bin64<0>(a.inverse ? yk : xk, K, x);
-    const double* ud = a.ud + i * a.ld_d;
+    const int K = KT > 0 ? KT : a.K;
+    const Rows64 rw = rows64<STRIDED>(a, i);
+    double xk[KA + 1], yk[KA + 1];
+    partition64<KT>(a.uw + rw.w, rw.ks, K, a.wh_scale, a.left, a.right, a.min_w, xk);
+    partition64<KT>(a.uh + rw.h, rw.ks, K, a.wh_scale, a.bottom, a.top, a.min_h, yk);
+    const int bin = a.inverse ? bin64<KT>(yk, K, x) : bin64<KT>(xk, K, x);
+    const double* ud = a.ud + rw.d;
     auto dlogit = [&](int k) -> double {
       const int j = dlogit_col64(k, K, a.tails);
-      return j < 0 ? a.edge : ud[j];
+      return j < 0 ? a.edge : ud[j * rw.ks];
     };
     const double d0 = a.min_d + softplus64(dlogit(bin));           // :121
     const double d1 = a.min_d + softplus64(dlogit(bin + 1));
-    const double x_lo = xk[bin], w = xk[bin + 1] - xk[bin];
-    const double y_lo = yk[bin], h = yk[bin + 1] - yk[bin];
+    double x_lo, x_hi, y_lo, y_hi;
+    pick_bin64<KT>(xk, yk, bin, K, x_lo, x_hi, y_lo, y_hi);
+    const double w = x_hi - x_lo;
+    const double h = y_hi - y_lo;
     const double s = h / w;                                          // :144
     double out, lad;
     if (a.inverse) {
@@ -123,6 +160,16 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
   }
 }
 
+template <bool STRIDED>
+static void launch_fwd64(const Rqs64Args& a, dim3 grid, hipStream_t st) {
+  switch (a.K) {
+    case 8: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<8, STRIDED>), grid, dim3(256), 0, st, a); break;
+    case 10: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<10, STRIDED>), grid, dim3(256), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<16, STRIDED>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<0, STRIDED>), grid, dim3(256), 0, st, a); break;
+  }
+}
+
 
 // ------------------------------------------------------------------ VJP (training path of .double() models)
 // The adjoint of rqs_elementwise_f64_kernel, as rqs_backward.hip does it in fp32: the element is re-evaluated with
@@ -133,8 +180,9 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
 struct Rqs64BwdArgs {
   Rqs64Args f;                     // forward operands (y, lad, bad unused)
   const double *gy, *glad;
-  double *gx, *guw, *guh, *gud;    // dense gradient rows: K, K, nd
+  double *gx, *guw, *guh, *gud;    // dense: gradient rows of K, K, nd; strided: the layout of the logits (rows64)
   int nd;
+  long long lad_div;               // strided: g_logabsdet read at i / lad_div (dense: at i)
 };
 
 struct RqsBin64 {
@@ -145,7 +193,7 @@ struct RqsBin64 {
 // unrolled by the compiler: compile-time indices;
 // the bin's values are picked by comparison, never by a runtime index).  KT == 0 (any other K up to 64): the same
 // code with runtime-indexed arrays, which go to scratch.
-template <int KT, bool INV>
+template <int KT, bool INV, bool STRIDED>
 __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs64BwdArgs g) {
   const Rqs64Args& a = g.f;
   constexpr int KA = KT > 0 ? KT : kMaxBins64;
@@ -153,34 +201,30 @@ __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs6
   const int nd = g.nd;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long long)gridDim.x * blockDim.x) {
     const double x = a.x[i];
-    const double gy = g.gy[i], gl = g.glad[i];
-    double* guw = g.guw + i * K;
-    double* guh = g.guh + i * K;
-    double* gud = g.gud + i * nd;
+    const double gy = g.gy[i], gl = g.glad[STRIDED && g.lad_div != 1 ? i / g.lad_div : i];
+    const Rows64 rw = rows64<STRIDED>(a, i);
+    const long long ks = rw.ks;
+    double* guw = g.guw + (STRIDED ? rw.w : i * K);
+    double* guh = g.guh + (STRIDED ? rw.h : i * K);
+    double* gud = g.gud + (STRIDED ? rw.d : i * nd);
     if (a.tails != VCNF_TAILS_NONE && !(x >= a.left && x <= a.right)) {   // identity outside: dy/dx = 1
       g.gx[i] = gy;
-      for (int k = 0; k < K; ++k) { guw[k] = 0.0; guh[k] = 0.0; }
-      for (int k = 0; k < nd; ++k) gud[k] = 0.0;
+      for (int k = 0; k < K; ++k) { guw[k * ks] = 0.0; guh[k * ks] = 0.0; }
+      for (int k = 0; k < nd; ++k) gud[k * ks] = 0.0;
       continue;
     }
     double xk[KA + 1], yk[KA + 1], pw[KA], ph[KA];
-    partition64<KT>(a.uw + i * a.ld_w, K, a.wh_scale, a.left, a.right, a.min_w, xk, pw);
-    partition64<KT>(a.uh + i * a.ld_h, K, a.wh_scale, a.bottom, a.top, a.min_h, yk, ph);
+    partition64<KT>(a.uw + rw.w, ks, K, a.wh_scale, a.left, a.right, a.min_w, xk, pw);
+    partition64<KT>(a.uh + rw.h, ks, K, a.wh_scale, a.bottom, a.top, a.min_h, yk, ph);
     const int bin = bin64<KT>(INV ? yk : xk, K, x);
     RqsBin64 b;
     double xr, yr;
-    if (KT > 0) {
-      b.xl = xk[0]; xr = xk[1]; b.yl = yk[0]; yr = yk[1];
-      for (int k = 1; k < K; ++k)
-        if (bin == k) { b.xl = xk[k]; xr = xk[k + 1]; b.yl = yk[k]; yr = yk[k + 1]; }
-    } else {
-      b.xl = xk[bin]; xr = xk[bin + 1]; b.yl = yk[bin]; yr = yk[bin + 1];
-    }
+    pick_bin64<KT>(xk, yk, bin, K, b.xl, xr, b.yl, yr);
     b.w = xr - b.xl;
     b.h = yr - b.yl;
-    const double* ud = a.ud + i * a.ld_d;
+    const double* ud = a.ud + rw.d;
     const int j0 = dlogit_col64(bin, K, a.tails), j1 = dlogit_col64(bin + 1, K, a.tails);
-    const double l0 = j0 < 0 ? a.edge : ud[j0], l1 = j1 < 0 ? a.edge : ud[j1];
+    const double l0 = j0 < 0 ? a.edge : ud[j0 * ks], l1 = j1 < 0 ? a.edge : ud[j1 * ks];
     b.d0 = a.min_d + softplus64(l0);
     b.d1 = a.min_d + softplus64(l1);
     BinGradT<double> bg;
@@ -212,25 +256,25 @@ __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs6
     for (int k = 0; k < K; ++k) {
       const double gWk = cx * ((k < bin ? gXl : 0.0) + (k < bin + 1 ? gXr : 0.0));
       const double gHk = cy * ((k < bin ? gYl : 0.0) + (k < bin + 1 ? gYr : 0.0));
-      guw[k] = a.wh_scale * pw[k] * (gWk - dotw);
-      guh[k] = a.wh_scale * ph[k] * (gHk - doth);
+      guw[k * ks] = a.wh_scale * pw[k] * (gWk - dotw);
+      guh[k * ks] = a.wh_scale * ph[k] * (gHk - doth);
     }
     // derivative logits: d softplus / dv = sigmoid(v) (1 above the threshold 20); circular with one bin: both knots
     // share logit 0 and the two contributions add
     double gd0 = j0 < 0 ? 0.0 : bg.gd0 * (l0 > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-l0)));
     double gd1 = j1 < 0 ? 0.0 : bg.gd1 * (l1 > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-l1)));
     if (j0 == j1) { gd0 += gd1; gd1 = 0.0; }
-    for (int k = 0; k < nd; ++k) gud[k] = k == j0 ? gd0 : (k == j1 ? gd1 : 0.0);
+    for (int k = 0; k < nd; ++k) gud[k * ks] = k == j0 ? gd0 : (k == j1 ? gd1 : 0.0);
   }
 }
 
-template <bool INV>
+template <bool INV, bool STRIDED>
 static void launch_bwd64(const Rqs64BwdArgs& g, dim3 grid, hipStream_t st) {
   switch (g.f.K) {
-    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<8, INV>), grid, dim3(256), 0, st, g); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<10, INV>), grid, dim3(256), 0, st, g); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<16, INV>), grid, dim3(256), 0, st, g); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<0, INV>), grid, dim3(256), 0, st, g); break;
+    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<8, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
+    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<10, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
+    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<16, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
+    default: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<0, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
   }
 }
 
@@ -238,38 +282,27 @@ static void launch_bwd64(const Rqs64BwdArgs& g, dim3 grid, hipStream_t st) {
 
 using namespace vcnf;
 
-extern "C" int vcnf_rqs_elementwise_f64(const double* x, const double* uw, const double* uh, const double* ud,
-                                        int64_t ld_w, int64_t ld_h, int64_t ld_d,
-                                        double* y, double* logabsdet, int64_t n,
-                                        const vcnf_rqs_cfg_f64* cfg, int inverse, int32_t* bad_disc, void* stream) {
+// constants of the spline, the same for every entry point
+static void fill64(Rqs64Args& a, const vcnf_rqs_cfg_f64* cfg, int inverse) {
+  a.K = cfg->num_bins; a.tails = cfg->tails; a.inverse = inverse ? 1 : 0;
+  a.left = cfg->left; a.right = cfg->right; a.bottom = cfg->bottom; a.top = cfg->top;
+  a.min_w = cfg->min_bin_width; a.min_h = cfg->min_bin_height; a.min_d = cfg->min_derivative;
+  a.wh_scale = cfg->wh_scale;
+  a.edge = log(exp(1.0 - cfg->min_derivative) - 1.0);
+  a.inner = 1; a.ks = 1; a.period = 0;
+}
+
+static int check_fwd64(const vcnf_rqs_cfg_f64* cfg, int64_t n) {
   if (!cfg) return VCNF_ERR_NULL;
   if (n < 0 || cfg->num_bins < 1 || cfg->num_bins > kMaxBins64) return VCNF_ERR_SHAPE;
   if (cfg->tails < VCNF_TAILS_NONE || cfg->tails > VCNF_TAILS_CIRCULAR) return VCNF_ERR_UNSUPPORTED;
   const int K = cfg->num_bins;
   if (cfg->min_bin_width * K > 1.0 || cfg->min_bin_height * K > 1.0) return VCNF_ERR_VALUE;
-  if (n == 0) return VCNF_OK;
-  if (!x || !uw || !uh || !ud || !y || !logabsdet) return VCNF_ERR_NULL;
-  Rqs64Args a;
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
-  a.y = y; a.lad = logabsdet; a.n = n; a.K = K; a.tails = cfg->tails; a.inverse = inverse ? 1 : 0;
-  a.left = cfg->left; a.right = cfg->right; a.bottom = cfg->bottom; a.top = cfg->top;
-  a.min_w = cfg->min_bin_width; a.min_h = cfg->min_bin_height; a.min_d = cfg->min_derivative;
-  a.wh_scale = cfg->wh_scale;
-  a.edge = log(exp(1.0 - cfg->min_derivative) - 1.0);
-  a.bad = bad_disc;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL(rqs_elementwise_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return VCNF_OK;
 }
 
-
-extern "C" int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, const double* uh, const double* ud,
-                                            int64_t ld_w, int64_t ld_h, int64_t ld_d,
-                                            const double* g_y, const double* g_logabsdet,
-                                            double* g_x, double* g_uw, double* g_uh, double* g_ud, int64_t n,
-                                            const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream) {
-  // validation as bwd_common / vcnf_rqs_elementwise_bwd_f32 (rqs_backward.hip)
+// validation as bwd_common / vcnf_rqs_elementwise_bwd_f32 (rqs_backward.hip)
+static int check_bwd64(const vcnf_rqs_cfg_f64* cfg, int64_t n) {
   if (!cfg) return VCNF_ERR_NULL;
   const int K = cfg->num_bins;
   if (K < 1 || K > kMaxBins64) return VCNF_ERR_SHAPE;
@@ -277,23 +310,102 @@ extern "C" int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, c
     return VCNF_ERR_UNSUPPORTED;
   if (cfg->tails == VCNF_TAILS_LINEAR && K < 2) return VCNF_ERR_SHAPE;
   if (cfg->min_bin_width * K > 1.0 || cfg->min_bin_height * K > 1.0) return VCNF_ERR_VALUE;
-  if (n < 0 || ld_w < 0 || ld_h < 0 || ld_d < 0) return VCNF_ERR_SHAPE;
+  if (n < 0) return VCNF_ERR_SHAPE;
+  return VCNF_OK;
+}
+
+static int n_deriv64(const vcnf_rqs_cfg_f64* cfg) {
+  const int K = cfg->num_bins;
+  return cfg->tails == VCNF_TAILS_LINEAR ? K - 1 : cfg->tails == VCNF_TAILS_CIRCULAR ? K : K + 1;
+}
+
+static dim3 grid64(int64_t n) {
+  long long blocks = (n + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  return dim3((unsigned)blocks);
+}
+
+static int launched64() { return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH; }
+
+extern "C" int vcnf_rqs_elementwise_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                        int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                        double* y, double* logabsdet, int64_t n,
+                                        const vcnf_rqs_cfg_f64* cfg, int inverse, int32_t* bad_disc, void* stream) {
+  const int rc = check_fwd64(cfg, n);
+  if (rc != VCNF_OK) return rc;
+  if (n == 0) return VCNF_OK;
+  if (!x || !uw || !uh || !ud || !y || !logabsdet) return VCNF_ERR_NULL;
+  Rqs64Args a;
+  fill64(a, cfg, inverse);
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
+  a.y = y; a.lad = logabsdet; a.n = n; a.bad = bad_disc;
+  launch_fwd64<false>(a, grid64(n), (hipStream_t)stream);
+  return launched64();
+}
+
+extern "C" int vcnf_rqs_elementwise_strided_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                                int64_t row_w, int64_t row_h, int64_t row_d, int64_t inner,
+                                                int64_t k_stride, int64_t period,
+                                                double* y, double* logabsdet, int64_t n,
+                                                const vcnf_rqs_cfg_f64* cfg, int inverse, int32_t* bad_disc,
+                                                void* stream) {
+  const int rc = check_fwd64(cfg, n);
+  if (rc != VCNF_OK) return rc;
+  if (row_w < 0 || row_h < 0 || row_d < 0 || inner < 1 || k_stride < 1 || period < 0) return VCNF_ERR_SHAPE;
+  if (n == 0) return VCNF_OK;
+  if (!x || !uw || !uh || !ud || !y || !logabsdet) return VCNF_ERR_NULL;
+  Rqs64Args a;
+  fill64(a, cfg, inverse);
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = row_w; a.ld_h = row_h; a.ld_d = row_d;
+  a.inner = inner; a.ks = k_stride; a.period = period;
+  a.y = y; a.lad = logabsdet; a.n = n; a.bad = bad_disc;
+  launch_fwd64<true>(a, grid64(n), (hipStream_t)stream);
+  return launched64();
+}
+
+extern "C" int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                            int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                            const double* g_y, const double* g_logabsdet,
+                                            double* g_x, double* g_uw, double* g_uh, double* g_ud, int64_t n,
+                                            const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream) {
+  const int rc = check_bwd64(cfg, n);
+  if (rc != VCNF_OK) return rc;
+  if (ld_w < 0 || ld_h < 0 || ld_d < 0) return VCNF_ERR_SHAPE;
   if (n == 0) return VCNF_OK;
   if (!x || !uw || !uh || !ud || !g_y || !g_logabsdet || !g_x || !g_uw || !g_uh || !g_ud) return VCNF_ERR_NULL;
   Rqs64BwdArgs g;
   Rqs64Args& a = g.f;
+  fill64(a, cfg, inverse);
   a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
-  a.y = nullptr; a.lad = nullptr; a.n = n; a.K = K; a.tails = cfg->tails; a.inverse = inverse ? 1 : 0;
-  a.left = cfg->left; a.right = cfg->right; a.bottom = cfg->bottom; a.top = cfg->top;
-  a.min_w = cfg->min_bin_width; a.min_h = cfg->min_bin_height; a.min_d = cfg->min_derivative;
-  a.wh_scale = cfg->wh_scale;
-  a.edge = log(exp(1.0 - cfg->min_derivative) - 1.0);
-  a.bad = nullptr;
+  a.y = nullptr; a.lad = nullptr; a.n = n; a.bad = nullptr;
   g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x; g.guw = g_uw; g.guh = g_uh; g.gud = g_ud;
-  g.nd = cfg->tails == VCNF_TAILS_LINEAR ? K - 1 : cfg->tails == VCNF_TAILS_CIRCULAR ? K : K + 1;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  if (inverse) launch_bwd64<true>(g, dim3((unsigned)blocks), (hipStream_t)stream);
-  else launch_bwd64<false>(g, dim3((unsigned)blocks), (hipStream_t)stream);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  g.nd = n_deriv64(cfg); g.lad_div = 1;
+  if (inverse) launch_bwd64<true, false>(g, grid64(n), (hipStream_t)stream);
+  else launch_bwd64<false, false>(g, grid64(n), (hipStream_t)stream);
+  return launched64();
+}
+
+extern "C" int vcnf_rqs_packed_bwd_f64(const double* x, const double* params, int64_t inner, int64_t lad_div,
+                                       const double* g_y, const double* g_logabsdet,
+                                       double* g_x, double* g_params, int64_t n,
+                                       const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream) {
+  const int rc = check_bwd64(cfg, n);
+  if (rc != VCNF_OK) return rc;
+  if (inner < 1 || lad_div < 1) return VCNF_ERR_SHAPE;
+  if (n == 0) return VCNF_OK;
+  if (!x || !params || !g_y || !g_logabsdet || !g_x || !g_params) return VCNF_ERR_NULL;
+  Rqs64BwdArgs g;
+  Rqs64Args& a = g.f;
+  fill64(a, cfg, inverse);
+  const long long K = cfg->num_bins, nd = n_deriv64(cfg), P = 2 * K + nd;
+  // params / g_params [rows, P, inner]: logit k of element i = row * P * inner + s + k * inner
+  a.x = x; a.uw = params; a.uh = params + K * inner; a.ud = params + 2 * K * inner;
+  a.ld_w = a.ld_h = a.ld_d = P * inner; a.inner = inner; a.ks = inner; a.period = 0;
+  a.y = nullptr; a.lad = nullptr; a.n = n; a.bad = nullptr;
+  g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x;
+  g.guw = g_params; g.guh = g_params + K * inner; g.gud = g_params + 2 * K * inner;
+  g.nd = (int)nd; g.lad_div = lad_div;
+  if (inverse) launch_bwd64<true, true>(g, grid64(n), (hipStream_t)stream);
+  else launch_bwd64<false, true>(g, grid64(n), (hipStream_t)stream);
+  return launched64();
 }
