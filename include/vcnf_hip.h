@@ -91,6 +91,37 @@ int vcnf_rqs_elementwise_strided_f32(const float* x, const float* uw, const floa
                                      const vcnf_rqs_cfg* cfg, int inverse, int32_t* bad_discriminant,
                                      void* stream);
 
+/* Interval limits of the functional spline given per element (splines.py:99-102, tensor `left / right / bottom /
+ * top`).  Limit j (0 left, 1 right, 2 bottom, 3 top) of element i is lim_j[(i / inner[j]) % period[j]]: a
+ * full-shape tensor is period = n, inner = 1; a trailing-shape one ([D] against [B, D]) period = D, inner = 1; a
+ * leading one ([B, 1] against [B, D]) period = B, inner = D; a 0-dim one period = inner = 1.  period, inner >= 1. */
+typedef struct vcnf_rqs_limit_bcast {
+  int64_t period[4];
+  int64_t inner[4];
+} vcnf_rqs_limit_bcast;
+
+/* vcnf_rqs_elementwise_f32 with per-element limits: the knots of element i are lo + (hi - lo) * c_k with
+ * hi - lo evaluated in the working precision (the reference's tensor branch).  cfg->tails must be
+ * VCNF_TAILS_NONE (K + 1 derivative logits; the limits in cfg are ignored); inputs outside their interval are
+ * evaluated in the nearest edge bin.  K <= 64. */
+int vcnf_rqs_elementwise_limits_f32(const float* x, const float* uw, const float* uh, const float* ud,
+                                    int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                    const float* left, const float* right, const float* bottom, const float* top,
+                                    const vcnf_rqs_limit_bcast* bcast, float* y, float* logabsdet, int64_t n,
+                                    const vcnf_rqs_cfg* cfg, int inverse, int32_t* bad_disc, void* stream);
+
+/* VJP of vcnf_rqs_elementwise_limits_f32: the outputs of vcnf_rqs_elementwise_bwd_f32 (dense gradient rows) plus the
+ * PER-ELEMENT gradients g_left[n], g_right[n], g_bottom[n], g_top[n] of the limits (the caller reduces them to the
+ * limits' own shapes).  A NULL limit gradient is not computed.  K <= 64. */
+int vcnf_rqs_elementwise_limits_bwd_f32(const float* x, const float* uw, const float* uh, const float* ud,
+                                        int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                        const float* left, const float* right, const float* bottom, const float* top,
+                                        const vcnf_rqs_limit_bcast* bcast,
+                                        const float* g_y, const float* g_logabsdet,
+                                        float* g_x, float* g_uw, float* g_uh, float* g_ud,
+                                        float* g_left, float* g_right, float* g_bottom, float* g_top, int64_t n,
+                                        const vcnf_rqs_cfg* cfg, int inverse, void* stream);
+
 /* Whole AffineCouplingBlock on x[B, features] in one launch when the conditioner is an MLP with two
  * hidden layers of equal width: Linear(c_in, hidden), LeakyReLU, Linear(hidden, hidden), LeakyReLU,
  * Linear(hidden, n_out), n_out = 2*d_t (interleaved shift, scale) or d_t (scale map NONE).
@@ -594,6 +625,21 @@ int vcnf_rqs_packed_bwd_f64(const double* x, const double* params, int64_t inner
                             const double* g_y, const double* g_logabsdet,
                             double* g_x, double* g_params, int64_t n,
                             const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream);
+/* vcnf_rqs_elementwise_limits_f32 / _bwd_f32 in double: per element the bin and the arithmetic of
+ * vcnf_rqs_elementwise_f64 / vcnf_rqs_elementwise_bwd_f64 with that element's limits. */
+int vcnf_rqs_elementwise_limits_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                    int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                    const double* left, const double* right, const double* bottom, const double* top,
+                                    const vcnf_rqs_limit_bcast* bcast, double* y, double* logabsdet, int64_t n,
+                                    const vcnf_rqs_cfg_f64* cfg, int inverse, int32_t* bad_disc, void* stream);
+int vcnf_rqs_elementwise_limits_bwd_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                        int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                        const double* left, const double* right, const double* bottom,
+                                        const double* top, const vcnf_rqs_limit_bcast* bcast,
+                                        const double* g_y, const double* g_logabsdet,
+                                        double* g_x, double* g_uw, double* g_uh, double* g_ud,
+                                        double* g_left, double* g_right, double* g_bottom, double* g_top, int64_t n,
+                                        const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream);
 /* vcnf_maf_affine_f32 in double; params must be 16-byte aligned (one double2 load per feature). */
 int vcnf_maf_affine_f64(const double* x, const double* params, double* out, double* logdet, int64_t batch,
                         int32_t features, int inverse, int ld_mode, double ld_sign, void* stream);

@@ -47,6 +47,11 @@ class RqsCfg64(ctypes.Structure):
                 ("min_bin_height", _F64), ("min_derivative", _F64), ("wh_scale", _F64)]
 
 
+class RqsLimitBcast(ctypes.Structure):
+    """struct vcnf_rqs_limit_bcast: limit j of element i is lim_j[(i // inner[j]) % period[j]]"""
+    _fields_ = [("period", _I64 * 4), ("inner", _I64 * 4)]
+
+
 class RqsStackLayer(ctypes.Structure):
     """struct vcnf_rqs_stack_layer"""
     _fields_ = [("transform_idx", ctypes.c_void_p), ("identity_idx", ctypes.c_void_p), ("wpack", ctypes.c_void_p),
@@ -158,6 +163,16 @@ PROTOTYPES = {
     "vcnf_merge_columns_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
     "vcnf_diag_gaussian_log_prob_f64": ([_P, _P, _P, _F64, _P, _I64, _I32, _INT, _F64, _P], _INT),
     "vcnf_diag_gaussian_sample_f64": ([_P, _P, _P, _F64, _P, _P, _I64, _I32, _P], _INT),
+    "vcnf_rqs_elementwise_limits_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, ctypes.POINTER(RqsLimitBcast),
+                                         _P, _P, _I64, ctypes.POINTER(RqsCfg), _INT, _P, _P], _INT),
+    "vcnf_rqs_elementwise_limits_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, ctypes.POINTER(RqsLimitBcast),
+                                         _P, _P, _I64, ctypes.POINTER(RqsCfg64), _INT, _P, _P], _INT),
+    "vcnf_rqs_elementwise_limits_bwd_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
+                                             ctypes.POINTER(RqsLimitBcast), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             _I64, ctypes.POINTER(RqsCfg), _INT, _P], _INT),
+    "vcnf_rqs_elementwise_limits_bwd_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
+                                             ctypes.POINTER(RqsLimitBcast), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                             _I64, ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
 }
 
 _LIB = None
@@ -529,6 +544,117 @@ def rqs_elementwise_bwd(x, uw, uh, ud, gy, glad, cfg, inverse):
                 xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)), _stream())
     _check(st, "vcnf_rqs_elementwise_bwd" + _sfx(xf))
     return gx.view(shape), gw.view(shape + (k,)), gh.view(shape + (k,)), gd.view(shape + (nd,))
+
+
+LIMIT_NAMES = ("left", "right", "bottom", "top")
+
+
+def limit_layout(lim, shape):
+    """(flat tensor, period, inner) of one interval limit broadcast against inputs of ``shape``: element i reads
+    flat[(i // inner) % period].  Limits whose non-unit dimensions are one contiguous run of the inputs' dimensions
+    (full shape, trailing shape, [B, 1], [C, 1, 1], 0-dim) are read in place; any other broadcastable shape is
+    expanded to the full shape first."""
+    shape = tuple(shape)
+    try:
+        ok = tuple(torch.broadcast_shapes(tuple(lim.shape), shape)) == shape
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise VcnfError("interval limit of shape %s does not broadcast to the inputs' shape %s" % (
+            tuple(lim.shape), shape))
+    ls = (1,) * (len(shape) - lim.dim()) + tuple(lim.shape)
+    big = [j for j, s in enumerate(ls) if s != 1]
+    if not big:
+        return lim.reshape(1), 1, 1
+    a, b = big[0], big[-1] + 1
+    if all(ls[j] == shape[j] for j in range(a, b)):
+        return lim.contiguous().reshape(-1), max(1, math.prod(shape[a:b])), max(1, math.prod(shape[b:]))
+    return lim.expand(shape).contiguous().reshape(-1), max(1, math.prod(shape)), 1
+
+
+def _limit_layouts(limits, x, allow_grad):
+    """Checks of the four limit tensors against the inputs ``x`` and their layouts.  Same dtype as the inputs; on the
+    inputs' device, except 0-dim host tensors (torch mixes those with device tensors), which are copied over."""
+    lims = []
+    for name, t in zip(LIMIT_NAMES, limits):
+        if not torch.is_tensor(t):
+            raise TypeError("interval limit %s is not a tensor" % name)
+        if t.dtype != x.dtype:
+            raise VcnfError("interval limit %s is %s, the inputs are %s" % (name, t.dtype, x.dtype))
+        if not t.is_cuda:
+            if t.dim() != 0:
+                raise VcnfError("vcnf_amd computes on MI355X only (interval limit %s on %s); there is no CPU path"
+                                % (name, t.device))
+            t = t.to(x.device)
+        lims.append(t)
+    require_device(x, *lims, allow_grad=allow_grad, f64=True)
+    return [limit_layout(t.detach(), x.shape) for t in lims]
+
+
+def _limits_operands(x, uw, uh, ud, cfg, what):
+    if cfg.tails != TAILS_NONE:
+        raise VcnfError("%s: tensor interval limits belong to the spline without tails" % what)
+    k = cfg.num_bins
+    shape = tuple(x.shape)
+    if tuple(uw.shape) != shape + (k,) or tuple(uh.shape) != shape + (k,) or tuple(ud.shape) != shape + (k + 1,):
+        raise VcnfError("spline parameter shapes %s %s %s do not match inputs %s with K=%d" % (
+            tuple(uw.shape), tuple(uh.shape), tuple(ud.shape), shape, k))
+    if not all(t.dtype == x.dtype for t in (uw, uh, ud)):
+        raise VcnfError("%s: inputs and logits must share one dtype" % what)
+    return (x.detach().reshape(-1).contiguous(), uw.detach().reshape(-1, k).contiguous(),
+            uh.detach().reshape(-1, k).contiguous(), ud.detach().reshape(-1, k + 1).contiguous())
+
+
+def _bcast(lay):
+    return RqsLimitBcast((_I64 * 4)(*[l[1] for l in lay]), (_I64 * 4)(*[l[2] for l in lay]))
+
+
+def rqs_elementwise_limits(x, uw, uh, ud, limits, cfg, inverse, allow_grad=False):
+    """rqs_elementwise with tensor interval limits ``limits`` = (left, right, bottom, top), each broadcastable to the
+    shape of x (splines.py:99-102; no tails, K+1 derivative logits).  fp32 or fp64 (every tensor)."""
+    dev = require_device(x, uw, uh, ud, allow_grad=allow_grad, f64=True)
+    xf, w2, h2, d2 = _limits_operands(x, uw, uh, ud, cfg, "rqs_elementwise_limits")
+    lay = _limit_layouts(limits, x, allow_grad)
+    k = cfg.num_bins
+    y, lad = torch.empty_like(xf), torch.empty_like(xf)
+    f64 = xf.dtype == torch.float64
+    bc = _bcast(lay)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), "vcnf_rqs_elementwise_limits" + _sfx(xf))(
+            _ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), k, k, k + 1, *[_ptr(l[0]) for l in lay], ctypes.byref(bc),
+            _ptr(y), _ptr(lad), xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)),
+            _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
+    _check(st, "vcnf_rqs_elementwise_limits" + _sfx(xf))
+    return y.view(x.shape), lad.view(x.shape)
+
+
+def rqs_elementwise_limits_bwd(x, uw, uh, ud, limits, gy, glad, cfg, inverse, want=(True, True, True, True)):
+    """VJP of rqs_elementwise_limits: (g_x, g_uw, g_uh, g_ud, [g_left, g_right, g_bottom, g_top]).  The kernel writes
+    each limit's gradient per element; it is reduced to the limit's own shape with sum_to_size (deterministic, no
+    atomics).  ``want[j]`` false: that limit's gradient is not computed (None)."""
+    dev = require_device(x, uw, uh, ud, gy, glad, allow_grad=True, f64=True)
+    if gy.dtype != x.dtype or glad.dtype != x.dtype:
+        raise VcnfError("rqs_elementwise_limits_bwd: inputs and upstream gradients must share one dtype")
+    xf, w2, h2, d2 = _limits_operands(x, uw, uh, ud, cfg, "rqs_elementwise_limits_bwd")
+    lay = _limit_layouts(limits, x, True)
+    k = cfg.num_bins
+    shape = x.shape
+    gyf, glf = gy.detach().reshape(-1).contiguous(), glad.detach().reshape(-1).contiguous()
+    gx = torch.empty_like(xf)
+    gw, gh, gd = torch.empty_like(w2), torch.empty_like(h2), torch.empty_like(d2)
+    glim = [torch.empty_like(xf) if w else None for w in want]
+    f64 = xf.dtype == torch.float64
+    bc = _bcast(lay)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), "vcnf_rqs_elementwise_limits_bwd" + _sfx(xf))(
+            _ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), k, k, k + 1, *[_ptr(l[0]) for l in lay], ctypes.byref(bc),
+            _ptr(gyf), _ptr(glf), _ptr(gx), _ptr(gw), _ptr(gh), _ptr(gd), *[_ptr(g) for g in glim],
+            xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)), _stream())
+    _check(st, "vcnf_rqs_elementwise_limits_bwd" + _sfx(xf))
+    out = []
+    for g, t in zip(glim, limits):
+        out.append(None if g is None else g.view(shape).sum_to_size(t.shape).to(t.device))
+    return gx.view(shape), gw.view(shape + (k,)), gh.view(shape + (k,)), gd.view(shape + (k + 1,)), out
 
 
 def rqs_coupling(x, params, tf_idx, id_idx, shared, cfg, inverse, logdet=None, sign=1.0):

@@ -37,6 +37,34 @@ def rqs_spline(x, uw, uh, ud, cfg, inverse=False):
                              ud.expand(x.shape + ud.shape[-1:]), cfg, inverse)
 
 
+class RqsLimitsFn(torch.autograd.Function):
+    """(y, logabsdet) = spline(x; uw, uh, ud) on per-element intervals [left, right] -> [bottom, top] (tensor limits,
+    splines.py:99-102), elementwise: forward vcnf_rqs_elementwise_limits_*, backward vcnf_rqs_elementwise_limits_bwd_*,
+    which also returns the gradients of the four limit tensors (None for a limit that does not require grad)."""
+
+    @staticmethod
+    def forward(ctx, x, uw, uh, ud, left, right, bottom, top, cfg, inverse):
+        with torch.no_grad():
+            y, lad = _lib.rqs_elementwise_limits(x, uw, uh, ud, (left, right, bottom, top), cfg, inverse,
+                                                 allow_grad=True)
+        ctx.save_for_backward(x, uw, uh, ud, left, right, bottom, top)
+        ctx.cfg, ctx.inverse = cfg, inverse
+        return y, lad
+
+    @staticmethod
+    def backward(ctx, gy, glad):
+        x, uw, uh, ud, *limits = ctx.saved_tensors
+        gx, gw, gh, gd, glim = _lib.rqs_elementwise_limits_bwd(x, uw, uh, ud, limits, gy.contiguous(),
+                                                               glad.contiguous(), ctx.cfg, ctx.inverse,
+                                                               want=ctx.needs_input_grad[4:8])
+        return (gx, gw, gh, gd, *glim, None, None)
+
+
+def rqs_spline_limits(x, uw, uh, ud, left, right, bottom, top, cfg, inverse=False):
+    return RqsLimitsFn.apply(x, uw.expand(x.shape + uw.shape[-1:]), uh.expand(x.shape + uh.shape[-1:]),
+                             ud.expand(x.shape + ud.shape[-1:]), left, right, bottom, top, cfg, inverse)
+
+
 _ARANGE32 = {}
 
 

@@ -35,6 +35,8 @@ struct BwdArgs {
   long long n;
   int nd;                          // derivative logits per element
   RqsConst c;
+  LimitsT<float> lim;              // LIM kernels only: per-element interval limits ...
+  float* glim[4];                  // ... and their per-element gradients (NULL: not wanted)
 };
 
 // gradient of softplus (beta 1, threshold 20)
@@ -71,11 +73,12 @@ __device__ __forceinline__ BinGrad bin_inverse_vjp(float u, float v0, const RqsB
 // rows - one contiguous block - travel through LDS with coalesced accesses in both directions: the
 // logits are staged, every thread reads and then overwrites ITS row in LDS (odd P: conflict free), and
 // the block of gradients leaves with coalesced stores.
-template <int KT, bool INV, bool PACKED>
+// LIM (dense rows only): the interval of element i comes from a.lim, the logit gradients use its span, and the
+// gradients of the four limits are written per element.
+template <int KT, bool INV, bool PACKED, bool LIM = false>
 __global__ __launch_bounds__(kBwdBlock) void rqs_elementwise_bwd_kernel(const BwdArgs a) {
   extern __shared__ float stage[];                 // PACKED: [kBwdBlock][P]
-  const RqsConst& c = a.c;
-  const int K = KT > 0 ? KT : c.K;
+  const int K = KT > 0 ? KT : a.c.K;
   constexpr int KA = KT > 0 ? KT : kBwdMaxK;
   const int P = 2 * K + a.nd;
   for (long long base = (long long)blockIdx.x * kBwdBlock; base < a.n; base += (long long)gridDim.x * kBwdBlock) {
@@ -89,6 +92,19 @@ __global__ __launch_bounds__(kBwdBlock) void rqs_elementwise_bwd_kernel(const Bw
       __syncthreads();
     }
     if (active) do {
+    RqsConst ce;
+    if (LIM) {
+      float v[4];
+      a.lim.load(i, v);
+      ce = a.c;
+      ce.lo_x = v[0];
+      ce.hi_x = v[1];
+      ce.span_x = v[1] - v[0];                       // in fp32, as the forward kernel
+      ce.lo_y = v[2];
+      ce.hi_y = v[3];
+      ce.span_y = v[3] - v[2];
+    }
+    const RqsConst& c = LIM ? ce : a.c;
     const float x = a.x[i];
     const float gy = a.gy[i], gl = a.glad[a.lad_div == 1 ? i : i / a.lad_div];
     const long long outer = a.inner == 1 ? i : i / a.inner, inn = a.inner == 1 ? 0 : i - outer * a.inner;
@@ -124,16 +140,22 @@ __global__ __launch_bounds__(kBwdBlock) void rqs_elementwise_bwd_kernel(const Bw
     RqsBin b;
     int bin = 0;
     b.xl = xl; b.yl = yl; b.w = 1.f; b.h = 1.f;
+    float fx0 = 0.f, fx1 = 1.f, fy0 = 0.f, fy1 = 1.f;    // LIM: cumulative fractions of the bin's two knots
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       pw[k] *= rsw;
       ph[k] *= rsh;
+      const float cw0 = cw, ch0 = ch;
       cw += fmaf(pw[k], c.free_w, c.min_w);
       ch += fmaf(ph[k], c.free_h, c.min_h);
       const float xr = (k == K - 1) ? c.hi_x : fmaf(c.span_x, cw, c.lo_x);
       const float yr = (k == K - 1) ? c.hi_y : fmaf(c.span_y, ch, c.lo_y);
       const bool take = (k == 0) || (INV ? (x >= yl) : (x >= xl));
       if (take) { bin = k; b.xl = xl; b.w = xr - xl; b.yl = yl; b.h = yr - yl; }
+      if (LIM && take) {
+        fx0 = cw0; fx1 = (k == K - 1) ? 1.f : cw;
+        fy0 = ch0; fy1 = (k == K - 1) ? 1.f : ch;
+      }
       xl = xr; yl = yr;
     }
     // knot derivatives of the bin: logit index (or boundary constant)
@@ -181,6 +203,14 @@ __global__ __launch_bounds__(kBwdBlock) void rqs_elementwise_bwd_kernel(const Bw
     for (int k = 0; k < a.nd; ++k) gud[k * ks] = 0.f;
     if (has0) gud[i0 * ks] += g.gd0 * softplus_grad(l0);
     if (has1) gud[i1 * ks] += g.gd1 * softplus_grad(l1);        // circular, one bin: both knots share logit 0
+    if (LIM) {
+      float gv[4];
+      limit_vjp<float>(g.gxl - g.gw, g.gw, fx0, fx1, gv[0], gv[1]);
+      limit_vjp<float>(g.gyl - g.gh, g.gh, fy0, fy1, gv[2], gv[3]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (a.glim[j]) a.glim[j][i] = gv[j];
+    }
     } while (0);
     if (PACKED) {
       const long long lim = (a.n - base < kBwdBlock ? a.n - base : kBwdBlock) * P;
@@ -346,15 +376,15 @@ static int launch_shared_bwd(const SharedBwdArgs& a, dim3 grid, hipStream_t st) 
   return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
 }
 
-template <bool INV, bool PACKED>
+template <bool INV, bool PACKED, bool LIM = false>
 static void launch_bwd(const BwdArgs& a, dim3 grid, hipStream_t st) {
   const size_t lds = PACKED ? (size_t)kBwdBlock * (2 * a.c.K + a.nd) * sizeof(float) : 0;
   switch (a.c.K) {
-    case 4: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<4, INV, PACKED>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<8, INV, PACKED>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<10, INV, PACKED>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<16, INV, PACKED>), grid, dim3(kBwdBlock), lds, st, a); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<0, INV, PACKED>), grid, dim3(kBwdBlock), lds, st, a); break;
+    case 4: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<4, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
+    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<8, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
+    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<10, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
+    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<16, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
+    default: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<0, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
   }
 }
 
@@ -421,6 +451,36 @@ extern "C" int vcnf_rqs_elementwise_bwd_f32(const float* x, const float* uw, con
   a.gx = g_x; a.guw = g_uw; a.guh = g_uh; a.gud = g_ud;
   a.grow_w = a.c.K; a.grow_h = a.c.K; a.grow_d = a.nd;
   return bwd_launch(a, inverse, stream);
+}
+
+extern "C" int vcnf_rqs_elementwise_limits_bwd_f32(const float* x, const float* uw, const float* uh, const float* ud,
+                                                   int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                                   const float* left, const float* right, const float* bottom,
+                                                   const float* top, const vcnf_rqs_limit_bcast* bcast,
+                                                   const float* g_y, const float* g_logabsdet,
+                                                   float* g_x, float* g_uw, float* g_uh, float* g_ud,
+                                                   float* g_left, float* g_right, float* g_bottom, float* g_top,
+                                                   int64_t n, const vcnf_rqs_cfg* cfg, int inverse, void* stream) {
+  const int vc = limits_validate(cfg, n, ld_w, ld_h, ld_d, bcast);
+  if (vc != VCNF_OK) return vc;
+  BwdArgs a;
+  const int rc = bwd_common(cfg, a, n);
+  if (rc != VCNF_OK) return rc;
+  if (n == 0) return VCNF_OK;
+  if (!x || !uw || !uh || !ud || !left || !right || !bottom || !top || !g_y || !g_logabsdet || !g_x || !g_uw ||
+      !g_uh || !g_ud)
+    return VCNF_ERR_NULL;
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.row_w = ld_w; a.row_h = ld_h; a.row_d = ld_d; a.inner = 1; a.ks = 1;
+  a.gy = g_y; a.glad = g_logabsdet; a.lad_div = 1;
+  a.gx = g_x; a.guw = g_uw; a.guh = g_uh; a.gud = g_ud;
+  a.grow_w = a.c.K; a.grow_h = a.c.K; a.grow_d = a.nd;
+  a.lim = make_limits(left, right, bottom, top, bcast, n);
+  a.glim[0] = g_left; a.glim[1] = g_right; a.glim[2] = g_bottom; a.glim[3] = g_top;
+  const long long blocks = (n + kBwdBlock - 1) / kBwdBlock;
+  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
+  if (inverse) launch_bwd<true, false, true>(a, grid, (hipStream_t)stream);
+  else launch_bwd<false, false, true>(a, grid, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
 }
 
 extern "C" int vcnf_rqs_packed_bwd_f32(const float* x, const float* params, int64_t inner, int64_t lad_div,

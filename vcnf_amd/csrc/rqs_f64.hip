@@ -26,6 +26,7 @@ struct Rqs64Args {
   double left, right, bottom, top, min_w, min_h, min_d, wh_scale, edge;
   int32_t* bad;
   long long inner, ks, period;     // strided addressing only (see rows64)
+  LimitsT<double> lim;             // LIM kernels only: per-element interval limits (left, right, bottom, top)
 };
 
 // Offsets of element i's logit rows.  Dense (vcnf_rqs_elementwise_f64): row i at i * ld, logit k at + k.  Strided
@@ -48,10 +49,11 @@ __device__ __forceinline__ Rows64 rows64(const Rqs64Args& a, long long i) {
 // of both kernels keep every array in registers); KT == 0: runtime K (their generic instances).
 
 // knots of one side: cum[0..K] from K logits lg[k * ks] (splines.py:109-119 / :123-133); ``prob`` (optional) receives
-// the softmax probabilities
+// the softmax probabilities, ``frac`` (optional) the cumulative fractions of the knots (0 and 1 at the ends)
 template <int KT>
 __device__ __forceinline__ void partition64(const double* lg, long long ks, int Kr, double scale, double lo, double hi,
-                                            double floor_, double* cum, double* prob = nullptr) {
+                                            double floor_, double* cum, double* prob = nullptr,
+                                            double* frac = nullptr) {
   const int K = KT > 0 ? KT : Kr;
   double m = -INFINITY;
   for (int k = 0; k < K; ++k) m = fmax(m, lg[k * ks] * scale);
@@ -64,8 +66,13 @@ __device__ __forceinline__ void partition64(const double* lg, long long ks, int 
     const double p = floor_ + (1.0 - floor_ * K) * (exp(lg[k * ks] * scale - m) / s);
     run += p;
     cum[k + 1] = (hi - lo) * run + lo;
+    if (frac) frac[k + 1] = run;
   }
   cum[K] = hi;
+  if (frac) {
+    frac[0] = 0.0;
+    frac[K] = 1.0;
+  }
 }
 
 // bin: number of knots <= value, last knot bumped by eps (splines.py:12-17), clamped to [0, K-1]
@@ -102,8 +109,9 @@ __device__ __forceinline__ void pick_bin64(const double* xk, const double* yk, i
 }
 
 // KT > 0: compile-time bin count, every array in registers (K = 8, 10, 16); KT == 0: any K up to 64 (runtime-indexed
-// arrays in scratch).  Both instances evaluate the same expressions in the same order.
-template <int KT, bool STRIDED>
+// arrays in scratch).  Both instances evaluate the same expressions in the same order.  LIM (dense rows, no tails): the
+// interval of element i comes from a.lim (tensor limits, splines.py:99-102).
+template <int KT, bool STRIDED, bool LIM = false>
 __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Args a) {
   constexpr int KA = KT > 0 ? KT : kMaxBins64;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long long)gridDim.x * blockDim.x) {
@@ -113,11 +121,14 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
       a.lad[i] = 0.0;
       continue;
     }
+    double lv[4] = {a.left, a.right, a.bottom, a.top};
+    if (LIM) a.lim.load(i, lv);
+    const double left = lv[0], right = lv[1], bottom = lv[2], top = lv[3];
     const int K = KT > 0 ? KT : a.K;
     const Rows64 rw = rows64<STRIDED>(a, i);
     double xk[KA + 1], yk[KA + 1];
-    partition64<KT>(a.uw + rw.w, rw.ks, K, a.wh_scale, a.left, a.right, a.min_w, xk);
-    partition64<KT>(a.uh + rw.h, rw.ks, K, a.wh_scale, a.bottom, a.top, a.min_h, yk);
+    partition64<KT>(a.uw + rw.w, rw.ks, K, a.wh_scale, left, right, a.min_w, xk);
+    partition64<KT>(a.uh + rw.h, rw.ks, K, a.wh_scale, bottom, top, a.min_h, yk);
     const int bin = a.inverse ? bin64<KT>(yk, K, x) : bin64<KT>(xk, K, x);
     const double* ud = a.ud + rw.d;
     auto dlogit = [&](int k) -> double {
@@ -160,13 +171,13 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
   }
 }
 
-template <bool STRIDED>
+template <bool STRIDED, bool LIM = false>
 static void launch_fwd64(const Rqs64Args& a, dim3 grid, hipStream_t st) {
   switch (a.K) {
-    case 8: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<8, STRIDED>), grid, dim3(256), 0, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<10, STRIDED>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<16, STRIDED>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<0, STRIDED>), grid, dim3(256), 0, st, a); break;
+    case 8: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<8, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
+    case 10: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<10, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<16, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<0, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
   }
 }
 
@@ -183,6 +194,7 @@ struct Rqs64BwdArgs {
   double *gx, *guw, *guh, *gud;    // dense: gradient rows of K, K, nd; strided: the layout of the logits (rows64)
   int nd;
   long long lad_div;               // strided: g_logabsdet read at i / lad_div (dense: at i)
+  double* glim[4];                 // LIM: per-element gradients of the limits (NULL: not wanted)
 };
 
 struct RqsBin64 {
@@ -193,7 +205,8 @@ struct RqsBin64 {
 // unrolled by the compiler: compile-time indices;
 // the bin's values are picked by comparison, never by a runtime index).  KT == 0 (any other K up to 64): the same
 // code with runtime-indexed arrays, which go to scratch.
-template <int KT, bool INV, bool STRIDED>
+// LIM (dense rows, no tails): per-element limits as in the forward kernel, plus their per-element gradients.
+template <int KT, bool INV, bool STRIDED, bool LIM = false>
 __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs64BwdArgs g) {
   const Rqs64Args& a = g.f;
   constexpr int KA = KT > 0 ? KT : kMaxBins64;
@@ -213,9 +226,14 @@ __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs6
       for (int k = 0; k < nd; ++k) gud[k * ks] = 0.0;
       continue;
     }
+    double lv[4] = {a.left, a.right, a.bottom, a.top};
+    if (LIM) a.lim.load(i, lv);
+    const double left = lv[0], right = lv[1], bottom = lv[2], top = lv[3];
     double xk[KA + 1], yk[KA + 1], pw[KA], ph[KA];
-    partition64<KT>(a.uw + rw.w, ks, K, a.wh_scale, a.left, a.right, a.min_w, xk, pw);
-    partition64<KT>(a.uh + rw.h, ks, K, a.wh_scale, a.bottom, a.top, a.min_h, yk, ph);
+    constexpr int KF = LIM ? KA + 1 : 1;
+    double fx[KF], fy[KF];                           // LIM: cumulative fractions of the knots
+    partition64<KT>(a.uw + rw.w, ks, K, a.wh_scale, left, right, a.min_w, xk, pw, LIM ? fx : nullptr);
+    partition64<KT>(a.uh + rw.h, ks, K, a.wh_scale, bottom, top, a.min_h, yk, ph, LIM ? fy : nullptr);
     const int bin = bin64<KT>(INV ? yk : xk, K, x);
     RqsBin64 b;
     double xr, yr;
@@ -247,7 +265,7 @@ __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs6
     // are constants.  dX_k / dW_j = span (1 - min K) for j < k.
     const double gXl = bin >= 1 ? bg.gxl - bg.gw : 0.0, gXr = bin + 1 <= K - 1 ? bg.gw : 0.0;
     const double gYl = bin >= 1 ? bg.gyl - bg.gh : 0.0, gYr = bin + 1 <= K - 1 ? bg.gh : 0.0;
-    const double cx = (a.right - a.left) * (1.0 - a.min_w * K), cy = (a.top - a.bottom) * (1.0 - a.min_h * K);
+    const double cx = (right - left) * (1.0 - a.min_w * K), cy = (top - bottom) * (1.0 - a.min_h * K);
     double dotw = 0.0, doth = 0.0;
     for (int k = 0; k < K; ++k) {
       dotw += pw[k] * (cx * ((k < bin ? gXl : 0.0) + (k < bin + 1 ? gXr : 0.0)));
@@ -265,16 +283,24 @@ __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs6
     double gd1 = j1 < 0 ? 0.0 : bg.gd1 * (l1 > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-l1)));
     if (j0 == j1) { gd0 += gd1; gd1 = 0.0; }
     for (int k = 0; k < nd; ++k) gud[k * ks] = k == j0 ? gd0 : (k == j1 ? gd1 : 0.0);
+    if (LIM) {
+      double fx0, fx1, fy0, fy1, gv[4];
+      pick_bin64<KT>(fx, fy, bin, K, fx0, fx1, fy0, fy1);
+      limit_vjp<double>(bg.gxl - bg.gw, bg.gw, fx0, fx1, gv[0], gv[1]);
+      limit_vjp<double>(bg.gyl - bg.gh, bg.gh, fy0, fy1, gv[2], gv[3]);
+      for (int j = 0; j < 4; ++j)
+        if (g.glim[j]) g.glim[j][i] = gv[j];
+    }
   }
 }
 
-template <bool INV, bool STRIDED>
+template <bool INV, bool STRIDED, bool LIM = false>
 static void launch_bwd64(const Rqs64BwdArgs& g, dim3 grid, hipStream_t st) {
   switch (g.f.K) {
-    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<8, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<10, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<16, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<0, INV, STRIDED>), grid, dim3(256), 0, st, g); break;
+    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<8, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
+    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<10, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
+    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<16, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
+    default: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<0, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
   }
 }
 
@@ -382,6 +408,54 @@ extern "C" int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, c
   g.nd = n_deriv64(cfg); g.lad_div = 1;
   if (inverse) launch_bwd64<true, false>(g, grid64(n), (hipStream_t)stream);
   else launch_bwd64<false, false>(g, grid64(n), (hipStream_t)stream);
+  return launched64();
+}
+
+extern "C" int vcnf_rqs_elementwise_limits_f64(const double* x, const double* uw, const double* uh, const double* ud,
+                                               int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                               const double* left, const double* right, const double* bottom,
+                                               const double* top, const vcnf_rqs_limit_bcast* bcast,
+                                               double* y, double* logabsdet, int64_t n,
+                                               const vcnf_rqs_cfg_f64* cfg, int inverse, int32_t* bad_disc,
+                                               void* stream) {
+  const int rc = limits_validate(cfg, n, ld_w, ld_h, ld_d, bcast);
+  if (rc != VCNF_OK) return rc;
+  if (n == 0) return VCNF_OK;
+  if (!x || !uw || !uh || !ud || !left || !right || !bottom || !top || !y || !logabsdet) return VCNF_ERR_NULL;
+  Rqs64Args a;
+  fill64(a, cfg, inverse);
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
+  a.y = y; a.lad = logabsdet; a.n = n; a.bad = bad_disc;
+  a.lim = make_limits(left, right, bottom, top, bcast, n);
+  launch_fwd64<false, true>(a, grid64(n), (hipStream_t)stream);
+  return launched64();
+}
+
+extern "C" int vcnf_rqs_elementwise_limits_bwd_f64(const double* x, const double* uw, const double* uh,
+                                                   const double* ud, int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                                   const double* left, const double* right, const double* bottom,
+                                                   const double* top, const vcnf_rqs_limit_bcast* bcast,
+                                                   const double* g_y, const double* g_logabsdet,
+                                                   double* g_x, double* g_uw, double* g_uh, double* g_ud,
+                                                   double* g_left, double* g_right, double* g_bottom, double* g_top,
+                                                   int64_t n, const vcnf_rqs_cfg_f64* cfg, int inverse, void* stream) {
+  const int rc = limits_validate(cfg, n, ld_w, ld_h, ld_d, bcast);
+  if (rc != VCNF_OK) return rc;
+  if (n == 0) return VCNF_OK;
+  if (!x || !uw || !uh || !ud || !left || !right || !bottom || !top || !g_y || !g_logabsdet || !g_x || !g_uw ||
+      !g_uh || !g_ud)
+    return VCNF_ERR_NULL;
+  Rqs64BwdArgs g;
+  Rqs64Args& a = g.f;
+  fill64(a, cfg, inverse);
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
+  a.y = nullptr; a.lad = nullptr; a.n = n; a.bad = nullptr;
+  a.lim = make_limits(left, right, bottom, top, bcast, n);
+  g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x; g.guw = g_uw; g.guh = g_uh; g.gud = g_ud;
+  g.nd = n_deriv64(cfg); g.lad_div = 1;
+  g.glim[0] = g_left; g.glim[1] = g_right; g.glim[2] = g_bottom; g.glim[3] = g_top;
+  if (inverse) launch_bwd64<true, false, true>(g, grid64(n), (hipStream_t)stream);
+  else launch_bwd64<false, false, true>(g, grid64(n), (hipStream_t)stream);
   return launched64();
 }
 

@@ -20,6 +20,7 @@
 #include "../../include/vcnf_hip.h"
 #include "rqs_math.hpp"
 #include "rqs_lean.hpp"
+#include "rqs_vjp.hpp"
 
 namespace vcnf {
 
@@ -361,6 +362,33 @@ __global__ __launch_bounds__(kBlock) void rqs_elementwise_kernel(const ElemArgs 
   if (INV && a.bad && bad) atomicAdd(a.bad, 1);
 }
 
+// The same spline with the interval read per element (tensor limits, splines.py:99-102): the six interval fields of
+// the constants are filled from the limit tensors, the span in fp32 as the reference's tensor branch computes it
+// ((hi - lo) * cum + lo, splines.py:116 / :130), then the same rqs_point.  NARROW (l.narrow, every size of a
+// realistic call): 32-bit limit addressing without the 64-bit division code in the loop.
+template <int KT, bool INV, bool NARROW>
+__global__ __launch_bounds__(kBlock) void rqs_elementwise_limits_kernel(const ElemArgs a, const LimitsT<float> l) {
+  const int K = KT > 0 ? KT : a.c.K;
+  bool bad = false;
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (long long)gridDim.x * kBlock) {
+    float v[4];
+    l.load_as<NARROW>(i, v);
+    RqsConst c = a.c;
+    c.lo_x = v[0];
+    c.hi_x = v[1];
+    c.span_x = v[1] - v[0];
+    c.lo_y = v[2];
+    c.hi_y = v[3];
+    c.span_y = v[3] - v[2];
+    SplitLogits p{a.uw + i * a.ld_w, a.uh + i * a.ld_h, a.ud + i * a.ld_d, K, a.c.wh_scale, a.c.edge_logit, a.c.tails};
+    float yv, lad;
+    rqs_point<KT, INV>(a.x[i], p, c, yv, lad, bad);
+    a.y[i] = yv;
+    a.lad[i] = lad;
+  }
+  if (INV && a.bad && bad) atomicAdd(a.bad, 1);
+}
+
 // General addressing of the per-element logit rows (images, batch-shared rows):
 //   r = period > 0 ? i % period : i;  outer = r / inner;  s = r % inner;
 //   logit k of element i at  base + outer * row + s + k * ks   (row per tensor: row_w, row_h, row_d).
@@ -689,6 +717,23 @@ static void launch_elem(const ElemArgs& a, int K, dim3 grid, hipStream_t st) {
   }
 }
 
+template <bool INV, bool NARROW>
+static void launch_elem_limits_as(const ElemArgs& a, const LimitsT<float>& l, int K, dim3 grid, hipStream_t st) {
+  switch (K) {
+    case 4: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<4, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
+    case 8: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<8, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
+    case 10: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<10, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
+    case 16: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<16, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
+    default: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<0, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
+  }
+}
+
+template <bool INV>
+static void launch_elem_limits(const ElemArgs& a, const LimitsT<float>& l, int K, dim3 grid, hipStream_t st) {
+  if (l.narrow) launch_elem_limits_as<INV, true>(a, l, K, grid, st);
+  else launch_elem_limits_as<INV, false>(a, l, K, grid, st);
+}
+
 constexpr size_t kLdsBudget = 60 * 1024;     // per workgroup; leaves >= 2 workgroups per CU
 constexpr size_t kTableBudget = 16 * 1024;   // knot tables of the shared spline; beyond: read logits directly
 
@@ -818,6 +863,31 @@ extern "C" int vcnf_rqs_elementwise_f32(const float* x, const float* uw, const f
   hipStream_t st = (hipStream_t)stream;
   if (inverse) launch_elem<true>(a, a.c.K, grid, st);
   else launch_elem<false>(a, a.c.K, grid, st);
+  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+}
+
+extern "C" int vcnf_rqs_elementwise_limits_f32(const float* x, const float* uw, const float* uh, const float* ud,
+                                               int64_t ld_w, int64_t ld_h, int64_t ld_d,
+                                               const float* left, const float* right, const float* bottom,
+                                               const float* top, const vcnf_rqs_limit_bcast* bcast,
+                                               float* y, float* logabsdet, int64_t n,
+                                               const vcnf_rqs_cfg* cfg, int inverse, int32_t* bad_disc, void* stream) {
+  const int vc = limits_validate(cfg, n, ld_w, ld_h, ld_d, bcast);
+  if (vc != VCNF_OK) return vc;
+  ElemArgs a;
+  int nd = 0;
+  const int rc = fill_const(cfg, a.c, nd);
+  if (rc != VCNF_OK) return rc;
+  if (n == 0) return VCNF_OK;
+  if (!x || !uw || !uh || !ud || !left || !right || !bottom || !top || !y || !logabsdet) return VCNF_ERR_NULL;
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
+  a.y = y; a.lad = logabsdet; a.bad = bad_disc; a.n = n;
+  const LimitsT<float> l = make_limits(left, right, bottom, top, bcast, n);
+  const long long blocks = (n + kBlock - 1) / kBlock;
+  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
+  hipStream_t st = (hipStream_t)stream;
+  if (inverse) launch_elem_limits<true>(a, l, a.c.K, grid, st);
+  else launch_elem_limits<false>(a, l, a.c.K, grid, st);
   return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
 }
 

@@ -78,6 +78,20 @@ def _spline(inputs, uw, uh, ud, cfg, inverse):
     return _lib.rqs_elementwise(inputs, uw, uh, ud, cfg, inverse)
 
 
+def _limits_spline(inputs, uw, uh, ud, inverse, limits, min_bin_width, min_bin_height, min_derivative):
+    """Tensor interval limits: one call of the per-element-limit kernel, through its VJP when a gradient is needed."""
+    from .. import autograd
+    for name, t in zip(_lib.LIMIT_NAMES[1:], limits[1:]):
+        if not torch.is_tensor(t):
+            # the reference indexes every limit once ``left`` is a tensor (splines.py:116, :130)
+            raise TypeError("left is a tensor, so %s must be one too (got %s)" % (name, type(t).__name__))
+    cfg = _lib.make_cfg(uw.shape[-1], None, min_bin_width=min_bin_width, min_bin_height=min_bin_height,
+                        min_derivative=min_derivative)
+    if autograd.needs_grad(inputs, uw, uh, ud, *limits):
+        return autograd.rqs_spline_limits(inputs, uw, uh, ud, *limits, cfg, inverse=inverse)
+    return _lib.rqs_elementwise_limits(inputs, uw, uh, ud, limits, cfg, inverse)
+
+
 def _check_bins(num_bins, min_bin_width, min_bin_height):
     # splines.py:104-107
     if min_bin_width * num_bins > 1.0:
@@ -94,11 +108,14 @@ def rational_quadratic_spline(inputs, unnormalized_widths, unnormalized_heights,
                               min_derivative=DEFAULT_MIN_DERIVATIVE):
     """splines.py:88-193: spline on [left, right] -> [bottom, top] with K+1
     derivative logits per element.  Inputs outside the interval are evaluated in
-    the nearest edge bin (the reference indexes out of range there)."""
-    if torch.is_tensor(left):
-        raise NotImplementedError("tensor interval limits are not built (SURVEY 8f row 4)")
+    the nearest edge bin (the reference indexes out of range there).
+    Tensor limits (:99-102): when ``left`` is a tensor, all four are tensors broadcastable to the shape of
+    ``inputs``, of the inputs' dtype; each element then has its own interval, and the limits receive gradients."""
     num_bins = unnormalized_widths.shape[-1]
     _check_bins(num_bins, min_bin_width, min_bin_height)
+    if torch.is_tensor(left):
+        return _limits_spline(inputs, unnormalized_widths, unnormalized_heights, unnormalized_derivatives, inverse,
+                              (left, right, bottom, top), min_bin_width, min_bin_height, min_derivative)
     cfg = _lib.make_cfg(num_bins, None, left=left, right=right, bottom=bottom, top=top,
                         min_bin_width=min_bin_width, min_bin_height=min_bin_height,
                         min_derivative=min_derivative)
