@@ -49,8 +49,10 @@
 #ifndef VCNF_ABL
 #define VCNF_ABL 0
 #endif
-// -DVCNF_TIME=1: s_memtime stamps at every barrier; wave 0 of workgroup 0 leaves the per-phase sums in
-// the first output row (timing builds only, read by profiles/tools/v6_phase_timing.py)
+// -DVCNF_TIME=1: s_memtime stamps at every barrier; waves 0 (group A) and 4 (group B) of workgroup 0 leave their
+// per-phase sums in a buffer of the timing build's own (kTimeSlots floats per wave; results are untouched), read
+// through vcnf_v6_phase_stamps by profiles/tools/v6_phase_timing.py.  Slots: 0-13 the steps in program order, 15 all
+// barriers between steps, 16-19 the four waits that shift group B one step behind group A and re-align them.
 #ifndef VCNF_TIME
 #define VCNF_TIME 0
 #endif
@@ -60,8 +62,12 @@
 #endif
 #if VCNF_TIME
 #define VCNF_T(I) { const long long t_ = clock64(); tacc[I] += t_ - tlast; tlast = t_; }
+#define VCNF_TIME_PARAM , float* tstamps
+#define VCNF_TIME_ARG , time_buffer()
 #else
 #define VCNF_T(I)
+#define VCNF_TIME_PARAM
+#define VCNF_TIME_ARG
 #endif
 
 // Workgroup barrier.  Not __syncthreads(): its release fence drains EVERY outstanding vector-memory operation
@@ -76,8 +82,22 @@
 
 namespace vcnf {
 
+#if VCNF_TIME
+constexpr int kTimeSlots = 24;              // per stamping wave: 20 phase sums, shader cycles, 100 MHz ticks of the kernel
+static float* time_buffer() {
+  static float* buf = nullptr;
+  if (!buf && hipMalloc(&buf, 2 * kTimeSlots * sizeof(float)) != hipSuccess) buf = nullptr;
+  return buf;
+}
+// stamps of the last launch (any shape, either direction): [wave 0 | wave 4][kTimeSlots]
+extern "C" int vcnf_v6_phase_stamps(float* out) {
+  if (!time_buffer() || hipDeviceSynchronize() != hipSuccess) return VCNF_ERR_LAUNCH;
+  return hipMemcpy(out, time_buffer(), 2 * kTimeSlots * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+}
+#endif
+
 template <int DI, int DT, int C, int H, int NBLK, int K, bool INV>
-__global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedArgs a) {
+__global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedArgs a VCNF_TIME_PARAM) {
   static_assert(H == 128 && K == 8, "4 row blocks of 32 over 4 waves; 3 K - 1 = 23 logits: two features per 48 rows");
   static_assert((DI == 16 || DI == 32) && DT == DI && (C == 0 || C == 16), "shape family");
   constexpr int kBlock = 512;
@@ -110,8 +130,15 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   float* ldt = tab + ((DI * TABW + 3) & ~3);               // [128] identity-half log|det|
   int* tfi = reinterpret_cast<int*>(ldt + kTile);
   int* idi = tfi + DT;
-  float* biasf = reinterpret_cast<float*>(idi + DI + 4);   // [NG][lane half][48] last-layer bias (3 KB)
-  int* tflag = reinterpret_cast<int*>(biasf + NG * 96);    // this tile held a value the fp16 halves cannot carry
+  // Bias tables, one plane per lane half (a lane half shares its 16 accumulator rows' biases; one per-lane base
+  // address serves every table read): last layer [NG][48] (3 KB in all), then the trunk's vectors [NBT][row block][16]
+  // - b0, then ba | bb (| bc) of every residual block.  From global memory a bias read returned 1 KiB per instruction
+  // for 128 distinct bytes, in the vector steps that the vector-memory path paces (profiles/fused_tile_handover.md).
+  constexpr int NBV = C > 0 ? 3 : 2;        // bias vectors per residual block
+  constexpr int NBT = 1 + NBLK * NBV;
+  constexpr int BPL = NG * 48 + NBT * (H / 2);             // floats per plane
+  float* biasf = reinterpret_cast<float*>(idi + DI + 4);
+  int* tflag = reinterpret_cast<int*>(biasf + 2 * BPL);    // this tile held a value the fp16 halves cannot carry
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -127,7 +154,15 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   // the second-dispatched wave group loses the issue arbitration on every step (MI355X_MICROARCH.md, two waves per
   // SIMD, item 4): one static priority for it, no per-step flips (+0.5 %)
   if (ch == 1) __builtin_amdgcn_s_setprio(1);
-  for (int i = tid; i < NG * 96; i += kBlock) biasf[i] = a.wpack[L::BF + i];
+  for (int i = tid; i < NG * 96; i += kBlock) {            // packed [group][lane half][48]
+    const int g = i / 96, hf = i % 96 / 48;
+    biasf[hf * BPL + g * 48 + i % 48] = a.wpack[L::BF + i];
+  }
+  for (int i = tid; i < NBT * H; i += kBlock) {             // packed [row block][lane half][16] per vector
+    const int v = i / H, blk = (v - 1) / NBV, sel = (v - 1) % NBV, r = i % H;
+    const int off = v == 0 ? L::B0 : L::BLK0 + blk * L::BLK + (sel == 0 ? L::BA : sel == 1 ? L::BB : L::BC);
+    biasf[(r >> 4 & 1) * BPL + NG * 48 + v * (H / 2) + (r >> 5) * 16 + (r & 15)] = a.wpack[off + r];
+  }
   for (int i = tid; i < DT; i += kBlock) tfi[i] = a.tf_idx[i];
   for (int i = tid; i < DI; i += kBlock) idi[i] = a.id_idx[i];
   if (shared) {
@@ -142,15 +177,15 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   const __amdgpu_buffer_rsrc_t wr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wpack), 0, a.wpack_bytes, 0x00020000);
   const int voff = lane * 16;
-  const int boff = kg * 64;                 // bias rows of this lane half: [nb][kg][16] floats
+  const float* bplane = biasf + kg * BPL;                   // bias tables of this lane half
 
   const long long ntiles = (a.B + kTile - 1) / kTile;
   bool bad = false;
   float satm = 0.f;
 #if VCNF_TIME
-  long long tacc[16], tlast = clock64();
+  long long tacc[20], tlast = clock64();
   const long long tstart = tlast, rstart = wall_clock64();
-  for (int i = 0; i < 16; ++i) tacc[i] = 0;
+  for (int i = 0; i < 20; ++i) tacc[i] = 0;
 #endif
   // rows of the next tile travel in registers: bounds-checked buffer loads (rows past the batch read 0)
   float4 xpre[kTile * (D / 4) / kBlock], cpre[1];
@@ -247,7 +282,11 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       }
       lsum += __shfl_xor(lsum, 1, 64);
       lsum += __shfl_xor(lsum, 2, 64);
-      if (part == 0) ldt[mi] = lsum;
+      // the address is rebuilt here (two instructions) rather than hoisted out of the tile loop: kept live through the
+      // tile it was spilled to scratch and reloaded behind an s_waitcnt vmcnt(0) in the sampling direction
+      int tid_ = tid;
+      asm volatile("" : "+v"(tid_));
+      if (part == 0) ldt[tid_ >> 2] = lsum;
       // raw inputs of the conditioner: NaN / Inf count as out of range (fmaxf in the splits drops NaNs)
 #pragma unroll
       for (int k = 0; k < UNR; ++k) satm = fmaxf(satm, fv[k] == fv[k] ? 0.f : __builtin_inff());
@@ -280,23 +319,23 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       }
     }
     { VCNF_T(2) VCNF_SYNC(); VCNF_T(15) }
-    if (ch == 1) { VCNF_T(14) VCNF_SYNC(); VCNF_T(15) }            // ---- group B now runs one step behind group A
+    if (ch == 1) { VCNF_T(14) VCNF_SYNC(); VCNF_T(16) }            // ---- group B now runs one step behind group A
 
     // stationary weights of a hidden->hidden layer for this wave's 32 rows, bias in accumulator order
     half8 ahi[NTH], alo[NTH];
     floatx16 abias;
-#define VCNF_LOAD_BIAS16(DST, FOFF)                                                       \
+#define VCNF_LOAD_BIAS16(DST, VEC)                                                        \
   _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                      \
-    const floatx4 b4_ = wload(wr, boff, 4 * ((FOFF) + 32 * rp) + 16 * i_);                \
+    const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bplane + NG * 48 + (VEC) * (H / 2) + 16 * rp + 4 * i_); \
     DST[4 * i_ + 0] = b4_[0]; DST[4 * i_ + 1] = b4_[1]; DST[4 * i_ + 2] = b4_[2]; DST[4 * i_ + 3] = b4_[3]; \
   }
-#define VCNF_LOAD_HIDDEN(WOFF, BOFF)                                                      \
+#define VCNF_LOAD_HIDDEN(WOFF, BVEC)                                                      \
   {                                                                                       \
     _Pragma("unroll") for (int t = 0; t < NTH; ++t) {                                     \
       ahi[t] = __builtin_bit_cast(half8, wload(wr, voff, 4 * ((WOFF) + ((rp * NTH + t) * 2 + 0) * 256))); \
       alo[t] = __builtin_bit_cast(half8, wload(wr, voff, 4 * ((WOFF) + ((rp * NTH + t) * 2 + 1) * 256))); \
     }                                                                                     \
-    VCNF_LOAD_BIAS16(abias, BOFF)                                                         \
+    VCNF_LOAD_BIAS16(abias, BVEC)                                                         \
   }
 
     // ---- step M0: first layer, 32 rows x 2 column blocks per wave                      resnet.py:92-99
@@ -309,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
         w0h[t] = __builtin_bit_cast(half8, wload(wr, voff, 4 * (L::W0 + ((rp * NT0 + t) * 2 + 0) * 256)));
         w0l[t] = __builtin_bit_cast(half8, wload(wr, voff, 4 * (L::W0 + ((rp * NT0 + t) * 2 + 1) * 256)));
       }
-      VCNF_LOAD_BIAS16(bias0, L::B0)
+      VCNF_LOAD_BIAS16(bias0, 0)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int cb = 2 * ch + j;
@@ -342,7 +381,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     }                                                                                     \
   }
     // ---- step V1: first hidden layer's weights requested, relu(h) published
-    VCNF_LOAD_HIDDEN(L::BLK0 + L::WA, L::BLK0 + L::BA)
+    VCNF_LOAD_HIDDEN(L::BLK0 + L::WA, 1)
     VCNF_PUBLISH(h, true)
     { VCNF_T(4) VCNF_SYNC(); VCNF_T(15) }
 
@@ -392,13 +431,13 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       VCNF_HIDDEN_COMPUTE(t)
       { VCNF_T(5) VCNF_SYNC(); VCNF_T(15) }
       // ---- step V: publish relu(t) (:46); second layer's and gate weights requested
-      VCNF_LOAD_HIDDEN(base + L::WB, base + L::BB)
+      VCNF_LOAD_HIDDEN(base + L::WB, 2 + blk * NBV)
       half8 wch, wcl;
       floatx16 gate[2], gbias;
       if (C > 0) {
         wch = __builtin_bit_cast(half8, wload(wr, voff, 4 * (base + L::WC + (rp * 2 + 0) * 256)));
         wcl = __builtin_bit_cast(half8, wload(wr, voff, 4 * (base + L::WC + (rp * 2 + 1) * 256)));
-        VCNF_LOAD_BIAS16(gbias, base + L::BC)
+        VCNF_LOAD_BIAS16(gbias, 3 + blk * NBV)
       }
       VCNF_PUBLISH(t, true)
       { VCNF_T(6) VCNF_SYNC(); VCNF_T(15) }
@@ -424,7 +463,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       // ---- step V: GLU gate (the packed gate weights carry log2 e: sigmoid(g) = 1 / (1 + 2^-g')),
       // residual update, publish                                                       :49-57
       if (blk + 1 < NBLK) {
-        VCNF_LOAD_HIDDEN(base + L::BLK + L::WA, base + L::BLK + L::BA)
+        VCNF_LOAD_HIDDEN(base + L::BLK + L::WA, 1 + (blk + 1) * NBV)
       }
       if (C > 0 && VCNF_ABL != 6) {
 #pragma unroll
@@ -446,7 +485,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       }
       { VCNF_T(7) VCNF_SYNC(); VCNF_T(15) }
     }
-    if (ch == 0) { VCNF_T(14) VCNF_SYNC(); VCNF_T(15) }            // ---- groups re-aligned: all activations are published
+    if (ch == 0) { VCNF_T(14) VCNF_SYNC(); VCNF_T(17) }            // ---- groups re-aligned: all activations are published
 #undef VCNF_HIDDEN_COMPUTE
 #undef VCNF_READ_B
 #undef VCNF_LOAD_HIDDEN
@@ -473,7 +512,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
 #define VCNF_LOAD_BIASF(G)                                                                \
   _Pragma("unroll") for (int b = 0; b < 3; ++b) {                                         \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                    \
-      const floatx4 b4_ = *reinterpret_cast<const floatx4*>(biasf + (G) * 96 + kg * 48 + 16 * b + 4 * i_); \
+      const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bplane + (G) * 48 + 16 * b + 4 * i_); \
       pa[b][4 * i_ + 0] = b4_[0]; pa[b][4 * i_ + 1] = b4_[1]; pa[b][4 * i_ + 2] = b4_[2]; pa[b][4 * i_ + 3] = b4_[3]; \
     }                                                                                     \
   }
@@ -482,7 +521,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     VCNF_STAGE_DMA(ch)                                                 // first feature group of each wave group
     wait_vector_memory();
     { VCNF_T(9) VCNF_SYNC(); VCNF_T(15) }
-    if (ch == 1) { VCNF_T(14) VCNF_SYNC(); VCNF_T(15) }            // ---- group B one step behind again
+    if (ch == 1) { VCNF_T(14) VCNF_SYNC(); VCNF_T(18) }            // ---- group B one step behind again
     for (int rnd = 0; rnd < (VCNF_ABL == 3 ? 0 : NR); ++rnd) {
       const int g = 2 * rnd + ch;
       // the two elements this lane transforms (features 4 g + 2 kg + {0, 1} of sample c32)
@@ -561,7 +600,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       if (rnd + 1 < NR && VCNF_ABL != 2) wait_vector_memory();
       { VCNF_T(11) VCNF_SYNC(); VCNF_T(15) }
     }
-    if (ch == 0) { VCNF_T(14) VCNF_SYNC(); VCNF_T(15) }            // ---- groups re-aligned: every spline of the tile is done
+    if (ch == 0) { VCNF_T(14) VCNF_SYNC(); VCNF_T(19) }            // ---- groups re-aligned: every spline of the tile is done
 #undef VCNF_PREFETCH_ROWS
 #undef VCNF_STAGE_DMA
 #undef VCNF_LOAD_BIASF
@@ -598,10 +637,12 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   }
 #if VCNF_TIME
   VCNF_T(13)
-  if (blockIdx.x == 0 && tid == 0) {
-    for (int i = 0; i < 16; ++i) a.y[i] = (float)tacc[i];
-    a.y[16] = (float)(clock64() - tstart);             // shader cycles of the whole kernel ...
-    a.y[17] = (float)(wall_clock64() - rstart);        // ... and 100 MHz ticks: in-kernel clock = 100 MHz * y[16] / y[17]
+  if (blockIdx.x == 0 && (tid & 255) == 0 && tstamps) {
+    float* ts = tstamps + (tid >> 8) * kTimeSlots;
+    for (int i = 0; i < 20; ++i) ts[i] = (float)tacc[i];
+    ts[20] = (float)(clock64() - tstart);              // shader cycles of the whole kernel ...
+    ts[21] = (float)(wall_clock64() - rstart);         // ... and 100 MHz ticks: in-kernel clock = 100 MHz * ts[20] / ts[21]
+    ts[22] = (float)((ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x);   // tiles this workgroup walked
   }
 #endif
   if (INV && a.bad && bad) atomicAdd(a.bad, 1);
@@ -612,7 +653,8 @@ static int launch_v6(const FusedArgs& a, int inverse, hipStream_t st) {
   constexpr int D = DI + DT;
   constexpr int TILE = 128;
   constexpr size_t WIN = (size_t)2 * 3 * (H / 16) * 2 * 64 * 16;   // two feature groups
-  const size_t lds = ((size_t)TILE * (D + 4) + ((DI * 3 * (K + 1) + 3) & ~3) + TILE + D + 8 + (DT / 4) * 96) * 4 +
+  constexpr int NBT = 1 + NBLK * (C > 0 ? 3 : 2);                 // trunk bias vectors beside the last layer's
+  const size_t lds = ((size_t)TILE * (D + 4) + ((DI * 3 * (K + 1) + 3) & ~3) + TILE + D + 8 + (DT / 4) * 96 + NBT * H) * 4 +
                      (C > 0 ? 4 * 2 * 64 * 16 : 0) + WIN + 64;
   static bool attr_set[2] = {false, false};
   if (!attr_set[inverse ? 1 : 0]) {
@@ -629,9 +671,9 @@ static int launch_v6(const FusedArgs& a, int inverse, hipStream_t st) {
   const long long ntiles = (a.B + TILE - 1) / TILE;
   dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
   if (inverse)
-    hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, a);
+    hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, a VCNF_TIME_ARG);
   else
-    hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, a);
+    hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, a VCNF_TIME_ARG);
   return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
 }
 
