@@ -665,6 +665,59 @@ int vcnf_diag_gaussian_sample_f64(const double* eps, const double* loc, const do
                                   double log_temperature, double* z, double* logp, int64_t batch,
                                   int32_t features, void* stream);
 
+/* ---- Class-conditional diagonal Gaussian end caps: GlowBase (normflow/distributions/base.py:778-869) and
+ * ClassCondDiagGaussian (:715-775).  z / eps [B, C, P] contiguous (d = C * P elements per sample: C channels of
+ * P = pixels elements); the parameters are tables loc_rows, log_scale_rows [rows, C].  Sample b uses table row
+ * row_index[b] (int32 [B]); with row_index == NULL it uses row b (rows == B) or row 0 (rows == 1).  A row_index entry
+ * outside [0, rows) reads nothing out of bounds: that sample's logp and its z / dz / d_eps row (and its d_loc / d_ls
+ * rows) are written as NaN, with no host synchronisation.  With ls = log_scale_rows[row, c] + log_temperature:
+ *   log_prob:  logp[b] = -0.5 d log(2 pi) - P sum_c ls - 0.5 sum_{c,p} ((z - loc) / exp(ls))^2   (per ld_mode / ld_sign)
+ *   sample:    z = loc + exp(ls) eps,  logp[b] = -0.5 d log(2 pi) - P sum_c ls - 0.5 sum eps^2
+ *   log_prob_bwd (g[B]):  dz = -g u / s,  d_loc[b, c] = sum_p g u / s,  d_log_scale[b, c] = sum_p g (u^2 - 1),
+ *                         u = (z - loc) / s, s = exp(ls)
+ *   sample_bwd (g_z[B, d], g_logp[B]):  d_eps = g_z s - g_logp eps,  d_loc[b, c] = sum_p g_z,
+ *                         d_log_scale[b, c] = sum_p g_z s eps - P g_logp
+ * d_loc / d_log_scale are [B, C] (per sample); vcnf_cc_gaussian_reduce_rows_* sums them onto the table rows:
+ * out_rows[r, c] = sum over {b: row_index[b] == r} of per_sample[b, c], in a fixed order (rows <= 65535).
+ * No atomics: every call is bitwise reproducible.  Status: channels < 1, pixels < 1, rows < 1 or (row_index == NULL
+ * and rows not in {1, batch}) -> VCNF_ERR_SHAPE; batch == 0 -> VCNF_OK without a launch; NULL required pointer ->
+ * VCNF_ERR_NULL; a pointer not aligned to its element size -> VCNF_ERR_ALIGN.  16-byte accesses are used when the
+ * buffers are 16-byte aligned and pixels % V == 0, or pixels == 1 and channels % V == 0 (V = 4 floats / 2 doubles). */
+int vcnf_cc_gaussian_log_prob_f32(const float* z, const float* loc_rows, const float* log_scale_rows,
+                                  const int32_t* row_index, float log_temperature, float* logp, int64_t batch,
+                                  int32_t channels, int32_t pixels, int64_t rows, int ld_mode, float ld_sign,
+                                  void* stream);
+int vcnf_cc_gaussian_sample_f32(const float* eps, const float* loc_rows, const float* log_scale_rows,
+                                const int32_t* row_index, float log_temperature, float* z, float* logp,
+                                int64_t batch, int32_t channels, int32_t pixels, int64_t rows, void* stream);
+int vcnf_cc_gaussian_log_prob_bwd_f32(const float* z, const float* loc_rows, const float* log_scale_rows,
+                                      const int32_t* row_index, float log_temperature, const float* g, float* dz,
+                                      float* d_loc, float* d_log_scale, int64_t batch, int32_t channels,
+                                      int32_t pixels, int64_t rows, void* stream);
+int vcnf_cc_gaussian_sample_bwd_f32(const float* eps, const float* log_scale_rows, const int32_t* row_index,
+                                    float log_temperature, const float* g_z, const float* g_logp, float* d_eps,
+                                    float* d_loc, float* d_log_scale, int64_t batch, int32_t channels,
+                                    int32_t pixels, int64_t rows, void* stream);
+int vcnf_cc_gaussian_reduce_rows_f32(const float* per_sample, const int32_t* row_index, float* out_rows,
+                                     int64_t batch, int32_t channels, int64_t rows, void* stream);
+int vcnf_cc_gaussian_log_prob_f64(const double* z, const double* loc_rows, const double* log_scale_rows,
+                                  const int32_t* row_index, double log_temperature, double* logp, int64_t batch,
+                                  int32_t channels, int32_t pixels, int64_t rows, int ld_mode, double ld_sign,
+                                  void* stream);
+int vcnf_cc_gaussian_sample_f64(const double* eps, const double* loc_rows, const double* log_scale_rows,
+                                const int32_t* row_index, double log_temperature, double* z, double* logp,
+                                int64_t batch, int32_t channels, int32_t pixels, int64_t rows, void* stream);
+int vcnf_cc_gaussian_log_prob_bwd_f64(const double* z, const double* loc_rows, const double* log_scale_rows,
+                                      const int32_t* row_index, double log_temperature, const double* g, double* dz,
+                                      double* d_loc, double* d_log_scale, int64_t batch, int32_t channels,
+                                      int32_t pixels, int64_t rows, void* stream);
+int vcnf_cc_gaussian_sample_bwd_f64(const double* eps, const double* log_scale_rows, const int32_t* row_index,
+                                    double log_temperature, const double* g_z, const double* g_logp, double* d_eps,
+                                    double* d_loc, double* d_log_scale, int64_t batch, int32_t channels,
+                                    int32_t pixels, int64_t rows, void* stream);
+int vcnf_cc_gaussian_reduce_rows_f64(const double* per_sample, const int32_t* row_index, double* out_rows,
+                                     int64_t batch, int32_t channels, int64_t rows, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

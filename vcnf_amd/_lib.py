@@ -173,6 +173,16 @@ PROTOTYPES = {
     "vcnf_rqs_elementwise_limits_bwd_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
                                              ctypes.POINTER(RqsLimitBcast), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                              _I64, ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
+    "vcnf_cc_gaussian_log_prob_f32": ([_P, _P, _P, _P, _F32, _P, _I64, _I32, _I32, _I64, _INT, _F32, _P], _INT),
+    "vcnf_cc_gaussian_sample_f32": ([_P, _P, _P, _P, _F32, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
+    "vcnf_cc_gaussian_log_prob_bwd_f32": ([_P, _P, _P, _P, _F32, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
+    "vcnf_cc_gaussian_sample_bwd_f32": ([_P, _P, _P, _F32, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
+    "vcnf_cc_gaussian_reduce_rows_f32": ([_P, _P, _P, _I64, _I32, _I64, _P], _INT),
+    "vcnf_cc_gaussian_log_prob_f64": ([_P, _P, _P, _P, _F64, _P, _I64, _I32, _I32, _I64, _INT, _F64, _P], _INT),
+    "vcnf_cc_gaussian_sample_f64": ([_P, _P, _P, _P, _F64, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
+    "vcnf_cc_gaussian_log_prob_bwd_f64": ([_P, _P, _P, _P, _F64, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
+    "vcnf_cc_gaussian_sample_bwd_f64": ([_P, _P, _P, _F64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
+    "vcnf_cc_gaussian_reduce_rows_f64": ([_P, _P, _P, _I64, _I32, _I64, _P], _INT),
 }
 
 _LIB = None
@@ -1290,6 +1300,114 @@ def diag_gaussian_sample(eps, loc, log_scale, temperature=None):
             _ptr(e2), _ptr(loc.contiguous()), _ptr(log_scale.contiguous()), lt, _ptr(z), _ptr(logp), b, e2.shape[1], _stream())
     _check(st, "vcnf_diag_gaussian_sample" + _sfx(eps))
     return z.view(eps.shape), logp
+
+
+def _cc_operands(x, loc_rows, ls_rows, row_index, pixels, what):
+    """Checked operands of the class-conditional Gaussian entry points: x [B, C, P...] (C * pixels elements per sample),
+    tables [R, C], row_index int32 [B] or None (then R is 1 or B).  Returns (device, x as [B, d], B, C, R)."""
+    dev = require_device(x, loc_rows, ls_rows, row_index, f64=True)
+    if any(u is not None and u.dtype != x.dtype for u in (loc_rows, ls_rows)):
+        raise VcnfError(what + ": mixed dtypes")
+    b = x.shape[0]
+    x2 = x.reshape(b, -1).contiguous()
+    if ls_rows.dim() != 2 or (loc_rows is not None and loc_rows.shape != ls_rows.shape):
+        raise VcnfError(what + ": parameter tables must be [rows, channels] of one shape")
+    r, c = ls_rows.shape
+    if pixels < 1 or c * pixels != x2.shape[1]:
+        raise VcnfError("%s: %d channels x %d pixels for rows of %d elements" % (what, c, pixels, x2.shape[1]))
+    if row_index is not None and (row_index.dtype != torch.int32 or tuple(row_index.shape) != (b,)):
+        raise VcnfError(what + ": row_index must be an int32 tensor [batch]")
+    if row_index is None and r not in (1, b):
+        raise VcnfError("%s: %d table rows for a batch of %d without row_index" % (what, r, b))
+    return dev, x2, b, c, r
+
+
+def _log_t(temperature):
+    return 0.0 if temperature is None else math.log(temperature)
+
+
+def cc_gaussian_log_prob(z, loc_rows, ls_rows, row_index, pixels, temperature=None, logp=None, sign=1.0):
+    """vcnf_cc_gaussian_log_prob_*: log density [B] of z [B, C, pixels...] under per-sample, per-channel Gaussians from
+    the tables loc_rows / ls_rows [R, C]; ``logp``: accumulate into it."""
+    name = "vcnf_cc_gaussian_log_prob" + _sfx(z)
+    dev, z2, b, c, r = _cc_operands(z, loc_rows, ls_rows, row_index, pixels, name)
+    require_device(logp, f64=True)
+    mode = LD_ACCUM
+    if logp is None:
+        logp = torch.empty(b, dtype=z.dtype, device=dev)
+        mode = LD_STORE
+    elif logp.dtype != z.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
+        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z2), _ptr(loc_rows.contiguous()), _ptr(ls_rows.contiguous()), _ptr(row_index),
+                                  _log_t(temperature), _ptr(logp), b, c, pixels, r, mode, float(sign), _stream())
+    _check(st, name)
+    return logp
+
+
+def cc_gaussian_sample(eps, loc_rows, ls_rows, row_index, pixels, temperature=None):
+    """vcnf_cc_gaussian_sample_*: (z, log p(z)) for the standard-normal draw eps [B, C, pixels...]."""
+    name = "vcnf_cc_gaussian_sample" + _sfx(eps)
+    dev, e2, b, c, r = _cc_operands(eps, loc_rows, ls_rows, row_index, pixels, name)
+    z = torch.empty_like(e2)
+    logp = torch.empty(b, dtype=eps.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(e2), _ptr(loc_rows.contiguous()), _ptr(ls_rows.contiguous()), _ptr(row_index),
+                                  _log_t(temperature), _ptr(z), _ptr(logp), b, c, pixels, r, _stream())
+    _check(st, name)
+    return z.view(eps.shape), logp
+
+
+def cc_gaussian_log_prob_bwd(z, loc_rows, ls_rows, row_index, pixels, temperature, g):
+    """vcnf_cc_gaussian_log_prob_bwd_*: (dz like z, d_loc [B, C], d_log_scale [B, C]) for the cotangent g [B]."""
+    name = "vcnf_cc_gaussian_log_prob_bwd" + _sfx(z)
+    dev, z2, b, c, r = _cc_operands(z, loc_rows, ls_rows, row_index, pixels, name)
+    require_device(g, f64=True)
+    dz = torch.empty_like(z2)
+    d_loc = torch.empty(b, c, dtype=z.dtype, device=dev)
+    d_ls = torch.empty(b, c, dtype=z.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z2), _ptr(loc_rows.contiguous()), _ptr(ls_rows.contiguous()), _ptr(row_index),
+                                  _log_t(temperature), _ptr(g.to(z.dtype).contiguous()), _ptr(dz), _ptr(d_loc), _ptr(d_ls),
+                                  b, c, pixels, r, _stream())
+    _check(st, name)
+    return dz.view(z.shape), d_loc, d_ls
+
+
+def cc_gaussian_sample_bwd(eps, ls_rows, row_index, pixels, temperature, g_z, g_logp):
+    """vcnf_cc_gaussian_sample_bwd_*: (d_eps like eps, d_loc [B, C], d_log_scale [B, C]) for the cotangents
+    g_z (like eps) and g_logp [B]."""
+    name = "vcnf_cc_gaussian_sample_bwd" + _sfx(eps)
+    dev, e2, b, c, r = _cc_operands(eps, None, ls_rows, row_index, pixels, name)
+    require_device(g_z, g_logp, f64=True)
+    gz2 = g_z.to(eps.dtype).reshape(b, -1).contiguous()
+    if gz2.shape != e2.shape:
+        raise VcnfError(name + ": g_z does not have the shape of eps")
+    d_eps = torch.empty_like(e2)
+    d_loc = torch.empty(b, c, dtype=eps.dtype, device=dev)
+    d_ls = torch.empty(b, c, dtype=eps.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(e2), _ptr(ls_rows.contiguous()), _ptr(row_index), _log_t(temperature), _ptr(gz2),
+                                  _ptr(g_logp.to(eps.dtype).contiguous()), _ptr(d_eps), _ptr(d_loc), _ptr(d_ls),
+                                  b, c, pixels, r, _stream())
+    _check(st, name)
+    return d_eps.view(eps.shape), d_loc, d_ls
+
+
+def cc_gaussian_reduce_rows(per_sample, row_index, rows):
+    """vcnf_cc_gaussian_reduce_rows_*: [rows, C] sums of per_sample [B, C] over the samples of each row_index value, in
+    a fixed order (bitwise reproducible; entries of row_index outside [0, rows) contribute to no row)."""
+    name = "vcnf_cc_gaussian_reduce_rows" + _sfx(per_sample)
+    dev = require_device(per_sample, row_index, f64=True)
+    per_sample = per_sample.contiguous()
+    b, c = per_sample.shape
+    if row_index.dtype != torch.int32 or tuple(row_index.shape) != (b,):
+        raise VcnfError(name + ": row_index must be an int32 tensor [batch]")
+    out = torch.empty(rows, c, dtype=per_sample.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(per_sample), _ptr(row_index), _ptr(out), b, c, rows, _stream())
+    _check(st, name)
+    return out
 
 
 PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2

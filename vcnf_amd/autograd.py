@@ -346,6 +346,58 @@ class DiagGaussianSampleFn(torch.autograd.Function):
         g_eps = gz * sig - g_lp[:, None] * e
         return g_eps.reshape(eps.shape), gz.sum(0), (gz * sig * e - g_lp[:, None]).sum(0), None
 
+def _onto_rows(per_sample, row_index, rows):
+    """Per-sample gradients [B, C] summed onto the [rows, C] parameter table they were read from: the fixed-order
+    segmented sum kernel under a row index, a column sum for one shared row, nothing for one row per sample."""
+    if row_index is not None:
+        return _lib.cc_gaussian_reduce_rows(per_sample, row_index, rows)
+    return per_sample.sum(0, keepdim=True) if rows == 1 and per_sample.shape[0] != 1 else per_sample
+
+
+class ClassCondGaussianLogProbFn(torch.autograd.Function):
+    """vcnf_cc_gaussian_log_prob_*: log density of z [B, C, P...] under the Gaussians of the table rows
+    loc_rows / ls_rows [R, C] picked by row_index (int32 [B], or None with R in {1, B}); backward on
+    vcnf_cc_gaussian_log_prob_bwd_* and vcnf_cc_gaussian_reduce_rows_*."""
+
+    @staticmethod
+    def forward(ctx, z, loc_rows, ls_rows, row_index, pixels, temperature):
+        with torch.no_grad():
+            lp = _lib.cc_gaussian_log_prob(z, loc_rows, ls_rows, row_index, pixels, temperature)
+        ctx.save_for_backward(z, loc_rows, ls_rows, row_index)
+        ctx.pixels, ctx.temperature = pixels, temperature
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        z, loc_rows, ls_rows, row_index = ctx.saved_tensors
+        dz, d_loc, d_ls = _lib.cc_gaussian_log_prob_bwd(z, loc_rows, ls_rows, row_index, ctx.pixels, ctx.temperature, g)
+        rows = ls_rows.shape[0]
+        return (dz, _onto_rows(d_loc, row_index, rows) if ctx.needs_input_grad[1] else None,
+                _onto_rows(d_ls, row_index, rows) if ctx.needs_input_grad[2] else None, None, None, None)
+
+
+class ClassCondGaussianSampleFn(torch.autograd.Function):
+    """vcnf_cc_gaussian_sample_*: (z, log p(z)) = (loc + e^ls eps, ...) for the draw eps [B, C, P...]; backward on
+    vcnf_cc_gaussian_sample_bwd_* and vcnf_cc_gaussian_reduce_rows_*."""
+
+    @staticmethod
+    def forward(ctx, eps, loc_rows, ls_rows, row_index, pixels, temperature):
+        with torch.no_grad():
+            z, lp = _lib.cc_gaussian_sample(eps, loc_rows, ls_rows, row_index, pixels, temperature)
+        ctx.save_for_backward(eps, ls_rows, row_index)
+        ctx.pixels, ctx.temperature = pixels, temperature
+        return z, lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_z, g_lp):
+        eps, ls_rows, row_index = ctx.saved_tensors
+        d_eps, d_loc, d_ls = _lib.cc_gaussian_sample_bwd(eps, ls_rows, row_index, ctx.pixels, ctx.temperature, g_z, g_lp)
+        rows = ls_rows.shape[0]
+        return (d_eps, _onto_rows(d_loc, row_index, rows) if ctx.needs_input_grad[1] else None,
+                _onto_rows(d_ls, row_index, rows) if ctx.needs_input_grad[2] else None, None, None, None)
+
 # Matrix path of the conditioner's dense layers on the training path at large batches: 'fp16x3' - forward products, the
 # 128 -> 128 layers' input gradients (csrc/linear_f16x3.hip) and the weight gradients (csrc/linear_wgrad.hip, split-half
 # form) on fp16 split-half operands with fp32 accumulation (error against fp64 below the library's fp32 GEMM on every

@@ -209,23 +209,51 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         self.load_state_dict(torch.load(path, weights_only=True))
 
 
+class ClassCondFlow(NormalizingFlow):
+    """Normalizing flow with a class-conditional base distribution (normflow/core.py:200-268): the loops of
+    NormalizingFlow, with the labels ``y`` (int64 [B] or a float matrix [B, num_classes]) given to the base only."""
+
+    def __init__(self, q0, flows):
+        super().__init__(q0, flows)
+
+    def log_prob(self, x, y):
+        z, log_q = self._walk(x, torch.zeros(len(x), dtype=x.dtype, device=x.device), None, True)
+        self.q0.log_prob(z, y, out=log_q)
+        return log_q
+
+    def forward_kld(self, x, y):
+        """-mean log q(x | y) (core.py:214-231)."""
+        return -torch.mean(self.log_prob(x, y))
+
+    def sample(self, num_samples=1, y=None):
+        """(z, log q(z | y)); labels are drawn by the base when ``y`` is None (core.py:233-249)."""
+        z, log_q = self.q0(num_samples, y)
+        return self._walk(z, log_q, None, False)
+
+    def sample_from(self, eps, y=None):
+        """``sample`` with the standard-normal base draw given."""
+        z, log_q = self.q0.from_noise(eps, y)
+        return self._walk(z, log_q, None, False)
+
+
 class MultiscaleFlow(_PackedWeightsMixin, nn.Module):
     """Multiscale (RealNVP / Glow) container: per level a list of flows, a Merge between
     levels and one base distribution per level.  Reference: normflow/core.py:271-399
-    (sample :310-340, log_prob :342-367).  Class-conditional bases are out of scope."""
+    (sample :310-340, log_prob :342-367).  With ``class_cond`` the bases that take labels (GlowBase,
+    ClassCondDiagGaussian: ``takes_labels``) are called with ``y``; DiagGaussian bases are called without it."""
 
     def __init__(self, q0, flows, merges, transform=None, class_cond=True):
         super().__init__()
         self._install_pack_hooks()
         if class_cond and any(not hasattr(q, 'from_noise') for q in q0):
-            raise NotImplementedError("class-conditional base distributions are out of scope; "
-                                      "use DiagGaussian bases with class_cond=False")
+            raise NotImplementedError("a base distribution without from_noise is not supported; use GlowBase, "
+                                      "ClassCondDiagGaussian or DiagGaussian bases")
         self.q0 = nn.ModuleList(q0)
         self.num_levels = len(self.q0)
         self.flows = nn.ModuleList([nn.ModuleList(f) for f in flows])
         self.merges = nn.ModuleList(merges)
         self.transform = transform
-        self.class_cond = False
+        self.class_cond = bool(class_cond)
 
     def forward(self, x, y=None):
         return -self.log_prob(x, y)
@@ -252,23 +280,31 @@ class MultiscaleFlow(_PackedWeightsMixin, nn.Module):
                 log_q = log_q + log_det
             else:
                 z_ = z
-            log_q = log_q + self.q0[i].log_prob(z_)
+            log_q = log_q + (self.q0[i].log_prob(z_, y) if self._labelled(i) else self.q0[i].log_prob(z_))
         return log_q
+
+    def _labelled(self, i):
+        """Base ``i`` is called with the labels (core.py:334-337, :361-364)."""
+        return self.class_cond and getattr(self.q0[i], 'takes_labels', False)
 
     def sample(self, num_samples=1, y=None, temperature=None):
         if temperature is not None:
             self.set_temperature(temperature)
+        if y is not None:
+            num_samples = len(y)
         noise = [torch.randn((num_samples,) + q.shape, dtype=q.loc.dtype, device=q.loc.device) for q in self.q0]
-        out = self.sample_from(noise)
-        if temperature is not None:
-            self.reset_temperature()
-        return out
+        try:
+            return self.sample_from(noise, y)
+        finally:
+            if temperature is not None:
+                self.reset_temperature()
 
-    def sample_from(self, noise):
-        """core.py:320-340 with the per-level standard-normal draws supplied."""
+    def sample_from(self, noise, y=None):
+        """core.py:320-340 with the per-level standard-normal draws supplied.  A base that takes labels draws its own
+        (torch.randint, as in the reference) when ``y`` is None."""
         z, log_q = None, None
         for i in range(self.num_levels):
-            z_, log_q_ = self.q0[i].from_noise(noise[i])
+            z_, log_q_ = self.q0[i].from_noise(noise[i], y) if self._labelled(i) else self.q0[i].from_noise(noise[i])
             if i == 0:
                 z, log_q = z_, log_q_
             else:

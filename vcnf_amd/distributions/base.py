@@ -1,6 +1,7 @@
-"""Base distribution end caps of the flow.  Only the diagonal Gaussian is on the
-hot path; the reference's research distributions are out of
-scope.  Reference: normflow/distributions/base.py:609-652."""
+"""Base distribution end caps of the flow: the diagonal Gaussian (SURVEY 2 row 10;
+normflow/distributions/base.py:609-652) and the class-conditional bases of the
+reference's Glow, ClassCondDiagGaussian (:715-775) and GlowBase (:778-869).  The
+reference's research distributions are out of scope."""
 import numpy as np
 import torch
 from torch import nn
@@ -59,3 +60,128 @@ class DiagGaussian(BaseDistribution):
             lp = autograd.DiagGaussianLogProbFn.apply(z, loc, ls, self.temperature)
             return lp if out is None else out.add_(lp)
         return _lib.diag_gaussian_log_prob(z, loc, ls, self.temperature, logp=out)
+
+
+class _ClassCondBase(BaseDistribution):
+    """Shared end of the class-conditional bases: labels to kernel operands, and the calls of the
+    vcnf_cc_gaussian_* kernels (csrc/class_cond_gaussian.hip) with or without autograd.  A subclass provides
+    ``_tables(row_index, soft)`` -> (loc_rows, ls_rows) [R, C] and ``_pixels`` (elements per channel)."""
+    takes_labels = True
+
+    def _labels(self, y, like):
+        """(row_index, soft): int32 labels [B] for the kernel's table lookup (hard labels; nothing indexes a tensor
+        with them, an out-of-range label ends as NaN in the kernel), or the float matrix [B, num_classes] the
+        reference takes as is."""
+        if not y.is_cuda:
+            raise _lib.VcnfError("vcnf_amd computes on MI355X only (labels on %s); there is no CPU path" % y.device)
+        if len(y) != len(like):
+            raise _lib.VcnfError("%d labels for a batch of %d" % (len(y), len(like)))
+        if y.dim() == 1:
+            return y.to(torch.int32).contiguous(), None
+        return None, y.to(like.dtype)
+
+    def _draw_labels(self, num_samples):
+        return torch.randint(self.num_classes, (num_samples,), device=self.loc.device)
+
+    def forward(self, num_samples=1, y=None):
+        """Labels drawn with torch.randint when the distribution is class-conditional and none are given, the
+        standard-normal draw with torch.randn, then one kernel for z and log p."""
+        if y is not None:
+            num_samples = len(y)
+        eps = torch.randn((num_samples,) + self.shape, dtype=self.loc.dtype, device=self.loc.device)
+        return self.from_noise(eps, y)
+
+    def from_noise(self, eps, y=None):
+        """``forward`` with the standard-normal draw supplied."""
+        _lib.require_device(eps, allow_grad=True, f64=True)
+        row_index, soft = self._operand_labels(eps, y, draw=True)
+        loc, ls = self._tables(row_index, soft)
+        if autograd.needs_grad(eps, loc, ls):
+            return autograd.ClassCondGaussianSampleFn.apply(eps, loc, ls, row_index, self._pixels, self.temperature)
+        return _lib.cc_gaussian_sample(eps, loc.detach(), ls.detach(), row_index, self._pixels, self.temperature)
+
+    def log_prob(self, z, y=None, out=None):
+        """``out`` [B]: accumulate into it instead of allocating."""
+        _lib.require_device(z, allow_grad=True, f64=True)
+        row_index, soft = self._operand_labels(z, y, draw=False)
+        loc, ls = self._tables(row_index, soft)
+        if autograd.needs_grad(z, loc, ls, out):
+            lp = autograd.ClassCondGaussianLogProbFn.apply(z, loc, ls, row_index, self._pixels, self.temperature)
+            return lp if out is None else out.add_(lp)
+        return _lib.cc_gaussian_log_prob(z, loc.detach(), ls.detach(), row_index, self._pixels, self.temperature, logp=out)
+
+    def _operand_labels(self, x, y, draw):
+        if self.num_classes is None:
+            return None, None
+        if y is None:
+            if not draw:
+                raise _lib.VcnfError("%s.log_prob needs the labels y of a class-conditional base" % type(self).__name__)
+            y = self._draw_labels(len(x))
+        return self._labels(y, x)
+
+
+class ClassCondDiagGaussian(_ClassCondBase):
+    """One diagonal Gaussian over ``shape`` per class (base.py:715-775); parameters [*shape, num_classes], zeros.
+    ``y``: int64 labels [B], or a float matrix [B, num_classes] whose rows mix the classes' parameters
+    (loc_b = loc @ y_b).  Kernel mapping: every element is its own channel (C = d, P = 1); hard labels look their row
+    up in the [num_classes, d] table inside the kernel, a float ``y`` gives one row per sample."""
+
+    def __init__(self, shape, num_classes):
+        super().__init__()
+        if isinstance(shape, int):
+            shape = (shape,)
+        self.shape = tuple(shape)
+        self.n_dim = len(self.shape)
+        self.perm = [self.n_dim] + list(range(self.n_dim))
+        self.d = int(np.prod(self.shape))
+        self.num_classes = num_classes
+        self.loc = nn.Parameter(torch.zeros(*self.shape, num_classes))
+        self.log_scale = nn.Parameter(torch.zeros(*self.shape, num_classes))
+        self.temperature = None
+        self._pixels = 1
+
+    def _tables(self, row_index, soft):
+        loc, ls = self.loc.reshape(self.d, self.num_classes).t(), self.log_scale.reshape(self.d, self.num_classes).t()
+        if soft is not None:
+            return soft @ loc, soft @ ls
+        return loc.contiguous(), ls.contiguous()
+
+
+class GlowBase(_ClassCondBase):
+    """Glow's base (base.py:778-869): per channel loc * exp(loc_logs * logscale_factor) and the same form for
+    log_scale, shared by the channel's ``num_pix`` pixels, plus the class rows y_onehot @ loc_cc / log_scale_cc when
+    ``num_classes`` is given.  Parameters [1, C, 1, ...] and [num_classes, C], zeros.  Kernel mapping: P = num_pix;
+    hard labels look their row up in the [num_classes, C] table inside the kernel, a float ``y`` [B, num_classes] gives
+    one row per sample, ``num_classes=None`` one row for all (``y`` is ignored)."""
+
+    def __init__(self, shape, num_classes=None, logscale_factor=3.):
+        super().__init__()
+        if isinstance(shape, int):
+            shape = (shape,)
+        self.shape = tuple(shape)
+        self.n_dim = len(self.shape)
+        self.num_pix = int(np.prod(self.shape[1:]))
+        self.d = int(np.prod(self.shape))
+        self.sum_dim = list(range(1, self.n_dim + 1))
+        self.num_classes = num_classes
+        self.class_cond = num_classes is not None
+        self.logscale_factor = logscale_factor
+        per_channel = (1, self.shape[0]) + (self.n_dim - 1) * (1,)
+        self.loc = nn.Parameter(torch.zeros(*per_channel))
+        self.loc_logs = nn.Parameter(torch.zeros(*per_channel))
+        self.log_scale = nn.Parameter(torch.zeros(*per_channel))
+        self.log_scale_logs = nn.Parameter(torch.zeros(*per_channel))
+        if self.class_cond:
+            self.loc_cc = nn.Parameter(torch.zeros(num_classes, self.shape[0]))
+            self.log_scale_cc = nn.Parameter(torch.zeros(num_classes, self.shape[0]))
+        self.temperature = None
+        self._pixels = self.num_pix
+
+    def _tables(self, row_index, soft):
+        loc = (self.loc * torch.exp(self.loc_logs * self.logscale_factor)).reshape(1, -1)
+        ls = (self.log_scale * torch.exp(self.log_scale_logs * self.logscale_factor)).reshape(1, -1)
+        if soft is not None:
+            return loc + soft @ self.loc_cc, ls + soft @ self.log_scale_cc
+        if row_index is not None:
+            return loc + self.loc_cc, ls + self.log_scale_cc
+        return loc, ls
