@@ -718,6 +718,50 @@ int vcnf_cc_gaussian_sample_bwd_f64(const double* eps, const double* log_scale_r
 int vcnf_cc_gaussian_reduce_rows_f64(const double* per_sample, const int32_t* row_index, double* out_rows,
                                      int64_t batch, int32_t channels, int64_t rows, void* stream);
 
+/* ---- Gaussian mixture base distribution (normflow 1.2 distributions/base.py GaussianMixture).  z / eps [B, D]
+ * contiguous; the parameters are tables loc, log_scale [M, D] and the log mixture weights log_w [M]
+ * (log softmax of the module's weight_scores).  With u = (z - loc[m]) / exp(log_scale[m]):
+ *   a[b, m]  = log_w[m] - sum_d log_scale[m, d] - 0.5 D log(2 pi) - 0.5 sum_d u^2
+ *   log_prob:  logp[b] = sign * logsumexp_m a[b, m]   (ld_mode VCNF_LD_STORE writes it, VCNF_LD_ACCUM adds it to logp);
+ *              a running maximum keeps it finite wherever the exact value is
+ *   sample:    z[b] = eps[b] * exp(log_scale[mode[b]]) + loc[mode[b]], logp[b] = the mixture log density of that z.
+ *              mode is int32 [B]; an entry outside [0, M) reads row 0 and that sample's z row and logp are written as
+ *              NaN: no out-of-bounds access, nothing for the host to check
+ *   log_prob_bwd (lse[B] = the forward's logp, cotangent g[B], gz_in[B, D] or NULL): with r = exp(a - lse)
+ *              dz = gz_in - g sum_m r u / s,  and per workgroup k one block partials[k] [M, 2 D + 1] holding the
+ *              workgroup's share of  d_loc[m] = sum_b g r u / s | d_log_scale[m] = sum_b g r (u^2 - 1) | d_log_w[m] =
+ *              sum_b g r,  added in a fixed order.  partials has vcnf_gmm_bwd_groups(batch, D, M) blocks; every block
+ *              is written in full.  partials == NULL: only dz is computed (no table needs a gradient)
+ *   reduce_partials: d_loc, d_log_scale [M, D] and d_log_w [M] = the sum of `groups` blocks in a fixed order
+ * vcnf_gmm_bwd_groups is a pure function of its arguments (no device query; 0 for an unsupported shape).
+ * Supported: features >= 1, modes >= 1, features * modes <= 8192, else VCNF_ERR_SHAPE (groups < 1 as well); unknown
+ * ld_mode -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a
+ * pointer not aligned to its element size -> VCNF_ERR_ALIGN.  The tables are staged in LDS once per workgroup;
+ * 16-byte (8-byte) accesses are used when features % V == 0 and the row buffers are aligned to them.  No atomics,
+ * no allocation, no host synchronisation: every call is bitwise reproducible and capturable. */
+int64_t vcnf_gmm_bwd_groups(int64_t batch, int32_t features, int32_t modes);
+int vcnf_gmm_log_prob_f32(const float* z, const float* loc, const float* log_scale, const float* log_w, float* logp,
+                          int64_t batch, int32_t features, int32_t modes, int ld_mode, float sign, void* stream);
+int vcnf_gmm_sample_f32(const float* eps, const int32_t* mode, const float* loc, const float* log_scale,
+                        const float* log_w, float* z, float* logp, int64_t batch, int32_t features, int32_t modes,
+                        void* stream);
+int vcnf_gmm_log_prob_bwd_f32(const float* z, const float* loc, const float* log_scale, const float* log_w,
+                              const float* lse, const float* g, const float* gz_in, float* dz, float* partials,
+                              int64_t batch, int32_t features, int32_t modes, void* stream);
+int vcnf_gmm_reduce_partials_f32(const float* partials, int64_t groups, int32_t modes, int32_t features, float* d_loc,
+                                 float* d_log_scale, float* d_log_w, void* stream);
+int vcnf_gmm_log_prob_f64(const double* z, const double* loc, const double* log_scale, const double* log_w,
+                          double* logp, int64_t batch, int32_t features, int32_t modes, int ld_mode, double sign,
+                          void* stream);
+int vcnf_gmm_sample_f64(const double* eps, const int32_t* mode, const double* loc, const double* log_scale,
+                        const double* log_w, double* z, double* logp, int64_t batch, int32_t features, int32_t modes,
+                        void* stream);
+int vcnf_gmm_log_prob_bwd_f64(const double* z, const double* loc, const double* log_scale, const double* log_w,
+                              const double* lse, const double* g, const double* gz_in, double* dz, double* partials,
+                              int64_t batch, int32_t features, int32_t modes, void* stream);
+int vcnf_gmm_reduce_partials_f64(const double* partials, int64_t groups, int32_t modes, int32_t features,
+                                 double* d_loc, double* d_log_scale, double* d_log_w, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

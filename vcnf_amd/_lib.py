@@ -183,6 +183,15 @@ PROTOTYPES = {
     "vcnf_cc_gaussian_log_prob_bwd_f64": ([_P, _P, _P, _P, _F64, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
     "vcnf_cc_gaussian_sample_bwd_f64": ([_P, _P, _P, _F64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
     "vcnf_cc_gaussian_reduce_rows_f64": ([_P, _P, _P, _I64, _I32, _I64, _P], _INT),
+    "vcnf_gmm_bwd_groups": ([_I64, _I32, _I32], _I64),
+    "vcnf_gmm_log_prob_f32": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F32, _P], _INT),
+    "vcnf_gmm_sample_f32": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
+    "vcnf_gmm_log_prob_bwd_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
+    "vcnf_gmm_reduce_partials_f32": ([_P, _I64, _I32, _I32, _P, _P, _P, _P], _INT),
+    "vcnf_gmm_log_prob_f64": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F64, _P], _INT),
+    "vcnf_gmm_sample_f64": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
+    "vcnf_gmm_log_prob_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
+    "vcnf_gmm_reduce_partials_f64": ([_P, _I64, _I32, _I32, _P, _P, _P, _P], _INT),
 }
 
 _LIB = None
@@ -1408,6 +1417,97 @@ def cc_gaussian_reduce_rows(per_sample, row_index, rows):
         st = getattr(lib(), name)(_ptr(per_sample), _ptr(row_index), _ptr(out), b, c, rows, _stream())
     _check(st, name)
     return out
+
+
+GMM_MAX_TABLE = 8192
+
+
+def _gmm_operands(x, loc, ls, log_w, what):
+    """Checked operands of the Gaussian mixture entry points: x [B, D], tables loc / ls [M, D], log_w [M], one dtype.
+    Returns (device, x, loc, ls, log_w contiguous, B, D, M)."""
+    dev = require_device(x, loc, ls, log_w, f64=True)
+    if any(u.dtype != x.dtype for u in (loc, ls, log_w)):
+        raise VcnfError(what + ": mixed dtypes")
+    if ls.dim() != 2 or loc.shape != ls.shape or tuple(log_w.shape) != (ls.shape[0],):
+        raise VcnfError(what + ": parameter tables must be [modes, features] and log_w [modes]")
+    m, d = ls.shape
+    if x.dim() != 2 or x.shape[1] != d:
+        raise VcnfError("%s: inputs %s for %d features" % (what, tuple(x.shape), d))
+    return dev, x.contiguous(), loc.contiguous(), ls.contiguous(), log_w.contiguous(), x.shape[0], d, m
+
+
+def gmm_log_prob(z, loc, ls, log_w, logp=None, sign=1.0):
+    """vcnf_gmm_log_prob_*: mixture log density [B] of z [B, D] under the modes loc / ls [M, D] with log weights
+    log_w [M]; ``logp``: accumulate into it."""
+    name = "vcnf_gmm_log_prob" + _sfx(z)
+    dev, z2, loc, ls, log_w, b, d, m = _gmm_operands(z, loc, ls, log_w, name)
+    require_device(logp, f64=True)
+    mode = LD_ACCUM
+    if logp is None:
+        logp = torch.empty(b, dtype=z.dtype, device=dev)
+        mode = LD_STORE
+    elif logp.dtype != z.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
+        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(logp), b, d, m, mode, float(sign),
+                                  _stream())
+    _check(st, name)
+    return logp
+
+
+def gmm_sample(eps, mode, loc, ls, log_w):
+    """vcnf_gmm_sample_*: (z, log p(z)) for the standard-normal draw eps [B, D] and the drawn modes (int32 [B])."""
+    name = "vcnf_gmm_sample" + _sfx(eps)
+    dev, e2, loc, ls, log_w, b, d, m = _gmm_operands(eps, loc, ls, log_w, name)
+    require_device(mode)
+    if mode.dtype != torch.int32 or tuple(mode.shape) != (b,) or not mode.is_contiguous():
+        raise VcnfError(name + ": mode must be a contiguous int32 tensor [batch]")
+    z = torch.empty_like(e2)
+    logp = torch.empty(b, dtype=eps.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(e2), _ptr(mode), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(z), _ptr(logp), b, d, m,
+                                  _stream())
+    _check(st, name)
+    return z, logp
+
+
+def gmm_log_prob_bwd(z, loc, ls, log_w, lse, g, gz_in=None, tables=True):
+    """vcnf_gmm_log_prob_bwd_* and vcnf_gmm_reduce_partials_*: (dz [B, D], d_loc [M, D], d_log_scale [M, D],
+    d_log_w [M]) for the cotangent g [B] of the log density; ``lse`` is the forward's result, ``gz_in`` [B, D] is added
+    to dz.  ``tables`` false: no table needs a gradient - dz only (the three others are None), no workspace, one launch."""
+    name = "vcnf_gmm_log_prob_bwd" + _sfx(z)
+    dev, z2, loc, ls, log_w, b, d, m = _gmm_operands(z, loc, ls, log_w, name)
+    require_device(lse, g, gz_in, f64=True)
+    lse, g = lse.to(z.dtype).contiguous(), g.to(z.dtype).contiguous()
+    if tuple(lse.shape) != (b,) or tuple(g.shape) != (b,):
+        raise VcnfError(name + ": lse and g must be [batch]")
+    if gz_in is not None:
+        gz_in = gz_in.to(z.dtype).contiguous()
+        if gz_in.shape != z2.shape:
+            raise VcnfError(name + ": gz_in does not have the shape of z")
+    dz = torch.empty_like(z2)
+    if not tables:
+        with torch.cuda.device(dev):
+            st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(lse), _ptr(g), _ptr(gz_in), _ptr(dz),
+                                      None, b, d, m, _stream())
+        _check(st, name)
+        return dz, None, None, None
+    d_loc, d_ls = torch.empty_like(loc), torch.empty_like(ls)
+    d_w = torch.empty_like(log_w)
+    if b == 0:
+        return dz, d_loc.zero_(), d_ls.zero_(), d_w.zero_()
+    groups = int(lib().vcnf_gmm_bwd_groups(b, d, m))
+    if groups < 1:
+        _check(2, name)
+    partials = torch.empty(groups, m, 2 * d + 1, dtype=z.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(lse), _ptr(g), _ptr(gz_in), _ptr(dz),
+                                  _ptr(partials), b, d, m, _stream())
+        _check(st, name)
+        name = "vcnf_gmm_reduce_partials" + _sfx(z)
+        st = getattr(lib(), name)(_ptr(partials), groups, m, d, _ptr(d_loc), _ptr(d_ls), _ptr(d_w), _stream())
+    _check(st, name)
+    return dz, d_loc, d_ls, d_w
 
 
 PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2

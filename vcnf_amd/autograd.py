@@ -398,6 +398,55 @@ class ClassCondGaussianSampleFn(torch.autograd.Function):
         return (d_eps, _onto_rows(d_loc, row_index, rows) if ctx.needs_input_grad[1] else None,
                 _onto_rows(d_ls, row_index, rows) if ctx.needs_input_grad[2] else None, None, None, None)
 
+
+class GaussianMixtureLogProbFn(torch.autograd.Function):
+    """vcnf_gmm_log_prob_*: mixture log density of z [B, D] under the modes loc / ls [M, D] with log weights log_w [M];
+    backward on vcnf_gmm_log_prob_bwd_* (the saved result is its lse) and vcnf_gmm_reduce_partials_*."""
+
+    @staticmethod
+    def forward(ctx, z, loc, ls, log_w):
+        with torch.no_grad():
+            lp = _lib.gmm_log_prob(z, loc, ls, log_w)
+        ctx.save_for_backward(z, loc, ls, log_w, lp)
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        z, loc, ls, log_w, lp = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dz, d_loc, d_ls, d_w = _lib.gmm_log_prob_bwd(z, loc, ls, log_w, lp, g, tables=any(need[1:4]))
+        return dz, d_loc if need[1] else None, d_ls if need[2] else None, d_w if need[3] else None
+
+
+class GaussianMixtureSampleFn(torch.autograd.Function):
+    """vcnf_gmm_sample_*: (z, log p(z)) with z = loc[mode] + e^ls[mode] eps for the drawn modes (int32 [B], no
+    gradient).  Backward: the density's VJP kernel gives dz_total = g_z + g_lp dlogp/dz and the parameters' share through
+    the density; the reparametrisation's share is d_eps = dz_total e^ls[mode] and the rows dz_total / dz_total eps
+    e^ls[mode] summed onto their mode's table row by vcnf_cc_gaussian_reduce_rows_* (fixed order)."""
+
+    @staticmethod
+    def forward(ctx, eps, loc, ls, log_w, mode):
+        with torch.no_grad():
+            z, lp = _lib.gmm_sample(eps, mode, loc, ls, log_w)
+        ctx.save_for_backward(eps, loc, ls, log_w, mode, z, lp)
+        return z, lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_z, g_lp):
+        eps, loc, ls, log_w, mode, z, lp = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dz, d_loc, d_ls, d_w = _lib.gmm_log_prob_bwd(z, loc, ls, log_w, lp, g_lp, gz_in=g_z, tables=any(need[1:4]))
+        m = ls.shape[0]
+        # a mode outside the table never indexes a tensor: its z row is NaN already
+        scale = torch.exp(ls).index_select(0, mode.clamp(0, m - 1).long())
+        if need[1]:
+            d_loc = d_loc + _lib.cc_gaussian_reduce_rows(dz, mode, m)
+        if need[2]:
+            d_ls = d_ls + _lib.cc_gaussian_reduce_rows(dz * eps * scale, mode, m)
+        return dz * scale, d_loc if need[1] else None, d_ls if need[2] else None, d_w if need[3] else None, None
+
 # Matrix path of the conditioner's dense layers on the training path at large batches: 'fp16x3' - forward products, the
 # 128 -> 128 layers' input gradients (csrc/linear_f16x3.hip) and the weight gradients (csrc/linear_wgrad.hip, split-half
 # form) on fp16 split-half operands with fp32 accumulation (error against fp64 below the library's fp32 GEMM on every

@@ -1,7 +1,8 @@
 """Base distribution end caps of the flow: the diagonal Gaussian (SURVEY 2 row 10;
 normflow/distributions/base.py:609-652) and the class-conditional bases of the
-reference's Glow, ClassCondDiagGaussian (:715-775) and GlowBase (:778-869).  The
-reference's research distributions are out of scope."""
+reference's Glow, ClassCondDiagGaussian (:715-775) and GlowBase (:778-869), and the
+GaussianMixture of normflow 1.2.  The reference's other research distributions
+(GenNormal, T, GGD, ...) are out of scope."""
 import numpy as np
 import torch
 from torch import nn
@@ -185,3 +186,68 @@ class GlowBase(_ClassCondBase):
         if row_index is not None:
             return loc + self.loc_cc, ls + self.log_scale_cc
         return loc, ls
+
+
+class GaussianMixture(BaseDistribution):
+    """Mixture of ``n_modes`` diagonal Gaussians over ``dim`` features (normflow 1.2 GaussianMixture).  Parameters
+    (buffers with ``trainable=False``): loc, log_scale [1, n_modes, dim] and weight_scores [1, n_modes], the log of
+    the normalised ``weights``; the mixture weights are softmax(weight_scores).  ``loc=None`` draws np.random.randn,
+    ``scale=None`` / ``weights=None`` give ones.  Tensors are created in torch's default dtype (the reference builds
+    float64 tensors from numpy arrays and its users cast the model).  Density, sampling and their gradients run on the
+    vcnf_gmm_* kernels (csrc/gaussian_mixture.hip); the mode draw is a torch.multinomial on the device and carries no
+    gradient."""
+    MAX_TABLE = _lib.GMM_MAX_TABLE
+
+    def __init__(self, n_modes, dim, loc=None, scale=None, weights=None, trainable=True):
+        super().__init__()
+        self.n_modes = n_modes
+        self.dim = dim
+        loc = np.random.randn(n_modes, dim) if loc is None else np.array(loc, dtype=np.float64)
+        scale = np.ones((n_modes, dim)) if scale is None else np.array(scale, dtype=np.float64)
+        weights = np.ones(n_modes) if weights is None else np.array(weights, dtype=np.float64)
+        loc, scale, weights = loc.reshape(1, n_modes, dim), scale.reshape(1, n_modes, dim), weights.reshape(1, n_modes)
+        weights = weights / weights.sum(1)
+        dtype = torch.get_default_dtype()
+        tensors = (("loc", torch.tensor(loc, dtype=dtype)), ("log_scale", torch.tensor(np.log(scale), dtype=dtype)),
+                   ("weight_scores", torch.tensor(np.log(weights), dtype=dtype)))
+        for name, t in tensors:
+            if trainable:
+                setattr(self, name, nn.Parameter(t))
+            else:
+                self.register_buffer(name, t)
+
+    def _tables(self):
+        """(loc [M, D], log_scale [M, D], log w [M]); the step from weight_scores to log w stays torch autograd."""
+        if self.n_modes * self.dim > self.MAX_TABLE:
+            raise NotImplementedError("GaussianMixture: n_modes * dim = %d is beyond the kernels' limit of %d table "
+                                      "entries" % (self.n_modes * self.dim, self.MAX_TABLE))
+        return self.loc[0], self.log_scale[0], torch.log_softmax(self.weight_scores, 1)[0]
+
+    def forward(self, num_samples=1):
+        """Modes drawn with torch.multinomial, the standard-normal draw with torch.randn, then one kernel for z and
+        log p."""
+        _lib.require_device(self.loc, allow_grad=True, f64=True)
+        eps = torch.randn(num_samples, self.dim, dtype=self.loc.dtype, device=self.loc.device)
+        return self.from_noise(eps)
+
+    def from_noise(self, eps, mode=None):
+        """``forward`` with the standard-normal draw supplied, and optionally the modes (integer tensor [B]; a mode
+        outside [0, n_modes) ends as NaN in that sample's z and log p)."""
+        _lib.require_device(eps, self.loc, mode, allow_grad=True, f64=True)
+        loc, ls, log_w = self._tables()
+        if mode is None:
+            with torch.no_grad():
+                mode = torch.multinomial(torch.softmax(self.weight_scores, 1)[0], len(eps), replacement=True)
+        mode = mode.to(torch.int32).contiguous()
+        if autograd.needs_grad(eps, loc, ls, log_w):
+            return autograd.GaussianMixtureSampleFn.apply(eps, loc, ls, log_w, mode)
+        return _lib.gmm_sample(eps, mode, loc.detach(), ls.detach(), log_w.detach())
+
+    def log_prob(self, z, out=None):
+        """``out`` [B]: accumulate into it instead of allocating."""
+        _lib.require_device(z, self.loc, allow_grad=True, f64=True)
+        loc, ls, log_w = self._tables()
+        if autograd.needs_grad(z, loc, ls, log_w, out):
+            lp = autograd.GaussianMixtureLogProbFn.apply(z, loc, ls, log_w)
+            return lp if out is None else out.add_(lp)
+        return _lib.gmm_log_prob(z, loc.detach(), ls.detach(), log_w.detach(), logp=out)
