@@ -5,7 +5,9 @@ Needs a library whose v6 translation unit (two residual blocks) was compiled wit
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -DVCNF_V6_NBLK=2 -DVCNF_TIME=1 \
         -c vcnf_amd/csrc/fused_layer_v6.hip -o scratch/v6_time.o
     hipcc --offload-arch=gfx950 -shared -fPIC -o scratch/libvcnf_time.so $(ls scratch/obj/*.o | grep -v fused_layer_v6_b2.o) scratch/v6_time.o
-    VCNF_LIB=$PWD/scratch/libvcnf_time.so python profiles/tools/v6_phase_timing.py [batch]
+    VCNF_LIB=$PWD/scratch/libvcnf_time.so python profiles/tools/v6_phase_timing.py [batch] [into]
+"into": the accumulating calls of a flow (inverse_into / forward_into: log-det added onto a running log-density, one
+value per row) instead of the store-mode ones.
 Waves 0 (group A) and 4 (group B) of workgroup 0 sum the shader cycles of every step over the tiles the workgroup walks;
 the timing build keeps them in a buffer of its own (vcnf_v6_phase_stamps), the layer's results are untouched.  Printed:
 cycles per tile.  A wave's slots add up to its whole tile; the four waits that shift group B one step behind group A
@@ -28,6 +30,7 @@ NAMES = ["tail of the previous tile (store) + loop top", "x rows, context -> LDS
 SLOTS = 24
 torch.manual_seed(0)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
+INTO = len(sys.argv) > 2 and sys.argv[2] == "into"
 lay = nf.flows.CoupledRationalQuadraticSpline(64, 2, 128, 8, num_context_channels=16).cuda().eval()
 handle = _lib.lib()
 if not hasattr(handle, "vcnf_v6_phase_stamps"):
@@ -35,17 +38,18 @@ if not hasattr(handle, "vcnf_v6_phase_stamps"):
 handle.vcnf_v6_phase_stamps.argtypes, handle.vcnf_v6_phase_stamps.restype = [ctypes.c_void_p], ctypes.c_int
 with torch.no_grad():
     xb, cb = torch.randn(B, 64, device="cuda"), torch.randn(B, 16, device="cuda")
+    lq = torch.randn(B, device="cuda")
     for dirn in ("inverse", "forward"):
         for _ in range(3):
-            getattr(lay, dirn)(xb, context=cb)
+            getattr(lay, dirn + "_into")(xb, lq, context=cb) if INTO else getattr(lay, dirn)(xb, context=cb)
         torch.cuda.synchronize()
         out = (ctypes.c_float * (2 * SLOTS))()
         assert handle.vcnf_v6_phase_stamps(ctypes.cast(out, ctypes.c_void_p)) == 0
         for w in (0, 1):
             v = [float(f) for f in out[w * SLOTS:(w + 1) * SLOTS]]
             tiles = max(v[22], 1.0)
-            print("%s, wave %d (group %s): %d tiles, %.0f shader cycles in all, %.2f us, in-kernel clock %.0f MHz" % (
-                "density" if dirn == "inverse" else "sampling", 4 * w, "AB"[w], tiles, v[20], v[21] / 100.0,
+            print("%s%s, wave %d (group %s): %d tiles, %.0f shader cycles in all, %.2f us, in-kernel clock %.0f MHz" % (
+                "density" if dirn == "inverse" else "sampling", " (accumulate)" if INTO else "", 4 * w, "AB"[w], tiles, v[20], v[21] / 100.0,
                 100.0 * v[20] / max(v[21], 1.0)))
             for i, n in enumerate(NAMES):
                 if i != 14:

@@ -138,7 +138,8 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   constexpr int NBT = 1 + NBLK * NBV;
   constexpr int BPL = NG * 48 + NBT * (H / 2);             // floats per plane
   float* biasf = reinterpret_cast<float*>(idi + DI + 4);
-  int* tflag = reinterpret_cast<int*>(biasf + 2 * BPL);    // this tile held a value the fp16 halves cannot carry
+  float* ldold = biasf + 2 * BPL;                           // [128] accumulate mode: the log|det| values the tile adds onto
+  int* tflag = reinterpret_cast<int*>(ldold + kTile);      // this tile held a value the fp16 halves cannot carry
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -205,7 +206,22 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       cpre[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cr_, tid * 16, 0, 0)); \
     }                                                                                     \
   }
+  // the compiler waits for the prefetched rows where their registers are first touched
+#define VCNF_ROWS_ARRIVED()                                                               \
+  {                                                                                       \
+    _Pragma("unroll") for (int k = 0; k < kTile * (D / 4) / kBlock; ++k) {                \
+      floatx4 v_ = __builtin_bit_cast(floatx4, xpre[k]);                                  \
+      asm volatile("" : "+v"(v_));                                                        \
+      xpre[k] = __builtin_bit_cast(float4, v_);                                           \
+    }                                                                                     \
+    if (C > 0) {                                                                          \
+      floatx4 v_ = __builtin_bit_cast(floatx4, cpre[0]);                                  \
+      asm volatile("" : "+v"(v_));                                                        \
+      cpre[0] = __builtin_bit_cast(float4, v_);                                           \
+    }                                                                                     \
+  }
   VCNF_PREFETCH_ROWS((long long)blockIdx.x)
+  VCNF_ROWS_ARRIVED()                         // first tile: on entry to the loop nothing is pending on either path
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long b0 = tile * kTile;
     const int rows = (int)min((long long)kTile, a.B - b0);
@@ -519,6 +535,14 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     VCNF_LOAD_BIASF(ch)
     { VCNF_T(8) VCNF_SYNC(); VCNF_T(15) }                         // every wave has its operand fragments: the window may be written
     VCNF_STAGE_DMA(ch)                                                 // first feature group of each wave group
+    // accumulate mode: the values this tile adds onto travel beside the first window straight into LDS
+    // (buffer_load_dword ... lds, no register; rows past the batch read 0) and are covered by the same wait; the
+    // tail reads them from LDS
+    if (ch == 0 && rp < 2 && a.ld_mode) {
+      const __amdgpu_buffer_rsrc_t or_ = __builtin_amdgcn_make_buffer_rsrc(a.logdet + b0, 0, rows * 4, 0x00020000);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(or_, (__attribute__((address_space(3))) void*)(ldold + rp * 64), 4,
+                                               lane * 4, rp * 256, 0, 0);
+    }
     wait_vector_memory();
     { VCNF_T(9) VCNF_SYNC(); VCNF_T(15) }
     if (ch == 1) { VCNF_T(14) VCNF_SYNC(); VCNF_T(18) }            // ---- group B one step behind again
@@ -611,28 +635,47 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     if (ch == 1 && kg == 0) ldt[rp * 32 + c32] += ld_acc;
     if (satm > 65504.f) *tflag = 1;
     { VCNF_T(12) VCNF_SYNC(); VCNF_T(15) }
+    // The next tile's rows are waited for HERE, in front of the tail's stores: they were requested a whole vector step
+    // ago, and the loop top then waits for nothing (the vector-memory counter is in order and counts stores as well).
+    VCNF_ROWS_ARRIVED()
+#undef VCNF_ROWS_ARRIVED
     // A tile that held a non-finite input or a value beyond the fp16 range is not written at all when the caller
     // gave a flag array: the exact fp32 kernel evaluates it from the untouched inputs (vcnf_rqs_layer_fused_f32,
     // redo_tiles).  Without the array the clamped results are stored and only counted (sat).
+    // Every store of the tail goes through a bounds-checked descriptor with a wave-uniform base (the hardware drops
+    // what lies past the batch) and a per-lane offset made from the thread index on the spot: no per-lane address
+    // stays live through the tile.
+    int tid_ = tid;
+    asm volatile("" : "+v"(tid_));
     const bool over = *tflag != 0;
     if (tid == 0 && over && a.sat) atomicAdd(a.sat, 1);
-    if (a.redo && tid < kTile / kFusedFlagRows && b0 + tid * kFusedFlagRows < a.B)   // one flag per 32 rows
-      a.redo[tile * (kTile / kFusedFlagRows) + tid] = over ? 1 : 0;
-    if (over && a.redo) continue;
-    if (ch == 0 && kg == 0) {
-      const int mrow = rp * 32 + c32;
-      if (mrow < rows) {
-        const float o = a.ld_sign * (ld_acc + ldt[mrow]);
-        a.logdet[b0 + mrow] = a.ld_mode ? a.logdet[b0 + mrow] + o : o;
+    if (a.redo) {
+      if (tid_ < kTile / kFusedFlagRows) {                     // one flag per 32 rows
+        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+            a.redo + tile * (kTile / kFusedFlagRows), 0, 4 * ((rows + kFusedFlagRows - 1) / kFusedFlagRows), 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b32(over ? 1 : 0, rr, tid_ * 4, 0, 0);
       }
+      if (over) continue;
+    }
+    if (ch == 0 && (tid_ & 32) == 0) {
+      const int mrow = (tid_ >> 6) * 32 + (tid_ & 31);         // ch == 0: tid >> 6 is the column block
+      const __amdgpu_buffer_rsrc_t lr = __builtin_amdgcn_make_buffer_rsrc(a.logdet + b0, 0, rows * 4, 0x00020000);
+      const float o = a.ld_sign * (ld_acc + ldt[mrow]);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a.ld_mode ? ldold[mrow] + o : o), lr, mrow * 4, 0, 0);
     }
     {
       constexpr int D4 = D / 4;
-      float4* dst = reinterpret_cast<float4*>(a.y) + b0 * D4;
-      for (int i = tid; i < rows * D4; i += kBlock) {
+      const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(a.y + b0 * D, 0, rows * (D * 4), 0x00020000);
+      floatx4 yv[kTile * D4 / kBlock];
+#pragma unroll
+      for (int k = 0; k < kTile * D4 / kBlock; ++k) {
+        const int i = tid_ + kBlock * k;
         const int r = i / D4, o = i - r * D4;
-        dst[i] = *reinterpret_cast<const float4*>(xt + r * XS + 4 * o);
+        yv[k] = *reinterpret_cast<const floatx4*>(xt + r * XS + 4 * o);
       }
+#pragma unroll
+      for (int k = 0; k < kTile * D4 / kBlock; ++k)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, yv[k]), yr, (tid_ + kBlock * k) * 16, 0, 0);
     }
   }
 #if VCNF_TIME
@@ -654,7 +697,7 @@ static int launch_v6(const FusedArgs& a, int inverse, hipStream_t st) {
   constexpr int TILE = 128;
   constexpr size_t WIN = (size_t)2 * 3 * (H / 16) * 2 * 64 * 16;   // two feature groups
   constexpr int NBT = 1 + NBLK * (C > 0 ? 3 : 2);                 // trunk bias vectors beside the last layer's
-  const size_t lds = ((size_t)TILE * (D + 4) + ((DI * 3 * (K + 1) + 3) & ~3) + TILE + D + 8 + (DT / 4) * 96 + NBT * H) * 4 +
+  const size_t lds = ((size_t)TILE * (D + 4) + ((DI * 3 * (K + 1) + 3) & ~3) + 2 * TILE + D + 8 + (DT / 4) * 96 + NBT * H) * 4 +
                      (C > 0 ? 4 * 2 * 64 * 16 : 0) + WIN + 64;
   static bool attr_set[2] = {false, false};
   if (!attr_set[inverse ? 1 : 0]) {
