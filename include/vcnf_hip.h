@@ -762,6 +762,66 @@ int vcnf_gmm_log_prob_bwd_f64(const double* z, const double* loc, const double* 
 int vcnf_gmm_reduce_partials_f64(const double* partials, int64_t groups, int32_t modes, int32_t features,
                                  double* d_loc, double* d_log_scale, double* d_log_w, void* stream);
 
+/* ---- Heavy-tailed product base distributions: Student-t and the generalised Gaussian, one tail parameter per
+ * feature.  z / eps / gamma [B, D] contiguous; the parameters are the rows loc, log_scale, shape (nu or beta) and cst
+ * (the normalisers) [D].  The caller computes cst - for Student-t lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2, for
+ * the generalised Gaussian log(beta) - log 2 - lgamma(1/beta) - and draws the random numbers: no kernel evaluates a
+ * special function or draws.  With u = (z - loc) / exp(log_scale):
+ *   f(u; nu)   = -(nu + 1)/2 log1p(u^2 / nu)                         VCNF_TAIL_STUDENT_T
+ *   f(u; beta) = -|u|^beta = -exp(beta log|u|), 0 at u == 0          VCNF_TAIL_GEN_GAUSSIAN
+ *   log_prob:  logp[b] = sign * sum_d (cst[d] - log_scale[d] + f(u; shape[d]))   (ld_mode as for vcnf_gmm_log_prob_*)
+ *   sample:    u = eps sqrt(nu / (2 gamma)) with eps ~ N(0, 1), gamma ~ Gamma(nu/2, 1), or
+ *              u = sign(eps) gamma^(1/beta) with gamma ~ Gamma(1/beta, 1), where |u|^beta = gamma is used as is;
+ *              z[b] = loc + exp(log_scale) u and logp[b] = the log density of that z
+ *   log_prob_bwd (cotangent g[B], gz_in[B, D] or NULL): dz = gz_in + g df/du / s, and per workgroup k one block
+ *              partials[k] [3, D] with the workgroup's share of  d_loc = -sum_b g df/du / s | d_log_scale =
+ *              sum_b g (-1 - u df/du) | sum_b g df/dshape (the part of d_shape that does not go through cst), added in a
+ *              fixed order.  Student-t: df/du = -(nu+1) u / (nu + u^2), df/dnu = -log1p(u^2/nu)/2 + (nu+1) u^2 /
+ *              (2 nu (nu + u^2)).  Generalised Gaussian: df/du = -beta |u|^beta / u, df/dbeta = -|u|^beta log|u|, and
+ *              both 0 at u == 0 for every beta (for beta < 1, where df/du is unbounded there, a convention).
+ *              partials has vcnf_tail_bwd_groups(batch, D) blocks, every block is written in full; partials == NULL:
+ *              only dz is computed
+ *   sample_bwd (cotangents g_z[B, D] and g_lp[B], either may be NULL = zero): deps (may be NULL) and dgamma [B, D], and
+ *              blocks as above for the three rows.  du/deps = sqrt(nu / (2 gamma)), du/dgamma = -u / (2 gamma),
+ *              du/dnu = u / (2 nu);  du/deps = 0, du/dgamma = u / (beta gamma), du/dbeta = -u log(gamma) / beta^2
+ *   reduce_partials: d_loc, d_log_scale, d_shape [D] = the sum of `groups` blocks in a fixed order
+ * vcnf_tail_bwd_groups is a pure function of its arguments (no device query; 0 for an unsupported shape).
+ * features >= 1 (no upper limit) and batch >= 0, else VCNF_ERR_SHAPE (groups < 1 as well); unknown family or ld_mode ->
+ * VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a pointer not
+ * aligned to its element size -> VCNF_ERR_ALIGN.  16-byte (8-byte) accesses are used when features % V == 0 and the
+ * [B, D] buffers are aligned to them.  No atomics, no allocation, no host synchronisation: every call is bitwise
+ * reproducible and capturable. */
+enum { VCNF_TAIL_STUDENT_T = 0, VCNF_TAIL_GEN_GAUSSIAN = 1 };
+int64_t vcnf_tail_bwd_groups(int64_t batch, int32_t features);
+int vcnf_tail_log_prob_f32(const float* z, const float* loc, const float* log_scale, const float* shape,
+                           const float* cst, float* logp, int64_t batch, int32_t features, int family, int ld_mode,
+                           float sign, void* stream);
+int vcnf_tail_sample_f32(const float* eps, const float* gamma, const float* loc, const float* log_scale,
+                         const float* shape, const float* cst, float* z, float* logp, int64_t batch, int32_t features,
+                         int family, void* stream);
+int vcnf_tail_log_prob_bwd_f32(const float* z, const float* loc, const float* log_scale, const float* shape,
+                               const float* g, const float* gz_in, float* dz, float* partials, int64_t batch,
+                               int32_t features, int family, void* stream);
+int vcnf_tail_sample_bwd_f32(const float* eps, const float* gamma, const float* loc, const float* log_scale,
+                             const float* shape, const float* g_z, const float* g_lp, float* deps, float* dgamma,
+                             float* partials, int64_t batch, int32_t features, int family, void* stream);
+int vcnf_tail_reduce_partials_f32(const float* partials, int64_t groups, int32_t features, float* d_loc,
+                                  float* d_log_scale, float* d_shape, void* stream);
+int vcnf_tail_log_prob_f64(const double* z, const double* loc, const double* log_scale, const double* shape,
+                           const double* cst, double* logp, int64_t batch, int32_t features, int family, int ld_mode,
+                           double sign, void* stream);
+int vcnf_tail_sample_f64(const double* eps, const double* gamma, const double* loc, const double* log_scale,
+                         const double* shape, const double* cst, double* z, double* logp, int64_t batch, int32_t features,
+                         int family, void* stream);
+int vcnf_tail_log_prob_bwd_f64(const double* z, const double* loc, const double* log_scale, const double* shape,
+                               const double* g, const double* gz_in, double* dz, double* partials, int64_t batch,
+                               int32_t features, int family, void* stream);
+int vcnf_tail_sample_bwd_f64(const double* eps, const double* gamma, const double* loc, const double* log_scale,
+                             const double* shape, const double* g_z, const double* g_lp, double* deps, double* dgamma,
+                             double* partials, int64_t batch, int32_t features, int family, void* stream);
+int vcnf_tail_reduce_partials_f64(const double* partials, int64_t groups, int32_t features, double* d_loc,
+                                  double* d_log_scale, double* d_shape, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

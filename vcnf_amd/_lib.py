@@ -192,6 +192,17 @@ PROTOTYPES = {
     "vcnf_gmm_sample_f64": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
     "vcnf_gmm_log_prob_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
     "vcnf_gmm_reduce_partials_f64": ([_P, _I64, _I32, _I32, _P, _P, _P, _P], _INT),
+    "vcnf_tail_bwd_groups": ([_I64, _I32], _I64),
+    "vcnf_tail_log_prob_f32": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P], _INT),
+    "vcnf_tail_sample_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
+    "vcnf_tail_log_prob_bwd_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
+    "vcnf_tail_sample_bwd_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
+    "vcnf_tail_reduce_partials_f32": ([_P, _I64, _I32, _P, _P, _P, _P], _INT),
+    "vcnf_tail_log_prob_f64": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F64, _P], _INT),
+    "vcnf_tail_sample_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
+    "vcnf_tail_log_prob_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
+    "vcnf_tail_sample_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
+    "vcnf_tail_reduce_partials_f64": ([_P, _I64, _I32, _P, _P, _P, _P], _INT),
 }
 
 _LIB = None
@@ -1508,6 +1519,130 @@ def gmm_log_prob_bwd(z, loc, ls, log_w, lse, g, gz_in=None, tables=True):
         st = getattr(lib(), name)(_ptr(partials), groups, m, d, _ptr(d_loc), _ptr(d_ls), _ptr(d_w), _stream())
     _check(st, name)
     return dz, d_loc, d_ls, d_w
+
+
+TAIL_STUDENT_T, TAIL_GEN_GAUSSIAN = 0, 1
+
+
+def _tail_operands(x, rows, what):
+    """Checked operands of the heavy-tailed base entry points: x [B, ...] with D elements per sample and parameter rows of
+    D elements each, one dtype.  Returns (device, x as [B, D] contiguous, the rows flat and contiguous, B, D)."""
+    dev = require_device(x, *rows, f64=True)
+    if any(u.dtype != x.dtype for u in rows):
+        raise VcnfError(what + ": mixed dtypes")
+    if x.dim() < 1:
+        raise VcnfError(what + ": inputs need a batch dimension")
+    b = x.shape[0]
+    d = rows[0].numel()
+    if d < 1 or any(u.numel() != d for u in rows) or x.numel() != b * d:
+        raise VcnfError("%s: inputs %s for parameter rows of %s elements" % (what, tuple(x.shape), [u.numel() for u in rows]))
+    return dev, x.reshape(b, d).contiguous(), [u.reshape(-1).contiguous() for u in rows], b, d
+
+
+def _tail_like(t, x2, dtype, what, name):
+    t = t.to(dtype).reshape(len(x2), -1).contiguous()
+    if t.shape != x2.shape:
+        raise VcnfError("%s: %s does not have the shape of the input" % (what, name))
+    return t
+
+
+def tail_log_prob(z, loc, ls, shape, cst, family, logp=None, sign=1.0):
+    """vcnf_tail_log_prob_*: log density [B] of z [B, ...] under the product of Student-t (family 0) or generalised
+    Gaussian (1) factors with the rows loc / ls / shape / cst [D]; ``logp``: accumulate into it."""
+    name = "vcnf_tail_log_prob" + _sfx(z)
+    dev, z2, (loc, ls, shape, cst), b, d = _tail_operands(z, (loc, ls, shape, cst), name)
+    require_device(logp, f64=True)
+    mode = LD_ACCUM
+    if logp is None:
+        logp = torch.empty(b, dtype=z.dtype, device=dev)
+        mode = LD_STORE
+    elif logp.dtype != z.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
+        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(cst), _ptr(logp), b, d, int(family), mode,
+                                  float(sign), _stream())
+    _check(st, name)
+    return logp
+
+
+def tail_sample(eps, gamma, loc, ls, shape, cst, family):
+    """vcnf_tail_sample_*: (z like eps, log p(z) [B]) for the standard-normal draw eps and the gamma draw of its shape."""
+    name = "vcnf_tail_sample" + _sfx(eps)
+    dev, e2, (loc, ls, shape, cst), b, d = _tail_operands(eps, (loc, ls, shape, cst), name)
+    require_device(gamma, f64=True)
+    if gamma.dtype != eps.dtype:
+        raise VcnfError(name + ": mixed dtypes")
+    g2 = _tail_like(gamma, e2, eps.dtype, name, "gamma")
+    z = torch.empty_like(e2)
+    logp = torch.empty(b, dtype=eps.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(e2), _ptr(g2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(cst), _ptr(z), _ptr(logp), b, d,
+                                  int(family), _stream())
+    _check(st, name)
+    return z.view(eps.shape), logp
+
+
+def _tail_row_sums(launch, what, like, b, d, dev, rows):
+    """The VJP launch (given the workspace pointer) and, with ``rows``, vcnf_tail_reduce_partials_*: (d_loc, d_log_scale,
+    d_shape) [D], or three None without a launch of the reduction."""
+    if not rows:
+        _check(launch(None), what)
+        return None, None, None
+    out = torch.empty(3, d, dtype=like.dtype, device=dev)
+    if b == 0:
+        return tuple(out.zero_())
+    groups = int(lib().vcnf_tail_bwd_groups(b, d))
+    if groups < 1:
+        _check(2, what)
+    partials = torch.empty(groups, 3, d, dtype=like.dtype, device=dev)
+    _check(launch(_ptr(partials)), what)
+    name = "vcnf_tail_reduce_partials" + _sfx(like)
+    _check(getattr(lib(), name)(_ptr(partials), groups, d, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), name)
+    return tuple(out)
+
+
+def tail_log_prob_bwd(z, loc, ls, shape, family, g, gz_in=None, rows=True):
+    """vcnf_tail_log_prob_bwd_* and vcnf_tail_reduce_partials_*: (dz like z, d_loc, d_log_scale, d_shape [D]) for the
+    cotangent g [B] of the log density; d_shape is the part that does not go through cst, ``gz_in`` (like z) is added
+    to dz.  ``rows`` false: no row needs a gradient - dz only (the three others are None), no workspace, one launch."""
+    name = "vcnf_tail_log_prob_bwd" + _sfx(z)
+    dev, z2, (loc, ls, shape), b, d = _tail_operands(z, (loc, ls, shape), name)
+    require_device(g, gz_in, f64=True)
+    g = g.to(z.dtype).contiguous()
+    if tuple(g.shape) != (b,):
+        raise VcnfError(name + ": g must be [batch]")
+    if gz_in is not None:
+        gz_in = _tail_like(gz_in, z2, z.dtype, name, "gz_in")
+    dz = torch.empty_like(z2)
+    with torch.cuda.device(dev):
+        fn = getattr(lib(), name)
+        launch = lambda ws: fn(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(g), _ptr(gz_in), _ptr(dz), ws, b, d,
+                               int(family), _stream())
+        sums = _tail_row_sums(launch, name, z, b, d, dev, rows)
+    return (dz.view(z.shape),) + sums
+
+
+def tail_sample_bwd(eps, gamma, loc, ls, shape, family, g_z=None, g_lp=None, rows=True, want_eps=True):
+    """vcnf_tail_sample_bwd_* and vcnf_tail_reduce_partials_*: (d_eps like eps or None, d_gamma like eps, d_loc,
+    d_log_scale, d_shape [D]) for the cotangents g_z (like eps) and g_lp [B] of vcnf_tail_sample_*; None is zero."""
+    name = "vcnf_tail_sample_bwd" + _sfx(eps)
+    dev, e2, (loc, ls, shape), b, d = _tail_operands(eps, (loc, ls, shape), name)
+    require_device(gamma, g_z, g_lp, f64=True)
+    g2 = _tail_like(gamma, e2, eps.dtype, name, "gamma")
+    if g_z is not None:
+        g_z = _tail_like(g_z, e2, eps.dtype, name, "g_z")
+    if g_lp is not None:
+        g_lp = g_lp.to(eps.dtype).contiguous()
+        if tuple(g_lp.shape) != (b,):
+            raise VcnfError(name + ": g_lp must be [batch]")
+    d_eps = torch.empty_like(e2) if want_eps else None
+    d_gamma = torch.empty_like(e2)
+    with torch.cuda.device(dev):
+        fn = getattr(lib(), name)
+        launch = lambda ws: fn(_ptr(e2), _ptr(g2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(g_z), _ptr(g_lp), _ptr(d_eps),
+                               _ptr(d_gamma), ws, b, d, int(family), _stream())
+        sums = _tail_row_sums(launch, name, eps, b, d, dev, rows)
+    return (d_eps.view(eps.shape) if want_eps else None, d_gamma.view(eps.shape)) + sums
 
 
 PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2

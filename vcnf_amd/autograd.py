@@ -447,6 +447,54 @@ class GaussianMixtureSampleFn(torch.autograd.Function):
             d_ls = d_ls + _lib.cc_gaussian_reduce_rows(dz * eps * scale, mode, m)
         return dz * scale, d_loc if need[1] else None, d_ls if need[2] else None, d_w if need[3] else None, None
 
+
+class HeavyTailLogProbFn(torch.autograd.Function):
+    """vcnf_tail_log_prob_*: log density of z [B, ...] under the product of Student-t / generalised Gaussian factors with
+    the rows loc, ls, shape (nu or beta) and cst (the normalisers) [D]; backward on vcnf_tail_log_prob_bwd_* and
+    vcnf_tail_reduce_partials_*.  d_shape is the density's own share; cst gets sum_b g per feature and the caller's
+    autograd carries it on to the tail parameter."""
+
+    @staticmethod
+    def forward(ctx, z, loc, ls, shape, cst, family):
+        with torch.no_grad():
+            lp = _lib.tail_log_prob(z, loc, ls, shape, cst, family)
+        ctx.save_for_backward(z, loc, ls, shape)
+        ctx.family = family
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        z, loc, ls, shape = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dz, d_loc, d_ls, d_sh = _lib.tail_log_prob_bwd(z, loc, ls, shape, ctx.family, g, rows=any(need[1:4]))
+        return (dz, d_loc if need[1] else None, d_ls if need[2] else None, d_sh if need[3] else None,
+                g.sum().expand(shape.shape) if need[4] else None, None)
+
+
+class HeavyTailSampleFn(torch.autograd.Function):
+    """vcnf_tail_sample_*: (z, log p(z)) from the standard-normal draw eps and the gamma draw; backward on
+    vcnf_tail_sample_bwd_* and vcnf_tail_reduce_partials_*, with respect to both draws and the four rows (the gradient
+    of gamma is what carries the tail parameter's pathwise share through torch's gamma sampler)."""
+
+    @staticmethod
+    def forward(ctx, eps, gamma, loc, ls, shape, cst, family):
+        with torch.no_grad():
+            z, lp = _lib.tail_sample(eps, gamma, loc, ls, shape, cst, family)
+        ctx.save_for_backward(eps, gamma, loc, ls, shape)
+        ctx.family = family
+        return z, lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_z, g_lp):
+        eps, gamma, loc, ls, shape = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_eps, d_gamma, d_loc, d_ls, d_sh = _lib.tail_sample_bwd(eps, gamma, loc, ls, shape, ctx.family, g_z, g_lp,
+                                                                 rows=any(need[2:5]), want_eps=need[0])
+        return (d_eps, d_gamma if need[1] else None, d_loc if need[2] else None, d_ls if need[3] else None,
+                d_sh if need[4] else None, g_lp.sum().expand(shape.shape) if need[5] else None, None)
+
 # Matrix path of the conditioner's dense layers on the training path at large batches: 'fp16x3' - forward products, the
 # 128 -> 128 layers' input gradients (csrc/linear_f16x3.hip) and the weight gradients (csrc/linear_wgrad.hip, split-half
 # form) on fp16 split-half operands with fp32 accumulation (error against fp64 below the library's fp32 GEMM on every

@@ -1,8 +1,12 @@
 """Base distribution end caps of the flow: the diagonal Gaussian (SURVEY 2 row 10;
 normflow/distributions/base.py:609-652) and the class-conditional bases of the
 reference's Glow, ClassCondDiagGaussian (:715-775) and GlowBase (:778-869), and the
-GaussianMixture of normflow 1.2.  The reference's other research distributions
-(GenNormal, T, GGD, ...) are out of scope."""
+GaussianMixture of normflow 1.2.  Of the heavy-tailed bases the followed fork adds, the
+product Student-t (its T) and the generalised Gaussian (its GGD) are StudentT and
+GeneralizedGaussian here, with one trainable tail parameter per feature; its other
+research distributions (GenNormal, the multivariate t, ...) are out of scope."""
+import math
+
 import numpy as np
 import torch
 from torch import nn
@@ -251,3 +255,104 @@ class GaussianMixture(BaseDistribution):
             lp = autograd.GaussianMixtureLogProbFn.apply(z, loc, ls, log_w)
             return lp if out is None else out.add_(lp)
         return _lib.gmm_log_prob(z, loc.detach(), ls.detach(), log_w.detach(), logp=out)
+
+
+class _HeavyTailBase(BaseDistribution):
+    """Shared end of the heavy-tailed product bases: location-scale families over ``shape`` with one tail parameter per
+    feature, u = (z - loc) / exp(log_scale) and a density cst - log_scale + f(u; tail) per feature.  Density, sampling
+    and their gradients run on the vcnf_tail_* kernels (csrc/heavy_tail.hip).  Everything of size [D] stays in torch:
+    a subclass gives ``_tail_rows()`` -> (tail row, normaliser row cst, gamma concentration), all functions of its log
+    tail parameter, and autograd carries the kernels' row gradients through them.  cst is computed in fp64 whatever the
+    module's dtype (in fp32 its lgamma terms cancel), then cast.  The random draws are torch's - a standard normal and a
+    gamma per element - and the kernels only transform them; the gamma draw is taken with autograd on, so torch's
+    implicit derivative carries the pathwise gradient to the tail parameter."""
+    _family = None
+    _tail = None          # name of the log tail parameter
+
+    def __init__(self, shape, tail, trainable):
+        super().__init__()
+        if isinstance(shape, int):
+            shape = (shape,)
+        self.shape = tuple(shape)
+        self.n_dim = len(self.shape)
+        self.d = int(np.prod(self.shape))
+        tail = np.broadcast_to(np.asarray(tail, dtype=np.float64), self.shape)
+        if not (tail > 0).all():
+            raise ValueError("%s: the tail parameter must be positive" % type(self).__name__)
+        dtype = torch.get_default_dtype()
+        tensors = (("loc", torch.zeros(1, *self.shape, dtype=dtype)), ("log_scale", torch.zeros(1, *self.shape, dtype=dtype)),
+                   (self._tail, torch.tensor(np.log(tail), dtype=dtype).reshape(1, *self.shape)))
+        for name, t in tensors:
+            if trainable:
+                setattr(self, name, nn.Parameter(t))
+            else:
+                self.register_buffer(name, t)
+
+    def _rows(self):
+        """(loc, log_scale, tail, cst [D], gamma concentration [1, *shape])"""
+        tail, cst, conc = self._tail_rows(getattr(self, self._tail))
+        return self.loc.reshape(-1), self.log_scale.reshape(-1), tail.reshape(-1), cst.to(tail.dtype).reshape(-1), conc
+
+    def forward(self, num_samples=1):
+        """Both draws on the device with torch, then one kernel for z and log p."""
+        _lib.require_device(self.loc, allow_grad=True, f64=True)
+        eps = torch.randn((num_samples,) + self.shape, dtype=self.loc.dtype, device=self.loc.device)
+        return self.from_noise(eps)
+
+    def from_noise(self, eps, gamma=None):
+        """``forward`` with the standard-normal draw supplied, and optionally the gamma draw (like eps)."""
+        _lib.require_device(eps, self.loc, gamma, allow_grad=True, f64=True)
+        loc, ls, tail, cst, conc = self._rows()
+        if gamma is None:
+            gamma = torch._standard_gamma(conc.expand(eps.shape))
+        if autograd.needs_grad(eps, gamma, loc, ls, tail, cst):
+            return autograd.HeavyTailSampleFn.apply(eps, gamma, loc, ls, tail, cst, self._family)
+        return _lib.tail_sample(eps, gamma, loc, ls, tail, cst, self._family)
+
+    def log_prob(self, z, out=None):
+        """``out`` [B]: accumulate into it instead of allocating."""
+        _lib.require_device(z, self.loc, allow_grad=True, f64=True)
+        loc, ls, tail, cst, _ = self._rows()
+        if autograd.needs_grad(z, loc, ls, tail, cst, out):
+            lp = autograd.HeavyTailLogProbFn.apply(z, loc, ls, tail, cst, self._family)
+            return lp if out is None else out.add_(lp)
+        return _lib.tail_log_prob(z, loc.detach(), ls.detach(), tail.detach(), cst.detach(), self._family, logp=out)
+
+
+class StudentT(_HeavyTailBase):
+    """Product of Student-t factors over ``shape``: per feature lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2 -
+    log_scale - (nu+1)/2 log1p(u^2/nu).  Parameters (buffers with ``trainable=False``) loc, log_scale, log_df
+    [1, *shape] with nu = exp(log_df); zeros, zeros, log(df), ``df`` a float or an array of ``shape``.  Sampling:
+    u = eps sqrt(nu / (2 gamma)) with eps ~ N(0, 1) and gamma ~ Gamma(nu/2, 1)."""
+    _family = _lib.TAIL_STUDENT_T
+    _tail = "log_df"
+
+    def __init__(self, shape, df=3.0, trainable=True):
+        super().__init__(shape, df, trainable)
+
+    def _tail_rows(self, log_df):
+        nu = torch.exp(log_df)
+        l64 = log_df.double()
+        n64 = torch.exp(l64)
+        cst = torch.lgamma(0.5 * (n64 + 1.0)) - torch.lgamma(0.5 * n64) - 0.5 * (l64 + math.log(math.pi))
+        return nu, cst, 0.5 * nu
+
+
+class GeneralizedGaussian(_HeavyTailBase):
+    """Product of generalised Gaussian factors over ``shape``: per feature log(beta) - log 2 - lgamma(1/beta) -
+    log_scale - |u|^beta; beta = 2 is a Gaussian of scale exp(log_scale) / sqrt 2, beta = 1 is Laplace.  Parameters
+    (buffers with ``trainable=False``) loc, log_scale, log_beta [1, *shape]; zeros, zeros, log(beta), ``beta`` a float or
+    an array of ``shape``.  At u == 0 the gradients of |u|^beta with respect to u and beta are 0 for every beta (for
+    beta < 1 a convention: the derivative is unbounded there).  Sampling: u = sign(eps) gamma^(1/beta) with
+    gamma ~ Gamma(1/beta, 1), so |u|^beta is gamma itself."""
+    _family = _lib.TAIL_GEN_GAUSSIAN
+    _tail = "log_beta"
+
+    def __init__(self, shape, beta=2.0, trainable=True):
+        super().__init__(shape, beta, trainable)
+
+    def _tail_rows(self, log_beta):
+        beta = torch.exp(log_beta)
+        l64 = log_beta.double()
+        cst = l64 - math.log(2.0) - torch.lgamma(torch.exp(-l64))
+        return beta, cst, 1.0 / beta
