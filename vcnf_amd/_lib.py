@@ -58,35 +58,26 @@ class RqsStackLayer(ctypes.Structure):
                 ("shared_w", ctypes.c_void_p), ("shared_h", ctypes.c_void_p), ("shared_d", ctypes.c_void_p)]
 
 
+_CFG, _CFG64 = ctypes.POINTER(RqsCfg), ctypes.POINTER(RqsCfg64)
+
 # name -> argtypes, exactly the prototypes of include/vcnf_hip.h
 PROTOTYPES = {
     "vcnf_abi_version": ([], _INT),
     "vcnf_status_string": ([_INT], ctypes.c_char_p),
-    "vcnf_rqs_elementwise_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64,
-                                  ctypes.POINTER(RqsCfg), _INT, _P, _P], _INT),
-    "vcnf_rqs_elementwise_strided_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64,
-                                          ctypes.POINTER(RqsCfg), _INT, _P, _P], _INT),
-    "vcnf_rqs_elementwise_bwd_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64,
-                                      ctypes.POINTER(RqsCfg), _INT, _P], _INT),
     "vcnf_affine_layer_fused_supported": ([_I32, _I32, _I32, _I32], _INT),
     "vcnf_affine_stack_fused_supported": ([_I32, _I32, _I32, _I32], _INT),
     "vcnf_affine_layer_fused_pack_floats": ([_I32, _I32, _I32], _I64),
-    "vcnf_affine_layer_fused_f32": ([_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _INT, _P, _I64,
-                                     _P, _P, _INT, _INT, _F32, _P], _INT),
-    "vcnf_rqs_shared_f32": ([_P, _P, _P, _P, _I64, _P, _P, _P, _I64, ctypes.POINTER(RqsCfg), _INT, _P, _P], _INT),
+    "vcnf_affine_layer_fused_f32": ([_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _INT, _P, _I64, _P,
+                                     _P, _INT, _INT, _F32, _P], _INT),
+    "vcnf_rqs_shared_f32": ([_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _CFG, _INT, _P, _P], _INT),
     "vcnf_rqs_final_fused_supported": ([_I32, _I32, _I32, _I32], _INT),
     "vcnf_rqs_final_fused_pack_floats": ([_I32, _I32, _I32], _I64),
     "vcnf_rqs_final_fused_partial_rows": ([_I32, _I32], _I64),
-    "vcnf_rqs_final_fused_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, ctypes.POINTER(RqsCfg), _INT,
-                                  _P, _P], _INT),
-    "vcnf_rqs_packed_bwd_f32": ([_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, ctypes.POINTER(RqsCfg), _INT, _P], _INT),
+    "vcnf_rqs_final_fused_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _CFG, _INT, _P, _P], _INT),
     "vcnf_rqs_shared_bwd_groups": ([_I64, _I64], _I64),
-    "vcnf_rqs_shared_bwd_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64,
-                                 ctypes.POINTER(RqsCfg), _INT, _P], _INT),
-    "vcnf_rqs_coupling_f32": ([_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _I64,
-                               ctypes.POINTER(RqsCfg), _INT, _INT, _F32, _P, _P], _INT),
-    "vcnf_rqs_conditioner_input_f32": ([_P, _I64, _I32, _P, _I32, _P, _I32, _P, _P, _P,
-                                        ctypes.POINTER(RqsCfg), _INT, _P, _P], _INT),
+    "vcnf_rqs_shared_bwd_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _CFG, _INT, _P], _INT),
+    "vcnf_rqs_coupling_f32": ([_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _I64, _CFG, _INT, _INT, _F32, _P, _P], _INT),
+    "vcnf_rqs_conditioner_input_f32": ([_P, _I64, _I32, _P, _I32, _P, _I32, _P, _P, _P, _CFG, _INT, _P, _P], _INT),
     "vcnf_conv1x1_supported": ([_I32, _I32], _INT),
     "vcnf_conv1x1_pack_floats": ([_I32, _I32], _I64),
     "vcnf_conv1x1_f16x3_f32": ([_P, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _I64, _INT, _F32, _INT, _F32, _P, _P], _INT),
@@ -99,111 +90,85 @@ PROTOTYPES = {
     "vcnf_conv3x3_1x1_f16x3_f32": ([_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _F32, _F32, _P, _P], _INT),
     "vcnf_convnet3_supported": ([_I32, _I32, _I32], _INT),
     "vcnf_convnet3_w3_pack_floats": ([_I32], _I64),
-    "vcnf_convnet3_taps_f16x3_f32": ([_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, _F32, _F32,
-                                      _P, _P], _INT),
+    "vcnf_convnet3_taps_f16x3_f32": ([_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, _F32,
+                                      _F32, _P, _P], _INT),
     "vcnf_col2im3x3_f32": ([_P, _P, _P, _I64, _I32, _I32, _I32, _P], _INT),
     "vcnf_resblock_elementwise_f32": ([_INT, _P, _P, _P, _P, _P, _I64, _P], _INT),
     "vcnf_channel_mix_supported": ([_I32], _INT),
     "vcnf_channel_mix_f32": ([_P, _P, _P, _P, _I64, _I32, _I64, _P], _INT),
     "vcnf_rqs_identity_half_supported": ([_I32, _I32], _INT),
     "vcnf_rqs_identity_half_partial_rows": ([_I32], _I64),
-    "vcnf_rqs_identity_half_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P, _P, ctypes.POINTER(RqsCfg), _INT, _INT,
-                                    _P, _P], _INT),
+    "vcnf_rqs_identity_half_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _CFG, _INT, _INT, _P, _P], _INT),
     "vcnf_rqs_layer_fused_pack_floats": ([_I32, _I32, _I32, _I32], _I64),
     "vcnf_rqs_layer_fused_supported": ([_I32, _I32, _I32, _I32, _I32, _I32, _I32], _INT),
     "vcnf_rqs_layer_fused_tile_rows": ([], _I32),
     "vcnf_rqs_layer_fused_small_batch_rows": ([_I64], _I64),
     "vcnf_masked_affine_stack_supported": ([_I32, _I32], _INT),
-    "vcnf_masked_affine_stack_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F32, _P], _INT),
-    "vcnf_masked_affine_stack_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F64, _P], _INT),
-    "vcnf_masked_affine_stack_bwd_f32": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _P], _INT),
-    "vcnf_masked_affine_stack_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _P], _INT),
     "vcnf_linear_f16x3_supported": ([_I32, _I32], _INT),
     "vcnf_linear_f16x3_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _INT, _INT, _P, _P, _P, _P], _INT),
     "vcnf_rqs_stack_fused_max_layers": ([], _I32),
-    "vcnf_rqs_stack_fused_f32": ([_P, _P, _P, _P, _I64, ctypes.POINTER(RqsStackLayer), _I32, _I32, _I32, _I32, _I32, _I32,
-                                  _I32, _I64, ctypes.POINTER(RqsCfg), _INT, _INT, _F32, _P, _P, _P, _P], _INT),
-    "vcnf_rqs_layer_fused_f32": ([_P, _P, _P, _P, _I64, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64,
-                                  _P, _P, _P, ctypes.POINTER(RqsCfg), _INT, _INT, _F32, _P, _P, _P, _P], _INT),
-    "vcnf_affine_coupling_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT, _INT,
-                                  _INT, _F32, _P], _INT),
+    "vcnf_rqs_stack_fused_f32": ([_P, _P, _P, _P, _I64, ctypes.POINTER(RqsStackLayer), _I32, _I32, _I32, _I32, _I32,
+                                  _I32, _I32, _I64, _CFG, _INT, _INT, _F32, _P, _P, _P, _P], _INT),
+    "vcnf_rqs_layer_fused_f32": ([_P, _P, _P, _P, _I64, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P,
+                                  _P, _CFG, _INT, _INT, _F32, _P, _P, _P, _P], _INT),
     "vcnf_resnet_trunk_supported": ([_I32, _I32, _I32], _INT),
     "vcnf_resnet_trunk_pack_floats": ([_I32, _I32, _I32], _I64),
     "vcnf_resnet_trunk_f32": ([_P, _P, _I64, _I32, _I32, _I32, _P, _I64, _P], _INT),
     "vcnf_resnet_trunk_split_f32": ([_P, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P], _INT),
-    "vcnf_rqs_final_fused_presplit_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, ctypes.POINTER(RqsCfg), _INT,
-                                           _P, _P], _INT),
-    "vcnf_affine_stack_fused_f32": ([_P, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _F32, _INT, _P, _I64, _P, _I32,
-                                     _INT, _INT, _F32, _P], _INT),
+    "vcnf_rqs_final_fused_presplit_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _CFG, _INT, _P, _P], _INT),
+    "vcnf_affine_stack_fused_f32": ([_P, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _F32, _INT, _P, _I64, _P,
+                                     _I32, _INT, _INT, _F32, _P], _INT),
     "vcnf_affine_layer_fused_h3_pack_floats": ([_I32, _I32, _I32], _I64),
-    "vcnf_affine_stack_fused_f16x3_f32": ([_P, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _F32, _INT, _P, _I64, _P, _I64,
-                                           _P, _I32, _INT, _INT, _F32, _P, _P], _INT),
-    "vcnf_maf_affine_f32": ([_P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P], _INT),
-    "vcnf_masked_affine_f32": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P], _INT),
-    "vcnf_affine_const_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _P], _INT),
-    "vcnf_permute_f32": ([_P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_split_columns_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_merge_columns_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_diag_gaussian_log_prob_f32": ([_P, _P, _P, _F32, _P, _I64, _I32, _INT, _F32, _P], _INT),
-    "vcnf_diag_gaussian_sample_f32": ([_P, _P, _P, _F32, _P, _P, _I64, _I32, _P], _INT),
+    "vcnf_affine_stack_fused_f16x3_f32": ([_P, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _F32, _INT, _P, _I64,
+                                           _P, _I64, _P, _I32, _INT, _INT, _F32, _P, _P], _INT),
     "vcnf_linear_probe_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _P, _P], _INT),
-    "vcnf_rqs_elementwise_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64,
-                                  ctypes.POINTER(RqsCfg64), _INT, _P, _P], _INT),
-    "vcnf_rqs_elementwise_bwd_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64,
-                                      ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
-    "vcnf_rqs_elementwise_strided_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64,
-                                          ctypes.POINTER(RqsCfg64), _INT, _P, _P], _INT),
-    "vcnf_rqs_packed_bwd_f64": ([_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
-    "vcnf_maf_affine_f64": ([_P, _P, _P, _P, _I64, _I32, _INT, _INT, _F64, _P], _INT),
-    "vcnf_affine_coupling_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT, _INT, _INT, _F64, _P], _INT),
-    "vcnf_masked_affine_f64": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F64, _P], _INT),
-    "vcnf_affine_const_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _P], _INT),
-    "vcnf_permute_f64": ([_P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_split_columns_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_merge_columns_f64": ([_P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_diag_gaussian_log_prob_f64": ([_P, _P, _P, _F64, _P, _I64, _I32, _INT, _F64, _P], _INT),
-    "vcnf_diag_gaussian_sample_f64": ([_P, _P, _P, _F64, _P, _P, _I64, _I32, _P], _INT),
-    "vcnf_rqs_elementwise_limits_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, ctypes.POINTER(RqsLimitBcast),
-                                         _P, _P, _I64, ctypes.POINTER(RqsCfg), _INT, _P, _P], _INT),
-    "vcnf_rqs_elementwise_limits_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, ctypes.POINTER(RqsLimitBcast),
-                                         _P, _P, _I64, ctypes.POINTER(RqsCfg64), _INT, _P, _P], _INT),
-    "vcnf_rqs_elementwise_limits_bwd_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
-                                             ctypes.POINTER(RqsLimitBcast), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                             _I64, ctypes.POINTER(RqsCfg), _INT, _P], _INT),
-    "vcnf_rqs_elementwise_limits_bwd_f64": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
-                                             ctypes.POINTER(RqsLimitBcast), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                             _I64, ctypes.POINTER(RqsCfg64), _INT, _P], _INT),
-    "vcnf_cc_gaussian_log_prob_f32": ([_P, _P, _P, _P, _F32, _P, _I64, _I32, _I32, _I64, _INT, _F32, _P], _INT),
-    "vcnf_cc_gaussian_sample_f32": ([_P, _P, _P, _P, _F32, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
-    "vcnf_cc_gaussian_log_prob_bwd_f32": ([_P, _P, _P, _P, _F32, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
-    "vcnf_cc_gaussian_sample_bwd_f32": ([_P, _P, _P, _F32, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
-    "vcnf_cc_gaussian_reduce_rows_f32": ([_P, _P, _P, _I64, _I32, _I64, _P], _INT),
-    "vcnf_cc_gaussian_log_prob_f64": ([_P, _P, _P, _P, _F64, _P, _I64, _I32, _I32, _I64, _INT, _F64, _P], _INT),
-    "vcnf_cc_gaussian_sample_f64": ([_P, _P, _P, _P, _F64, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
-    "vcnf_cc_gaussian_log_prob_bwd_f64": ([_P, _P, _P, _P, _F64, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
-    "vcnf_cc_gaussian_sample_bwd_f64": ([_P, _P, _P, _F64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P], _INT),
-    "vcnf_cc_gaussian_reduce_rows_f64": ([_P, _P, _P, _I64, _I32, _I64, _P], _INT),
     "vcnf_gmm_bwd_groups": ([_I64, _I32, _I32], _I64),
-    "vcnf_gmm_log_prob_f32": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F32, _P], _INT),
-    "vcnf_gmm_sample_f32": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_gmm_log_prob_bwd_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_gmm_reduce_partials_f32": ([_P, _I64, _I32, _I32, _P, _P, _P, _P], _INT),
-    "vcnf_gmm_log_prob_f64": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F64, _P], _INT),
-    "vcnf_gmm_sample_f64": ([_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_gmm_log_prob_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P], _INT),
-    "vcnf_gmm_reduce_partials_f64": ([_P, _I64, _I32, _I32, _P, _P, _P, _P], _INT),
     "vcnf_tail_bwd_groups": ([_I64, _I32], _I64),
-    "vcnf_tail_log_prob_f32": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P], _INT),
-    "vcnf_tail_sample_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
-    "vcnf_tail_log_prob_bwd_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
-    "vcnf_tail_sample_bwd_f32": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
-    "vcnf_tail_reduce_partials_f32": ([_P, _I64, _I32, _P, _P, _P, _P], _INT),
-    "vcnf_tail_log_prob_f64": ([_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F64, _P], _INT),
-    "vcnf_tail_sample_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
-    "vcnf_tail_log_prob_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
-    "vcnf_tail_sample_bwd_f64": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P], _INT),
-    "vcnf_tail_reduce_partials_f64": ([_P, _I64, _I32, _P, _P, _P, _P], _INT),
 }
+
+# Entry points that exist as name_f32 and name_f64 (all return int), stated once with the fp32 argument types: the
+# fp64 twin takes double for float and vcnf_rqs_cfg_f64 for vcnf_rqs_cfg
+_PAIRS = {
+    "vcnf_rqs_elementwise": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _CFG, _INT, _P, _P],
+    "vcnf_rqs_elementwise_strided": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _CFG, _INT, _P,
+                                     _P],
+    "vcnf_rqs_elementwise_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _CFG, _INT, _P],
+    "vcnf_rqs_packed_bwd": [_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, _CFG, _INT, _P],
+    "vcnf_masked_affine_stack": [_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F32, _P],
+    "vcnf_masked_affine_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _P],
+    "vcnf_affine_coupling": [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT, _INT, _INT, _F32, _P],
+    "vcnf_maf_affine": [_P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
+    "vcnf_masked_affine": [_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
+    "vcnf_affine_const": [_P, _P, _P, _P, _I64, _I32, _I32, _INT, _P],
+    "vcnf_permute": [_P, _P, _P, _I64, _I32, _I32, _P],
+    "vcnf_split_columns": [_P, _P, _P, _P, _I64, _I32, _I32, _P],
+    "vcnf_merge_columns": [_P, _P, _P, _P, _I64, _I32, _I32, _P],
+    "vcnf_diag_gaussian_log_prob": [_P, _P, _P, _F32, _P, _I64, _I32, _INT, _F32, _P],
+    "vcnf_diag_gaussian_sample": [_P, _P, _P, _F32, _P, _P, _I64, _I32, _P],
+    "vcnf_rqs_elementwise_limits": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, ctypes.POINTER(RqsLimitBcast),
+                                    _P, _P, _I64, _CFG, _INT, _P, _P],
+    "vcnf_rqs_elementwise_limits_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
+                                        ctypes.POINTER(RqsLimitBcast), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
+                                        _CFG, _INT, _P],
+    "vcnf_cc_gaussian_log_prob": [_P, _P, _P, _P, _F32, _P, _I64, _I32, _I32, _I64, _INT, _F32, _P],
+    "vcnf_cc_gaussian_sample": [_P, _P, _P, _P, _F32, _P, _P, _I64, _I32, _I32, _I64, _P],
+    "vcnf_cc_gaussian_log_prob_bwd": [_P, _P, _P, _P, _F32, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P],
+    "vcnf_cc_gaussian_sample_bwd": [_P, _P, _P, _F32, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P],
+    "vcnf_cc_gaussian_reduce_rows": [_P, _P, _P, _I64, _I32, _I64, _P],
+    "vcnf_gmm_log_prob": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F32, _P],
+    "vcnf_gmm_sample": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
+    "vcnf_gmm_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
+    "vcnf_gmm_reduce_partials": [_P, _I64, _I32, _I32, _P, _P, _P, _P],
+    "vcnf_tail_log_prob": [_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
+    "vcnf_tail_sample": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
+    "vcnf_tail_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
+    "vcnf_tail_sample_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
+    "vcnf_tail_reduce_partials": [_P, _I64, _I32, _P, _P, _P, _P],
+}
+_F64_TWIN = {_F32: _F64, _CFG: _CFG64}
+for _name, _args in _PAIRS.items():
+    PROTOTYPES[_name + "_f32"] = (_args, _INT)
+    PROTOTYPES[_name + "_f64"] = ([_F64_TWIN.get(a, a) for a in _args], _INT)
 
 _LIB = None
 
@@ -1288,6 +1253,47 @@ def merge_columns(pa, pb, idx32):
     return out
 
 
+def _log_t(temperature):
+    return 0.0 if temperature is None else math.log(temperature)
+
+
+def _logp_out(logp, b, like, dev, name):
+    """(logp, ld_mode) of a log_prob wrapper: a fresh [batch] tensor to store into, or the checked caller's tensor to
+    accumulate into."""
+    require_device(logp, f64=True)
+    if logp is None:
+        return torch.empty(b, dtype=like.dtype, device=dev), LD_STORE
+    if logp.dtype != like.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
+        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    return logp, LD_ACCUM
+
+
+def _check_index(idx, b, what, contiguous=False):
+    """A per-sample index (class label, mixture mode): int32 [batch]."""
+    if idx.dtype != torch.int32 or tuple(idx.shape) != (b,) or (contiguous and not idx.is_contiguous()):
+        raise VcnfError("%s must be %s int32 tensor [batch]" % (what, "a contiguous" if contiguous else "an"))
+
+
+def _block_sums(launch, what, outs, block, groups, reduce):
+    """Tail of the VJPs that sum over the batch.  ``launch`` (given the workspace pointer) writes one partial block of
+    shape ``block`` per workgroup; ``groups`` = (entry point that gives the number of workgroups, its arguments
+    (batch, ...)); ``reduce`` = (entry point that adds the blocks into the tensors ``outs`` in a fixed order, its size
+    arguments).  ``outs`` None: nobody wants the sums - one launch without a workspace, None."""
+    if outs is None:
+        _check(launch(None), what)
+        return None
+    (count, args), (red, dims) = groups, reduce
+    if args[0] == 0:
+        return tuple(t.zero_() for t in outs)
+    n = int(getattr(lib(), count)(*args))
+    if n < 1:
+        _check(2, what)
+    partials = torch.empty((n,) + tuple(block), dtype=outs[0].dtype, device=outs[0].device)
+    _check(launch(_ptr(partials)), what)
+    _check(getattr(lib(), red)(_ptr(partials), n, *dims, *map(_ptr, outs), _stream()), red)
+    return outs
+
+
 def diag_gaussian_log_prob(z, loc, log_scale, temperature=None, logp=None, sign=1.0):
     dev = require_device(z, loc, log_scale, logp, f64=True)
     if any(u is not None and u.dtype != z.dtype for u in (loc, log_scale, logp)):
@@ -1298,7 +1304,7 @@ def diag_gaussian_log_prob(z, loc, log_scale, temperature=None, logp=None, sign=
     if logp is None:
         logp = torch.empty(b, dtype=z.dtype, device=dev)
         mode = LD_STORE
-    lt = 0.0 if temperature is None else math.log(temperature)
+    lt = _log_t(temperature)
     with torch.cuda.device(dev):
         st = getattr(lib(), "vcnf_diag_gaussian_log_prob" + _sfx(z))(
             _ptr(z2), _ptr(loc.contiguous()), _ptr(log_scale.contiguous()), lt, _ptr(logp), b, z2.shape[1], mode, float(sign), _stream())
@@ -1314,7 +1320,7 @@ def diag_gaussian_sample(eps, loc, log_scale, temperature=None):
     e2 = eps.reshape(b, -1).contiguous()
     z = torch.empty_like(e2)
     logp = torch.empty(b, dtype=eps.dtype, device=dev)
-    lt = 0.0 if temperature is None else math.log(temperature)
+    lt = _log_t(temperature)
     with torch.cuda.device(dev):
         st = getattr(lib(), "vcnf_diag_gaussian_sample" + _sfx(eps))(
             _ptr(e2), _ptr(loc.contiguous()), _ptr(log_scale.contiguous()), lt, _ptr(z), _ptr(logp), b, e2.shape[1], _stream())
@@ -1335,15 +1341,11 @@ def _cc_operands(x, loc_rows, ls_rows, row_index, pixels, what):
     r, c = ls_rows.shape
     if pixels < 1 or c * pixels != x2.shape[1]:
         raise VcnfError("%s: %d channels x %d pixels for rows of %d elements" % (what, c, pixels, x2.shape[1]))
-    if row_index is not None and (row_index.dtype != torch.int32 or tuple(row_index.shape) != (b,)):
-        raise VcnfError(what + ": row_index must be an int32 tensor [batch]")
+    if row_index is not None:
+        _check_index(row_index, b, what + ": row_index")
     if row_index is None and r not in (1, b):
         raise VcnfError("%s: %d table rows for a batch of %d without row_index" % (what, r, b))
     return dev, x2, b, c, r
-
-
-def _log_t(temperature):
-    return 0.0 if temperature is None else math.log(temperature)
 
 
 def cc_gaussian_log_prob(z, loc_rows, ls_rows, row_index, pixels, temperature=None, logp=None, sign=1.0):
@@ -1351,13 +1353,7 @@ def cc_gaussian_log_prob(z, loc_rows, ls_rows, row_index, pixels, temperature=No
     the tables loc_rows / ls_rows [R, C]; ``logp``: accumulate into it."""
     name = "vcnf_cc_gaussian_log_prob" + _sfx(z)
     dev, z2, b, c, r = _cc_operands(z, loc_rows, ls_rows, row_index, pixels, name)
-    require_device(logp, f64=True)
-    mode = LD_ACCUM
-    if logp is None:
-        logp = torch.empty(b, dtype=z.dtype, device=dev)
-        mode = LD_STORE
-    elif logp.dtype != z.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
-        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    logp, mode = _logp_out(logp, b, z, dev, name)
     with torch.cuda.device(dev):
         st = getattr(lib(), name)(_ptr(z2), _ptr(loc_rows.contiguous()), _ptr(ls_rows.contiguous()), _ptr(row_index),
                                   _log_t(temperature), _ptr(logp), b, c, pixels, r, mode, float(sign), _stream())
@@ -1421,8 +1417,7 @@ def cc_gaussian_reduce_rows(per_sample, row_index, rows):
     dev = require_device(per_sample, row_index, f64=True)
     per_sample = per_sample.contiguous()
     b, c = per_sample.shape
-    if row_index.dtype != torch.int32 or tuple(row_index.shape) != (b,):
-        raise VcnfError(name + ": row_index must be an int32 tensor [batch]")
+    _check_index(row_index, b, name + ": row_index")
     out = torch.empty(rows, c, dtype=per_sample.dtype, device=dev)
     with torch.cuda.device(dev):
         st = getattr(lib(), name)(_ptr(per_sample), _ptr(row_index), _ptr(out), b, c, rows, _stream())
@@ -1452,13 +1447,7 @@ def gmm_log_prob(z, loc, ls, log_w, logp=None, sign=1.0):
     log_w [M]; ``logp``: accumulate into it."""
     name = "vcnf_gmm_log_prob" + _sfx(z)
     dev, z2, loc, ls, log_w, b, d, m = _gmm_operands(z, loc, ls, log_w, name)
-    require_device(logp, f64=True)
-    mode = LD_ACCUM
-    if logp is None:
-        logp = torch.empty(b, dtype=z.dtype, device=dev)
-        mode = LD_STORE
-    elif logp.dtype != z.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
-        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    logp, mode = _logp_out(logp, b, z, dev, name)
     with torch.cuda.device(dev):
         st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(logp), b, d, m, mode, float(sign),
                                   _stream())
@@ -1471,8 +1460,7 @@ def gmm_sample(eps, mode, loc, ls, log_w):
     name = "vcnf_gmm_sample" + _sfx(eps)
     dev, e2, loc, ls, log_w, b, d, m = _gmm_operands(eps, loc, ls, log_w, name)
     require_device(mode)
-    if mode.dtype != torch.int32 or tuple(mode.shape) != (b,) or not mode.is_contiguous():
-        raise VcnfError(name + ": mode must be a contiguous int32 tensor [batch]")
+    _check_index(mode, b, name + ": mode", contiguous=True)
     z = torch.empty_like(e2)
     logp = torch.empty(b, dtype=eps.dtype, device=dev)
     with torch.cuda.device(dev):
@@ -1497,28 +1485,14 @@ def gmm_log_prob_bwd(z, loc, ls, log_w, lse, g, gz_in=None, tables=True):
         if gz_in.shape != z2.shape:
             raise VcnfError(name + ": gz_in does not have the shape of z")
     dz = torch.empty_like(z2)
-    if not tables:
-        with torch.cuda.device(dev):
-            st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(lse), _ptr(g), _ptr(gz_in), _ptr(dz),
-                                      None, b, d, m, _stream())
-        _check(st, name)
-        return dz, None, None, None
-    d_loc, d_ls = torch.empty_like(loc), torch.empty_like(ls)
-    d_w = torch.empty_like(log_w)
-    if b == 0:
-        return dz, d_loc.zero_(), d_ls.zero_(), d_w.zero_()
-    groups = int(lib().vcnf_gmm_bwd_groups(b, d, m))
-    if groups < 1:
-        _check(2, name)
-    partials = torch.empty(groups, m, 2 * d + 1, dtype=z.dtype, device=dev)
+    outs = (torch.empty_like(loc), torch.empty_like(ls), torch.empty_like(log_w)) if tables else None
     with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(lse), _ptr(g), _ptr(gz_in), _ptr(dz),
-                                  _ptr(partials), b, d, m, _stream())
-        _check(st, name)
-        name = "vcnf_gmm_reduce_partials" + _sfx(z)
-        st = getattr(lib(), name)(_ptr(partials), groups, m, d, _ptr(d_loc), _ptr(d_ls), _ptr(d_w), _stream())
-    _check(st, name)
-    return dz, d_loc, d_ls, d_w
+        fn = getattr(lib(), name)
+        launch = lambda ws: fn(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(lse), _ptr(g), _ptr(gz_in), _ptr(dz), ws,
+                               b, d, m, _stream())
+        sums = _block_sums(launch, name, outs, (m, 2 * d + 1), ("vcnf_gmm_bwd_groups", (b, d, m)),
+                           ("vcnf_gmm_reduce_partials" + _sfx(z), (m, d)))
+    return (dz,) + (sums or (None, None, None))
 
 
 TAIL_STUDENT_T, TAIL_GEN_GAUSSIAN = 0, 1
@@ -1551,13 +1525,7 @@ def tail_log_prob(z, loc, ls, shape, cst, family, logp=None, sign=1.0):
     Gaussian (1) factors with the rows loc / ls / shape / cst [D]; ``logp``: accumulate into it."""
     name = "vcnf_tail_log_prob" + _sfx(z)
     dev, z2, (loc, ls, shape, cst), b, d = _tail_operands(z, (loc, ls, shape, cst), name)
-    require_device(logp, f64=True)
-    mode = LD_ACCUM
-    if logp is None:
-        logp = torch.empty(b, dtype=z.dtype, device=dev)
-        mode = LD_STORE
-    elif logp.dtype != z.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
-        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    logp, mode = _logp_out(logp, b, z, dev, name)
     with torch.cuda.device(dev):
         st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(cst), _ptr(logp), b, d, int(family), mode,
                                   float(sign), _stream())
@@ -1582,23 +1550,11 @@ def tail_sample(eps, gamma, loc, ls, shape, cst, family):
     return z.view(eps.shape), logp
 
 
-def _tail_row_sums(launch, what, like, b, d, dev, rows):
-    """The VJP launch (given the workspace pointer) and, with ``rows``, vcnf_tail_reduce_partials_*: (d_loc, d_log_scale,
-    d_shape) [D], or three None without a launch of the reduction."""
-    if not rows:
-        _check(launch(None), what)
-        return None, None, None
-    out = torch.empty(3, d, dtype=like.dtype, device=dev)
-    if b == 0:
-        return tuple(out.zero_())
-    groups = int(lib().vcnf_tail_bwd_groups(b, d))
-    if groups < 1:
-        _check(2, what)
-    partials = torch.empty(groups, 3, d, dtype=like.dtype, device=dev)
-    _check(launch(_ptr(partials)), what)
-    name = "vcnf_tail_reduce_partials" + _sfx(like)
-    _check(getattr(lib(), name)(_ptr(partials), groups, d, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), name)
-    return tuple(out)
+def _tail_row_sums(launch, what, like, b, d, rows):
+    """``launch`` and, with ``rows``, vcnf_tail_reduce_partials_*: (d_loc, d_log_scale, d_shape) [D], or three None."""
+    outs = tuple(torch.empty(3, d, dtype=like.dtype, device=like.device)) if rows else None
+    return _block_sums(launch, what, outs, (3, d), ("vcnf_tail_bwd_groups", (b, d)),
+                       ("vcnf_tail_reduce_partials" + _sfx(like), (d,))) or (None, None, None)
 
 
 def tail_log_prob_bwd(z, loc, ls, shape, family, g, gz_in=None, rows=True):
@@ -1618,7 +1574,7 @@ def tail_log_prob_bwd(z, loc, ls, shape, family, g, gz_in=None, rows=True):
         fn = getattr(lib(), name)
         launch = lambda ws: fn(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(g), _ptr(gz_in), _ptr(dz), ws, b, d,
                                int(family), _stream())
-        sums = _tail_row_sums(launch, name, z, b, d, dev, rows)
+        sums = _tail_row_sums(launch, name, z2, b, d, rows)
     return (dz.view(z.shape),) + sums
 
 
@@ -1641,7 +1597,7 @@ def tail_sample_bwd(eps, gamma, loc, ls, shape, family, g_z=None, g_lp=None, row
         fn = getattr(lib(), name)
         launch = lambda ws: fn(_ptr(e2), _ptr(g2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(g_z), _ptr(g_lp), _ptr(d_eps),
                                _ptr(d_gamma), ws, b, d, int(family), _stream())
-        sums = _tail_row_sums(launch, name, eps, b, d, dev, rows)
+        sums = _tail_row_sums(launch, name, e2, b, d, rows)
     return (d_eps.view(eps.shape) if want_eps else None, d_gamma.view(eps.shape)) + sums
 
 

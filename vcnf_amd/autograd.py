@@ -4,7 +4,6 @@ RQS couplings: when gradients are required the coupling layer 
 gather / conditioner / scatter in PyTorch (all differentiable) around this op, exactly the
 structure of the reference (flows/neural_spline/coupling.py:70-125), with the spline
 arithmetic and its gradient on the HIP kernels."""
-import math
 
 import torch
 from torch.nn import functional as F
@@ -313,7 +312,7 @@ class DiagGaussianLogProbFn(torch.autograd.Function):
         with torch.no_grad():
             lp = _lib.diag_gaussian_log_prob(z, loc, ls, temperature)
         ctx.save_for_backward(z, loc, ls)
-        ctx.lt = 0.0 if temperature is None else math.log(temperature)
+        ctx.lt = _lib._log_t(temperature)
         return lp
 
     @staticmethod
@@ -334,7 +333,7 @@ class DiagGaussianSampleFn(torch.autograd.Function):
         with torch.no_grad():
             z, lp = _lib.diag_gaussian_sample(eps, loc, ls, temperature)
         ctx.save_for_backward(eps, ls)
-        ctx.lt = 0.0 if temperature is None else math.log(temperature)
+        ctx.lt = _lib._log_t(temperature)
         return z, lp
 
     @staticmethod

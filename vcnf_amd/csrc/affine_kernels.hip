@@ -4,49 +4,23 @@
 // reduction: one group of G lanes (power of two <= 64) owns a sample, strides over
 // its row with coalesced accesses, and the log|det| partials are combined with
 // wave shuffles - no second pass over the data and no atomics.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
+#include <type_traits>
 
-#include "../../include/vcnf_hip.h"
+#include "stream_common.hpp"
 
 namespace vcnf {
 
+using namespace vcnf_stream;
+
 constexpr int kBlock = 256;
+constexpr int kMaxBlocks = 256 * 16;
+
+static inline dim3 grid_for(long long groups, int G) { return vcnf_stream::grid_for(groups, G, kBlock, kMaxBlocks); }
 
 // The kernels below that the reference's fp64 drivers reach (runadultvdeq.py:101-108,183: model.double() over
 // MaskedAffineFlow / ActNorm / DiagGaussian stacks) are templates on the scalar type; the fp32 instantiations are the
 // code they always were, the fp64 ones use the double-precision library functions.
-template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-  for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ void put_ld(T* ld, long long b, T v, int mode) {
-  ld[b] = mode ? ld[b] + v : v;
-}
-
-__device__ __forceinline__ float exp_(float v) { return expf(v); }
-__device__ __forceinline__ double exp_(double v) { return exp(v); }
-__device__ __forceinline__ float log_(float v) { return logf(v); }
-__device__ __forceinline__ double log_(double v) { return log(v); }
-
-// lanes per sample for a row of n elements
-static int pick_lanes(long long n) {
-  int G = 1;
-  while (G < 64 && G < n) G <<= 1;
-  return G;
-}
-
-static dim3 grid_for(long long batch, int G) {
-  const long long per_block = kBlock / G;
-  long long blocks = (batch + per_block - 1) / per_block;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (blocks < 1) blocks = 1;
-  return dim3((unsigned)blocks);
-}
+// Row sums are lanes_sum_descending throughout this unit.
 
 // torch.sigmoid and log(sigmoid) evaluated like the reference does
 // (flows/affine/coupling.py:128-136): sigma = 1/(1+exp(-v)), then log(sigma).
@@ -65,7 +39,6 @@ struct AffineArgsT {
   int scale_map, inverse, G, ld_mode;
   T ld_sign;
 };
-using AffineArgs = AffineArgsT<float>;
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void affine_coupling_kernel(const AffineArgsT<T> a) {
@@ -107,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void affine_coupling_kernel(const AffineArg
       }
       orow[e] = v;
     }
-    acc = group_sum(acc, a.G);
+    acc = lanes_sum_descending(acc, a.G);
     if (g == 0 && a.logdet) put_ld(a.logdet, b, a.ld_sign * acc, a.ld_mode);
   }
 }
@@ -126,7 +99,6 @@ struct MafArgsT {
   int D, inverse, G, ld_mode;
   T ld_sign;
 };
-using MafArgs = MafArgsT<float>;
 
 // one (scale logit, shift) pair per 8 / 16-byte load
 template <typename T> struct Pair;
@@ -149,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void maf_affine_kernel(const MafArgsT<T> a)
       a.out[b * a.D + j] = a.inverse ? (v - p.y) / scale : scale * v + p.y;
       acc += log_(scale);
     }
-    acc = group_sum(acc, a.G);
+    acc = lanes_sum_descending(acc, a.G);
     if (g == 0) put_ld(a.logdet, b, a.ld_sign * (a.inverse ? -acc : acc), a.ld_mode);
   }
 }
@@ -164,7 +136,6 @@ struct MaskedArgsT {
   int D, inverse, G, ld_mode;
   T ld_sign;
 };
-using MaskedArgs = MaskedArgsT<float>;
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void masked_affine_kernel(const MaskedArgsT<T> a) {
@@ -190,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void masked_affine_kernel(const MaskedArgsT
       a.out[e] = v;
       acc += om * sc;                                      // :210 / :221
     }
-    acc = group_sum(acc, a.G);
+    acc = lanes_sum_descending(acc, a.G);
     if (g == 0) put_ld(a.logdet, r, a.ld_sign * (a.inverse ? -acc : acc), a.ld_mode);
   }
 }
@@ -203,7 +174,6 @@ struct ConstArgsT {
   long long total;
   int C, inner, inverse;
 };
-using ConstArgs = ConstArgsT<float>;
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void affine_const_kernel(const ConstArgsT<T> a) {
@@ -223,7 +193,6 @@ struct PermArgsT {
   long long total;
   int C, inner;
 };
-using PermArgs = PermArgsT<float>;
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void permute_kernel(const PermArgsT<T> a) {
@@ -278,7 +247,6 @@ struct GaussArgsT {
   int D, G, ld_mode, sample;
   T log_temp, ld_sign, norm;   // norm = -0.5 * D * log(2 pi)
 };
-using GaussArgs = GaussArgsT<float>;
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void diag_gaussian_kernel(const GaussArgsT<T> a) {
@@ -298,7 +266,7 @@ __global__ __launch_bounds__(kBlock) void diag_gaussian_kernel(const GaussArgsT<
         acc += ls + T(0.5) * u * u;
       }
     }
-    acc = group_sum(acc, a.G);
+    acc = lanes_sum_descending(acc, a.G);
     if (g == 0) put_ld(a.logp, r, a.ld_sign * (a.norm - acc), a.ld_mode);
   }
 }
@@ -308,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void diag_gaussian_kernel(const GaussArgsT<
 // outputs, so the compiler cannot hoist them out of the row loop above), and two rows are in flight per lane group.
 // 1M x 64: 201 -> 151 us per call (HBM floor 32 us); the four-columns-per-lane kernel below takes the aligned shapes.
 template <int NC>
-__global__ __launch_bounds__(kBlock) void diag_gaussian_cols_kernel(const GaussArgs a) {
+__global__ __launch_bounds__(kBlock) void diag_gaussian_cols_kernel(const GaussArgsT<float> a) {
   const int g = threadIdx.x & (a.G - 1);
   const int per_block = kBlock / a.G;
   float ls[NC], sc[NC], lc[NC];
@@ -347,8 +315,8 @@ __global__ __launch_bounds__(kBlock) void diag_gaussian_cols_kernel(const GaussA
         }
       }
     }
-    acc0 = group_sum(acc0, a.G);
-    acc1 = group_sum(acc1, a.G);
+    acc0 = lanes_sum_descending(acc0, a.G);
+    acc1 = lanes_sum_descending(acc1, a.G);
     if (g == 0) {
       put_ld(a.logp, r, a.ld_sign * (a.norm - acc0), a.ld_mode);
       if (two) put_ld(a.logp, r2, a.ld_sign * (a.norm - acc1), a.ld_mode);
@@ -359,7 +327,7 @@ __global__ __launch_bounds__(kBlock) void diag_gaussian_cols_kernel(const GaussA
 // D % 4 == 0, D <= 256, 16-byte aligned rows: a lane owns FOUR ADJACENT columns (one 16-byte load / store per row), a
 // row is shared by G = pow2 >= D / 4 lanes, so the log2(G) shuffle steps of the row sum are paid once per four elements
 // (with one column per lane a 64-feature row spent more instructions in the reduction than in the density).
-__global__ __launch_bounds__(kBlock) void diag_gaussian_vec4_kernel(const GaussArgs a) {
+__global__ __launch_bounds__(kBlock) void diag_gaussian_vec4_kernel(const GaussArgsT<float> a) {
   const int g = threadIdx.x & (a.G - 1);
   const int per_block = kBlock / a.G;
   const bool have = 4 * g < a.D;
@@ -398,8 +366,8 @@ __global__ __launch_bounds__(kBlock) void diag_gaussian_vec4_kernel(const GaussA
       reinterpret_cast<float4*>(a.z)[r * d4 + g] = make_float4(o0[0], o0[1], o0[2], o0[3]);
       if (two) reinterpret_cast<float4*>(a.z)[r2 * d4 + g] = make_float4(o1[0], o1[1], o1[2], o1[3]);
     }
-    acc0 = group_sum(have ? acc0 : 0.f, a.G);
-    acc1 = group_sum(have ? acc1 : 0.f, a.G);
+    acc0 = lanes_sum_descending(have ? acc0 : 0.f, a.G);
+    acc1 = lanes_sum_descending(have ? acc1 : 0.f, a.G);
     if (g == 0) {
       put_ld(a.logp, r, a.ld_sign * (a.norm - acc0), a.ld_mode);
       if (two) put_ld(a.logp, r2, a.ld_sign * (a.norm - acc1), a.ld_mode);
@@ -407,8 +375,114 @@ __global__ __launch_bounds__(kBlock) void diag_gaussian_vec4_kernel(const GaussA
   }
 }
 
-static inline bool ok_ld(int m) { return m == VCNF_LD_STORE || m == VCNF_LD_ACCUM; }
-static inline int launched() { return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH; }
+
+// ------------------------------------------------------------------ host side: one function per entry point, T = float / double
+template <typename T>
+static int affine_coupling(const T* z, const T* param, T* out, T* logdet, int64_t batch, int32_t channels, int32_t inner,
+                           int32_t t_off, int32_t d_t, int scale_map, int inverse, int ld_mode, T ld_sign, void* stream) {
+  if (batch < 0 || channels < 1 || inner < 1 || t_off < 0 || d_t < 0 || t_off + d_t > channels) return VCNF_ERR_SHAPE;
+  if (scale_map < VCNF_SCALE_EXP || scale_map > VCNF_SCALE_NONE) return VCNF_ERR_UNSUPPORTED;
+  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
+  if (batch == 0) return VCNF_OK;
+  if (!z || !out || (d_t > 0 && !param)) return VCNF_ERR_NULL;
+  if (scale_map != VCNF_SCALE_NONE && !logdet) return VCNF_ERR_NULL;
+  AffineArgsT<T> a{z, param, out, logdet, batch, channels, inner, t_off, d_t, scale_map, inverse ? 1 : 0,
+                   pick_lanes((long long)channels * inner), ld_mode, ld_sign};
+  hipLaunchKernelGGL(affine_coupling_kernel<T>, grid_for(batch, a.G), dim3(kBlock), 0,
+                     (hipStream_t)stream, a);
+  return launched();
+}
+
+template <typename T>
+static int maf_affine(const T* x, const T* params, T* out, T* logdet, int64_t batch, int32_t features, int inverse,
+                      int ld_mode, T ld_sign, void* stream) {
+  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
+  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
+  if (batch == 0) return VCNF_OK;
+  if (!x || !params || !out || !logdet) return VCNF_ERR_NULL;
+  if (reinterpret_cast<uintptr_t>(params) & (2 * sizeof(T) - 1)) return VCNF_ERR_ALIGN;   // float2 / double2 loads
+  MafArgsT<T> a{x, params, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
+  hipLaunchKernelGGL(maf_affine_kernel<T>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
+  return launched();
+}
+
+template <typename T>
+static int masked_affine(const T* z, const T* s, const T* t, const T* b, T* out, T* logdet, int64_t batch,
+                         int32_t features, int inverse, int ld_mode, T ld_sign, void* stream) {
+  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
+  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
+  if (batch == 0) return VCNF_OK;
+  if (!z || !b || !out || !logdet) return VCNF_ERR_NULL;
+  MaskedArgsT<T> a{z, s, t, b, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
+  hipLaunchKernelGGL(masked_affine_kernel<T>, grid_for(batch, a.G), dim3(kBlock), 0,
+                     (hipStream_t)stream, a);
+  return launched();
+}
+
+template <typename T>
+static int affine_const(const T* z, const T* s, const T* t, T* out, int64_t batch, int32_t channels, int32_t inner,
+                        int inverse, void* stream) {
+  if (batch < 0 || channels < 1 || inner < 1) return VCNF_ERR_SHAPE;
+  if (batch == 0) return VCNF_OK;
+  if (!z || !out) return VCNF_ERR_NULL;
+  ConstArgsT<T> a{z, s, t, out, batch * (long long)channels * inner, channels, inner, inverse ? 1 : 0};
+  hipLaunchKernelGGL(affine_const_kernel<T>, grid_for(a.total, 1), dim3(kBlock), 0, (hipStream_t)stream, a);
+  return launched();
+}
+
+template <typename T>
+static int permute(const T* z, const int32_t* idx, T* out, int64_t batch, int32_t channels, int32_t inner, void* stream) {
+  if (batch < 0 || channels < 1 || inner < 1) return VCNF_ERR_SHAPE;
+  if (batch == 0) return VCNF_OK;
+  if (!z || !idx || !out) return VCNF_ERR_NULL;
+  PermArgsT<T> a{z, idx, out, batch * (long long)channels * inner, channels, inner};
+  hipLaunchKernelGGL(permute_kernel<T>, grid_for(a.total, 1), dim3(kBlock), 0, (hipStream_t)stream, a);
+  return launched();
+}
+
+template <typename T, bool MERGE>
+static int split_merge(const T* z, T* out, T* pa, T* pb, const int32_t* idx, int64_t batch, int32_t channels,
+                       int32_t first, void* stream) {
+  if (batch < 0 || channels < 1 || first < 0 || first > channels) return VCNF_ERR_SHAPE;
+  if (batch == 0) return VCNF_OK;
+  if (!(MERGE ? (const void*)out : (const void*)z) || !idx || (first > 0 && !pa) || (first < channels && !pb)) return VCNF_ERR_NULL;
+  SplitArgsT<T> a{z, out, pa, pb, idx, batch * (long long)channels, channels, first};
+  hipLaunchKernelGGL((split_merge_kernel<T, MERGE>), grid_for(a.total, 1), dim3(kBlock), 0,
+                     (hipStream_t)stream, a);
+  return launched();
+}
+
+// fp32 rows of at most 4 columns per lane take the kernels that keep the column constants in registers; everything
+// else, and fp64 always, takes the generic kernel
+template <typename T>
+static int gauss(const T* in, const T* loc, const T* log_scale, T log_temperature, T* z, T* logp, int64_t batch,
+                 int32_t features, int ld_mode, T ld_sign, int sample, void* stream) {
+  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
+  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
+  if (batch == 0) return VCNF_OK;
+  if (!in || !loc || !log_scale || !logp || (sample && !z)) return VCNF_ERR_NULL;
+  GaussArgsT<T> a{in, loc, log_scale, z, logp, batch, features, pick_lanes(features), ld_mode, sample,
+                  log_temperature, ld_sign, (T)(-0.5 * (double)features * log(2.0 * M_PI))};
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec4 = std::is_same<T, float>::value && features % 4 == 0 && features <= 256 &&
+                    all_aligned({in, sample ? z : nullptr}, 16);
+  if (vec4) a.G = pick_lanes(features / 4);
+  const dim3 grid = grid_for(batch, a.G);
+  if constexpr (std::is_same<T, float>::value) {
+    if (vec4) {
+      hipLaunchKernelGGL(diag_gaussian_vec4_kernel, grid, dim3(kBlock), 0, st, a);
+      return launched();
+    }
+    switch ((features + a.G - 1) / a.G) {
+      case 1: hipLaunchKernelGGL(diag_gaussian_cols_kernel<1>, grid, dim3(kBlock), 0, st, a); return launched();
+      case 2: hipLaunchKernelGGL(diag_gaussian_cols_kernel<2>, grid, dim3(kBlock), 0, st, a); return launched();
+      case 3: hipLaunchKernelGGL(diag_gaussian_cols_kernel<3>, grid, dim3(kBlock), 0, st, a); return launched();
+      case 4: hipLaunchKernelGGL(diag_gaussian_cols_kernel<4>, grid, dim3(kBlock), 0, st, a); return launched();
+    }
+  }
+  hipLaunchKernelGGL(diag_gaussian_kernel<T>, grid, dim3(kBlock), 0, st, a);
+  return launched();
+}
 
 }  // namespace vcnf
 
@@ -429,228 +503,48 @@ extern "C" const char* vcnf_status_string(int status) {
   }
 }
 
-extern "C" int vcnf_affine_coupling_f32(const float* z, const float* param, float* out, float* logdet,
-                                        int64_t batch, int32_t channels, int32_t inner,
-                                        int32_t t_off, int32_t d_t, int scale_map, int inverse,
-                                        int ld_mode, float ld_sign, void* stream) {
-  if (batch < 0 || channels < 1 || inner < 1 || t_off < 0 || d_t < 0 || t_off + d_t > channels) return VCNF_ERR_SHAPE;
-  if (scale_map < VCNF_SCALE_EXP || scale_map > VCNF_SCALE_NONE) return VCNF_ERR_UNSUPPORTED;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !out || (d_t > 0 && !param)) return VCNF_ERR_NULL;
-  if (scale_map != VCNF_SCALE_NONE && !logdet) return VCNF_ERR_NULL;
-  AffineArgs a{z, param, out, logdet, batch, channels, inner, t_off, d_t, scale_map, inverse ? 1 : 0,
-               pick_lanes((long long)channels * inner), ld_mode, ld_sign};
-  hipLaunchKernelGGL(affine_coupling_kernel<float>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_maf_affine_f32(const float* x, const float* params, float* out, float* logdet, int64_t batch,
-                                   int32_t features, int inverse, int ld_mode, float ld_sign, void* stream) {
-  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!x || !params || !out || !logdet) return VCNF_ERR_NULL;
-  if (reinterpret_cast<uintptr_t>(params) & 7) return VCNF_ERR_ALIGN;
-  MafArgs a{x, params, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
-  hipLaunchKernelGGL(maf_affine_kernel<float>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_masked_affine_f32(const float* z, const float* s, const float* t, const float* b,
-                                      float* out, float* logdet, int64_t batch, int32_t features,
-                                      int inverse, int ld_mode, float ld_sign, void* stream) {
-  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !b || !out || !logdet) return VCNF_ERR_NULL;
-  MaskedArgs a{z, s, t, b, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
-  hipLaunchKernelGGL(masked_affine_kernel<float>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_affine_const_f32(const float* z, const float* s, const float* t, float* out,
-                                     int64_t batch, int32_t channels, int32_t inner, int inverse, void* stream) {
-  if (batch < 0 || channels < 1 || inner < 1) return VCNF_ERR_SHAPE;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !out) return VCNF_ERR_NULL;
-  ConstArgs a{z, s, t, out, batch * (long long)channels * inner, channels, inner, inverse ? 1 : 0};
-  long long blocks = (a.total + kBlock - 1) / kBlock;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(affine_const_kernel<float>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_permute_f32(const float* z, const int32_t* idx, float* out,
-                                int64_t batch, int32_t channels, int32_t inner, void* stream) {
-  if (batch < 0 || channels < 1 || inner < 1) return VCNF_ERR_SHAPE;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !idx || !out) return VCNF_ERR_NULL;
-  PermArgs a{z, idx, out, batch * (long long)channels * inner, channels, inner};
-  long long blocks = (a.total + kBlock - 1) / kBlock;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(permute_kernel<float>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-template <typename T, bool MERGE>
-static int split_merge(const T* z, T* out, T* pa, T* pb, const int32_t* idx, int64_t batch, int32_t channels,
-                       int32_t first, void* stream) {
-  if (batch < 0 || channels < 1 || first < 0 || first > channels) return VCNF_ERR_SHAPE;
-  if (batch == 0) return VCNF_OK;
-  if (!(MERGE ? (const void*)out : (const void*)z) || !idx || (first > 0 && !pa) || (first < channels && !pb)) return VCNF_ERR_NULL;
-  SplitArgsT<T> a{z, out, pa, pb, idx, batch * (long long)channels, channels, first};
-  long long blocks = (a.total + kBlock - 1) / kBlock;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL((split_merge_kernel<T, MERGE>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_split_columns_f32(const float* z, const int32_t* idx, float* first_part, float* second_part,
-                                      int64_t batch, int32_t channels, int32_t first, void* stream) {
-  return split_merge<float, false>(z, nullptr, first_part, second_part, idx, batch, channels, first, stream);
-}
-extern "C" int vcnf_merge_columns_f32(const float* first_part, const float* second_part, const int32_t* idx, float* out,
-                                      int64_t batch, int32_t channels, int32_t first, void* stream) {
-  return split_merge<float, true>(nullptr, out, const_cast<float*>(first_part), const_cast<float*>(second_part), idx,
-                                  batch, channels, first, stream);
-}
-extern "C" int vcnf_split_columns_f64(const double* z, const int32_t* idx, double* first_part, double* second_part,
-                                      int64_t batch, int32_t channels, int32_t first, void* stream) {
-  return split_merge<double, false>(z, nullptr, first_part, second_part, idx, batch, channels, first, stream);
-}
-extern "C" int vcnf_merge_columns_f64(const double* first_part, const double* second_part, const int32_t* idx, double* out,
-                                      int64_t batch, int32_t channels, int32_t first, void* stream) {
-  return split_merge<double, true>(nullptr, out, const_cast<double*>(first_part), const_cast<double*>(second_part), idx,
-                                   batch, channels, first, stream);
-}
-
-static int gauss(const float* in, const float* loc, const float* log_scale, float log_temperature,
-                 float* z, float* logp, int64_t batch, int32_t features, int ld_mode, float ld_sign,
-                 int sample, void* stream) {
-  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!in || !loc || !log_scale || !logp || (sample && !z)) return VCNF_ERR_NULL;
-  GaussArgs a{in, loc, log_scale, z, logp, batch, features, pick_lanes(features), ld_mode, sample,
-              log_temperature, ld_sign, (float)(-0.5 * (double)features * log(2.0 * M_PI))};
-  hipStream_t st = (hipStream_t)stream;
-  const bool al16 = ((reinterpret_cast<uintptr_t>(in) | (sample ? reinterpret_cast<uintptr_t>(z) : 0)) & 15) == 0;
-  if (features % 4 == 0 && features <= 256 && al16) {
-    a.G = pick_lanes(features / 4);
-    hipLaunchKernelGGL(diag_gaussian_vec4_kernel, grid_for(batch, a.G), dim3(kBlock), 0, st, a);
-    return launched();
+#define VCNF_AFFINE_ENTRY_POINTS(T, SFX)                                                                               \
+  extern "C" int vcnf_affine_coupling_##SFX(const T* z, const T* param, T* out, T* logdet, int64_t batch,              \
+                                            int32_t channels, int32_t inner, int32_t t_off, int32_t d_t,               \
+                                            int scale_map, int inverse, int ld_mode, T ld_sign, void* stream) {        \
+    return affine_coupling<T>(z, param, out, logdet, batch, channels, inner, t_off, d_t, scale_map, inverse, ld_mode,  \
+                              ld_sign, stream);                                                                        \
+  }                                                                                                                    \
+  extern "C" int vcnf_maf_affine_##SFX(const T* x, const T* params, T* out, T* logdet, int64_t batch,                  \
+                                       int32_t features, int inverse, int ld_mode, T ld_sign, void* stream) {          \
+    return maf_affine<T>(x, params, out, logdet, batch, features, inverse, ld_mode, ld_sign, stream);                  \
+  }                                                                                                                    \
+  extern "C" int vcnf_masked_affine_##SFX(const T* z, const T* s, const T* t, const T* b, T* out, T* logdet,           \
+                                          int64_t batch, int32_t features, int inverse, int ld_mode, T ld_sign,        \
+                                          void* stream) {                                                              \
+    return masked_affine<T>(z, s, t, b, out, logdet, batch, features, inverse, ld_mode, ld_sign, stream);              \
+  }                                                                                                                    \
+  extern "C" int vcnf_affine_const_##SFX(const T* z, const T* s, const T* t, T* out, int64_t batch, int32_t channels,  \
+                                         int32_t inner, int inverse, void* stream) {                                   \
+    return affine_const<T>(z, s, t, out, batch, channels, inner, inverse, stream);                                     \
+  }                                                                                                                    \
+  extern "C" int vcnf_permute_##SFX(const T* z, const int32_t* idx, T* out, int64_t batch, int32_t channels,           \
+                                    int32_t inner, void* stream) {                                                     \
+    return permute<T>(z, idx, out, batch, channels, inner, stream);                                                    \
+  }                                                                                                                    \
+  extern "C" int vcnf_split_columns_##SFX(const T* z, const int32_t* idx, T* first_part, T* second_part,               \
+                                          int64_t batch, int32_t channels, int32_t first, void* stream) {              \
+    return split_merge<T, false>(z, nullptr, first_part, second_part, idx, batch, channels, first, stream);            \
+  }                                                                                                                    \
+  extern "C" int vcnf_merge_columns_##SFX(const T* first_part, const T* second_part, const int32_t* idx, T* out,       \
+                                          int64_t batch, int32_t channels, int32_t first, void* stream) {              \
+    return split_merge<T, true>(nullptr, out, const_cast<T*>(first_part), const_cast<T*>(second_part), idx, batch,     \
+                                channels, first, stream);                                                              \
+  }                                                                                                                    \
+  extern "C" int vcnf_diag_gaussian_log_prob_##SFX(const T* z, const T* loc, const T* log_scale, T log_temperature,    \
+                                                   T* logp, int64_t batch, int32_t features, int ld_mode, T ld_sign,   \
+                                                   void* stream) {                                                     \
+    return gauss<T>(z, loc, log_scale, log_temperature, nullptr, logp, batch, features, ld_mode, ld_sign, 0, stream);  \
+  }                                                                                                                    \
+  extern "C" int vcnf_diag_gaussian_sample_##SFX(const T* eps, const T* loc, const T* log_scale, T log_temperature,    \
+                                                 T* z, T* logp, int64_t batch, int32_t features, void* stream) {       \
+    return gauss<T>(eps, loc, log_scale, log_temperature, z, logp, batch, features, VCNF_LD_STORE, T(1), 1, stream);   \
   }
-  const int nc = (features + a.G - 1) / a.G;
-  const dim3 grid = grid_for(batch, a.G);
-  switch (nc) {
-    case 1: hipLaunchKernelGGL(diag_gaussian_cols_kernel<1>, grid, dim3(kBlock), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(diag_gaussian_cols_kernel<2>, grid, dim3(kBlock), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(diag_gaussian_cols_kernel<3>, grid, dim3(kBlock), 0, st, a); break;
-    case 4: hipLaunchKernelGGL(diag_gaussian_cols_kernel<4>, grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL(diag_gaussian_kernel<float>, grid, dim3(kBlock), 0, st, a); break;
-  }
-  return launched();
-}
 
-extern "C" int vcnf_diag_gaussian_log_prob_f32(const float* z, const float* loc, const float* log_scale,
-                                               float log_temperature, float* logp, int64_t batch,
-                                               int32_t features, int ld_mode, float ld_sign, void* stream) {
-  return gauss(z, loc, log_scale, log_temperature, nullptr, logp, batch, features, ld_mode, ld_sign, 0, stream);
-}
-
-extern "C" int vcnf_diag_gaussian_sample_f32(const float* eps, const float* loc, const float* log_scale,
-                                             float log_temperature, float* z, float* logp, int64_t batch,
-                                             int32_t features, void* stream) {
-  return gauss(eps, loc, log_scale, log_temperature, z, logp, batch, features, VCNF_LD_STORE, 1.f, 1, stream);
-}
-
-// ------------------------------------------------------------------ fp64 entry points (same contracts, T = double)
-extern "C" int vcnf_affine_coupling_f64(const double* z, const double* param, double* out, double* logdet,
-                                        int64_t batch, int32_t channels, int32_t inner,
-                                        int32_t t_off, int32_t d_t, int scale_map, int inverse,
-                                        int ld_mode, double ld_sign, void* stream) {
-  if (batch < 0 || channels < 1 || inner < 1 || t_off < 0 || d_t < 0 || t_off + d_t > channels) return VCNF_ERR_SHAPE;
-  if (scale_map < VCNF_SCALE_EXP || scale_map > VCNF_SCALE_NONE) return VCNF_ERR_UNSUPPORTED;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !out || (d_t > 0 && !param)) return VCNF_ERR_NULL;
-  if (scale_map != VCNF_SCALE_NONE && !logdet) return VCNF_ERR_NULL;
-  AffineArgsT<double> a{z, param, out, logdet, batch, channels, inner, t_off, d_t, scale_map, inverse ? 1 : 0,
-                        pick_lanes((long long)channels * inner), ld_mode, ld_sign};
-  hipLaunchKernelGGL(affine_coupling_kernel<double>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_maf_affine_f64(const double* x, const double* params, double* out, double* logdet, int64_t batch,
-                                   int32_t features, int inverse, int ld_mode, double ld_sign, void* stream) {
-  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!x || !params || !out || !logdet) return VCNF_ERR_NULL;
-  if (reinterpret_cast<uintptr_t>(params) & 15) return VCNF_ERR_ALIGN;       // double2 loads
-  MafArgsT<double> a{x, params, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
-  hipLaunchKernelGGL(maf_affine_kernel<double>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_masked_affine_f64(const double* z, const double* s, const double* t, const double* b,
-                                      double* out, double* logdet, int64_t batch, int32_t features,
-                                      int inverse, int ld_mode, double ld_sign, void* stream) {
-  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !b || !out || !logdet) return VCNF_ERR_NULL;
-  MaskedArgsT<double> a{z, s, t, b, out, logdet, batch, features, inverse ? 1 : 0, pick_lanes(features), ld_mode, ld_sign};
-  hipLaunchKernelGGL(masked_affine_kernel<double>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_affine_const_f64(const double* z, const double* s, const double* t, double* out,
-                                     int64_t batch, int32_t channels, int32_t inner, int inverse, void* stream) {
-  if (batch < 0 || channels < 1 || inner < 1) return VCNF_ERR_SHAPE;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !out) return VCNF_ERR_NULL;
-  ConstArgsT<double> a{z, s, t, out, batch * (long long)channels * inner, channels, inner, inverse ? 1 : 0};
-  long long blocks = (a.total + kBlock - 1) / kBlock;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(affine_const_kernel<double>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_permute_f64(const double* z, const int32_t* idx, double* out,
-                                int64_t batch, int32_t channels, int32_t inner, void* stream) {
-  if (batch < 0 || channels < 1 || inner < 1) return VCNF_ERR_SHAPE;
-  if (batch == 0) return VCNF_OK;
-  if (!z || !idx || !out) return VCNF_ERR_NULL;
-  PermArgsT<double> a{z, idx, out, batch * (long long)channels * inner, channels, inner};
-  long long blocks = (a.total + kBlock - 1) / kBlock;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  hipLaunchKernelGGL(permute_kernel<double>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-static int gauss64(const double* in, const double* loc, const double* log_scale, double log_temperature,
-                   double* z, double* logp, int64_t batch, int32_t features, int ld_mode, double ld_sign,
-                   int sample, void* stream) {
-  if (batch < 0 || features < 1) return VCNF_ERR_SHAPE;
-  if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
-  if (batch == 0) return VCNF_OK;
-  if (!in || !loc || !log_scale || !logp || (sample && !z)) return VCNF_ERR_NULL;
-  GaussArgsT<double> a{in, loc, log_scale, z, logp, batch, features, pick_lanes(features), ld_mode, sample,
-                       log_temperature, ld_sign, -0.5 * (double)features * log(2.0 * M_PI)};
-  hipLaunchKernelGGL(diag_gaussian_kernel<double>, grid_for(batch, a.G), dim3(kBlock), 0, (hipStream_t)stream, a);
-  return launched();
-}
-
-extern "C" int vcnf_diag_gaussian_log_prob_f64(const double* z, const double* loc, const double* log_scale,
-                                               double log_temperature, double* logp, int64_t batch,
-                                               int32_t features, int ld_mode, double ld_sign, void* stream) {
-  return gauss64(z, loc, log_scale, log_temperature, nullptr, logp, batch, features, ld_mode, ld_sign, 0, stream);
-}
-
-extern "C" int vcnf_diag_gaussian_sample_f64(const double* eps, const double* loc, const double* log_scale,
-                                             double log_temperature, double* z, double* logp, int64_t batch,
-                                             int32_t features, void* stream) {
-  return gauss64(eps, loc, log_scale, log_temperature, z, logp, batch, features, VCNF_LD_STORE, 1.0, 1, stream);
-}
+VCNF_AFFINE_ENTRY_POINTS(float, f32)
+VCNF_AFFINE_ENTRY_POINTS(double, f64)

@@ -13,31 +13,19 @@
 //     shuffle sums inside the group; flat rows need no sum at all.
 //   reduce_rows: the per-sample [B, C] gradients summed onto the R table rows in a fixed order.
 // No atomics anywhere: the same call twice gives the same bits.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/vcnf_hip.h"
+#include "stream_common.hpp"
 
 namespace vcnf_cc {
+
+using namespace vcnf_stream;
 
 constexpr int kBlock = 256;
 constexpr int kMaxBlocks = 256 * 16;
 constexpr int kReduceWaves = 16;
 
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-  T v[V];
-};
+// Row and segment sums are lanes_sum_descending throughout this unit.
 
-template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-  for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-__device__ __forceinline__ float exp_(float v) { return expf(v); }
-__device__ __forceinline__ double exp_(double v) { return exp(v); }
+static inline dim3 grid_for(long long groups, int G) { return vcnf_stream::grid_for(groups, G, kBlock, kMaxBlocks); }
 
 // table row of sample b; bad: the label is outside the table (row 0 is read instead, R >= 1)
 __device__ __forceinline__ long long pick_row(const int32_t* idx, long long R, long long b, bool& bad) {
@@ -48,20 +36,6 @@ __device__ __forceinline__ long long pick_row(const int32_t* idx, long long R, l
   const long long r = idx[b];
   bad = r < 0 || r >= R;
   return bad ? 0 : r;
-}
-
-static int pick_lanes(long long n) {
-  int G = 1;
-  while (G < 64 && G < n) G <<= 1;
-  return G;
-}
-
-static dim3 grid_for(long long groups, int G) {
-  const long long per_block = kBlock / G;
-  long long blocks = (groups + per_block - 1) / per_block;
-  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-  if (blocks < 1) blocks = 1;
-  return dim3((unsigned)blocks);
 }
 
 // ------------------------------------------------------------------ log_prob / sample
@@ -140,10 +114,10 @@ __global__ __launch_bounds__(kBlock) void cc_gaussian_fwd_kernel(const FwdArgs<T
         out[v] = o;
       }
     }
-    acc = group_sum(acc, a.G);
+    acc = lanes_sum_descending(acc, a.G);
     if (g == 0) {
       const T lp = bad ? T(NAN) : a.ld_sign * (a.norm - acc);
-      a.logp[b] = a.ld_mode ? a.logp[b] + lp : lp;
+      put_ld(a.logp, b, lp, a.ld_mode);
     }
   }
 }
@@ -209,8 +183,8 @@ __global__ __launch_bounds__(kBlock) void cc_gaussian_bwd_kernel(const BwdArgs<T
       }
       out[v] = o;
     }
-    s1 = group_sum(s1, a.G);
-    s2 = group_sum(s2, a.G);
+    s1 = lanes_sum_descending(s1, a.G);
+    s2 = lanes_sum_descending(s2, a.G);
     if (g == 0) {
       const T dls = SAMPLE ? s2 - T(a.P) * gb : gb * (s2 - T(a.P));
       a.d_loc[r] = bad ? T(NAN) : s1;
@@ -299,10 +273,6 @@ __global__ __launch_bounds__(64 * kReduceWaves) void cc_gaussian_reduce_rows_ker
   }
 }
 
-static inline bool ok_ld(int m) { return m == VCNF_LD_STORE || m == VCNF_LD_ACCUM; }
-static inline int launched() { return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH; }
-static inline bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
 static int check_shape(int64_t batch, int32_t C, int32_t P, int64_t R, const int32_t* idx) {
   if (batch < 0 || C < 1 || P < 1 || R < 1 || (long long)C * P > (1LL << 30)) return VCNF_ERR_SHAPE;
   if (!idx && R != 1 && R != batch && batch != 0) return VCNF_ERR_SHAPE;
@@ -317,9 +287,7 @@ static int forward(const T* in, const T* loc, const T* ls, const int32_t* idx, T
   if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
   if (batch == 0) return VCNF_OK;
   if (!in || !loc || !ls || !logp || (sample && !z)) return VCNF_ERR_NULL;
-  if (!aligned(in, sizeof(T)) || !aligned(loc, sizeof(T)) || !aligned(ls, sizeof(T)) || !aligned(logp, sizeof(T)) ||
-      !aligned(z, sizeof(T)) || !aligned(idx, 4))
-    return VCNF_ERR_ALIGN;
+  if (!all_aligned({in, loc, ls, logp, z}, sizeof(T)) || !aligned(idx, 4)) return VCNF_ERR_ALIGN;
   const long long d = (long long)C * P;
   FwdArgs<T> a{in, loc, ls, idx, z, logp, batch, R, C, P, 1, ld_mode, sample,
                log_temp, ld_sign, (T)(-0.5 * (double)d * log(2.0 * M_PI))};
@@ -345,10 +313,7 @@ static int backward(const T* in, const T* gz, const T* loc, const T* ls, const i
   if (const int st = check_shape(batch, C, P, R, idx)) return st;
   if (batch == 0) return VCNF_OK;
   if (!in || (SAMPLE ? !gz : !loc) || !ls || !gvec || !out || !d_loc || !d_ls) return VCNF_ERR_NULL;
-  if (!aligned(in, sizeof(T)) || !aligned(gz, sizeof(T)) || !aligned(loc, sizeof(T)) || !aligned(ls, sizeof(T)) ||
-      !aligned(gvec, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(d_loc, sizeof(T)) || !aligned(d_ls, sizeof(T)) ||
-      !aligned(idx, 4))
-    return VCNF_ERR_ALIGN;
+  if (!all_aligned({in, gz, loc, ls, gvec, out, d_loc, d_ls}, sizeof(T)) || !aligned(idx, 4)) return VCNF_ERR_ALIGN;
   BwdArgs<T> a{in, gz, loc, ls, gvec, idx, out, d_loc, d_ls, batch, R, C, P, 1, log_temp};
   hipStream_t st = (hipStream_t)stream;
   const bool io16 = aligned(in, 16) && aligned(gz, 16) && aligned(out, 16);
@@ -370,7 +335,7 @@ template <typename T>
 static int reduce_rows(const T* per_sample, const int32_t* idx, T* out, int64_t batch, int32_t C, int64_t R, void* stream) {
   if (batch < 0 || C < 1 || R < 1 || R > 65535) return VCNF_ERR_SHAPE;
   if (!per_sample || !idx || !out) return VCNF_ERR_NULL;
-  if (!aligned(per_sample, sizeof(T)) || !aligned(out, sizeof(T)) || !aligned(idx, 4)) return VCNF_ERR_ALIGN;
+  if (!all_aligned({per_sample, out}, sizeof(T)) || !aligned(idx, 4)) return VCNF_ERR_ALIGN;
   ReduceArgs<T> a{per_sample, idx, out, batch, C};
   hipLaunchKernelGGL(cc_gaussian_reduce_rows_kernel<T>, dim3((unsigned)((C + 63) / 64), (unsigned)R),
                      dim3(64 * kReduceWaves), 0, (hipStream_t)stream, a);

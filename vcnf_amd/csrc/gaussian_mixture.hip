@@ -18,15 +18,11 @@
 //            caller's workspace when LDS cannot hold them), each table entry owned by one lane; the workgroup's block
 //            [M, 2 D + 1] goes to the workspace and reduce_partials adds the blocks in a fixed order.
 // No atomics anywhere: the same call twice gives the same bits.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include <initializer_list>
-
-#include "../../include/vcnf_hip.h"
+#include "stream_common.hpp"
 
 namespace vcnf_gmm {
+
+using namespace vcnf_stream;
 
 constexpr int kFwdBlock = 256;
 constexpr int kBwdBlock = 64;                 // one wave: the cross-sample sums are shuffles, no barrier in the loop
@@ -34,26 +30,8 @@ constexpr int kRegPacks = 4;                  // packs of a row a lane keeps in 
 constexpr int kMaxFwdBlocks = 2048;
 constexpr int kMaxTable = 8192;               // M * D
 constexpr size_t kLdsBytes = 160 * 1024;
-constexpr int kRedEl = 16, kRedSl = 16;       // reduce_partials: elements x group slices per workgroup
 
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-  T v[V];
-};
-
-__device__ __forceinline__ float exp_(float v) { return expf(v); }
-__device__ __forceinline__ double exp_(double v) { return exp(v); }
-__device__ __forceinline__ float log_(float v) { return logf(v); }
-__device__ __forceinline__ double log_(double v) { return log(v); }
-__device__ __forceinline__ float abs_(float v) { return fabsf(v); }
-__device__ __forceinline__ double abs_(double v) { return fabs(v); }
-
-// sum over the lanes whose index differs in the bits [from, to): inside a lane group (1, G) or across the groups (G, 64)
-template <typename T>
-__device__ __forceinline__ T lanes_sum(T v, int from, int to) {
-  for (int m = from; m < to; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
+// Every sum over lanes in this unit is the ascending lanes_sum: inside a lane group (1, G), across the groups (G, 64).
 
 // c[m] = log_w[m] - sum_d log_scale[m, d] + norm, summed by one whole wave in a fixed order
 template <typename T>
@@ -212,7 +190,7 @@ __global__ __launch_bounds__(kFwdBlock) void gmm_fwd_kernel(const FwdArgs<T> a) 
     }
     if (g == 0) {
       const T lp = bad ? T(NAN) : a.sign * (mx + log_(s));
-      a.logp[b] = a.ld_mode ? a.logp[b] + lp : lp;
+      put_ld(a.logp, b, lp, a.ld_mode);
     }
   }
 }
@@ -359,50 +337,22 @@ __global__ __launch_bounds__(kBwdBlock) void gmm_bwd_kernel(const BwdArgs<T> a) 
   }
 }
 
-// out = sum over the blocks k of partials[k]: slice s of a workgroup adds its run of blocks in ascending order, the slices
-// are added in ascending order
+// element (m, c) of the summed block [M, 2 D + 1] goes to d_loc [M, D] | d_log_scale [M, D] | d_log_w [M]
 template <typename T>
-__global__ __launch_bounds__(kRedEl * kRedSl) void gmm_reduce_partials_kernel(const T* __restrict__ partials, long long groups,
-                                                                             int M, int D, T* d_loc, T* d_ls, T* d_w) {
-  __shared__ T part[kRedSl][kRedEl];
-  const int el = threadIdx.x % kRedEl, sl = threadIdx.x / kRedEl;
-  const int W = 2 * D + 1;
-  const long long n = (long long)M * W;
-  const long long e = (long long)blockIdx.x * kRedEl + el;
-  const long long len = (groups + kRedSl - 1) / kRedSl;
-  const long long k0 = sl * len, k1 = (k0 + len < groups) ? k0 + len : groups;
-  T acc = 0;
-  if (e < n)
-    for (long long k = k0; k < k1; ++k) acc += partials[k * n + e];
-  part[sl][el] = acc;
-  __syncthreads();
-  if (sl == 0 && e < n) {
-    T s = part[0][el];
-    for (int k = 1; k < kRedSl; ++k) s += part[k][el];
+struct TableDest {
+  T *d_loc, *d_ls, *d_w;
+  int D;
+  __device__ T* operator()(long long e) const {
+    const int W = 2 * D + 1;
     const int m = (int)(e / W), c = (int)(e - (long long)m * W);
-    if (c < D)
-      d_loc[m * D + c] = s;
-    else if (c < 2 * D)
-      d_ls[m * D + c - D] = s;
-    else
-      d_w[m] = s;
+    return c < D ? d_loc + m * D + c : c < 2 * D ? d_ls + m * D + c - D : d_w + m;
   }
-}
+};
 
 // ------------------------------------------------------------------ host side
-static inline bool ok_ld(int m) { return m == VCNF_LD_STORE || m == VCNF_LD_ACCUM; }
-static inline int launched() { return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH; }
-static inline bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
 static int check_shape(int64_t batch, int32_t D, int32_t M) {
   if (batch < 0 || D < 1 || M < 1 || (long long)D * M > kMaxTable) return VCNF_ERR_SHAPE;
   return VCNF_OK;
-}
-
-static int pick_lanes(int n) {
-  int G = 1;
-  while (G < 64 && G < n) G <<= 1;
-  return G;
 }
 
 // number of partial blocks = workgroups of the VJP: a pure function of the shape
@@ -446,17 +396,6 @@ static int launch_bwd(const BwdArgs<T>& a, dim3 grid, size_t lds, hipStream_t st
   return launched();
 }
 
-// widest pack (in elements) that divides the rows and that every row buffer is aligned to
-template <typename T>
-static int pick_pack(int32_t D, std::initializer_list<const void*> rows) {
-  for (int V = 16 / (int)sizeof(T); V > 1; V >>= 1) {
-    bool ok = D % V == 0;
-    for (const void* p : rows) ok = ok && aligned(p, V * sizeof(T));
-    if (ok) return V;
-  }
-  return 1;
-}
-
 template <typename T>
 static int forward(const T* in, const int32_t* mode, const T* loc, const T* ls, const T* logw, T* z, T* logp, int64_t batch,
                    int32_t D, int32_t M, int ld_mode, T sign, int sample, void* stream) {
@@ -464,18 +403,13 @@ static int forward(const T* in, const int32_t* mode, const T* loc, const T* ls, 
   if (!ok_ld(ld_mode)) return VCNF_ERR_UNSUPPORTED;
   if (batch == 0) return VCNF_OK;
   if (!in || !loc || !ls || !logw || !logp || (sample && (!z || !mode))) return VCNF_ERR_NULL;
-  if (!aligned(in, sizeof(T)) || !aligned(loc, sizeof(T)) || !aligned(ls, sizeof(T)) || !aligned(logw, sizeof(T)) ||
-      !aligned(logp, sizeof(T)) || !aligned(z, sizeof(T)) || !aligned(mode, 4))
-    return VCNF_ERR_ALIGN;
+  if (!all_aligned({in, loc, ls, logw, logp, z}, sizeof(T)) || !aligned(mode, 4)) return VCNF_ERR_ALIGN;
   FwdArgs<T> a{make_tables(loc, ls, logw, D, M), in, mode, z, logp, batch, 1, ld_mode, sample, sign};
   const int V = pick_pack<T>(D, {in, z});
   const int nv = D / V;
   a.G = pick_lanes(nv);
   const bool reg = nv <= kRegPacks * a.G;
-  const long long per_block = kFwdBlock / a.G;
-  long long blocks = (batch + per_block - 1) / per_block;
-  blocks = blocks > kMaxFwdBlocks ? kMaxFwdBlocks : blocks;
-  const dim3 grid((unsigned)blocks);
+  const dim3 grid = grid_for(batch, a.G, kFwdBlock, kMaxFwdBlocks);
   const size_t lds = table_bytes(a.t);
   hipStream_t st = (hipStream_t)stream;
 #define VCNF_GMM_FWD(VV) (reg ? launch_fwd<T, VV, true>(a, grid, lds, st) : launch_fwd<T, VV, false>(a, grid, lds, st))
@@ -493,10 +427,7 @@ static int backward(const T* z, const T* loc, const T* ls, const T* logw, const 
   if (const int st = check_shape(batch, D, M)) return st;
   if (batch == 0) return VCNF_OK;
   if (!z || !loc || !ls || !logw || !lse || !g || !dz) return VCNF_ERR_NULL;
-  if (!aligned(z, sizeof(T)) || !aligned(loc, sizeof(T)) || !aligned(ls, sizeof(T)) || !aligned(logw, sizeof(T)) ||
-      !aligned(lse, sizeof(T)) || !aligned(g, sizeof(T)) || !aligned(gz_in, sizeof(T)) || !aligned(dz, sizeof(T)) ||
-      !aligned(partials, sizeof(T)))
-    return VCNF_ERR_ALIGN;
+  if (!all_aligned({z, loc, ls, logw, lse, g, gz_in, dz, partials}, sizeof(T))) return VCNF_ERR_ALIGN;
   BwdArgs<T> a{make_tables(loc, ls, logw, D, M), z, lse, g, gz_in, dz, partials, batch, 1};
   const int V = pick_pack<T>(D, {z, gz_in, dz});
   const int nv = D / V;
@@ -524,12 +455,8 @@ static int reduce_partials(const T* partials, int64_t groups, int32_t M, int32_t
   if (groups < 1) return VCNF_ERR_SHAPE;
   if (const int st = check_shape(0, D, M)) return st;
   if (!partials || !d_loc || !d_ls || !d_w) return VCNF_ERR_NULL;
-  if (!aligned(partials, sizeof(T)) || !aligned(d_loc, sizeof(T)) || !aligned(d_ls, sizeof(T)) || !aligned(d_w, sizeof(T)))
-    return VCNF_ERR_ALIGN;
-  const long long n = (long long)M * (2LL * D + 1);
-  hipLaunchKernelGGL(gmm_reduce_partials_kernel<T>, dim3((unsigned)((n + kRedEl - 1) / kRedEl)), dim3(kRedEl * kRedSl), 0,
-                     (hipStream_t)stream, partials, (long long)groups, M, D, d_loc, d_ls, d_w);
-  return launched();
+  if (!all_aligned({partials, d_loc, d_ls, d_w}, sizeof(T))) return VCNF_ERR_ALIGN;
+  return launch_reduce_partials(partials, groups, (long long)M * (2LL * D + 1), TableDest<T>{d_loc, d_ls, d_w, D}, stream);
 }
 
 }  // namespace vcnf_gmm

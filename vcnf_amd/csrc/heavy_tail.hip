@@ -17,43 +17,15 @@
 // for that go to a kernel in which a lane owns one pack of features and walks the samples.  Every workgroup writes one
 // block [3, D] (d_loc | d_log_scale | the data part of d_shape) and reduce_partials adds the blocks in a fixed order.
 // No atomics anywhere: the same call twice gives the same bits.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include <initializer_list>
-
-#include "../../include/vcnf_hip.h"
+#include "stream_common.hpp"
 
 namespace vcnf_tail {
+
+using namespace vcnf_stream;
 
 constexpr int kBlock = 256;
 constexpr int kRegPacks = 2;                  // packs of a row a lane keeps in registers
 constexpr int kMaxFwdBlocks = 2048;
-constexpr int kRedEl = 16, kRedSl = 16;       // reduce_partials: elements x group slices per workgroup
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) Pack {
-  T v[V];
-};
-
-__device__ __forceinline__ float exp_(float v) { return expf(v); }
-__device__ __forceinline__ double exp_(double v) { return exp(v); }
-__device__ __forceinline__ float log_(float v) { return logf(v); }
-__device__ __forceinline__ double log_(double v) { return log(v); }
-__device__ __forceinline__ float log1p_(float v) { return log1pf(v); }
-__device__ __forceinline__ double log1p_(double v) { return log1p(v); }
-__device__ __forceinline__ float sqrt_(float v) { return sqrtf(v); }
-__device__ __forceinline__ double sqrt_(double v) { return sqrt(v); }
-__device__ __forceinline__ float abs_(float v) { return fabsf(v); }
-__device__ __forceinline__ double abs_(double v) { return fabs(v); }
-
-// sum over the lanes of a lane group (lane indices that differ in the bits below G)
-template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-  for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // ------------------------------------------------------------------ the two families
 // f(u; shape)
@@ -173,10 +145,10 @@ __global__ __launch_bounds__(kBlock) void tail_fwd_kernel(const FwdArgs<T> a) {
     } else {
       for (int v = g; v < nv; v += G) pack(v, load_rows<T, V, SAMPLE>(a.r, v));
     }
-    s = group_sum(s, G);
+    s = lanes_sum(s, 1, G);
     if (g == 0) {
       const T lp = a.sign * s;
-      a.logp[b] = a.ld_mode ? a.logp[b] + lp : lp;
+      put_ld(a.logp, b, lp, a.ld_mode);
     }
   }
 }
@@ -331,61 +303,20 @@ __global__ __launch_bounds__(kBlock) void tail_bwd_cols_kernel(const BwdArgs<T> 
   }
 }
 
-// out = sum over the blocks k of partials[k]: slice s of a workgroup adds its run of blocks in ascending order, the slices
-// are added in ascending order
+// element e of the summed block [3, D] goes to d_loc | d_log_scale | d_shape [D]
 template <typename T>
-__global__ __launch_bounds__(kRedEl * kRedSl) void tail_reduce_partials_kernel(const T* __restrict__ partials, long long groups,
-                                                                              int D, T* d_loc, T* d_ls, T* d_shape) {
-  __shared__ T part[kRedSl][kRedEl];
-  const int el = threadIdx.x % kRedEl, sl = threadIdx.x / kRedEl;
-  const long long n = 3LL * D;
-  const long long e = (long long)blockIdx.x * kRedEl + el;
-  const long long len = (groups + kRedSl - 1) / kRedSl;
-  const long long k0 = sl * len, k1 = (k0 + len < groups) ? k0 + len : groups;
-  T acc = 0;
-  if (e < n)
-    for (long long k = k0; k < k1; ++k) acc += partials[k * n + e];
-  part[sl][el] = acc;
-  __syncthreads();
-  if (sl == 0 && e < n) {
-    T s = part[0][el];
-    for (int k = 1; k < kRedSl; ++k) s += part[k][el];
-    if (e < D)
-      d_loc[e] = s;
-    else if (e < 2LL * D)
-      d_ls[e - D] = s;
-    else
-      d_shape[e - 2LL * D] = s;
+struct RowsDest {
+  T *d_loc, *d_ls, *d_shape;
+  int D;
+  __device__ T* operator()(long long e) const {
+    return e < D ? d_loc + e : e < 2LL * D ? d_ls + (e - D) : d_shape + (e - 2LL * D);
   }
-}
+};
 
 // ------------------------------------------------------------------ host side
-static inline bool ok_ld(int m) { return m == VCNF_LD_STORE || m == VCNF_LD_ACCUM; }
 static inline bool ok_family(int f) { return f == VCNF_TAIL_STUDENT_T || f == VCNF_TAIL_GEN_GAUSSIAN; }
-static inline int launched() { return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH; }
-static inline bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 static int check_shape(int64_t batch, int32_t D) { return batch < 0 || D < 1 ? VCNF_ERR_SHAPE : VCNF_OK; }
-
-static bool all_aligned(std::initializer_list<const void*> ps, uintptr_t n) {
-  for (const void* p : ps)
-    if (!aligned(p, n)) return false;
-  return true;
-}
-
-static int pick_lanes(int n) {
-  int G = 1;
-  while (G < 64 && G < n) G <<= 1;
-  return G;
-}
-
-// widest pack (in elements) that divides the rows and that every streamed buffer is aligned to
-template <typename T>
-static int pick_pack(int32_t D, std::initializer_list<const void*> bufs) {
-  for (int V = 16 / (int)sizeof(T); V > 1; V >>= 1)
-    if (D % V == 0 && all_aligned(bufs, V * sizeof(T))) return V;
-  return 1;
-}
 
 // number of partial blocks = workgroups (workgroup rows) of a VJP: a pure function of the shape
 static long long bwd_groups(int64_t batch, int32_t D) {
@@ -448,10 +379,7 @@ static int forward(const T* in, const T* gamma, const T* loc, const T* ls, const
   const int nv = D / V;
   const bool reg = nv <= kRegPacks * 64;
   a.G = reg ? pick_lanes((nv + kRegPacks - 1) / kRegPacks) : 64;
-  const long long per_block = kBlock / a.G;
-  long long blocks = (batch + per_block - 1) / per_block;
-  blocks = blocks > kMaxFwdBlocks ? kMaxFwdBlocks : blocks;
-  const dim3 grid((unsigned)blocks);
+  const dim3 grid = grid_for(batch, a.G, kBlock, kMaxFwdBlocks);
   hipStream_t st = (hipStream_t)stream;
 #define VCNF_TAIL_FWD(VV, FF) launch_fwd<T, VV, FF>(a, reg, sample, grid, st)
   VCNF_TAIL_DISPATCH(VCNF_TAIL_FWD);
@@ -495,10 +423,7 @@ static int reduce_partials(const T* partials, int64_t groups, int32_t D, T* d_lo
   if (groups < 1 || D < 1) return VCNF_ERR_SHAPE;
   if (!partials || !d_loc || !d_ls || !d_shape) return VCNF_ERR_NULL;
   if (!all_aligned({partials, d_loc, d_ls, d_shape}, sizeof(T))) return VCNF_ERR_ALIGN;
-  const long long n = 3LL * D;
-  hipLaunchKernelGGL(tail_reduce_partials_kernel<T>, dim3((unsigned)((n + kRedEl - 1) / kRedEl)), dim3(kRedEl * kRedSl), 0,
-                     (hipStream_t)stream, partials, (long long)groups, D, d_loc, d_ls, d_shape);
-  return launched();
+  return launch_reduce_partials(partials, groups, 3LL * D, RowsDest<T>{d_loc, d_ls, d_shape, D}, stream);
 }
 
 }  // namespace vcnf_tail
