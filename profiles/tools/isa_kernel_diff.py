@@ -1,0 +1,91 @@
+"""Device code of two source trees, kernel by kernel, without a GPU (profiles/stream_helpers.md section 1,
+profiles/rqs_host.md section 1):
+
+    isa_kernel_diff.py PARENT_CSRC NEW_CSRC [--work DIR] [--jobs N] [--reuse]
+
+Each unit below is compiled in both trees with the build's own flags plus --cuda-device-only -S.  The two outputs are
+cut into kernels, from the kernel's label to its .end_amdhsa_kernel (descriptor block included); the per-function
+numbers of local labels (.LBB<n>_, BB<n>_) and runs of blanks are normalised.  Prints one table row per unit and exits
+non-zero if a kernel symbol came or went or a kernel differs.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]
+from vcnf_amd.build import UNITS as BUILD_UNITS   # (source, extra flags, object name): the build's own list
+
+# the units that include rqs_host.hpp or host_common.hpp, directly or through rqs_math.hpp / stream_common.hpp
+CHECKED = ("rqs_kernels.hip", "rqs_backward.hip", "rqs_f64.hip", "fused_layer.hip", "fused_final.hip",
+           "fused_layer_v6.hip", "fused_layer_v6s.hip", "affine_kernels.hip", "class_cond_gaussian.hip",
+           "gaussian_mixture.hip", "heavy_tail.hip")
+UNITS = sorted(((s, e) for s, e, _ in BUILD_UNITS if s in CHECKED), key=lambda u: CHECKED.index(u[0]))
+# the flags of every unit as vcnf_amd/build.py build() sets them (a local of that function: keep the two alike)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S"]
+
+
+def kernels(path):
+    """{symbol: normalised text from the symbol's label to its .end_amdhsa_kernel}"""
+    lines = open(path).read().split("\n")
+    label = {m.group(1): i for i, m in enumerate(re.match(r"([A-Za-z_$][\w$.]*):", l) for l in lines) if m}
+    out = {}
+    for i, l in enumerate(lines):
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l)
+        if not m:
+            continue
+        end = next(j for j in range(i, len(lines)) if lines[j].strip() == ".end_amdhsa_kernel")
+        text = "\n".join(lines[label[m.group(1)]:end + 1])
+        text = re.sub(r"\.LBB\d+_", ".LBBn_", text)
+        text = re.sub(r"\bBB\d+_", "BBn_", text)
+        out[m.group(1)] = re.sub(r"[ \t]+", " ", text)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parent")
+    ap.add_argument("new")
+    ap.add_argument("--work", default=None)
+    ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--reuse", action="store_true", help="compare the assembly files already in --work")
+    args = ap.parse_args()
+    work = args.work or tempfile.mkdtemp(prefix="isa_diff_")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+    def compile_one(job):
+        tree, side, (src, extra) = job
+        out = os.path.join(work, side, os.path.splitext(src)[0] + "".join(extra).replace("=", "") + ".s")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        if not (args.reuse and os.path.exists(out)):
+            subprocess.run([hipcc] + FLAGS + extra + [src, "-o", out], cwd=tree, check=True)
+        return out
+
+    jobs = [(os.path.abspath(t), side, u) for u in UNITS for t, side in ((args.parent, "parent"), (args.new, "new"))]
+    with ThreadPoolExecutor(max_workers=args.jobs) as pool:
+        outs = list(pool.map(compile_one, jobs))
+    bad = 0
+    total = [0, 0, 0]
+    print("| unit | kernels at the parent | kept their symbol | identical |\n|---|---|---|---|")
+    for k, (src, extra) in enumerate(UNITS):
+        a, b = kernels(outs[2 * k]), kernels(outs[2 * k + 1])
+        kept = sorted(set(a) & set(b))
+        same = [s for s in kept if a[s] == b[s]]
+        for s in sorted(set(a) ^ set(b)):
+            print("  symbol only in %s: %s" % ("parent" if s in a else "new", s), file=sys.stderr)
+        for s in kept:
+            if a[s] != b[s]:
+                print("  differs: %s %s" % (src, s), file=sys.stderr)
+        bad += len(set(a) ^ set(b)) + len(kept) - len(same)
+        total = [total[0] + len(a), total[1] + len(kept), total[2] + len(same)]
+        print("| `%s`%s | %d | %d | %d |" % (src, " " + " ".join("`%s`" % e for e in extra) if extra else "",
+                                             len(a), len(kept), len(same)))
+    print("| total | %d | %d | %d |" % tuple(total))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,90 @@
+// Host-only check of csrc/rqs_host.hpp (g++ -std=c++17, no HIP): the bin-count dispatcher over its three lists, the
+// spline constants of one configuration against the expressions the units carried before the header existed, and
+// the number of derivative logits.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "rqs_host.hpp"
+
+using namespace vcnf;
+
+static int failures = 0;
+#define CHECK(cond)                                             \
+  do {                                                          \
+    if (!(cond)) {                                              \
+      printf("FAILED line %d: %s\n", __LINE__, #cond);          \
+      ++failures;                                               \
+    }                                                           \
+  } while (0)
+
+template <int... Ks>
+static void check_list(BinList<Ks...> list, const char* name) {
+  const int members[] = {Ks...};
+  for (int K = 1; K <= 1024; K = K < 70 ? K + 1 : 1024) {
+    bool in_list = false;
+    for (int m : members) in_list = in_list || m == K;
+    int got = -1, calls = 0;
+    with_bins(list, K, [&](auto kt) { got = decltype(kt)::value; ++calls; });
+    if (got != (in_list ? K : 0) || calls != 1) {
+      printf("FAILED with_bins(%s, %d): handed over %d in %d calls\n", name, K, got, calls);
+      ++failures;
+    }
+    got = -1, calls = 0;
+    const bool found = with_bins_only(list, K, [&](auto kt) { got = decltype(kt)::value; ++calls; });
+    if (found != in_list || got != (in_list ? K : -1) || calls != (in_list ? 1 : 0)) {
+      printf("FAILED with_bins_only(%s, %d): %d, handed over %d in %d calls\n", name, K, (int)found, got, calls);
+      ++failures;
+    }
+    if (K == 1024) break;
+  }
+}
+
+static bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof a) == 0; }
+
+int main() {
+  check_list(kBins, "kBins");
+  check_list(kBins64, "kBins64");
+  check_list(kBinsIdHalf, "kBinsIdHalf");
+
+  // 8 bins, linear tails, bound 3, the default floors
+  vcnf_rqs_cfg cfg_v;
+  cfg_v.num_bins = 8; cfg_v.tails = VCNF_TAILS_LINEAR;
+  cfg_v.left = -3.f; cfg_v.right = 3.f; cfg_v.bottom = -3.f; cfg_v.top = 3.f;
+  cfg_v.min_bin_width = 1e-3f; cfg_v.min_bin_height = 1e-3f; cfg_v.min_derivative = 1e-3f; cfg_v.wh_scale = 1.f;
+  const vcnf_rqs_cfg* cfg = &cfg_v;
+  RqsConst c;
+  memset(&c, 0xff, sizeof c);
+  rqs_fill_const(*cfg, c);
+  const int K = cfg->num_bins;
+  CHECK(c.K == K);
+  CHECK(c.tails == cfg->tails);
+  CHECK(same_bits(c.lo_x, cfg->left));
+  CHECK(same_bits(c.hi_x, cfg->right));
+  CHECK(same_bits(c.span_x, (float)((double)cfg->right - (double)cfg->left)));
+  CHECK(same_bits(c.lo_y, cfg->bottom));
+  CHECK(same_bits(c.hi_y, cfg->top));
+  CHECK(same_bits(c.span_y, (float)((double)cfg->top - (double)cfg->bottom)));
+  CHECK(same_bits(c.min_w, cfg->min_bin_width));
+  CHECK(same_bits(c.min_h, cfg->min_bin_height));
+  CHECK(same_bits(c.min_d, cfg->min_derivative));
+  CHECK(same_bits(c.free_w, (float)(1.0 - (double)cfg->min_bin_width * K)));
+  CHECK(same_bits(c.free_h, (float)(1.0 - (double)cfg->min_bin_height * K)));
+  CHECK(same_bits(c.wh_scale, cfg->wh_scale));
+  CHECK(same_bits(c.edge_logit, (float)log(exp(1.0 - (double)cfg->min_derivative) - 1.0)));
+  CHECK(sizeof(RqsConst) == 15 * 4);               // 2 ints + 13 floats: part of every kernel's argument layout
+  CHECK(rqs_check_cfg(cfg, 64) == VCNF_OK);
+
+  CHECK(rqs_n_deriv(VCNF_TAILS_LINEAR, 8) == 7);
+  CHECK(rqs_n_deriv(VCNF_TAILS_CIRCULAR, 8) == 8);
+  CHECK(rqs_n_deriv(VCNF_TAILS_NONE, 8) == 9);
+
+  CHECK(elem_blocks(1, 256, 4096) == 1);
+  CHECK(elem_blocks(257, 256, 4096) == 2);
+  CHECK(elem_blocks(1LL << 40, 256, 4096) == 4096);
+
+  if (failures) return 1;
+  printf("rqs_host_check ok\n");
+  return 0;
+}

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/vcnf_hip.h"
+#include "host_common.hpp"
 #include "rqs_math.hpp"
 #include "rqs_lean.hpp"
 #include "fused_common.hpp"
@@ -242,7 +243,7 @@ static int launch_final_pre(const FinalArgs& a, int inverse, hipStream_t st) {
     hipLaunchKernelGGL((rqs_final_fused_kernel<K, true, PRE>), grid, dim3(kFinBlock), lds, st, a);
   else
     hipLaunchKernelGGL((rqs_final_fused_kernel<K, false, PRE>), grid, dim3(kFinBlock), lds, st, a);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return launched();
 }
 
 template <int K>
@@ -302,15 +303,7 @@ static int run_final(const float* x, const float* h, float* y, float* partial, i
   if (sblocks > tiles) sblocks = tiles;
   if (sblocks < 1) sblocks = 1;
   a.sblocks = (int)sblocks;
-  RqsConst& c = a.c;
-  c.K = K; c.tails = cfg->tails;
-  c.lo_x = cfg->left; c.hi_x = cfg->right; c.span_x = (float)((double)cfg->right - (double)cfg->left);
-  c.lo_y = cfg->bottom; c.hi_y = cfg->top; c.span_y = (float)((double)cfg->top - (double)cfg->bottom);
-  c.min_w = cfg->min_bin_width; c.min_h = cfg->min_bin_height; c.min_d = cfg->min_derivative;
-  c.free_w = (float)(1.0 - (double)cfg->min_bin_width * K);
-  c.free_h = (float)(1.0 - (double)cfg->min_bin_height * K);
-  c.wh_scale = cfg->wh_scale;
-  c.edge_logit = (float)log(exp(1.0 - (double)cfg->min_derivative) - 1.0);
+  rqs_fill_const(*cfg, a.c);
   hipStream_t st = (hipStream_t)stream;
   return K == 8 ? launch_final<8>(a, inverse, pre, st) : K == 10 ? launch_final<10>(a, inverse, pre, st)
                                                           : launch_final<16>(a, inverse, pre, st);

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "../../include/vcnf_hip.h"
+#include "host_common.hpp"
 #include "rqs_math.hpp"
 #include "fused_common.hpp"
 
@@ -352,7 +353,7 @@ static int launch_fused(const FusedStackArgs& sa, int inverse, hipStream_t st) {
     hipLaunchKernelGGL((fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, true, kCB, false>), grid, dim3(kFBlock), lds, st, sa);
   else
     hipLaunchKernelGGL((fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, false, kCB, false>), grid, dim3(kFBlock), lds, st, sa);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return launched();
 }
 
 // Shape family of the exact fp32 kernel: (d_id = d_t, ctx) with H = 128, 8 bins, NBLK residual blocks.
@@ -469,15 +470,7 @@ static int run_stack(const float* x, const float* context, float* y, float* logd
   a.sh_w = layers[0].shared_w; a.sh_h = layers[0].shared_h; a.sh_d = layers[0].shared_d;
   a.wpack = layers[0].wpack; a.wpack_bytes = (unsigned)(wpack_floats * 4);
   a.bad = bad_disc; a.sat = sat_count; a.redo = redo_tiles; a.B = batch; a.ld_mode = ld_mode; a.ld_sign = ld_sign;
-  const int K = cfg->num_bins;
-  a.c.K = K; a.c.tails = cfg->tails;
-  a.c.lo_x = cfg->left; a.c.hi_x = cfg->right; a.c.span_x = (float)((double)cfg->right - (double)cfg->left);
-  a.c.lo_y = cfg->bottom; a.c.hi_y = cfg->top; a.c.span_y = (float)((double)cfg->top - (double)cfg->bottom);
-  a.c.min_w = cfg->min_bin_width; a.c.min_h = cfg->min_bin_height; a.c.min_d = cfg->min_derivative;
-  a.c.free_w = (float)(1.0 - (double)cfg->min_bin_width * K);
-  a.c.free_h = (float)(1.0 - (double)cfg->min_bin_height * K);
-  a.c.wh_scale = cfg->wh_scale;
-  a.c.edge_logit = (float)log(exp(1.0 - (double)cfg->min_derivative) - 1.0);
+  rqs_fill_const(*cfg, a.c);
   sa.n_layers = n_layers;
   for (int l = 0; l < kMaxStackLayers; ++l) {
     const vcnf_rqs_stack_layer& q = layers[l < n_layers ? l : 0];

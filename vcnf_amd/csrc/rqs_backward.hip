@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/vcnf_hip.h"
+#include "host_common.hpp"
 #include "rqs_math.hpp"
 #include "rqs_vjp.hpp"
 
@@ -363,61 +364,53 @@ __global__ __launch_bounds__(kBwdBlock) void rqs_shared_bwd_kernel(const SharedB
   }
 }
 
-template <bool INV>
-static int launch_shared_bwd(const SharedBwdArgs& a, dim3 grid, hipStream_t st) {
+static int launch_shared_bwd(const SharedBwdArgs& a, int inverse, dim3 grid, hipStream_t st) {
   const size_t lds = (size_t)3 * (a.c.K + 1) * kBwdBlock * sizeof(float);
-  switch (a.c.K) {
-    case 4: hipLaunchKernelGGL((rqs_shared_bwd_kernel<4, INV>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_shared_bwd_kernel<8, INV>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_shared_bwd_kernel<10, INV>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_shared_bwd_kernel<16, INV>), grid, dim3(kBwdBlock), lds, st, a); break;
-    default: return VCNF_ERR_UNSUPPORTED;
-  }
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  const bool known = with_bins_only(kBins, a.c.K, [&](auto kt) {        // no generic instance
+    constexpr int KT = decltype(kt)::value;
+    if (inverse) hipLaunchKernelGGL((rqs_shared_bwd_kernel<KT, true>), grid, dim3(kBwdBlock), lds, st, a);
+    else hipLaunchKernelGGL((rqs_shared_bwd_kernel<KT, false>), grid, dim3(kBwdBlock), lds, st, a);
+  });
+  return known ? launched() : VCNF_ERR_UNSUPPORTED;
 }
 
-template <bool INV, bool PACKED, bool LIM = false>
-static void launch_bwd(const BwdArgs& a, dim3 grid, hipStream_t st) {
+template <bool PACKED, bool LIM = false>
+static void launch_bwd(const BwdArgs& a, int inverse, dim3 grid, hipStream_t st) {
   const size_t lds = PACKED ? (size_t)kBwdBlock * (2 * a.c.K + a.nd) * sizeof(float) : 0;
-  switch (a.c.K) {
-    case 4: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<4, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<8, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<10, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<16, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<0, INV, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a); break;
-  }
+  with_bins(kBins, a.c.K, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (inverse) hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<KT, true, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a);
+    else hipLaunchKernelGGL((rqs_elementwise_bwd_kernel<KT, false, PACKED, LIM>), grid, dim3(kBwdBlock), lds, st, a);
+  });
 }
 
 }  // namespace vcnf
 
 using namespace vcnf;
 
-static int bwd_common(const vcnf_rqs_cfg* cfg, BwdArgs& a, int64_t n) {
-  if (!cfg) return VCNF_ERR_NULL;
-  const int K = cfg->num_bins;
-  if (K < 1 || K > kBwdMaxK) return VCNF_ERR_SHAPE;
-  if (cfg->tails != VCNF_TAILS_NONE && cfg->tails != VCNF_TAILS_LINEAR && cfg->tails != VCNF_TAILS_CIRCULAR)
-    return VCNF_ERR_UNSUPPORTED;
-  if (cfg->tails == VCNF_TAILS_LINEAR && K < 2) return VCNF_ERR_SHAPE;
-  if ((double)cfg->min_bin_width * K > 1.0 || (double)cfg->min_bin_height * K > 1.0) return VCNF_ERR_VALUE;
+// validation shared by the VJP entry points (cfg, then n), the constants and the number of derivative logits
+static int bwd_common(const vcnf_rqs_cfg* cfg, int64_t n, RqsConst& c, int& nd) {
+  const int rc = rqs_check_cfg(cfg, kBwdMaxK);
+  if (rc != VCNF_OK) return rc;
   if (n < 0) return VCNF_ERR_SHAPE;
-  a.n = n;
-  a.nd = cfg->tails == VCNF_TAILS_LINEAR ? K - 1 : cfg->tails == VCNF_TAILS_CIRCULAR ? K : K + 1;
-  RqsConst& c = a.c;
-  c.K = K; c.tails = cfg->tails;
-  c.lo_x = cfg->left; c.hi_x = cfg->right; c.span_x = (float)((double)cfg->right - (double)cfg->left);
-  c.lo_y = cfg->bottom; c.hi_y = cfg->top; c.span_y = (float)((double)cfg->top - (double)cfg->bottom);
-  c.min_w = cfg->min_bin_width; c.min_h = cfg->min_bin_height; c.min_d = cfg->min_derivative;
-  c.free_w = (float)(1.0 - (double)cfg->min_bin_width * K);
-  c.free_h = (float)(1.0 - (double)cfg->min_bin_height * K);
-  c.wh_scale = cfg->wh_scale;
-  c.edge_logit = (float)log(exp(1.0 - (double)cfg->min_derivative) - 1.0);
+  rqs_fill_const(*cfg, c);
+  nd = rqs_n_deriv(c.tails, c.K);
   return VCNF_OK;
 }
 
+// operands of the two dense entry points: logit rows of ld_* floats, gradient rows of K, K, nd
+static void dense_operands(BwdArgs& a, const float* x, const float* uw, const float* uh, const float* ud,
+                           int64_t ld_w, int64_t ld_h, int64_t ld_d, const float* g_y, const float* g_logabsdet,
+                           float* g_x, float* g_uw, float* g_uh, float* g_ud, int64_t n) {
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.row_w = ld_w; a.row_h = ld_h; a.row_d = ld_d; a.inner = 1; a.ks = 1;
+  a.gy = g_y; a.glad = g_logabsdet; a.lad_div = 1;
+  a.gx = g_x; a.guw = g_uw; a.guh = g_uh; a.gud = g_ud;
+  a.grow_w = a.c.K; a.grow_h = a.c.K; a.grow_d = a.nd;
+  a.n = n;
+}
+
 static int bwd_launch(const BwdArgs& a, int inverse, void* stream) {
-  const long long blocks = (a.n + kBwdBlock - 1) / kBwdBlock;
-  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
+  dim3 grid(elem_blocks(a.n, kBwdBlock, 256 * 16));
   // rows of logits and of gradients packed alike and small enough for LDS: staged, coalesced variant
   const long long P = 2 * a.c.K + a.nd;
   const bool packed = a.inner == 1 && a.ks == 1 && a.row_w == P && a.row_h == P && a.row_d == P &&
@@ -425,14 +418,9 @@ static int bwd_launch(const BwdArgs& a, int inverse, void* stream) {
                       a.ud == a.uw + 2 * a.c.K && a.guh == a.guw + a.c.K && a.gud == a.guw + 2 * a.c.K &&
                       (size_t)kBwdBlock * P * sizeof(float) <= 48 * 1024;
   hipStream_t st = (hipStream_t)stream;
-  if (packed) {
-    if (inverse) launch_bwd<true, true>(a, grid, st);
-    else launch_bwd<false, true>(a, grid, st);
-  } else {
-    if (inverse) launch_bwd<true, false>(a, grid, st);
-    else launch_bwd<false, false>(a, grid, st);
-  }
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  if (packed) launch_bwd<true>(a, inverse, grid, st);
+  else launch_bwd<false>(a, inverse, grid, st);
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_bwd_f32(const float* x, const float* uw, const float* uh, const float* ud,
@@ -441,15 +429,12 @@ extern "C" int vcnf_rqs_elementwise_bwd_f32(const float* x, const float* uw, con
                                             float* g_x, float* g_uw, float* g_uh, float* g_ud, int64_t n,
                                             const vcnf_rqs_cfg* cfg, int inverse, void* stream) {
   BwdArgs a;
-  const int rc = bwd_common(cfg, a, n);
+  const int rc = bwd_common(cfg, n, a.c, a.nd);
   if (rc != VCNF_OK) return rc;
   if (ld_w < 0 || ld_h < 0 || ld_d < 0) return VCNF_ERR_SHAPE;
   if (n == 0) return VCNF_OK;
   if (!x || !uw || !uh || !ud || !g_y || !g_logabsdet || !g_x || !g_uw || !g_uh || !g_ud) return VCNF_ERR_NULL;
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.row_w = ld_w; a.row_h = ld_h; a.row_d = ld_d; a.inner = 1; a.ks = 1;
-  a.gy = g_y; a.glad = g_logabsdet; a.lad_div = 1;
-  a.gx = g_x; a.guw = g_uw; a.guh = g_uh; a.gud = g_ud;
-  a.grow_w = a.c.K; a.grow_h = a.c.K; a.grow_d = a.nd;
+  dense_operands(a, x, uw, uh, ud, ld_w, ld_h, ld_d, g_y, g_logabsdet, g_x, g_uw, g_uh, g_ud, n);
   return bwd_launch(a, inverse, stream);
 }
 
@@ -464,23 +449,18 @@ extern "C" int vcnf_rqs_elementwise_limits_bwd_f32(const float* x, const float* 
   const int vc = limits_validate(cfg, n, ld_w, ld_h, ld_d, bcast);
   if (vc != VCNF_OK) return vc;
   BwdArgs a;
-  const int rc = bwd_common(cfg, a, n);
+  const int rc = bwd_common(cfg, n, a.c, a.nd);
   if (rc != VCNF_OK) return rc;
   if (n == 0) return VCNF_OK;
   if (!x || !uw || !uh || !ud || !left || !right || !bottom || !top || !g_y || !g_logabsdet || !g_x || !g_uw ||
       !g_uh || !g_ud)
     return VCNF_ERR_NULL;
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.row_w = ld_w; a.row_h = ld_h; a.row_d = ld_d; a.inner = 1; a.ks = 1;
-  a.gy = g_y; a.glad = g_logabsdet; a.lad_div = 1;
-  a.gx = g_x; a.guw = g_uw; a.guh = g_uh; a.gud = g_ud;
-  a.grow_w = a.c.K; a.grow_h = a.c.K; a.grow_d = a.nd;
+  dense_operands(a, x, uw, uh, ud, ld_w, ld_h, ld_d, g_y, g_logabsdet, g_x, g_uw, g_uh, g_ud, n);
   a.lim = make_limits(left, right, bottom, top, bcast, n);
   a.glim[0] = g_left; a.glim[1] = g_right; a.glim[2] = g_bottom; a.glim[3] = g_top;
-  const long long blocks = (n + kBwdBlock - 1) / kBwdBlock;
-  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
-  if (inverse) launch_bwd<true, false, true>(a, grid, (hipStream_t)stream);
-  else launch_bwd<false, false, true>(a, grid, (hipStream_t)stream);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  dim3 grid(elem_blocks(n, kBwdBlock, 256 * 16));
+  launch_bwd<false, true>(a, inverse, grid, (hipStream_t)stream);
+  return launched();
 }
 
 extern "C" int vcnf_rqs_packed_bwd_f32(const float* x, const float* params, int64_t inner, int64_t lad_div,
@@ -488,7 +468,7 @@ extern "C" int vcnf_rqs_packed_bwd_f32(const float* x, const float* params, int6
                                        float* g_x, float* g_params, int64_t n,
                                        const vcnf_rqs_cfg* cfg, int inverse, void* stream) {
   BwdArgs a;
-  const int rc = bwd_common(cfg, a, n);
+  const int rc = bwd_common(cfg, n, a.c, a.nd);
   if (rc != VCNF_OK) return rc;
   if (inner < 1 || lad_div < 1) return VCNF_ERR_SHAPE;
   if (n == 0) return VCNF_OK;
@@ -499,6 +479,7 @@ extern "C" int vcnf_rqs_packed_bwd_f32(const float* x, const float* params, int6
   a.gy = g_y; a.glad = g_logabsdet; a.lad_div = lad_div;
   a.gx = g_x; a.guw = g_params; a.guh = g_params + K * inner; a.gud = g_params + 2 * K * inner;
   a.grow_w = a.grow_h = a.grow_d = P * inner;
+  a.n = n;
   return bwd_launch(a, inverse, stream);
 }
 
@@ -516,17 +497,15 @@ extern "C" int vcnf_rqs_shared_bwd_f32(const float* x, const float* sw, const fl
                                        const float* g_y, const float* g_logabsdet,
                                        float* g_x, float* partial, int64_t groups,
                                        const vcnf_rqs_cfg* cfg, int inverse, void* stream) {
-  BwdArgs tmp;
-  const int rc = bwd_common(cfg, tmp, batch);
+  SharedBwdArgs a;
+  const int rc = bwd_common(cfg, batch, a.c, a.nd);
   if (rc != VCNF_OK) return rc;
   if (period < 1 || lad_div < 1 || groups != vcnf_rqs_shared_bwd_groups(batch, period)) return VCNF_ERR_SHAPE;
   if (batch == 0) return VCNF_OK;
   if (!x || !sw || !sh || !sd || !g_y || !g_logabsdet || !g_x || !partial) return VCNF_ERR_NULL;
-  SharedBwdArgs a;
   a.x = x; a.sw = sw; a.sh = sh; a.sd = sd; a.gy = g_y; a.glad = g_logabsdet; a.lad_div = lad_div;
-  a.gx = g_x; a.partial = partial; a.B = batch; a.period = period; a.groups = groups; a.nd = tmp.nd; a.c = tmp.c;
+  a.gx = g_x; a.partial = partial; a.B = batch; a.period = period; a.groups = groups;
   const long long threads = groups * period;
   dim3 grid((unsigned)((threads + kBwdBlock - 1) / kBwdBlock));
-  return inverse ? launch_shared_bwd<true>(a, grid, (hipStream_t)stream)
-                 : launch_shared_bwd<false>(a, grid, (hipStream_t)stream);
+  return launch_shared_bwd(a, inverse, grid, (hipStream_t)stream);
 }

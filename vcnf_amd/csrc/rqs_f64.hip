@@ -11,6 +11,8 @@
 #include <stdint.h>
 
 #include "../../include/vcnf_hip.h"
+#include "host_common.hpp"
+#include "rqs_host.hpp"
 #include "rqs_vjp.hpp"
 
 namespace vcnf {
@@ -173,12 +175,9 @@ __global__ __launch_bounds__(256) void rqs_elementwise_f64_kernel(const Rqs64Arg
 
 template <bool STRIDED, bool LIM = false>
 static void launch_fwd64(const Rqs64Args& a, dim3 grid, hipStream_t st) {
-  switch (a.K) {
-    case 8: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<8, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<10, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<16, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_f64_kernel<0, STRIDED, LIM>), grid, dim3(256), 0, st, a); break;
-  }
+  with_bins(kBins64, a.K, [&](auto kt) {
+    hipLaunchKernelGGL((rqs_elementwise_f64_kernel<decltype(kt)::value, STRIDED, LIM>), grid, dim3(256), 0, st, a);
+  });
 }
 
 
@@ -294,21 +293,21 @@ __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs6
   }
 }
 
-template <bool INV, bool STRIDED, bool LIM = false>
+template <bool STRIDED, bool LIM = false>
 static void launch_bwd64(const Rqs64BwdArgs& g, dim3 grid, hipStream_t st) {
-  switch (g.f.K) {
-    case 8: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<8, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<10, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<16, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<0, INV, STRIDED, LIM>), grid, dim3(256), 0, st, g); break;
-  }
+  with_bins(kBins64, g.f.K, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (g.f.inverse) hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<KT, true, STRIDED, LIM>), grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<KT, false, STRIDED, LIM>), grid, dim3(256), 0, st, g);
+  });
 }
 
 }  // namespace vcnf
 
 using namespace vcnf;
 
-// constants of the spline, the same for every entry point
+// constants of the spline, the same for every entry point (kept in double, so not rqs_fill_const); dense rows
+// unless the caller sets inner / ks / period, no outputs of the forward map unless it sets y / lad / bad
 static void fill64(Rqs64Args& a, const vcnf_rqs_cfg_f64* cfg, int inverse) {
   a.K = cfg->num_bins; a.tails = cfg->tails; a.inverse = inverse ? 1 : 0;
   a.left = cfg->left; a.right = cfg->right; a.bottom = cfg->bottom; a.top = cfg->top;
@@ -316,8 +315,24 @@ static void fill64(Rqs64Args& a, const vcnf_rqs_cfg_f64* cfg, int inverse) {
   a.wh_scale = cfg->wh_scale;
   a.edge = log(exp(1.0 - cfg->min_derivative) - 1.0);
   a.inner = 1; a.ks = 1; a.period = 0;
+  a.y = nullptr; a.lad = nullptr; a.bad = nullptr;
 }
 
+// the input and its logit rows
+static void operands64(Rqs64Args& a, const double* x, const double* uw, const double* uh, const double* ud,
+                       int64_t ld_w, int64_t ld_h, int64_t ld_d, int64_t n) {
+  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d; a.n = n;
+}
+
+// the gradient operands of a VJP
+static void grads64(Rqs64BwdArgs& g, const vcnf_rqs_cfg_f64* cfg, const double* g_y, const double* g_logabsdet,
+                    double* g_x, double* g_uw, double* g_uh, double* g_ud, int64_t lad_div) {
+  g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x; g.guw = g_uw; g.guh = g_uh; g.gud = g_ud;
+  g.nd = rqs_n_deriv(cfg->tails, cfg->num_bins); g.lad_div = lad_div;
+}
+
+// Not rqs_check_cfg: this check tests n together with the bin count, ahead of the tails, and lets linear tails pass
+// with one bin; callers see both in the status they get.
 static int check_fwd64(const vcnf_rqs_cfg_f64* cfg, int64_t n) {
   if (!cfg) return VCNF_ERR_NULL;
   if (n < 0 || cfg->num_bins < 1 || cfg->num_bins > kMaxBins64) return VCNF_ERR_SHAPE;
@@ -329,29 +344,12 @@ static int check_fwd64(const vcnf_rqs_cfg_f64* cfg, int64_t n) {
 
 // validation as bwd_common / vcnf_rqs_elementwise_bwd_f32 (rqs_backward.hip)
 static int check_bwd64(const vcnf_rqs_cfg_f64* cfg, int64_t n) {
-  if (!cfg) return VCNF_ERR_NULL;
-  const int K = cfg->num_bins;
-  if (K < 1 || K > kMaxBins64) return VCNF_ERR_SHAPE;
-  if (cfg->tails != VCNF_TAILS_NONE && cfg->tails != VCNF_TAILS_LINEAR && cfg->tails != VCNF_TAILS_CIRCULAR)
-    return VCNF_ERR_UNSUPPORTED;
-  if (cfg->tails == VCNF_TAILS_LINEAR && K < 2) return VCNF_ERR_SHAPE;
-  if (cfg->min_bin_width * K > 1.0 || cfg->min_bin_height * K > 1.0) return VCNF_ERR_VALUE;
-  if (n < 0) return VCNF_ERR_SHAPE;
-  return VCNF_OK;
+  const int rc = rqs_check_cfg(cfg, kMaxBins64);
+  if (rc != VCNF_OK) return rc;
+  return n < 0 ? VCNF_ERR_SHAPE : VCNF_OK;
 }
 
-static int n_deriv64(const vcnf_rqs_cfg_f64* cfg) {
-  const int K = cfg->num_bins;
-  return cfg->tails == VCNF_TAILS_LINEAR ? K - 1 : cfg->tails == VCNF_TAILS_CIRCULAR ? K : K + 1;
-}
-
-static dim3 grid64(int64_t n) {
-  long long blocks = (n + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  return dim3((unsigned)blocks);
-}
-
-static int launched64() { return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH; }
+static dim3 grid64(int64_t n) { return dim3(elem_blocks(n, 256, 256 * 32)); }
 
 extern "C" int vcnf_rqs_elementwise_f64(const double* x, const double* uw, const double* uh, const double* ud,
                                         int64_t ld_w, int64_t ld_h, int64_t ld_d,
@@ -363,10 +361,10 @@ extern "C" int vcnf_rqs_elementwise_f64(const double* x, const double* uw, const
   if (!x || !uw || !uh || !ud || !y || !logabsdet) return VCNF_ERR_NULL;
   Rqs64Args a;
   fill64(a, cfg, inverse);
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
-  a.y = y; a.lad = logabsdet; a.n = n; a.bad = bad_disc;
+  operands64(a, x, uw, uh, ud, ld_w, ld_h, ld_d, n);
+  a.y = y; a.lad = logabsdet; a.bad = bad_disc;
   launch_fwd64<false>(a, grid64(n), (hipStream_t)stream);
-  return launched64();
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_strided_f64(const double* x, const double* uw, const double* uh, const double* ud,
@@ -382,11 +380,11 @@ extern "C" int vcnf_rqs_elementwise_strided_f64(const double* x, const double* u
   if (!x || !uw || !uh || !ud || !y || !logabsdet) return VCNF_ERR_NULL;
   Rqs64Args a;
   fill64(a, cfg, inverse);
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = row_w; a.ld_h = row_h; a.ld_d = row_d;
+  operands64(a, x, uw, uh, ud, row_w, row_h, row_d, n);
   a.inner = inner; a.ks = k_stride; a.period = period;
-  a.y = y; a.lad = logabsdet; a.n = n; a.bad = bad_disc;
+  a.y = y; a.lad = logabsdet; a.bad = bad_disc;
   launch_fwd64<true>(a, grid64(n), (hipStream_t)stream);
-  return launched64();
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, const double* uh, const double* ud,
@@ -402,13 +400,10 @@ extern "C" int vcnf_rqs_elementwise_bwd_f64(const double* x, const double* uw, c
   Rqs64BwdArgs g;
   Rqs64Args& a = g.f;
   fill64(a, cfg, inverse);
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
-  a.y = nullptr; a.lad = nullptr; a.n = n; a.bad = nullptr;
-  g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x; g.guw = g_uw; g.guh = g_uh; g.gud = g_ud;
-  g.nd = n_deriv64(cfg); g.lad_div = 1;
-  if (inverse) launch_bwd64<true, false>(g, grid64(n), (hipStream_t)stream);
-  else launch_bwd64<false, false>(g, grid64(n), (hipStream_t)stream);
-  return launched64();
+  operands64(a, x, uw, uh, ud, ld_w, ld_h, ld_d, n);
+  grads64(g, cfg, g_y, g_logabsdet, g_x, g_uw, g_uh, g_ud, 1);
+  launch_bwd64<false>(g, grid64(n), (hipStream_t)stream);
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_limits_f64(const double* x, const double* uw, const double* uh, const double* ud,
@@ -424,11 +419,11 @@ extern "C" int vcnf_rqs_elementwise_limits_f64(const double* x, const double* uw
   if (!x || !uw || !uh || !ud || !left || !right || !bottom || !top || !y || !logabsdet) return VCNF_ERR_NULL;
   Rqs64Args a;
   fill64(a, cfg, inverse);
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
-  a.y = y; a.lad = logabsdet; a.n = n; a.bad = bad_disc;
+  operands64(a, x, uw, uh, ud, ld_w, ld_h, ld_d, n);
+  a.y = y; a.lad = logabsdet; a.bad = bad_disc;
   a.lim = make_limits(left, right, bottom, top, bcast, n);
   launch_fwd64<false, true>(a, grid64(n), (hipStream_t)stream);
-  return launched64();
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_limits_bwd_f64(const double* x, const double* uw, const double* uh,
@@ -448,15 +443,12 @@ extern "C" int vcnf_rqs_elementwise_limits_bwd_f64(const double* x, const double
   Rqs64BwdArgs g;
   Rqs64Args& a = g.f;
   fill64(a, cfg, inverse);
-  a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
-  a.y = nullptr; a.lad = nullptr; a.n = n; a.bad = nullptr;
+  operands64(a, x, uw, uh, ud, ld_w, ld_h, ld_d, n);
   a.lim = make_limits(left, right, bottom, top, bcast, n);
-  g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x; g.guw = g_uw; g.guh = g_uh; g.gud = g_ud;
-  g.nd = n_deriv64(cfg); g.lad_div = 1;
+  grads64(g, cfg, g_y, g_logabsdet, g_x, g_uw, g_uh, g_ud, 1);
   g.glim[0] = g_left; g.glim[1] = g_right; g.glim[2] = g_bottom; g.glim[3] = g_top;
-  if (inverse) launch_bwd64<true, false, true>(g, grid64(n), (hipStream_t)stream);
-  else launch_bwd64<false, false, true>(g, grid64(n), (hipStream_t)stream);
-  return launched64();
+  launch_bwd64<false, true>(g, grid64(n), (hipStream_t)stream);
+  return launched();
 }
 
 extern "C" int vcnf_rqs_packed_bwd_f64(const double* x, const double* params, int64_t inner, int64_t lad_div,
@@ -470,16 +462,13 @@ extern "C" int vcnf_rqs_packed_bwd_f64(const double* x, const double* params, in
   if (!x || !params || !g_y || !g_logabsdet || !g_x || !g_params) return VCNF_ERR_NULL;
   Rqs64BwdArgs g;
   Rqs64Args& a = g.f;
-  fill64(a, cfg, inverse);
-  const long long K = cfg->num_bins, nd = n_deriv64(cfg), P = 2 * K + nd;
+  const long long K = cfg->num_bins, P = 2 * K + rqs_n_deriv(cfg->tails, cfg->num_bins);
   // params / g_params [rows, P, inner]: logit k of element i = row * P * inner + s + k * inner
-  a.x = x; a.uw = params; a.uh = params + K * inner; a.ud = params + 2 * K * inner;
-  a.ld_w = a.ld_h = a.ld_d = P * inner; a.inner = inner; a.ks = inner; a.period = 0;
-  a.y = nullptr; a.lad = nullptr; a.n = n; a.bad = nullptr;
-  g.gy = g_y; g.glad = g_logabsdet; g.gx = g_x;
-  g.guw = g_params; g.guh = g_params + K * inner; g.gud = g_params + 2 * K * inner;
-  g.nd = (int)nd; g.lad_div = lad_div;
-  if (inverse) launch_bwd64<true, true>(g, grid64(n), (hipStream_t)stream);
-  else launch_bwd64<false, true>(g, grid64(n), (hipStream_t)stream);
-  return launched64();
+  const long long row = P * inner;
+  fill64(a, cfg, inverse);
+  operands64(a, x, params, params + K * inner, params + 2 * K * inner, row, row, row, n);
+  a.inner = inner; a.ks = inner;
+  grads64(g, cfg, g_y, g_logabsdet, g_x, g_params, g_params + K * inner, g_params + 2 * K * inner, lad_div);
+  launch_bwd64<true>(g, grid64(n), (hipStream_t)stream);
+  return launched();
 }

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "../../include/vcnf_hip.h"
+#include "host_common.hpp"
 #include "rqs_math.hpp"
 #include "rqs_lean.hpp"
 #include "rqs_vjp.hpp"
@@ -418,17 +419,6 @@ __global__ __launch_bounds__(kBlock) void rqs_elementwise_strided_kernel(const E
   if (INV && a.bad && bad) atomicAdd(a.bad, 1);
 }
 
-template <bool INV>
-static void launch_elem_strided(const ElemStridedArgs& a, int K, dim3 grid, hipStream_t st) {
-  switch (K) {
-    case 4: hipLaunchKernelGGL((rqs_elementwise_strided_kernel<4, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_elementwise_strided_kernel<8, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_strided_kernel<10, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_strided_kernel<16, INV>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_strided_kernel<0, INV>), grid, dim3(kBlock), 0, st, a); break;
-  }
-}
-
 // Batch-shared per-position splines through knot tables: the K+K+nd logits of a position are turned
 // into knots ONCE (build kernel, one thread per position, table row xk | yk | dk in global memory,
 // L2-resident), the per-element kernel then only searches the row and evaluates the bin - no
@@ -464,17 +454,6 @@ __global__ __launch_bounds__(kBlock) void rqs_table_eval_kernel(const TableArgs 
     a.lad[i] = lad;
   }
   if (INV && a.bad && bad) atomicAdd(a.bad, 1);
-}
-
-template <bool INV>
-static void launch_table_eval(const TableArgs& a, dim3 grid, hipStream_t st) {
-  switch (a.c.K) {
-    case 4: hipLaunchKernelGGL((rqs_table_eval_kernel<4, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_table_eval_kernel<8, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_table_eval_kernel<10, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_table_eval_kernel<16, INV>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((rqs_table_eval_kernel<0, INV>), grid, dim3(kBlock), 0, st, a); break;
-  }
 }
 
 // ------------------------------------------------------------------ conditioner input
@@ -642,96 +621,13 @@ __global__ __launch_bounds__(kBlock) void rqs_identity_half_kernel(const IdHalfA
   if (INV && a.bad && bad) atomicAdd(a.bad, 1);
 }
 
-template <bool INV>
-static bool launch_identity_half(const IdHalfArgs& a, dim3 grid, hipStream_t st) {
-  switch (a.c.K) {
-    case 4: hipLaunchKernelGGL((rqs_identity_half_kernel<4, INV>), grid, dim3(kBlock), 0, st, a); return true;
-    case 8: hipLaunchKernelGGL((rqs_identity_half_kernel<8, INV>), grid, dim3(kBlock), 0, st, a); return true;
-    case 10: hipLaunchKernelGGL((rqs_identity_half_kernel<10, INV>), grid, dim3(kBlock), 0, st, a); return true;
-    case 16: hipLaunchKernelGGL((rqs_identity_half_kernel<16, INV>), grid, dim3(kBlock), 0, st, a); return true;
-    case 32: hipLaunchKernelGGL((rqs_identity_half_kernel<32, INV>), grid, dim3(kBlock), 0, st, a); return true;
-    default: return false;
-  }
-}
-
+// validated constants of an entry point's configuration and its number of derivative logits
 static int fill_const(const vcnf_rqs_cfg* cfg, RqsConst& c, int& n_deriv) {
-  if (!cfg) return VCNF_ERR_NULL;
-  const int K = cfg->num_bins;
-  if (K < 1 || K > 1024) return VCNF_ERR_SHAPE;
-  if (cfg->tails != VCNF_TAILS_NONE && cfg->tails != VCNF_TAILS_LINEAR && cfg->tails != VCNF_TAILS_CIRCULAR)
-    return VCNF_ERR_UNSUPPORTED;
-  if (cfg->tails == VCNF_TAILS_LINEAR && K < 2) return VCNF_ERR_SHAPE;
-  // splines.py:104-107
-  if ((double)cfg->min_bin_width * K > 1.0 || (double)cfg->min_bin_height * K > 1.0) return VCNF_ERR_VALUE;
-  c.K = K;
-  c.tails = cfg->tails;
-  c.lo_x = cfg->left;
-  c.hi_x = cfg->right;
-  c.span_x = (float)((double)cfg->right - (double)cfg->left);
-  c.lo_y = cfg->bottom;
-  c.hi_y = cfg->top;
-  c.span_y = (float)((double)cfg->top - (double)cfg->bottom);
-  c.min_w = cfg->min_bin_width;
-  c.min_h = cfg->min_bin_height;
-  c.min_d = cfg->min_derivative;
-  c.free_w = (float)(1.0 - (double)cfg->min_bin_width * K);
-  c.free_h = (float)(1.0 - (double)cfg->min_bin_height * K);
-  c.wh_scale = cfg->wh_scale;
-  c.edge_logit = (float)log(exp(1.0 - (double)cfg->min_derivative) - 1.0);
-  n_deriv = cfg->tails == VCNF_TAILS_LINEAR ? K - 1 : cfg->tails == VCNF_TAILS_CIRCULAR ? K : K + 1;
+  const int rc = rqs_check_cfg(cfg, 1024);
+  if (rc != VCNF_OK) return rc;
+  rqs_fill_const(*cfg, c);
+  n_deriv = rqs_n_deriv(c.tails, c.K);
   return VCNF_OK;
-}
-
-static inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-template <bool INV>
-static void launch_coupling(const CouplingArgs& a, int K, dim3 grid, size_t lds, hipStream_t st) {
-  switch (K) {
-    case 4: hipLaunchKernelGGL((rqs_coupling_kernel<4, INV>), grid, dim3(kBlock), lds, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_coupling_kernel<8, INV>), grid, dim3(kBlock), lds, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_coupling_kernel<10, INV>), grid, dim3(kBlock), lds, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_coupling_kernel<16, INV>), grid, dim3(kBlock), lds, st, a); break;
-    default: hipLaunchKernelGGL((rqs_coupling_kernel<0, INV>), grid, dim3(kBlock), lds, st, a); break;
-  }
-}
-
-template <bool INV>
-static void launch_coupling_pf(const CouplingArgs& a, int K, dim3 grid, size_t lds, hipStream_t st) {
-  switch (K) {
-    case 4: hipLaunchKernelGGL((rqs_coupling_pf_kernel<4, INV, 8>), grid, dim3(kBlock), lds, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_coupling_pf_kernel<8, INV, 8>), grid, dim3(kBlock), lds, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_coupling_pf_kernel<10, INV, 8>), grid, dim3(kBlock), lds, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_coupling_pf_kernel<16, INV, 8>), grid, dim3(kBlock), lds, st, a); break;
-    default: hipLaunchKernelGGL((rqs_coupling_pf_kernel<0, INV, 8>), grid, dim3(kBlock), lds, st, a); break;
-  }
-}
-
-template <bool INV>
-static void launch_elem(const ElemArgs& a, int K, dim3 grid, hipStream_t st) {
-  switch (K) {
-    case 4: hipLaunchKernelGGL((rqs_elementwise_kernel<4, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((rqs_elementwise_kernel<8, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_kernel<10, INV>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_kernel<16, INV>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_kernel<0, INV>), grid, dim3(kBlock), 0, st, a); break;
-  }
-}
-
-template <bool INV, bool NARROW>
-static void launch_elem_limits_as(const ElemArgs& a, const LimitsT<float>& l, int K, dim3 grid, hipStream_t st) {
-  switch (K) {
-    case 4: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<4, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
-    case 8: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<8, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
-    case 10: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<10, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
-    case 16: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<16, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
-    default: hipLaunchKernelGGL((rqs_elementwise_limits_kernel<0, INV, NARROW>), grid, dim3(kBlock), 0, st, a, l); break;
-  }
-}
-
-template <bool INV>
-static void launch_elem_limits(const ElemArgs& a, const LimitsT<float>& l, int K, dim3 grid, hipStream_t st) {
-  if (l.narrow) launch_elem_limits_as<INV, true>(a, l, K, grid, st);
-  else launch_elem_limits_as<INV, false>(a, l, K, grid, st);
 }
 
 constexpr size_t kLdsBudget = 60 * 1024;     // per workgroup; leaves >= 2 workgroups per CU
@@ -835,14 +731,14 @@ extern "C" int vcnf_rqs_coupling_f32(const float* x, const float* params,
   // the 8 + 2 float4 register slots a thread keeps in flight
   const bool pf = a.JC == d_t && a.vec_x && a.vec_p && (rowlen & 3) == 0 && (D & 3) == 0 &&
                   (long long)a.S * rowlen <= 8LL * 4 * kBlock && (long long)a.S * D <= 2LL * 4 * kBlock;
-  if (pf) {
-    if (inverse) launch_coupling_pf<true>(a, K, grid, lds, st);
-    else launch_coupling_pf<false>(a, K, grid, lds, st);
-  } else {
-    if (inverse) launch_coupling<true>(a, K, grid, lds, st);
-    else launch_coupling<false>(a, K, grid, lds, st);
-  }
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  with_bins(kBins, K, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (pf && inverse) hipLaunchKernelGGL((rqs_coupling_pf_kernel<KT, true, 8>), grid, dim3(kBlock), lds, st, a);
+    else if (pf) hipLaunchKernelGGL((rqs_coupling_pf_kernel<KT, false, 8>), grid, dim3(kBlock), lds, st, a);
+    else if (inverse) hipLaunchKernelGGL((rqs_coupling_kernel<KT, true>), grid, dim3(kBlock), lds, st, a);
+    else hipLaunchKernelGGL((rqs_coupling_kernel<KT, false>), grid, dim3(kBlock), lds, st, a);
+  });
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_f32(const float* x, const float* uw, const float* uh, const float* ud,
@@ -858,12 +754,14 @@ extern "C" int vcnf_rqs_elementwise_f32(const float* x, const float* uw, const f
   if (!x || !uw || !uh || !y || !logabsdet || (nd > 0 && !ud)) return VCNF_ERR_NULL;
   a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
   a.y = y; a.lad = logabsdet; a.bad = bad_disc; a.n = n;
-  const long long blocks = (n + kBlock - 1) / kBlock;
-  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
+  dim3 grid(elem_blocks(n, kBlock, 256 * 16));
   hipStream_t st = (hipStream_t)stream;
-  if (inverse) launch_elem<true>(a, a.c.K, grid, st);
-  else launch_elem<false>(a, a.c.K, grid, st);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  with_bins(kBins, a.c.K, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (inverse) hipLaunchKernelGGL((rqs_elementwise_kernel<KT, true>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((rqs_elementwise_kernel<KT, false>), grid, dim3(kBlock), 0, st, a);
+  });
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_limits_f32(const float* x, const float* uw, const float* uh, const float* ud,
@@ -883,12 +781,16 @@ extern "C" int vcnf_rqs_elementwise_limits_f32(const float* x, const float* uw, 
   a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.ld_w = ld_w; a.ld_h = ld_h; a.ld_d = ld_d;
   a.y = y; a.lad = logabsdet; a.bad = bad_disc; a.n = n;
   const LimitsT<float> l = make_limits(left, right, bottom, top, bcast, n);
-  const long long blocks = (n + kBlock - 1) / kBlock;
-  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
+  dim3 grid(elem_blocks(n, kBlock, 256 * 16));
   hipStream_t st = (hipStream_t)stream;
-  if (inverse) launch_elem_limits<true>(a, l, a.c.K, grid, st);
-  else launch_elem_limits<false>(a, l, a.c.K, grid, st);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  with_bins(kBins, a.c.K, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (inverse && l.narrow) hipLaunchKernelGGL((rqs_elementwise_limits_kernel<KT, true, true>), grid, dim3(kBlock), 0, st, a, l);
+    else if (inverse) hipLaunchKernelGGL((rqs_elementwise_limits_kernel<KT, true, false>), grid, dim3(kBlock), 0, st, a, l);
+    else if (l.narrow) hipLaunchKernelGGL((rqs_elementwise_limits_kernel<KT, false, true>), grid, dim3(kBlock), 0, st, a, l);
+    else hipLaunchKernelGGL((rqs_elementwise_limits_kernel<KT, false, false>), grid, dim3(kBlock), 0, st, a, l);
+  });
+  return launched();
 }
 
 extern "C" int vcnf_rqs_elementwise_strided_f32(const float* x, const float* uw, const float* uh, const float* ud,
@@ -906,12 +808,14 @@ extern "C" int vcnf_rqs_elementwise_strided_f32(const float* x, const float* uw,
   a.x = x; a.uw = uw; a.uh = uh; a.ud = ud; a.row_w = row_w; a.row_h = row_h; a.row_d = row_d;
   a.inner = inner; a.ks = k_stride; a.period = period;
   a.y = y; a.lad = logabsdet; a.bad = bad_disc; a.n = n;
-  const long long blocks = (n + kBlock - 1) / kBlock;
-  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
+  dim3 grid(elem_blocks(n, kBlock, 256 * 16));
   hipStream_t st = (hipStream_t)stream;
-  if (inverse) launch_elem_strided<true>(a, a.c.K, grid, st);
-  else launch_elem_strided<false>(a, a.c.K, grid, st);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  with_bins(kBins, a.c.K, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (inverse) hipLaunchKernelGGL((rqs_elementwise_strided_kernel<KT, true>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((rqs_elementwise_strided_kernel<KT, false>), grid, dim3(kBlock), 0, st, a);
+  });
+  return launched();
 }
 
 extern "C" int vcnf_rqs_shared_f32(const float* x, const float* sw, const float* sh, const float* sd, int64_t period,
@@ -927,15 +831,17 @@ extern "C" int vcnf_rqs_shared_f32(const float* x, const float* sw, const float*
   a.n = n; a.period = period;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(rqs_build_tables_kernel, dim3((unsigned)((period + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a);
-  const long long blocks = (n + kBlock - 1) / kBlock;
-  dim3 grid((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16));
-  if (inverse) launch_table_eval<true>(a, grid, st);
-  else launch_table_eval<false>(a, grid, st);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  dim3 grid(elem_blocks(n, kBlock, 256 * 16));
+  with_bins(kBins, a.c.K, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    if (inverse) hipLaunchKernelGGL((rqs_table_eval_kernel<KT, true>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((rqs_table_eval_kernel<KT, false>), grid, dim3(kBlock), 0, st, a);
+  });
+  return launched();
 }
 
 extern "C" int vcnf_rqs_identity_half_supported(int32_t num_bins, int32_t tails) {
-  return ((num_bins == 4 || num_bins == 8 || num_bins == 10 || num_bins == 16 || num_bins == 32) &&
+  return (in_bins(kBinsIdHalf, num_bins) &&
           (tails == VCNF_TAILS_NONE || tails == VCNF_TAILS_LINEAR)) ? 1 : 0;
 }
 
@@ -972,9 +878,12 @@ extern "C" int vcnf_rqs_identity_half_f32(const float* x, float* y, float* cond_
   if (rblocks * a.chunks > 0x7fffffffLL) return VCNF_ERR_SHAPE;
   dim3 grid((unsigned)(rblocks * a.chunks));
   hipStream_t st = (hipStream_t)stream;
-  const bool ok = inverse ? launch_identity_half<true>(a, grid, st) : launch_identity_half<false>(a, grid, st);
-  if (!ok) return VCNF_ERR_UNSUPPORTED;
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  const bool known = with_bins_only(kBinsIdHalf, a.c.K, [&](auto kt) {        // no generic instance
+    constexpr int KT = decltype(kt)::value;
+    if (inverse) hipLaunchKernelGGL((rqs_identity_half_kernel<KT, true>), grid, dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL((rqs_identity_half_kernel<KT, false>), grid, dim3(kBlock), 0, st, a);
+  });
+  return known ? launched() : VCNF_ERR_UNSUPPORTED;
 }
 
 extern "C" int vcnf_rqs_conditioner_input_f32(const float* x, int64_t batch, int32_t features,
@@ -997,8 +906,7 @@ extern "C" int vcnf_rqs_conditioner_input_f32(const float* x, int64_t batch, int
   const size_t lds = ((size_t)(a.apply == 1 ? d_id * 3 * (a.c.K + 1) : 0) + d_id) * 4 + 16;
   if (lds > 150 * 1024) return VCNF_ERR_SHAPE;
   const long long total = batch * (long long)(d_id + ctx_dim);
-  const long long blocks = (total + kBlock - 1) / kBlock;
-  dim3 grid((unsigned)(blocks < 256 * 8 ? blocks : 256 * 8));
+  dim3 grid(elem_blocks(total, kBlock, 256 * 8));
   hipLaunchKernelGGL(rqs_conditioner_input_kernel, grid, dim3(kBlock), lds, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return launched();
 }

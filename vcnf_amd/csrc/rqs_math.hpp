@@ -16,21 +16,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "rqs_host.hpp"           // RqsConst
+
 #pragma clang fp contract(off)
 
 namespace vcnf {
-
-struct RqsConst {
-  int K;
-  int tails;              // 0 none (K+1 derivative logits), 1 linear (K-1, identity outside),
-                          // 2 circular (K: the last knot shares the first knot's logit, identity outside)
-  float lo_x, hi_x, span_x;
-  float lo_y, hi_y, span_y;
-  float min_w, min_h, min_d;
-  float free_w, free_h;   // 1 - min*K, rounded from double like the reference's Python scalar
-  float wh_scale;
-  float edge_logit;       // log(exp(1 - min_d) - 1), splines.py:38
-};
 
 // Hardware transcendentals (v_exp_f32 = 2^x, v_log_f32 = log2, v_rcp_f32, v_sqrt_f32: 1 ulp
 // each).  The coupling kernel stays HBM-bound only if the ~30 transcendental calls per

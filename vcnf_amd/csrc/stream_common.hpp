@@ -11,6 +11,7 @@
 #include <initializer_list>
 
 #include "../../include/vcnf_hip.h"
+#include "host_common.hpp"
 
 namespace vcnf_stream {
 
@@ -80,15 +81,10 @@ __global__ __launch_bounds__(kRedEl * kRedSl) void reduce_partials_kernel(const 
 }
 
 // ------------------------------------------------------------------ host side
-static inline bool ok_ld(int m) { return m == VCNF_LD_STORE || m == VCNF_LD_ACCUM; }
-static inline int launched() { return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH; }
-static inline bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-static inline bool all_aligned(std::initializer_list<const void*> ps, uintptr_t n) {
-  for (const void* p : ps)
-    if (!aligned(p, n)) return false;
-  return true;
-}
+using vcnf::aligned;          // host_common.hpp
+using vcnf::all_aligned;
+using vcnf::launched;
+using vcnf::ok_ld;
 
 // lanes per group for n items (elements or packs)
 static inline int pick_lanes(long long n) {
