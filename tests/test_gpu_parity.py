@@ -1296,6 +1296,42 @@ def test_conv1x1_fused_kernel(hip, c_in, c_out, h, w):
     assert nf.check_saturation() == 0
 
 
+def test_conv1x1_fused_kernel_unaligned_input(hip):
+    """csrc/conv1x1.hip on an input whose pixel count per channel is a multiple of 4 but whose first element lies one
+    float past a 16-byte boundary: the launcher then stages the rows through registers instead of buffer_load ... lds
+    (the other shapes with inner % 4 == 0 are all aligned).  Same acceptance as test_conv1x1_fused_kernel; both staging
+    paths feed the same fragments to the same instruction sequence, so the result also equals the aligned call's."""
+    from vcnf_amd.nets.cnn import pack_conv1x1
+    c_in, c_out, h, w, b = 16, 7, 2, 2, 3
+    g = torch.Generator().manual_seed(c_in + c_out + h)
+    wgt = (torch.randn(c_out, c_in, generator=g) / c_in ** 0.5).cuda()
+    b_in, b_out = torch.randn(c_in, generator=g).cuda(), torch.randn(c_out, generator=g).cuda()
+    pack = pack_conv1x1(wgt)
+    lrelu = torch.nn.functional.leaky_relu
+    x = torch.randn(b, c_in, h, w, generator=g).cuda()
+    big = torch.empty(x.numel() + 1, device="cuda")
+    xo = big[1:].view(x.shape)
+    xo.copy_(x)
+    assert x.data_ptr() % 16 == 0 and xo.data_ptr() % 16 == 4 and xo.is_contiguous()
+    for bi, bo, si, so in ((b_in, b_out, 0.0, 0.0), (b_in, b_out, 0.1, 0.2), (None, None, None, None), (None, b_out, None, 0.0)):
+        got = _lib.conv1x1_fused(xo, pack, c_out, in_bias=bi, out_bias=bo, in_slope=si, out_slope=so)
+        aligned = _lib.conv1x1_fused(x, pack, c_out, in_bias=bi, out_bias=bo, in_slope=si, out_slope=so)
+
+        def ref(dt):
+            t = x.to(dt) + (bi.to(dt).view(1, -1, 1, 1) if bi is not None else 0)
+            t = lrelu(t, si) if si is not None else t
+            t = torch.einsum("oc,bchw->bohw", wgt.to(dt), t) + (bo.to(dt).view(1, -1, 1, 1) if bo is not None else 0)
+            return lrelu(t, so) if so is not None else t
+        r64, r32 = ref(torch.float64), ref(torch.float32)
+        scale = float(r64.abs().max())
+        e_got, e_ref = float((got.double() - r64).abs().max()), float((r32.double() - r64).abs().max())
+        print("unaligned conv1x1: e_got %.3e e_ref %.3e scale %.3e equal to aligned call: %s"
+              % (e_got, e_ref, scale, torch.equal(got, aligned)))
+        assert got.shape == r64.shape and e_got <= 2.0 * e_ref + 2e-6 * scale, (e_got, e_ref)
+        assert torch.equal(got, aligned)
+    assert nf.check_saturation() == 0
+
+
 @pytest.mark.parametrize("c_in,h,w", [(6, 16, 16), (12, 8, 8), (24, 4, 4), (3, 5, 7), (1, 2, 2)])
 def test_conv3x3_1x1_fused_kernel(hip, c_in, h, w):
     """csrc/conv3x3_1x1.hip: y = leaky(W2 leaky(conv3x3(x, padding 1) + b1) + b2) in one launch (first two layers of the

@@ -22,7 +22,7 @@ UNITS = [(s, NO_SLP if s == "fused_final.hip" else [], os.path.splitext(s)[0]) f
         [("fused_layer_v6.hip", ["-DVCNF_V6_NBLK=%d" % n] + NO_SLP, "fused_layer_v6_b%d" % n) for n in (2, 3, 1)] + \
         [("fused_layer_v6s.hip", ["-DVCNF_V6_NBLK=%d" % n] + NO_SLP, "fused_layer_v6s_b%d" % n) for n in (2, 3, 1)] + \
         [("fused_layer.hip", ["-DVCNF_F32_NBLK=%d" % n], "fused_layer_f32_b%d" % n) for n in (3, 1)]
-HEADERS = ["rqs_math.hpp", "rqs_vjp.hpp", "rqs_lean.hpp", "fused_common.hpp", "split_half.hpp", "stream_common.hpp",
+HEADERS = ["rqs_math.hpp", "rqs_vjp.hpp", "rqs_lean.hpp", "fused_common.hpp", "fused_lds.hpp", "split_half.hpp", "stream_common.hpp",
            "rqs_host.hpp", "host_common.hpp", os.path.join("..", "..", "include", "vcnf_hip.h")]
 
 

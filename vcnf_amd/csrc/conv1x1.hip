@@ -18,15 +18,24 @@
 //     independent accumulator chains (hi x hi, hi x lo, lo x hi) over the k-steps on the LDS fragments and stores its
 //     32 channels x 32 pixels (128-byte rows).
 // C_in multiple of 16 up to 256, C_out up to 256.
+//
+// Two ways to stage a pass's rows, one kernel body (template flag DMA):
+//   * DMA = false: every thread loads its rows into registers at the head of the pass.  With the weights in registers
+//     only one 8-wave workgroup fits a CU, so a pass is: wait for its rows, convert, matrix instructions, stores -
+//     nothing overlaps (15 us per pass at 256 -> 256 channels);
+//   * DMA = true: the raw rows of the NEXT pass travel straight from global memory into LDS (buffer_load ... lds: no
+//     registers) while the current pass is in its matrix phase.  A pass is: [barrier] convert raw -> fragments
+//     (LDS -> LDS), [barrier] request the next pass's rows, matrix instructions + stores.  Needs inner % 4 == 0 and
+//     16-byte aligned x (a lane moves 4 consecutive pixels of one channel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/vcnf_hip.h"
 #include "fused_common.hpp"
+#include "host_common.hpp"
+#include "split_half.hpp"
 
 namespace vcnf {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct Conv1Args {
   const float* x;
@@ -43,10 +52,19 @@ struct Conv1Args {
 
 constexpr int kC1Block = 512;
 constexpr int kC1Pix = 64;
+constexpr IntRange<1, 16> kC1KSteps{};      // C_in / 16
+// dynamic LDS: fragments [KS][2 column blocks][hi | lo][64 lanes] of 16 bytes, DMA: + raw rows [16 KS channels][64 pixels]
+constexpr size_t conv1_lds_bytes(int ks, bool dma) {
+  return (size_t)ks * 2 * 2 * 64 * 16 + (dma ? (size_t)ks * 16 * 64 * 4 : 0);
+}
 
-template <int KS>
+template <int KS, bool DMA>
 __global__ __launch_bounds__(kC1Block, 2) void conv1x1_f16x3_kernel(const Conv1Args a) {
-  extern __shared__ __align__(16) uint4 bfrag[];        // [KS][2 column blocks][hi | lo][64 lanes]
+  extern __shared__ __align__(16) uint4 smem[];
+  uint4* bfrag = smem;                                               // [KS][2 column blocks][hi | lo][64 lanes]
+  // DMA only: [16 KS channels][64 pixels].  Without DMA the launch allocates the fragments alone (conv1_lds_bytes), this
+  // address lies past them and nothing uses it.
+  float* raw = reinterpret_cast<float*>(smem + KS * 2 * 2 * 64);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -61,116 +79,25 @@ __global__ __launch_bounds__(kC1Block, 2) void conv1x1_f16x3_kernel(const Conv1A
   const int kq = tid >> 6;
   float satm = 0.f;
   const long long ntiles = (a.npix + kC1Pix - 1) / kC1Pix;
-  // a thread's share of a pass: NIT groups of 8 input channels of its pixel, requested two groups at a time (16 rows
-  // in flight per thread; all four at once, or the next pass during the matrix phase, spill 48 / 84 registers at
-  // C_in = 256 on top of the 128 weight registers)
-  constexpr int NIT = (2 * KS + 7) / 8;
-  constexpr int NCH = NIT > 2 ? 2 : NIT;             // groups requested together
-  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const long long g = tile * kC1Pix + px;
-    const bool ok = g < a.npix;
-    const long long b = ok ? (a.inner_shift >= 0 ? (g >> a.inner_shift) : g / a.inner) : 0;
-    const float* src = a.x + b * a.Cin * a.inner + (ok ? g - b * a.inner : 0);
-    __syncthreads();                 // the previous pass's fragments are consumed
-#pragma unroll 1
-    for (int it0 = 0; it0 < NIT; it0 += NCH) {
-      float v[NCH][8];
-#pragma unroll
-      for (int u = 0; u < NCH; ++u) {
-        const int cg = kq + 8 * (it0 + u);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[u][i] = (ok && cg < 2 * KS) ? src[(long long)(8 * cg + i) * a.inner] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < NCH; ++u) {
-        const int cg = kq + 8 * (it0 + u);
-        if (it0 + u < NIT && cg < 2 * KS) {
-          half8 hi, lo;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            float t = v[u][i];
-            if (a.in_bias) t += a.in_bias[8 * cg + i];
-            if (a.in_act) t = t >= 0.f ? t : t * a.in_slope;
-            satm = fmaxf(satm, __builtin_fabsf(t));
-            t = __builtin_amdgcn_fmed3f(t, -65504.f, 65504.f);
-            const _Float16 h = (_Float16)t;
-            hi[i] = h;
-            lo[i] = (_Float16)((t - (float)h) * kLoScale);
-          }
-          const int ks = cg >> 1, ln = 32 * (cg & 1) + (px & 31), ct = px >> 5;
-          bfrag[((ks * 2 + ct) * 2 + 0) * 64 + ln] = __builtin_bit_cast(uint4, hi);
-          bfrag[((ks * 2 + ct) * 2 + 1) * 64 + ln] = __builtin_bit_cast(uint4, lo);
-        }
-      }
-    }
-    __syncthreads();
-    if (active) {
-      // one 32-pixel column block at a time: three independent accumulator chains (main, hi x lo, lo x hi)
-#pragma unroll 1
-      for (int ct = 0; ct < 2; ++ct) {
-        floatx16 mainv, ca, cb;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {       // the bias is the accumulator's start value (its loads hide behind the k-steps)
-          const int row = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-          mainv[r] = (a.out_bias && row < a.Cout) ? a.out_bias[row] : 0.f;
-          ca[r] = 0.f;
-          cb[r] = 0.f;
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const half8 bh = __builtin_bit_cast(half8, bfrag[((ks * 2 + ct) * 2 + 0) * 64 + lane]);
-          const half8 bl = __builtin_bit_cast(half8, bfrag[((ks * 2 + ct) * 2 + 1) * 64 + lane]);
-          mainv = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], bh, mainv, 0, 0, 0);
-          ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], bl, ca, 0, 0, 0);
-          cb = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ks], bh, cb, 0, 0, 0);
-        }
-        const long long g = tile * kC1Pix + 32 * ct + (lane & 31);
-        if (g < a.npix) {
-          const long long b = a.inner_shift >= 0 ? (g >> a.inner_shift) : g / a.inner;
-          float* dst = a.y + b * a.Cout * a.inner + (g - b * a.inner);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-            if (row < a.Cout) {
-              float t = fmaf(ca[r] + cb[r], kLoUnscale, mainv[r]);
-              if (a.out_act) t = t >= 0.f ? t : t * a.out_slope;
-              dst[(long long)row * a.inner] = t;
-            }
-          }
-        }
-      }
-    }
-  }
-  if (a.sat && satm > 65504.f) atomicAdd(a.sat, 1);
-}
-
-// Same computation with the raw rows of the NEXT pass travelling straight from global memory into LDS
-// (buffer_load ... lds: no registers) while the current pass is in its matrix phase.  With the weights in registers
-// only one 8-wave workgroup fits a CU, so in the kernel above a pass is: wait for its rows, convert, matrix
-// instructions, stores - nothing overlaps (15 us per pass at 256 -> 256 channels).  Here a pass is: [barrier] convert
-// raw -> fragments (LDS -> LDS), [barrier] request the next pass's rows, matrix instructions + stores.
-// Needs inner % 4 == 0 and 16-byte aligned x (a lane moves 4 consecutive pixels of one channel).
-template <int KS>
-__global__ __launch_bounds__(kC1Block, 2) void conv1x1_f16x3_dma_kernel(const Conv1Args a) {
-  extern __shared__ __align__(16) uint4 smem[];
-  uint4* bfrag = smem;                                               // [KS][2 column blocks][hi | lo][64 lanes]
-  float* raw = reinterpret_cast<float*>(smem + KS * 2 * 2 * 64);     // [16 KS channels][64 pixels]
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool active = wave * 32 < a.Cout;
-  half8 wh[KS], wl[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    wh[ks] = __builtin_bit_cast(half8, a.wfrag[((wave * KS + ks) * 2 + 0) * 64 + lane]);
-    wl[ks] = __builtin_bit_cast(half8, a.wfrag[((wave * KS + ks) * 2 + 1) * 64 + lane]);
-  }
-  const int px = tid & 63;
-  const int kq = tid >> 6;
-  float satm = 0.f;
-  const long long ntiles = (a.npix + kC1Pix - 1) / kC1Pix;
   const long long total = a.npix * a.Cin;                            // floats of x
-  // request of a pass: wave w moves channels 4 w + 32 j .. + 3 (j < KS / 2), lane = (channel of the four, 4 pixels)
+  // channel group CG (8 input channels, VALUE the raw i-th) of this thread's pixel: bias, activation, split, one
+  // fragment entry each of hi and lo
+#define VCNF_C1_STAGE(CG, VALUE)                                                                     \
+  {                                                                                                  \
+    half8 hi, lo;                                                                                    \
+    _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                  \
+      float t = VALUE;                                                                               \
+      if (a.in_bias) t += a.in_bias[8 * (CG) + i];                                                   \
+      if (a.in_act) t = t >= 0.f ? t : t * a.in_slope;                                               \
+      const HiLo s = split_plain(t, satm);                                                           \
+      hi[i] = s.hi;                                                                                  \
+      lo[i] = s.lo;                                                                                  \
+    }                                                                                                \
+    const int ks = (CG) >> 1, ln = 32 * ((CG) & 1) + (px & 31), ct = px >> 5;                        \
+    bfrag[((ks * 2 + ct) * 2 + 0) * 64 + ln] = __builtin_bit_cast(uint4, hi);                        \
+    bfrag[((ks * 2 + ct) * 2 + 1) * 64 + ln] = __builtin_bit_cast(uint4, lo);                        \
+  }
+  // DMA request of a pass: wave w moves channels 4 w + 32 j .. + 3 (j < KS / 2), lane = (channel of the four, 4 pixels)
 #define VCNF_C1_DMA(TILE)                                                                            \
   {                                                                                                  \
     const long long g0_ = (TILE) * kC1Pix;                                                           \
@@ -191,37 +118,52 @@ __global__ __launch_bounds__(kC1Block, 2) void conv1x1_f16x3_dma_kernel(const Co
       }                                                                                              \
     }                                                                                                \
   }
-  if ((long long)blockIdx.x < ntiles) VCNF_C1_DMA((long long)blockIdx.x)
+  if constexpr (DMA)
+    if ((long long)blockIdx.x < ntiles) VCNF_C1_DMA((long long)blockIdx.x)
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    wait_vector_memory();            // this wave's rows of the pass have landed in LDS ...
-    __syncthreads();                 // ... and everyone's; the previous pass's fragments are consumed
+    if constexpr (DMA) {
+      wait_vector_memory();            // this wave's rows of the pass have landed in LDS ...
+      __syncthreads();                 // ... and everyone's; the previous pass's fragments are consumed
 #pragma unroll 1
-    for (int cg = kq; cg < 2 * KS; cg += 8) {
-      half8 hi, lo;
+      for (int cg = kq; cg < 2 * KS; cg += 8) VCNF_C1_STAGE(cg, raw[(8 * cg + i) * 64 + px])
+      __syncthreads();                 // fragments complete, raw rows consumed
+      if (tile + gridDim.x < ntiles) VCNF_C1_DMA(tile + gridDim.x)
+    } else {
+      // a thread's share of a pass: NIT groups of 8 input channels of its pixel, requested two groups at a time (16
+      // rows in flight per thread; all four at once, or the next pass during the matrix phase, spill 48 / 84 registers
+      // at C_in = 256 on top of the 128 weight registers)
+      constexpr int NIT = (2 * KS + 7) / 8;
+      constexpr int NCH = NIT > 2 ? 2 : NIT;             // groups requested together
+      const long long g = tile * kC1Pix + px;
+      const bool ok = g < a.npix;
+      const long long b = ok ? (a.inner_shift >= 0 ? (g >> a.inner_shift) : g / a.inner) : 0;
+      const float* src = a.x + b * a.Cin * a.inner + (ok ? g - b * a.inner : 0);
+      __syncthreads();                 // the previous pass's fragments are consumed
+#pragma unroll 1
+      for (int it0 = 0; it0 < NIT; it0 += NCH) {
+        float v[NCH][8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float t = raw[(8 * cg + i) * 64 + px];
-        if (a.in_bias) t += a.in_bias[8 * cg + i];
-        if (a.in_act) t = t >= 0.f ? t : t * a.in_slope;
-        satm = fmaxf(satm, __builtin_fabsf(t));
-        t = __builtin_amdgcn_fmed3f(t, -65504.f, 65504.f);
-        const _Float16 h = (_Float16)t;
-        hi[i] = h;
-        lo[i] = (_Float16)((t - (float)h) * kLoScale);
+        for (int u = 0; u < NCH; ++u) {
+          const int cg = kq + 8 * (it0 + u);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) v[u][i] = (ok && cg < 2 * KS) ? src[(long long)(8 * cg + i) * a.inner] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < NCH; ++u) {
+          const int cg = kq + 8 * (it0 + u);
+          if (it0 + u < NIT && cg < 2 * KS) VCNF_C1_STAGE(cg, v[u][i])
+        }
       }
-      const int ks = cg >> 1, ln = 32 * (cg & 1) + (px & 31), ct = px >> 5;
-      bfrag[((ks * 2 + ct) * 2 + 0) * 64 + ln] = __builtin_bit_cast(uint4, hi);
-      bfrag[((ks * 2 + ct) * 2 + 1) * 64 + ln] = __builtin_bit_cast(uint4, lo);
+      __syncthreads();
     }
-    __syncthreads();                 // fragments complete, raw rows consumed
-    if (tile + gridDim.x < ntiles) VCNF_C1_DMA(tile + gridDim.x)
     if (active) {
+      // one 32-pixel column block at a time: three independent accumulator chains (main, hi x lo, lo x hi)
 #pragma unroll 1
       for (int ct = 0; ct < 2; ++ct) {
         floatx16 mainv, ca, cb;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {       // the bias is the accumulator's start value (its loads hide behind the k-steps)
-          const int row = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+          const int row = acc_row(r, lane, 32 * wave);
           mainv[r] = (a.out_bias && row < a.Cout) ? a.out_bias[row] : 0.f;
           ca[r] = 0.f;
           cb[r] = 0.f;
@@ -230,9 +172,7 @@ __global__ __launch_bounds__(kC1Block, 2) void conv1x1_f16x3_dma_kernel(const Co
         for (int ks = 0; ks < KS; ++ks) {
           const half8 bh = __builtin_bit_cast(half8, bfrag[((ks * 2 + ct) * 2 + 0) * 64 + lane]);
           const half8 bl = __builtin_bit_cast(half8, bfrag[((ks * 2 + ct) * 2 + 1) * 64 + lane]);
-          mainv = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], bh, mainv, 0, 0, 0);
-          ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], bl, ca, 0, 0, 0);
-          cb = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ks], bh, cb, 0, 0, 0);
+          mfma32h_x3(wh[ks], wl[ks], bh, bl, mainv, ca, cb);
         }
         const long long g = tile * kC1Pix + 32 * ct + (lane & 31);
         if (g < a.npix) {
@@ -240,7 +180,7 @@ __global__ __launch_bounds__(kC1Block, 2) void conv1x1_f16x3_dma_kernel(const Co
           float* dst = a.y + b * a.Cout * a.inner + (g - b * a.inner);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int row = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+            const int row = acc_row(r, lane, 32 * wave);
             if (row < a.Cout) {
               float t = fmaf(ca[r] + cb[r], kLoUnscale, mainv[r]);
               if (a.out_act) t = t >= 0.f ? t : t * a.out_slope;
@@ -252,28 +192,19 @@ __global__ __launch_bounds__(kC1Block, 2) void conv1x1_f16x3_dma_kernel(const Co
     }
   }
 #undef VCNF_C1_DMA
+#undef VCNF_C1_STAGE
   if (a.sat && satm > 65504.f) atomicAdd(a.sat, 1);
 }
 
-template <int KS>
+template <int KS, bool DMA>
 static int launch_conv1(const Conv1Args& a, hipStream_t st) {
-  const bool dma = (a.inner % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0);
-  const size_t lds = (size_t)KS * 2 * 2 * 64 * 16 + (dma ? (size_t)KS * 16 * 64 * 4 : 0);
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[dma]) {
-    const void* fn = dma ? reinterpret_cast<const void*>(&conv1x1_f16x3_dma_kernel<KS>)
-                         : reinterpret_cast<const void*>(&conv1x1_f16x3_kernel<KS>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return VCNF_ERR_LAUNCH;
-    attr_set[dma] = true;
-  }
+  constexpr size_t lds = conv1_lds_bytes(KS, DMA);
+  if (!lds_limit_once<&conv1x1_f16x3_kernel<KS, DMA>>(lds)) return VCNF_ERR_LAUNCH;
   const long long ntiles = (a.npix + kC1Pix - 1) / kC1Pix;
   const long long cap = 256;                 // one 8-wave workgroup per CU (128 weight registers per lane)
   dim3 grid((unsigned)(ntiles < cap ? ntiles : cap));
-  if (dma)
-    hipLaunchKernelGGL((conv1x1_f16x3_dma_kernel<KS>), grid, dim3(kC1Block), lds, st, a);
-  else
-    hipLaunchKernelGGL((conv1x1_f16x3_kernel<KS>), grid, dim3(kC1Block), lds, st, a);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  hipLaunchKernelGGL((conv1x1_f16x3_kernel<KS, DMA>), grid, dim3(kC1Block), lds, st, a);
+  return launched();
 }
 
 }  // namespace vcnf
@@ -298,7 +229,7 @@ extern "C" int vcnf_conv1x1_f16x3_f32(const float* x, float* y, const float* wpa
   if (wpack_floats != vcnf_conv1x1_pack_floats(c_in, c_out)) return VCNF_ERR_SHAPE;
   if (batch == 0) return VCNF_OK;
   if (!x || !y || !wpack) return VCNF_ERR_NULL;
-  if (reinterpret_cast<uintptr_t>(wpack) & 15) return VCNF_ERR_ALIGN;
+  if (!aligned(wpack, 16)) return VCNF_ERR_ALIGN;
   Conv1Args a;
   a.x = x; a.y = y; a.wfrag = reinterpret_cast<const uint4*>(wpack); a.in_bias = in_bias; a.out_bias = out_bias;
   a.npix = batch * inner; a.inner = inner; a.Cin = c_in; a.Cout = c_out;
@@ -307,23 +238,8 @@ extern "C" int vcnf_conv1x1_f16x3_f32(const float* x, float* y, const float* wpa
   a.inner_shift = -1;
   for (int sh = 0; sh < 40; ++sh) if (((long long)1 << sh) == inner) a.inner_shift = sh;
   hipStream_t st = (hipStream_t)stream;
-  switch (c_in / 16) {
-    case 1: return launch_conv1<1>(a, st);
-    case 2: return launch_conv1<2>(a, st);
-    case 3: return launch_conv1<3>(a, st);
-    case 4: return launch_conv1<4>(a, st);
-    case 5: return launch_conv1<5>(a, st);
-    case 6: return launch_conv1<6>(a, st);
-    case 7: return launch_conv1<7>(a, st);
-    case 8: return launch_conv1<8>(a, st);
-    case 9: return launch_conv1<9>(a, st);
-    case 10: return launch_conv1<10>(a, st);
-    case 11: return launch_conv1<11>(a, st);
-    case 12: return launch_conv1<12>(a, st);
-    case 13: return launch_conv1<13>(a, st);
-    case 14: return launch_conv1<14>(a, st);
-    case 15: return launch_conv1<15>(a, st);
-    case 16: return launch_conv1<16>(a, st);
-    default: return VCNF_ERR_UNSUPPORTED;
-  }
+  const bool dma = (inner % 4 == 0) && aligned(x, 16);
+  return launch_listed(kC1KSteps, c_in / 16, [&](auto KS) {
+    return dma ? launch_conv1<KS(), true>(a, st) : launch_conv1<KS(), false>(a, st);
+  });
 }

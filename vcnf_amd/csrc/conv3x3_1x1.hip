@@ -11,8 +11,8 @@
 //     the whole launch, its W1 fragments (8-28 KB, L2-resident) stream in per pass;
 //   * a pass is 64 consecutive pixels: (1) all threads gather the pass's 3x3 patches (zero padded at the image
 //     borders) and write them as B fragments; (2) every wave multiplies its W1 rows with them, adds b1, applies the
-//     activation, splits the result and writes it as the B fragments of the second layer - accumulator register r of
-//     lane (column, half) is channel 32 w + 8 (r / 4) + 4 half + r % 4, i.e. four adjacent halves of a fragment entry;
+//     activation, splits the result and writes it as the B fragments of the second layer - four consecutive
+//     accumulator registers are four adjacent channels (acc_row, split_half.hpp), i.e. four adjacent halves of an entry;
 //     (3) the 1x1 layer as in conv1x1.hip; (4) 128-byte row stores of y.
 // C_in <= 24 (K <= 224), hidden = output = 256 channels.
 //
@@ -29,11 +29,10 @@
 
 #include "../../include/vcnf_hip.h"
 #include "fused_common.hpp"
+#include "host_common.hpp"
+#include "split_half.hpp"
 
 namespace vcnf {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 
 struct Conv31Args {
   const float* x;
@@ -54,6 +53,53 @@ struct Conv31Args {
 constexpr int kC31Block = 512;
 constexpr int kC31Pix = 64;
 constexpr int kC31KS2 = 16;          // 256 hidden channels
+constexpr IntRange<1, 14> kC31KSteps{};     // ceil(9 C_in / 16)
+
+// The kernel's two shared blocks are macros, not functions: as __forceinline__ functions they cost the instances that
+// sit at the 256-register limit scratch (profiles/split_half_units.md section 1).  Both use lane, wave and satm of
+// the kernel.
+//
+// Split-half product over KS k-steps with the A fragments streamed from global memory (W1, W3': L2-resident), one k-step
+// ahead of its use, rolled (unrolled, the compiler requests every k-step's fragments up front).  W: this lane's entry
+// of k-step 0 ([k-step][hi | lo][64 lanes]); FRAG: the B fragments of k-step 0 ([hi | lo][64 lanes]), KSTRIDE entries
+// between k-steps.
+#define VCNF_C31_STREAMED_CHAIN(KS, W, FRAG, KSTRIDE, M, CA, CB)                                      \
+  {                                                                                                  \
+    const uint4* w_ = (W);                                                                           \
+    const uint4* f_ = (FRAG);                                                                        \
+    half8 ah = __builtin_bit_cast(half8, w_[0]), al = __builtin_bit_cast(half8, w_[64]);             \
+    _Pragma("unroll 1") for (int ks = 0; ks < (KS); ++ks) {                                          \
+      const half8 ahc = ah, alc = al;                                                                \
+      if (ks + 1 < (KS)) {                                                                           \
+        ah = __builtin_bit_cast(half8, w_[((ks + 1) * 2 + 0) * 64]);                                 \
+        al = __builtin_bit_cast(half8, w_[((ks + 1) * 2 + 1) * 64]);                                 \
+      }                                                                                              \
+      const half8 bh = __builtin_bit_cast(half8, f_[ks * (KSTRIDE) + lane]);                         \
+      const half8 bl = __builtin_bit_cast(half8, f_[ks * (KSTRIDE) + 64 + lane]);                    \
+      mfma32h_x3(ahc, alc, bh, bl, M, CA, CB);                                                       \
+    }                                                                                                \
+  }
+
+// A layer's accumulators -> B fragments of the next layer: bias is in, activation and split happen here.  Register
+// r = 4 j + c of lane (column, half) is channel acc_row(r, lane, 32 wave) = 32 wave + 8 j + 4 half + c -> k-step
+// 2 wave + j / 2, lane half j % 2, halves 4 half + c of the entry.  FRAG and KSTRIDE as above.
+#define VCNF_C31_ACC_TO_FRAG(M, CA, CB, SLOPE, FRAG, KSTRIDE)                                         \
+  {                                                                                                  \
+    const int col = lane & 31, hh = lane >> 5;                                                       \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                  \
+      half4 h4, l4;                                                                                  \
+      _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                \
+        float t = fmaf(CA[4 * j + c] + CB[4 * j + c], kLoUnscale, M[4 * j + c]);                     \
+        t = t >= 0.f ? t : t * (SLOPE);                                                              \
+        const HiLo s = split_plain(t, satm);                                                         \
+        h4[c] = s.hi;                                                                                \
+        l4[c] = s.lo;                                                                                \
+      }                                                                                              \
+      uint4* e = (FRAG) + (2 * wave + (j >> 1)) * (KSTRIDE) + 32 * (j & 1) + col;                    \
+      *(reinterpret_cast<uint2*>(e) + hh) = __builtin_bit_cast(uint2, h4);                           \
+      *(reinterpret_cast<uint2*>(e + 64) + hh) = __builtin_bit_cast(uint2, l4);                      \
+    }                                                                                                \
+  }
 
 template <int KS1, bool THIRD>
 __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const Conv31Args a) {
@@ -97,11 +143,9 @@ __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const C
           const int yy = py + dy - 1, xx = pxx + dx - 1;
           if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) t = img[(long long)ci * hw + yy * a.W + xx];
         }
-        satm = fmaxf(satm, __builtin_fabsf(t));
-        t = __builtin_amdgcn_fmed3f(t, -65504.f, 65504.f);
-        const _Float16 h = (_Float16)t;
-        hi[i] = h;
-        lo[i] = (_Float16)((t - (float)h) * kLoScale);
+        const HiLo s = split_plain(t, satm);
+        hi[i] = s.hi;
+        lo[i] = s.lo;
       }
       const int ks = kg8 >> 1, ln = 32 * (kg8 & 1) + (pxl & 31), ct = pxl >> 5;
       bf1[((ks * 2 + ct) * 2 + 0) * 64 + ln] = __builtin_bit_cast(uint4, hi);
@@ -115,47 +159,12 @@ __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const C
       floatx16 mainv, ca, cb;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ch = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-        mainv[r] = a.b1 ? a.b1[ch] : 0.f;
+        mainv[r] = a.b1 ? a.b1[acc_row(r, lane, 32 * wave)] : 0.f;
         ca[r] = 0.f;
         cb[r] = 0.f;
       }
-      half8 ah = __builtin_bit_cast(half8, w1[0]), al = __builtin_bit_cast(half8, w1[64]);
-#pragma unroll 1
-      for (int ks = 0; ks < KS1; ++ks) {      // rolled: unrolled, the compiler requests every k-step's W1 fragments up front
-
-        const half8 ahc = ah, alc = al;
-        if (ks + 1 < KS1) {
-          ah = __builtin_bit_cast(half8, w1[((ks + 1) * 2 + 0) * 64]);
-          al = __builtin_bit_cast(half8, w1[((ks + 1) * 2 + 1) * 64]);
-        }
-        const half8 bh = __builtin_bit_cast(half8, bf1[((ks * 2 + ct) * 2 + 0) * 64 + lane]);
-        const half8 bl = __builtin_bit_cast(half8, bf1[((ks * 2 + ct) * 2 + 1) * 64 + lane]);
-        mainv = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahc, bh, mainv, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahc, bl, ca, 0, 0, 0);
-        cb = __builtin_amdgcn_mfma_f32_32x32x16_f16(alc, bh, cb, 0, 0, 0);
-      }
-      // register r = 4 j + c: channel 32 w + 8 j + 4 half + c -> k-step 2 w + j / 2, lane half j % 2, halves 4 half + c
-      const int col = lane & 31, hh = lane >> 5;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        half4v h4, l4;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float t = fmaf(ca[4 * j + c] + cb[4 * j + c], kLoUnscale, mainv[4 * j + c]);
-          t = t >= 0.f ? t : t * a.slope1;
-          satm = fmaxf(satm, __builtin_fabsf(t));
-          t = __builtin_amdgcn_fmed3f(t, -65504.f, 65504.f);
-          const _Float16 h = (_Float16)t;
-          h4[c] = h;
-          l4[c] = (_Float16)((t - (float)h) * kLoScale);
-        }
-        const int ks2 = 2 * wave + (j >> 1), ln = 32 * (j & 1) + col;
-        uint2* eh = reinterpret_cast<uint2*>(bf2 + ((ks2 * 2 + ct) * 2 + 0) * 64 + ln) + hh;
-        uint2* el = reinterpret_cast<uint2*>(bf2 + ((ks2 * 2 + ct) * 2 + 1) * 64 + ln) + hh;
-        *eh = __builtin_bit_cast(uint2, h4);
-        *el = __builtin_bit_cast(uint2, l4);
-      }
+      VCNF_C31_STREAMED_CHAIN(KS1, w1, bf1 + ct * 2 * 64, 4 * 64, mainv, ca, cb)
+      VCNF_C31_ACC_TO_FRAG(mainv, ca, cb, a.slope1, bf2 + ct * 2 * 64, 4 * 64)
     }
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
@@ -165,8 +174,7 @@ __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const C
       floatx16 mainv, ca, cb;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-        mainv[r] = a.b2 ? a.b2[row] : 0.f;
+        mainv[r] = a.b2 ? a.b2[acc_row(r, lane, 32 * wave)] : 0.f;
         ca[r] = 0.f;
         cb[r] = 0.f;
       }
@@ -174,9 +182,7 @@ __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const C
       for (int ks = 0; ks < kC31KS2; ++ks) {
         const half8 bh = __builtin_bit_cast(half8, bf2[((ks * 2 + ct) * 2 + 0) * 64 + lane]);
         const half8 bl = __builtin_bit_cast(half8, bf2[((ks * 2 + ct) * 2 + 1) * 64 + lane]);
-        mainv = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], bh, mainv, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ks], bl, ca, 0, 0, 0);
-        cb = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ks], bh, cb, 0, 0, 0);
+        mfma32h_x3(wh[ks], wl[ks], bh, bl, mainv, ca, cb);
       }
       const long long g = tile * kC31Pix + 32 * ct + (lane & 31);
       if constexpr (!THIRD) {
@@ -185,7 +191,7 @@ __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const C
           float* dst = a.y + b * 256 * hw + (g - b * hw);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int row = 32 * wave + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+            const int row = acc_row(r, lane, 32 * wave);
             float t = fmaf(ca[r] + cb[r], kLoUnscale, mainv[r]);
             t = t >= 0.f ? t : t * a.slope2;
             dst[(long long)row * hw] = t;
@@ -193,51 +199,20 @@ __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const C
         }
       } else {
         // ---- (5) y of this column block -> fragments (same register -> entry map as after the first layer)
-        const int col = lane & 31, hh = lane >> 5;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          half4v h4, l4;
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            float t = fmaf(ca[4 * j + c] + cb[4 * j + c], kLoUnscale, mainv[4 * j + c]);
-            t = t >= 0.f ? t : t * a.slope2;
-            satm = fmaxf(satm, __builtin_fabsf(t));
-            t = __builtin_amdgcn_fmed3f(t, -65504.f, 65504.f);
-            const _Float16 h = (_Float16)t;
-            h4[c] = h;
-            l4[c] = (_Float16)((t - (float)h) * kLoScale);
-          }
-          const int ks3 = 2 * wave + (j >> 1), ln = 32 * (j & 1) + col;
-          *(reinterpret_cast<uint2*>(bf3 + (ks3 * 2 + 0) * 64 + ln) + hh) = __builtin_bit_cast(uint2, h4);
-          *(reinterpret_cast<uint2*>(bf3 + (ks3 * 2 + 1) * 64 + ln) + hh) = __builtin_bit_cast(uint2, l4);
-        }
+        VCNF_C31_ACC_TO_FRAG(mainv, ca, cb, a.slope2, bf3, 2 * 64)
         __syncthreads();
         // ---- (6) nine 1x1 convolutions of the taps: row blocks of W3' shared out over the waves
         for (int rb = wave; rb < a.RB3; rb += 8) {
           floatx16 m3, c3a, c3b;
 #pragma unroll
           for (int r = 0; r < 16; ++r) { m3[r] = 0.f; c3a[r] = 0.f; c3b[r] = 0.f; }
-          const uint4* w3 = a.w3frag + (long long)rb * kC31KS2 * 2 * 64 + lane;
-          half8 ah = __builtin_bit_cast(half8, w3[0]), al = __builtin_bit_cast(half8, w3[64]);
-#pragma unroll 1
-          for (int ks = 0; ks < kC31KS2; ++ks) {
-            const half8 ahc = ah, alc = al;
-            if (ks + 1 < kC31KS2) {
-              ah = __builtin_bit_cast(half8, w3[((ks + 1) * 2 + 0) * 64]);
-              al = __builtin_bit_cast(half8, w3[((ks + 1) * 2 + 1) * 64]);
-            }
-            const half8 bh = __builtin_bit_cast(half8, bf3[(ks * 2 + 0) * 64 + lane]);
-            const half8 bl = __builtin_bit_cast(half8, bf3[(ks * 2 + 1) * 64 + lane]);
-            m3 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahc, bh, m3, 0, 0, 0);
-            c3a = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahc, bl, c3a, 0, 0, 0);
-            c3b = __builtin_amdgcn_mfma_f32_32x32x16_f16(alc, bh, c3b, 0, 0, 0);
-          }
+          VCNF_C31_STREAMED_CHAIN(kC31KS2, a.w3frag + (long long)rb * kC31KS2 * 2 * 64 + lane, bf3, 2 * 64, m3, c3a, c3b)
           if (g < a.npix) {
             const long long b = g / hw;
             float* dst = a.z + b * a.M3 * hw + (g - b * hw);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const int row = 32 * rb + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+              const int row = acc_row(r, lane, 32 * rb);
               if (row < a.M3) dst[(long long)row * hw] = fmaf(c3a[r] + c3b[r], kLoUnscale, m3[r]);
             }
           }
@@ -248,22 +223,18 @@ __global__ __launch_bounds__(kC31Block, 2) void conv3x3_1x1_f16x3_kernel(const C
   }
   if (a.sat && satm > 65504.f) atomicAdd(a.sat, 1);
 }
+#undef VCNF_C31_STREAMED_CHAIN
+#undef VCNF_C31_ACC_TO_FRAG
 
 template <int KS1, bool THIRD>
 static int launch_c31t(const Conv31Args& a, hipStream_t st) {
-  const size_t lds = ((size_t)KS1 + kC31KS2) * 2 * 2 * 64 * 16 + (THIRD ? (size_t)kC31KS2 * 2 * 64 * 16 : 0);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_1x1_f16x3_kernel<KS1, THIRD>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return VCNF_ERR_LAUNCH;
-    attr_set = true;
-  }
+  constexpr size_t lds = ((size_t)KS1 + kC31KS2) * 2 * 2 * 64 * 16 + (THIRD ? (size_t)kC31KS2 * 2 * 64 * 16 : 0);
+  if (!lds_limit_once<&conv3x3_1x1_f16x3_kernel<KS1, THIRD>>(lds)) return VCNF_ERR_LAUNCH;
   const long long ntiles = (a.npix + kC31Pix - 1) / kC31Pix;
   const long long cap = 256;               // one 8-wave workgroup per CU (128 weight registers per lane)
   dim3 grid((unsigned)(ntiles < cap ? ntiles : cap));
   hipLaunchKernelGGL((conv3x3_1x1_f16x3_kernel<KS1, THIRD>), grid, dim3(kC31Block), lds, st, a);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return launched();
 }
 
 template <int KS1>
@@ -314,23 +285,7 @@ extern "C" int64_t vcnf_conv3x3_1x1_pack_floats(int32_t c_in) {
 }
 
 static int dispatch_c31(const Conv31Args& a, int c_in, hipStream_t st) {
-  switch ((9 * c_in + 15) / 16) {
-    case 1: return launch_c31<1>(a, st);
-    case 2: return launch_c31<2>(a, st);
-    case 3: return launch_c31<3>(a, st);
-    case 4: return launch_c31<4>(a, st);
-    case 5: return launch_c31<5>(a, st);
-    case 6: return launch_c31<6>(a, st);
-    case 7: return launch_c31<7>(a, st);
-    case 8: return launch_c31<8>(a, st);
-    case 9: return launch_c31<9>(a, st);
-    case 10: return launch_c31<10>(a, st);
-    case 11: return launch_c31<11>(a, st);
-    case 12: return launch_c31<12>(a, st);
-    case 13: return launch_c31<13>(a, st);
-    case 14: return launch_c31<14>(a, st);
-    default: return VCNF_ERR_UNSUPPORTED;
-  }
+  return launch_listed(kC31KSteps, (9 * c_in + 15) / 16, [&](auto KS1) { return launch_c31<KS1()>(a, st); });
 }
 
 extern "C" int vcnf_conv3x3_1x1_f16x3_f32(const float* x, float* y, const float* w1pack, int64_t w1pack_floats,
@@ -342,7 +297,7 @@ extern "C" int vcnf_conv3x3_1x1_f16x3_f32(const float* x, float* y, const float*
   if (w1pack_floats != vcnf_conv3x3_1x1_pack_floats(c_in) || w2pack_floats != (int64_t)8 * 16 * 2 * 64 * 4) return VCNF_ERR_SHAPE;
   if (batch == 0) return VCNF_OK;
   if (!x || !y || !w1pack || !w2pack) return VCNF_ERR_NULL;
-  if ((reinterpret_cast<uintptr_t>(w1pack) | reinterpret_cast<uintptr_t>(w2pack)) & 15) return VCNF_ERR_ALIGN;
+  if (!all_aligned({w1pack, w2pack}, 16)) return VCNF_ERR_ALIGN;
   Conv31Args a;
   a.x = x; a.y = y; a.w1frag = reinterpret_cast<const uint4*>(w1pack); a.w2frag = reinterpret_cast<const uint4*>(w2pack);
   a.b1 = b1; a.b2 = b2; a.npix = batch * (long long)height * width; a.Cin = c_in; a.H = height; a.W = width;
@@ -374,8 +329,7 @@ extern "C" int vcnf_convnet3_taps_f16x3_f32(const float* x, float* z, const floa
     return VCNF_ERR_SHAPE;
   if (batch == 0) return VCNF_OK;
   if (!x || !z || !w1pack || !w2pack || !w3pack) return VCNF_ERR_NULL;
-  if ((reinterpret_cast<uintptr_t>(w1pack) | reinterpret_cast<uintptr_t>(w2pack) | reinterpret_cast<uintptr_t>(w3pack)) & 15)
-    return VCNF_ERR_ALIGN;
+  if (!all_aligned({w1pack, w2pack, w3pack}, 16)) return VCNF_ERR_ALIGN;
   Conv31Args a;
   a.x = x; a.y = nullptr; a.w1frag = reinterpret_cast<const uint4*>(w1pack); a.w2frag = reinterpret_cast<const uint4*>(w2pack);
   a.b1 = b1; a.b2 = b2; a.npix = batch * (long long)height * width; a.Cin = c_in; a.H = height; a.W = width;
@@ -396,5 +350,5 @@ extern "C" int vcnf_col2im3x3_f32(const float* z, const float* bias, float* out,
   const long long blocks = (a.n + 255) / 256;
   if (blocks > 0x7fffffffLL) return VCNF_ERR_SHAPE;
   hipLaunchKernelGGL(col2im3x3_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return launched();
 }

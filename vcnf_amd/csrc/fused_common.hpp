@@ -1,9 +1,15 @@
-// Shared pieces of the fused RQS-layer kernels (fused_layer.hip: exact fp32 matrix path;
-// fused_layer_v6.hip: fp16x3 split-half matrix path).
+// Shared pieces of the fused RQS-layer kernels (fused_layer.hip: exact fp32 matrix path; fused_layer_v6.hip,
+// fused_layer_v6s.hip: fp16x3 split-half matrix path): argument structs, packed-weight layouts, LDS layouts
+// (fused_lds.hpp), the shape-family dispatch and the per-block-count entry points.  Its vector types, kLoScale, split4,
+// wload and dma16_to_lds also serve fused_final.hip, resnet_trunk.hip and channel_mix.hip, and - beside split_half.hpp -
+// fused_affine.hip, linear_f16x3.hip, linear_wgrad.hip, gemm_probe.hip, conv1x1.hip and conv3x3_1x1.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "fused_lds.hpp"
 #include "rqs_math.hpp"
 
 namespace vcnf {
@@ -158,6 +164,25 @@ struct PackLayout6 {
   static constexpr int TOTAL = BF + NG * 96;
   static_assert(TOTAL == PackLayout<DI, DT, C, H, NBLK, K>::TOTAL, "both matrix paths take a buffer of the same size");
 };
+
+// Shape family of the fused layer kernels and of their packed weights: d_id = d_t in {16, 32}, context 0 or 16 (hidden
+// 128, 8 bins; the entry points have validated the shape).  f(DI, C) with std::integral_constants.
+template <class F>
+inline auto with_fused_shape(int d_id, int ctx_dim, F&& f) {
+  using I16 = std::integral_constant<int, 16>;
+  using I32 = std::integral_constant<int, 32>;
+  using I0 = std::integral_constant<int, 0>;
+  if (d_id == 32) return ctx_dim == 16 ? f(I32{}, I16{}) : f(I32{}, I0{});
+  return ctx_dim == 16 ? f(I16{}, I16{}) : f(I16{}, I0{});
+}
+
+// One translation unit per number of residual blocks (build.py compiles them in parallel): the unit built with NBLK = n
+// defines NAME<n>, which hands over to FAMILY<n>; fused_layer.hip picks the entry by the run-time block count.
+#define VCNF_BLOCKS_ENTRY_(NAME, NBLK, ARGS, FAMILY)                                        \
+  int NAME##NBLK(const ARGS& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {       \
+    return FAMILY<NBLK>(a, d_id, ctx_dim, inverse, st);                                     \
+  }
+#define VCNF_BLOCKS_ENTRY(NAME, NBLK, ARGS, FAMILY) VCNF_BLOCKS_ENTRY_(NAME, NBLK, ARGS, FAMILY)
 
 // defined in fused_layer.hip built with -DVCNF_F32_NBLK=1 / 3 (exact fp32 kernel, one / three residual blocks)
 int launch_fused_f32_b1(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);

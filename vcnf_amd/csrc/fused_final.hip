@@ -227,17 +227,10 @@ __global__ __launch_bounds__(kFinBlock, 2) void rqs_final_fused_kernel(const Fin
 template <int K, bool PRE>
 static int launch_final_pre(const FinalArgs& a, int inverse, hipStream_t st) {
   using S = FinalShape<K>;
-  const size_t lds = (size_t)S::GW * S::GFRAG * 16 + (size_t)S::GW * 16 * S::P4 * sizeof(float);
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[inverse ? 1 : 0]) {
-    hipError_t e = inverse
-        ? hipFuncSetAttribute(reinterpret_cast<const void*>(&rqs_final_fused_kernel<K, true, PRE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-        : hipFuncSetAttribute(reinterpret_cast<const void*>(&rqs_final_fused_kernel<K, false, PRE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return VCNF_ERR_LAUNCH;
-    attr_set[inverse ? 1 : 0] = true;
-  }
+  constexpr size_t lds = (size_t)S::GW * S::GFRAG * 16 + (size_t)S::GW * 16 * S::P4 * sizeof(float);
+  const bool set = inverse ? lds_limit_once<&rqs_final_fused_kernel<K, true, PRE>>(lds)
+                           : lds_limit_once<&rqs_final_fused_kernel<K, false, PRE>>(lds);
+  if (!set) return VCNF_ERR_LAUNCH;
   dim3 grid((unsigned)(a.gblocks * a.sblocks));
   if (inverse)
     hipLaunchKernelGGL((rqs_final_fused_kernel<K, true, PRE>), grid, dim3(kFinBlock), lds, st, a);

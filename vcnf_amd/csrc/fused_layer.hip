@@ -83,11 +83,13 @@ __global__ __launch_bounds__(kFBlock, 2) void fused_rqs_layer_kernel(const Fused
   static_assert(DI % 4 == 0 && DT % 4 == 0 && C % 4 == 0 && H % 16 == 0, "shape family");
 
   extern __shared__ __align__(16) float smem[];
-  float* xt = smem;                         // [kTile][XS]   x in, y out (in place)
-  float* ct = xt + kTile * XS;              // [kTile][CS]
-  float* tab = ct + kTile * CS;             // [DI][TABW]
-  int* tfi = reinterpret_cast<int*>(tab + ((DI * TABW + 3) & ~3));
-  int* idi = tfi + DT;
+  using S = LdsF32<DI, DT, C, H, NBLK, K, kCB>;      // the regions, their offsets and the launch's byte count
+  static_assert(S::TILE == kTile && S::XT_N == kTile * XS && S::CT_N == kTile * CS && S::TAB_N >= DI * TABW, "layout");
+  float* xt = smem + S::XT;                 // [kTile][XS]   x in, y out (in place)
+  float* ct = smem + S::CT;                 // [kTile][CS]
+  float* tab = smem + S::TAB;               // [DI][TABW]
+  int* tfi = reinterpret_cast<int*>(smem + S::TFI);
+  int* idi = reinterpret_cast<int*>(smem + S::IDI);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -338,9 +340,7 @@ template <int DI, int DT, int C, int H, int NBLK, int K, int kCB>
 static int launch_fused(const FusedStackArgs& sa, int inverse, hipStream_t st) {
   const FusedArgs& a = sa.a;
   constexpr int kTile = 4 * kCB * 16;
-  constexpr int D = DI + DT;
-  const size_t lds = ((size_t)kTile * (D + 4) + (size_t)kTile * ((C > 0 ? C : 4) + 4) +
-                      ((DI * 3 * (K + 1) + 3) & ~3) + D) * 4 + 64;
+  constexpr size_t lds = LdsF32<DI, DT, C, H, NBLK, K, kCB>::BYTES;  // below 64 KB: no limit to raise
   const long long ntiles = (a.B + kTile - 1) / kTile;
   const long long resident = 256 * 2;   // workgroups the chip holds at once
   dim3 grid((unsigned)(ntiles < resident ? ntiles : resident));
@@ -359,23 +359,15 @@ static int launch_fused(const FusedStackArgs& sa, int inverse, hipStream_t st) {
 // Shape family of the exact fp32 kernel: (d_id = d_t, ctx) with H = 128, 8 bins, NBLK residual blocks.
 template <int NBLK>
 static int launch_fused_f32_family(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  if (d_id == 32)
-    return ctx_dim == 16 ? launch_fused<32, 32, 16, 128, NBLK, 8, 2>(a, inverse, st)
-                         : launch_fused<32, 32, 0, 128, NBLK, 8, 2>(a, inverse, st);
-  return ctx_dim == 16 ? launch_fused<16, 16, 16, 128, NBLK, 8, 2>(a, inverse, st)
-                       : launch_fused<16, 16, 0, 128, NBLK, 8, 2>(a, inverse, st);
+  return with_fused_shape(d_id, ctx_dim, [&](auto DI, auto C) {
+    return launch_fused<DI(), DI(), C(), 128, NBLK, 8, 2>(a, inverse, st);
+  });
 }
 
 // One- and three-block layers are compiled as their own translation units (-DVCNF_F32_NBLK=1|3, build.py runs
 // them in parallel); the unit without the macro holds the two-block kernels and the C entry points.
-#if defined(VCNF_F32_NBLK) && VCNF_F32_NBLK == 1
-int launch_fused_f32_b1(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_fused_f32_family<1>(a, d_id, ctx_dim, inverse, st);
-}
-#elif defined(VCNF_F32_NBLK) && VCNF_F32_NBLK == 3
-int launch_fused_f32_b3(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_fused_f32_family<3>(a, d_id, ctx_dim, inverse, st);
-}
+#ifdef VCNF_F32_NBLK
+VCNF_BLOCKS_ENTRY(launch_fused_f32_b, VCNF_F32_NBLK, FusedStackArgs, launch_fused_f32_family)
 #endif
 
 }  // namespace vcnf
@@ -385,20 +377,15 @@ using namespace vcnf;
 
 // shape family: d_id = d_t in {16, 32}, context 0 or 16, 1-3 residual blocks (hidden 128, 8 bins, linear
 // tails), on both matrix paths.
-template <int NBLK>
-static int64_t pack_total(int d_id, int ctx_dim) {
-  if (d_id == 32) return ctx_dim == 16 ? PackLayout<32, 32, 16, 128, NBLK, 8>::TOTAL : PackLayout<32, 32, 0, 128, NBLK, 8>::TOTAL;
-  return ctx_dim == 16 ? PackLayout<16, 16, 16, 128, NBLK, 8>::TOTAL : PackLayout<16, 16, 0, 128, NBLK, 8>::TOTAL;
-}
-
 extern "C" int64_t vcnf_rqs_layer_fused_pack_floats(int32_t d_id, int32_t d_t, int32_t ctx_dim, int32_t num_blocks) {
   if (d_id != d_t || (d_id != 16 && d_id != 32) || (ctx_dim != 0 && ctx_dim != 16)) return 0;
-  switch (num_blocks) {
-    case 1: return pack_total<1>(d_id, ctx_dim);
-    case 2: return pack_total<2>(d_id, ctx_dim);
-    case 3: return pack_total<3>(d_id, ctx_dim);
-    default: return 0;
-  }
+  int64_t total = 0;
+  with_listed_only(IntRange<1, 3>{}, num_blocks, [&](auto NBLK) {
+    total = with_fused_shape(d_id, ctx_dim, [](auto DI, auto C) -> int64_t {
+      return PackLayout<DI(), DI(), C(), 128, decltype(NBLK)::value, 8>::TOTAL;
+    });
+  });
+  return total;
 }
 
 extern "C" int32_t vcnf_rqs_layer_fused_tile_rows(void) { return kFusedFlagRows; }

@@ -43,6 +43,7 @@
 #include "../../include/vcnf_hip.h"
 #include "rqs_math.hpp"
 #include "fused_common.hpp"
+#include "host_common.hpp"
 #include "rqs_lean.hpp"
 #include "split_half.hpp"
 
@@ -118,28 +119,30 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   constexpr int RING = VCNF_AHEAD + 1;
 
   extern __shared__ __align__(16) float smem[];
+  using S = LdsV6<DI, DT, C, H, NBLK, K>;                   // the regions, their offsets and the launch's byte count
+  static_assert(S::TILE == kTile && S::FRAG_N == 2 * GFRAG * 4 && S::XT_N == kTile * XS && S::TAB_N >= DI * TABW, "layout");
   // fragment region first (LDS offset 0: every fragment address is a per-lane base + 16-bit immediate).
   // Trunk: activation fragments [t][cb][lane] of 16 bytes, hi (32 KB) then lo (32 KB); last layer: the weight
   // window [group parity][b][t][hi|lo][lane] (96 KB).
-  uint4* act = reinterpret_cast<uint4*>(smem);
+  uint4* act = reinterpret_cast<uint4*>(smem + S::FRAG);
   uint4* act_hi = act;
   uint4* act_lo = act + NTH * NCB * 64;
-  float* xt = smem + 2 * GFRAG * 4;                        // [128][XS]  x in, y out (in place)
-  uint4* ctxf = reinterpret_cast<uint4*>(xt + kTile * XS); // [cb][hi|lo][lane] context fragments (8 KB)
-  float* tab = reinterpret_cast<float*>(ctxf + (C > 0 ? NCB * 2 * 64 : 0));   // [DI][TABW]
-  float* ldt = tab + ((DI * TABW + 3) & ~3);               // [128] identity-half log|det|
-  int* tfi = reinterpret_cast<int*>(ldt + kTile);
-  int* idi = tfi + DT;
+  float* xt = smem + S::XT;                                 // [128][XS]  x in, y out (in place)
+  uint4* ctxf = reinterpret_cast<uint4*>(smem + S::CTXF);   // [cb][hi|lo][lane] context fragments (8 KB)
+  float* tab = smem + S::TAB;                               // [DI][TABW]
+  float* ldt = smem + S::LDT;                               // [128] identity-half log|det|
+  int* tfi = reinterpret_cast<int*>(smem + S::TFI);
+  int* idi = reinterpret_cast<int*>(smem + S::IDI);
   // Bias tables, one plane per lane half (a lane half shares its 16 accumulator rows' biases; one per-lane base
   // address serves every table read): last layer [NG][48] (3 KB in all), then the trunk's vectors [NBT][row block][16]
   // - b0, then ba | bb (| bc) of every residual block.  From global memory a bias read returned 1 KiB per instruction
   // for 128 distinct bytes, in the vector steps that the vector-memory path paces (profiles/fused_tile_handover.md).
   constexpr int NBV = C > 0 ? 3 : 2;        // bias vectors per residual block
-  constexpr int NBT = 1 + NBLK * NBV;
-  constexpr int BPL = NG * 48 + NBT * (H / 2);             // floats per plane
-  float* biasf = reinterpret_cast<float*>(idi + DI + 4);
-  float* ldold = biasf + 2 * BPL;                           // [128] accumulate mode: the log|det| values the tile adds onto
-  int* tflag = reinterpret_cast<int*>(ldold + kTile);      // this tile held a value the fp16 halves cannot carry
+  constexpr int NBT = S::NBT;
+  constexpr int BPL = S::BPL;                               // floats per plane
+  float* biasf = smem + S::BIAS;
+  float* ldold = smem + S::LDOLD;                           // [128] accumulate mode: the log|det| values the tile adds onto
+  int* tflag = reinterpret_cast<int*>(smem + S::TFLAG);    // this tile held a value the fp16 halves cannot carry
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -693,31 +696,18 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
 
 template <int DI, int DT, int C, int H, int NBLK, int K>
 static int launch_v6(const FusedArgs& a, int inverse, hipStream_t st) {
-  constexpr int D = DI + DT;
   constexpr int TILE = 128;
-  constexpr size_t WIN = (size_t)2 * 3 * (H / 16) * 2 * 64 * 16;   // two feature groups
-  constexpr int NBT = 1 + NBLK * (C > 0 ? 3 : 2);                 // trunk bias vectors beside the last layer's
-  const size_t lds = ((size_t)TILE * (D + 4) + ((DI * 3 * (K + 1) + 3) & ~3) + 2 * TILE + D + 8 + (DT / 4) * 96 + NBT * H) * 4 +
-                     (C > 0 ? 4 * 2 * 64 * 16 : 0) + WIN + 64;
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[inverse ? 1 : 0]) {
-    hipError_t e;
-    if (inverse)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    else
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return VCNF_ERR_LAUNCH;
-    attr_set[inverse ? 1 : 0] = true;
-  }
+  constexpr size_t lds = LdsV6<DI, DT, C, H, NBLK, K>::BYTES;
+  const bool set = inverse ? lds_limit_once<&fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>>(lds)
+                           : lds_limit_once<&fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>>(lds);
+  if (!set) return VCNF_ERR_LAUNCH;
   const long long ntiles = (a.B + TILE - 1) / TILE;
   dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
   if (inverse)
     hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, a VCNF_TIME_ARG);
   else
     hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, a VCNF_TIME_ARG);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return launched();
 }
 
 // Shape family of the fused fp16 split-half kernel: (d_id = d_t, ctx, residual blocks) with H = 128, 8 bins.
@@ -726,32 +716,15 @@ static int launch_v6_family(const FusedArgs& a, int d_id, int ctx_dim, int inver
 #ifdef VCNF_DEV_ONLY
   return launch_v6<32, 32, 16, 128, NBLK, 8>(a, inverse, st);
 #else
-  if (d_id == 32) {
-    return ctx_dim == 16 ? launch_v6<32, 32, 16, 128, NBLK, 8>(a, inverse, st)
-                         : launch_v6<32, 32, 0, 128, NBLK, 8>(a, inverse, st);
-  }
-  return ctx_dim == 16 ? launch_v6<16, 16, 16, 128, NBLK, 8>(a, inverse, st)
-                       : launch_v6<16, 16, 0, 128, NBLK, 8>(a, inverse, st);
+  return with_fused_shape(d_id, ctx_dim,
+                          [&](auto DI, auto C) { return launch_v6<DI(), DI(), C(), 128, NBLK, 8>(a, inverse, st); });
 #endif
 }
 
-// One translation unit per number of residual blocks (-DVCNF_V6_NBLK=1|2|3; build.py runs them in
-// parallel); fused_layer.hip dispatches to launch_fused_v6_b<N>.
+// One translation unit per number of residual blocks (-DVCNF_V6_NBLK=1|2|3).
 #ifndef VCNF_V6_NBLK
 #define VCNF_V6_NBLK 2
 #endif
-#if VCNF_V6_NBLK == 1
-int launch_fused_v6_b1(const FusedArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_v6_family<1>(a, d_id, ctx_dim, inverse, st);
-}
-#elif VCNF_V6_NBLK == 2
-int launch_fused_v6_b2(const FusedArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_v6_family<2>(a, d_id, ctx_dim, inverse, st);
-}
-#else
-int launch_fused_v6_b3(const FusedArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_v6_family<3>(a, d_id, ctx_dim, inverse, st);
-}
-#endif
+VCNF_BLOCKS_ENTRY(launch_fused_v6_b, VCNF_V6_NBLK, FusedArgs, launch_v6_family)
 
 }  // namespace vcnf

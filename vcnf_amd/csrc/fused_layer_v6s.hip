@@ -23,6 +23,7 @@
 #include "../../include/vcnf_hip.h"
 #include "rqs_math.hpp"
 #include "fused_common.hpp"
+#include "host_common.hpp"
 #include "rqs_lean.hpp"
 #include "split_half.hpp"
 
@@ -73,18 +74,20 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
   constexpr int ABUF = NTH * 64;            // uint4 entries of one half (hi or lo) of one activation buffer
 
   extern __shared__ __align__(16) float smem[];
+  using S = LdsV6s<DI, DT, C, H, NBLK, K>;                 // the regions, their offsets and the launch's byte count
+  static_assert(S::TILE == kTile && S::ACT_N == 4 * ABUF * 4 && S::XT_N == kTile * XS, "layout");
   // activation fragments [buffer][hi | lo][t][lane] of 16 bytes
-  uint4* act = reinterpret_cast<uint4*>(smem);
-  float* xt = smem + 4 * ABUF * 4;                         // [32][XS]  x in, y out (in place)
-  uint4* ctxf = reinterpret_cast<uint4*>(xt + kTile * XS); // [hi | lo][lane] context fragment (2 KB)
-  float* ldt = reinterpret_cast<float*>(ctxf + (C > 0 ? 2 * 64 : 0));   // [32] identity-half log|det|
-  float* ldx = ldt + kTile;                                // [8][32] per-wave shares of the transformed half
-  int* tflag = reinterpret_cast<int*>(ldx + 8 * kTile);
+  uint4* act = reinterpret_cast<uint4*>(smem + S::ACT);
+  float* xt = smem + S::XT;                                // [32][XS]  x in, y out (in place)
+  uint4* ctxf = reinterpret_cast<uint4*>(smem + S::CTXF);  // [hi | lo][lane] context fragment (2 KB)
+  float* ldt = smem + S::LDT;                              // [32] identity-half log|det|
+  float* ldx = smem + S::LDX;                              // [8][32] per-wave shares of the transformed half
+  int* tflag = reinterpret_cast<int*>(smem + S::TFLAG);
   // per-layer tables, two sets (the set of the next layer is written while this layer runs):
   //   tab [DI][TABW] knot tables of the identity half | tfi [DT] | idi [DI + 4] | biasf [NG][lane half][48]
-  constexpr int TABF = (DI * TABW + 3) & ~3;
-  constexpr int TSET = TABF + DT + DI + 4 + NG * 96;
-  float* tsets = reinterpret_cast<float*>(tflag + 4);
+  constexpr int TABF = S::TABF;
+  constexpr int TSET = S::TSET;
+  float* tsets = smem + S::TSETS;
 #define VCNF_ACT_HI(BUF) (act + (BUF) * 2 * ABUF)
 #define VCNF_ACT_LO(BUF) (act + (BUF) * 2 * ABUF + ABUF)
 
@@ -596,46 +599,27 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
 template <int DI, int DT, int C, int H, int NBLK, int K>
 static int launch_v6s(const FusedStackArgs& sa, int inverse, hipStream_t st) {
   const FusedArgs& a = sa.a;
-  constexpr int D = DI + DT;
   constexpr int TILE = kFusedFlagRows;
-  constexpr size_t TSET = ((DI * 3 * (K + 1) + 3) & ~3) + DT + DI + 4 + (DT / 4) * 96;       // one set of per-layer tables
-  const size_t lds = (size_t)4 * (H / 16) * 64 * 16 + (C > 0 ? 2 * 64 * 16 : 0) +
-                     ((size_t)TILE * (D + 4) + TILE + 8 * TILE + 4 + 2 * TSET) * 4 + 64;
+  constexpr size_t lds = LdsV6s<DI, DT, C, H, NBLK, K>::BYTES;       // below 64 KB: no limit to raise
   const long long ntiles = (a.B + TILE - 1) / TILE;
   dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
   if (inverse)
     hipLaunchKernelGGL((fused_rqs_layer_v6s_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, sa);
   else
     hipLaunchKernelGGL((fused_rqs_layer_v6s_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, sa);
-  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+  return launched();
 }
 
 template <int NBLK>
 static int launch_v6s_family(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  if (d_id == 32) {
-    return ctx_dim == 16 ? launch_v6s<32, 32, 16, 128, NBLK, 8>(a, inverse, st)
-                         : launch_v6s<32, 32, 0, 128, NBLK, 8>(a, inverse, st);
-  }
-  return ctx_dim == 16 ? launch_v6s<16, 16, 16, 128, NBLK, 8>(a, inverse, st)
-                       : launch_v6s<16, 16, 0, 128, NBLK, 8>(a, inverse, st);
+  return with_fused_shape(d_id, ctx_dim,
+                          [&](auto DI, auto C) { return launch_v6s<DI(), DI(), C(), 128, NBLK, 8>(a, inverse, st); });
 }
 
 // One translation unit per number of residual blocks (-DVCNF_V6_NBLK=1|2|3), like fused_layer_v6.hip.
 #ifndef VCNF_V6_NBLK
 #define VCNF_V6_NBLK 2
 #endif
-#if VCNF_V6_NBLK == 1
-int launch_fused_v6s_b1(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_v6s_family<1>(a, d_id, ctx_dim, inverse, st);
-}
-#elif VCNF_V6_NBLK == 2
-int launch_fused_v6s_b2(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_v6s_family<2>(a, d_id, ctx_dim, inverse, st);
-}
-#else
-int launch_fused_v6s_b3(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-  return launch_v6s_family<3>(a, d_id, ctx_dim, inverse, st);
-}
-#endif
+VCNF_BLOCKS_ENTRY(launch_fused_v6s_b, VCNF_V6_NBLK, FusedStackArgs, launch_v6s_family)
 
 }  // namespace vcnf

@@ -375,7 +375,9 @@ static size_t table_bytes(const Tables<T>& t) {
   return ((size_t)2 * t.M * t.D + (t.c_lds ? t.M : 0)) * sizeof(T);
 }
 
-// a workgroup may take all of the CU's 160 KiB; beyond 64 KiB the runtime wants to be told (per device, so every time)
+// a workgroup may take all of the CU's 160 KiB; beyond 64 KiB the runtime wants to be told (per device, so every time:
+// unlike host_common.hpp's lds_limit_once, which tells it once per kernel instance, this sets the attribute on every
+// launch above 64 KiB)
 template <typename K>
 static bool allow_lds(K kernel, size_t lds) {
   return lds <= 64 * 1024 || hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),

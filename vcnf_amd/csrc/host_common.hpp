@@ -1,12 +1,43 @@
-// Host idioms of the entry points, each defined once: the status after a launch, pointer alignment, the log-det mode.
+// Host idioms of the entry points, each defined once: the dispatch from a run-time count to a kernel instance, the
+// status after a launch, pointer alignment, the log-det mode, the dynamic-LDS limit of a kernel.  The first part is
+// plain C++17 (rqs_host.hpp includes it and is compiled without HIP by tests/c_host/); the rest needs the HIP runtime.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <initializer_list>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/vcnf_hip.h"
+
+namespace vcnf {
+
+// Run-time integers that have kernel instances of their own (bin counts, k-step counts).
+template <int... Ns>
+using IntList = std::integer_sequence<int, Ns...>;
+
+template <int First, int... Is>
+constexpr IntList<(First + Is)...> int_range_from(std::integer_sequence<int, Is...>) { return {}; }
+// First, First + 1, ..., First + Count - 1
+template <int First, int Count>
+using IntRange = decltype(int_range_from<First>(std::make_integer_sequence<int, Count>{}));
+
+template <int... Ns>
+inline bool in_list(IntList<Ns...>, int n) {
+  return ((n == Ns) || ...);
+}
+
+// f(std::integral_constant<int, n>{}) if n is one of Ns (true), else nothing (false)
+template <int... Ns, class F>
+inline bool with_listed_only(IntList<Ns...>, int n, F&& f) {
+  return ((n == Ns && (f(std::integral_constant<int, Ns>{}), true)) || ...);
+}
+
+}  // namespace vcnf
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 
 namespace vcnf {
 
@@ -20,4 +51,25 @@ static inline bool all_aligned(std::initializer_list<const void*> ps, uintptr_t 
   return true;
 }
 
+// VCNF_ERR_UNSUPPORTED unless n is listed; else launch(std::integral_constant<int, n>{})'s status
+template <int... Ns, class F>
+inline int launch_listed(IntList<Ns...> list, int n, F&& launch) {
+  int rc = VCNF_ERR_UNSUPPORTED;
+  with_listed_only(list, n, [&](auto N) { rc = launch(N); });
+  return rc;
+}
+
+// Raises Kernel's dynamic-LDS limit to ``bytes`` on its first launch (above 64 KiB the runtime wants to be told); the
+// flag is per kernel instance, so ``bytes`` must be a constant of the instance.  False if the runtime refuses: the
+// caller returns VCNF_ERR_LAUNCH.
+template <auto Kernel>
+inline bool lds_limit_once(size_t bytes) {
+  static bool done = false;
+  if (!done)
+    done = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)bytes) == hipSuccess;
+  return done;
+}
+
 }  // namespace vcnf
+#endif  // __HIPCC__

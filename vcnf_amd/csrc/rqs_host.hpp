@@ -7,10 +7,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <type_traits>
-#include <utility>
-
 #include "../../include/vcnf_hip.h"
+#include "host_common.hpp"          // IntList and its dispatcher (the plain C++ part)
 
 namespace vcnf {
 
@@ -64,22 +62,23 @@ inline int rqs_check_cfg(const Cfg* cfg, int max_bins) {
   return VCNF_OK;
 }
 
-// Bin counts with kernel instances of their own; the lists differ on purpose.
+// Bin counts with kernel instances of their own; the lists differ on purpose.  The spline names of host_common.hpp's
+// integer-list dispatcher.
 template <int... Ks>
-using BinList = std::integer_sequence<int, Ks...>;
+using BinList = IntList<Ks...>;
 constexpr BinList<4, 8, 10, 16> kBins{};               // every other count: the generic instance (run-time K)
 constexpr BinList<8, 10, 16> kBins64{};                // fp64 kernels, generic instance likewise
 constexpr BinList<4, 8, 10, 16, 32> kBinsIdHalf{};     // identity half: no generic instance
 
 template <int... Ks>
-inline bool in_bins(BinList<Ks...>, int K) {
-  return ((K == Ks) || ...);
+inline bool in_bins(BinList<Ks...> list, int K) {
+  return in_list(list, K);
 }
 
 // f(std::integral_constant<int, K>{}) if K is one of Ks (true), else nothing (false)
 template <int... Ks, class F>
-inline bool with_bins_only(BinList<Ks...>, int K, F&& f) {
-  return ((K == Ks && (f(std::integral_constant<int, Ks>{}), true)) || ...);
+inline bool with_bins_only(BinList<Ks...> list, int K, F&& f) {
+  return with_listed_only(list, K, std::forward<F>(f));
 }
 
 // the same, and f(std::integral_constant<int, 0>{}) - the generic instance - for every other K

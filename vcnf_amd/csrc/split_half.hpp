@@ -1,7 +1,8 @@
-// The fp16 split-half ("fp16x3") operand arithmetic shared by the fused RQS layer kernel (fused_layer_v6.hip) and
-// the GEMM-level probe (gemm_probe.hip): an fp32 value v travels as hi = fp16(v), lo = fp16((v - hi) * 2^11); a
-// product keeps hi*hi + (hi*lo + lo*hi) * 2^-11 in two fp32 accumulators on v_mfma_f32_32x32x16_f16.
+// The fp16 split-half ("fp16x3") vocabulary of v_mfma_f32_32x32x16_f16, stated once: an fp32 value v travels as
+// hi = fp16(v), lo = fp16((v - hi) * 2^11); a product keeps hi*hi + (hi*lo + lo*hi) * 2^-11 in fp32 accumulators.
 // Reference arithmetic this stands in for: fp32 nn.Linear, normflow/nets/resnet.py:92-106.
+// Users: fused_layer_v6.hip, fused_layer_v6s.hip, fused_affine.hip, linear_f16x3.hip, linear_wgrad.hip, gemm_probe.hip
+// (split8 / mfma32h); conv1x1.hip, conv3x3_1x1.hip (split_plain, mfma32h_x3, acc_row).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,7 +18,36 @@ __device__ __forceinline__ floatx16 mfma32h(half8 a, half8 b, floatx16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
-// hi / lo halves of eight values; the running maximum of what was clamped goes to ``satm``
+// Row of accumulator register r (0..15) of lane ``lane`` in a 32 x 32 result whose first row is ``first``; the column
+// is lane % 32 (measured: profiles/r02_mfma_32x32x16_layout.txt).  Four consecutive registers are four adjacent rows.
+__host__ __device__ constexpr int acc_row(int r, int lane, int first = 0) {
+  return first + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+}
+
+// One k-step of a split-half product on three independent accumulator chains: hi x hi, hi x lo, lo x hi
+// (result: m + (ca + cb) * kLoUnscale).
+__device__ __forceinline__ void mfma32h_x3(half8 ah, half8 al, half8 bh, half8 bl, floatx16& m, floatx16& ca, floatx16& cb) {
+  m = mfma32h(ah, bh, m);
+  ca = mfma32h(ah, bl, ca);
+  cb = mfma32h(al, bh, cb);
+}
+
+// Two forms of the split live here.  They give the same bits (both differences are exact) with different instructions:
+// split_plain subtracts and scales, split8 scales inside one fma and converts in pairs.  Which one a kernel uses is
+// part of its device code - keep a kernel on the form it has.
+//
+// hi / lo halves of one value, plain form; the running maximum of |v| goes to ``satm`` (beyond 65504: clamped)
+struct HiLo {
+  _Float16 hi, lo;
+};
+__device__ __forceinline__ HiLo split_plain(float v, float& satm) {
+  satm = fmaxf(satm, __builtin_fabsf(v));
+  const float t = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
+  const _Float16 h = (_Float16)t;
+  return {h, (_Float16)((t - (float)h) * kLoScale)};
+}
+
+// hi / lo halves of eight values, fma form; the running maximum of what was clamped goes to ``satm``
 template <bool RELU>
 __device__ __forceinline__ void split8(const float (&v)[8], half8& hi, half8& lo, float& satm) {
 #pragma unroll

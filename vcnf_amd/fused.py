@@ -100,8 +100,8 @@ def _hi_lo_fragments(w):
 
 def _afrag_cols(k_total, chained, device):
     """k index of slot (lane half kg, i) of k-step t for v_mfma_f32_32x32x16_f16 operands: [t, 64, 8].
-    chained: the operand is the previous layer's accumulator (register r of lane half kg is row
-    8 (r / 4) + 4 kg + r % 4 of its 32-row block, registers 8 hh .. 8 hh + 7 feed k-step 2 nb + hh);
+    chained: the operand is the previous layer's accumulator (register r of lane half kg is row acc_row(r, 32 kg) of its
+    32-row block - csrc/split_half.hpp, written out below - and registers 8 hh .. 8 hh + 7 feed k-step 2 nb + hh);
     otherwise the natural order 16 t + 8 kg + i of an input vector."""
     t = torch.arange(k_total // 16, device=device).view(-1, 1, 1)
     kg = (torch.arange(64, device=device) >> 5).view(1, -1, 1)
@@ -121,7 +121,8 @@ def _pack_dense6(weight, chained):
 
 
 def _pack_bias6(bias):
-    """[N] -> accumulator order [N / 32][lane half][16]: register r of lane half kg is row 8 (r / 4) + 4 kg + r % 4."""
+    """[N] -> accumulator order [N / 32][lane half][16]: register r of lane half kg is row acc_row(r, 32 kg) of its block
+    (csrc/split_half.hpp, written out below)."""
     dev = bias.device
     nb = torch.arange(bias.numel() // 32, device=dev).view(-1, 1, 1)
     kg = torch.arange(2, device=dev).view(1, -1, 1)

@@ -55,13 +55,14 @@ class ConvNet2d(nn.Module):
             return False
         return bool(_lib.lib().vcnf_conv1x1_supported(c2.in_channels, c2.out_channels))
 
-    def _packed_conv1x1(self):
-        c2 = self.net[2]
-        key = (c2.weight.data_ptr(), c2.weight._version, str(c2.weight.device))
-        cache = self.__dict__.setdefault('_fused_conv_pack', {})
+    def _packed(self, slot, weight, make):
+        """``make()``'s packed buffer of ``weight``, kept in ``self.__dict__[slot]`` as {'key', 'buf'} (fused.refresh_packed
+        clears the key) and rebuilt when the parameter's storage, version or device changes."""
+        key = (weight.data_ptr(), weight._version, str(weight.device))
+        cache = self.__dict__.setdefault(slot, {})
         if cache.get('key') != key:
             with torch.no_grad():
-                buf = pack_conv1x1(c2.weight.detach().view(c2.out_channels, c2.in_channels))
+                buf = make()
             old = cache.get('buf')
             if old is not None and old.shape == buf.shape and old.device == buf.device:
                 old.copy_(buf)           # in place: a captured HIP graph keeps reading this address
@@ -70,23 +71,16 @@ class ConvNet2d(nn.Module):
             cache['key'] = key
         return cache['buf']
 
+    def _packed_conv1x1(self):
+        c2 = self.net[2]
+        return self._packed('_fused_conv_pack', c2.weight,
+                            lambda: pack_conv1x1(c2.weight.detach().view(c2.out_channels, c2.in_channels)))
+
     def _packed_conv3x3(self):
         c1 = self.net[0]
-        key = (c1.weight.data_ptr(), c1.weight._version, str(c1.weight.device))
-        cache = self.__dict__.setdefault('_fused_conv3_pack', {})
-        if cache.get('key') != key:
-            with torch.no_grad():
-                k1 = c1.in_channels * 9
-                w = c1.weight.detach().reshape(c1.out_channels, k1)          # k = ci * 9 + ky * 3 + kx
-                w = F.pad(w, (0, (-k1) % 16))
-                buf = pack_conv1x1(w)
-            old = cache.get('buf')
-            if old is not None and old.shape == buf.shape and old.device == buf.device:
-                old.copy_(buf)
-            else:
-                cache['buf'] = buf
-            cache['key'] = key
-        return cache['buf']
+        k1 = c1.in_channels * 9              # k = ci * 9 + ky * 3 + kx, padded to whole k-steps
+        return self._packed('_fused_conv3_pack', c1.weight,
+                            lambda: pack_conv1x1(F.pad(c1.weight.detach().reshape(c1.out_channels, k1), (0, (-k1) % 16))))
 
     def _first_two_fusable(self):
         """3x3 convolution (padding 1, stride 1) into 256 channels followed by the 256 -> 256 1x1 convolution: both on
@@ -101,20 +95,10 @@ class ConvNet2d(nn.Module):
 
     def _packed_taps(self):
         c3 = self.net[4]
-        key = (c3.weight.data_ptr(), c3.weight._version, str(c3.weight.device))
-        cache = self.__dict__.setdefault('_fused_taps_pack', {})
-        if cache.get('key') != key:
-            with torch.no_grad():
-                co = c3.out_channels
-                w = c3.weight.detach().permute(2, 3, 0, 1).reshape(9 * co, c3.in_channels)     # row t * c_out + o
-                buf = pack_conv1x1(w, row_blocks=(9 * co + 31) // 32)
-            old = cache.get('buf')
-            if old is not None and old.shape == buf.shape and old.device == buf.device:
-                old.copy_(buf)
-            else:
-                cache['buf'] = buf
-            cache['key'] = key
-        return cache['buf']
+        co = c3.out_channels                 # row t * c_out + o
+        return self._packed('_fused_taps_pack', c3.weight,
+                            lambda: pack_conv1x1(c3.weight.detach().permute(2, 3, 0, 1).reshape(9 * co, c3.in_channels),
+                                                 row_blocks=(9 * co + 31) // 32))
 
     def _all_three_fusable(self):
         """... followed by a 3x3 convolution (padding 1) to at most 56 channels: its nine taps run as one more matrix
@@ -128,42 +112,27 @@ class ConvNet2d(nn.Module):
     fused_conv_taps = True
 
     def forward(self, x):
-        if self._fusable(x) and self._first_two_fusable() and self._all_three_fusable():
-            from .. import _lib
-            c1, a1, c2, a2, c3 = self.net
-            return _lib.convnet3_fused(x, self._packed_conv3x3(), self._packed_conv1x1(), self._packed_taps(), c1.bias,
-                                       c2.bias, c3.bias, c3.out_channels, float(a1.negative_slope), float(a2.negative_slope))
-        if self._fusable(x) and self._first_two_fusable():
-            from .. import _lib
-            c1, a1, c2, a2, c3 = self.net
-            h = _lib.conv3x3_1x1_fused(x, self._packed_conv3x3(), self._packed_conv1x1(), c1.bias, c2.bias,
-                                       float(a1.negative_slope), float(a2.negative_slope))
-            return c3(h)
-        if self._fusable(x):
-            from .. import _lib
-            c1, a1, c2, a2, c3 = self.net
-            h = F.conv2d(x, c1.weight, None, c1.stride, c1.padding, c1.dilation, c1.groups)     # bias applied below
-            h = _lib.conv1x1_fused(h, self._packed_conv1x1(), c2.out_channels, in_bias=c1.bias, out_bias=c2.bias,
-                                   in_slope=float(a1.negative_slope), out_slope=float(a2.negative_slope))
-            return c3(h)
-        return self.net(x)
+        if not self._fusable(x):
+            return self.net(x)
+        from .. import _lib
+        c1, a1, c2, a2, c3 = self.net
+        slope1, slope2 = float(a1.negative_slope), float(a2.negative_slope)
+        if self._first_two_fusable():
+            if self._all_three_fusable():
+                return _lib.convnet3_fused(x, self._packed_conv3x3(), self._packed_conv1x1(), self._packed_taps(), c1.bias,
+                                           c2.bias, c3.bias, c3.out_channels, slope1, slope2)
+            return c3(_lib.conv3x3_1x1_fused(x, self._packed_conv3x3(), self._packed_conv1x1(), c1.bias, c2.bias,
+                                             slope1, slope2))
+        h = F.conv2d(x, c1.weight, None, c1.stride, c1.padding, c1.dilation, c1.groups)     # bias applied below
+        h = _lib.conv1x1_fused(h, self._packed_conv1x1(), c2.out_channels, in_bias=c1.bias, out_bias=c2.bias,
+                               in_slope=slope1, out_slope=slope2)
+        return c3(h)
 
 
 def pack_conv1x1(w, row_blocks=8):
     """W [c_out, c_in] -> A fragments of v_mfma_f32_32x32x16_f16 for csrc/conv1x1.hip: [8 row blocks][c_in / 16]
     [hi | lo][64 lanes][8 halves] (``row_blocks`` blocks of 32 rows), lane l holding row 32 rb + l % 32, input channels
-    16 ks + 8 (l / 32) + i; rows beyond c_out are zero; hi / lo = the fp16 split of fused._split_halves (w ~ hi + lo / 2048)."""
-    from ..fused import _split_halves, _as_floats
-    c_out, c_in = w.shape
-    dev = w.device
-    rb = torch.arange(row_blocks, device=dev).view(-1, 1, 1, 1)
-    ks = torch.arange(c_in // 16, device=dev).view(1, -1, 1, 1)
-    lane = torch.arange(64, device=dev).view(1, 1, -1, 1)
-    i = torch.arange(8, device=dev).view(1, 1, 1, -1)
-    shape = (row_blocks, c_in // 16, 64, 8)
-    rows = (32 * rb + (lane & 31)).expand(shape)
-    cols = (16 * ks + 8 * (lane >> 5) + i).expand(shape)
-    ok = rows < c_out
-    vals = torch.where(ok, w[torch.where(ok, rows, torch.zeros_like(rows)), cols], torch.zeros((), device=dev, dtype=w.dtype))
-    hi, lo = _split_halves(vals)                                   # [row blocks, ks, 64, 8]
-    return _as_floats(torch.stack([hi, lo], dim=2)).contiguous()   # [row blocks, ks, 2, 64, 8]
+    16 ks + 8 (l / 32) + i; rows beyond c_out are zero; hi / lo = the fp16 split of fused._split_halves (w ~ hi + lo / 2048).
+    The fragment order of the fused layers' first matrix (fused._pack_dense6, natural k order) over zero-padded rows."""
+    from ..fused import _pack_dense6
+    return _pack_dense6(F.pad(w, (0, 0, 0, 32 * row_blocks - w.shape[0])), False).contiguous()
