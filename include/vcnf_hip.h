@@ -822,6 +822,69 @@ int vcnf_tail_sample_bwd_f64(const double* eps, const double* gamma, const doubl
 int vcnf_tail_reduce_partials_f64(const double* partials, int64_t groups, int32_t features, double* d_loc,
                                   double* d_log_scale, double* d_shape, void* stream);
 
+/* ---- Full-covariance base distributions: the multivariate Gaussian and the multivariate Student-t over D = features
+ * <= 128.  z / eps [B, D] contiguous, gamma [B], loc [D]; tri [D, D] row-major is a lower-triangular matrix of which
+ * only the lower triangle including the diagonal is ever read: the scale L for sampling, its inverse M = L^-1 for the
+ * density.  consts [2] = (cst, nu) on the device, cst = the normaliser - sum log diag L (Gaussian: -D/2 log 2 pi;
+ * Student-t: lgamma((nu+D)/2) - lgamma(nu/2) - D/2 log(nu pi)); nu is ignored by the Gaussian.  The caller inverts L
+ * and evaluates cst: no kernel solves or calls lgamma, and the caller draws the random numbers.  With x = z - loc,
+ * y = M x, q = |y|^2:
+ *   f(q) = -q / 2                        VCNF_MVN_GAUSSIAN
+ *   f(q) = -(nu + D)/2 log1p(q / nu)     VCNF_MVN_STUDENT_T
+ *   log_prob:  logp[b] = sign * (cst + f(q))   (ld_mode as for vcnf_tail_log_prob_*)
+ *   sample:    z[b] = loc + s L eps with s = 1, or s = sqrt(nu / (2 gamma[b])) with gamma ~ Gamma(nu/2, 1) (gamma is
+ *              required for the Student-t and ignored, possibly NULL, for the Gaussian); logp[b] = cst + f(s^2 |eps|^2),
+ *              the log density of that z without a solve
+ *   log_prob_bwd (cotangent g[B], gz_in[B, D] or NULL): with c = g 2 df/dq (df/dq = -1/2, or -(nu+D)/(2(nu+q))),
+ *              dz = gz_in + c M^T y, and per workgroup k one block partials[k] [D D + D + 1] with the workgroup's share
+ *              of  Y = tril(sum_b c y y^T) as a full square with zeros above the diagonal | d_loc = -sum_b c M^T y
+ *              | sum_b g (-log1p(q/nu)/2 + (nu+D) q / (2 nu (nu+q))), the part of d_nu that does not go through cst (0
+ *              for the Gaussian).  d_cst = sum_b g is the caller's, and so is the step from the symmetric sum to the
+ *              gradient of L: d_L = -tril(M^T (Y + strict(Y)^T)).  (The gradient of M itself, sum_b c y x^T = Y L^T, is
+ *              not what is summed: the way from it to d_L undoes the factor L^T and multiplies the sum's rounding by
+ *              cond(L).)  partials has vcnf_mvn_bwd_groups(batch, D) blocks,
+ *              every block is written in full; partials == NULL: only dz is computed
+ *   sample_bwd (cotangents g_z[B, D] and g_lp[B], either may be NULL = zero): with w = L^T g_z and k = g_lp 2 df/dq,
+ *              deps = s w + k s^2 eps (deps may be NULL), ds = w.eps + k s |eps|^2, dgamma[b] = -ds s / (2 gamma)
+ *              (Student-t only; the Gaussian writes none and takes NULL), and blocks as above with  d_tri =
+ *              tril(sum_b s g_z eps^T) | d_loc = sum_b g_z | d_nu = sum_b (ds s / (2 nu) + g_lp df/dnu at fixed q)
+ *   reduce_partials: d_loc [D], d_tri [D, D], d_nu [1] = the sum of `groups` blocks in a fixed order
+ * vcnf_mvn_bwd_groups is a pure function of its arguments (no device query; 0 for an unsupported shape): one workgroup
+ * per 64 samples, at most 256, and at most 2^22 elements of partial blocks in all (16 MiB in fp32, 32 MiB in fp64).
+ * Workgroup k takes the sample tiles k, k + groups, ...: every sum's order is fixed by the shape alone.
+ * 1 <= features <= 128 and batch >= 0, else VCNF_ERR_SHAPE (groups < 1 as well); unknown family or ld_mode ->
+ * VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a pointer not
+ * aligned to its element size -> VCNF_ERR_ALIGN.  16-byte (8-byte) accesses are used when features % V == 0 and the
+ * [B, D] buffers are aligned to them.  No atomics, no allocation, no host synchronisation: every call is bitwise
+ * reproducible and capturable. */
+enum { VCNF_MVN_GAUSSIAN = 0, VCNF_MVN_STUDENT_T = 1 };
+int64_t vcnf_mvn_bwd_groups(int64_t batch, int32_t features);
+int vcnf_mvn_log_prob_f32(const float* z, const float* loc, const float* tri_inv, const float* consts, float* logp,
+                          int64_t batch, int32_t features, int family, int ld_mode, float sign, void* stream);
+int vcnf_mvn_sample_f32(const float* eps, const float* gamma, const float* loc, const float* tri, const float* consts,
+                        float* z, float* logp, int64_t batch, int32_t features, int family, void* stream);
+int vcnf_mvn_log_prob_bwd_f32(const float* z, const float* loc, const float* tri_inv, const float* consts,
+                              const float* g, const float* gz_in, float* dz, float* partials, int64_t batch,
+                              int32_t features, int family, void* stream);
+int vcnf_mvn_sample_bwd_f32(const float* eps, const float* gamma, const float* tri, const float* consts,
+                            const float* g_z, const float* g_lp, float* deps, float* dgamma, float* partials,
+                            int64_t batch, int32_t features, int family, void* stream);
+int vcnf_mvn_reduce_partials_f32(const float* partials, int64_t groups, int32_t features, float* d_loc, float* d_tri,
+                                 float* d_nu, void* stream);
+int vcnf_mvn_log_prob_f64(const double* z, const double* loc, const double* tri_inv, const double* consts, double* logp,
+                          int64_t batch, int32_t features, int family, int ld_mode, double sign, void* stream);
+int vcnf_mvn_sample_f64(const double* eps, const double* gamma, const double* loc, const double* tri,
+                        const double* consts, double* z, double* logp, int64_t batch, int32_t features, int family,
+                        void* stream);
+int vcnf_mvn_log_prob_bwd_f64(const double* z, const double* loc, const double* tri_inv, const double* consts,
+                              const double* g, const double* gz_in, double* dz, double* partials, int64_t batch,
+                              int32_t features, int family, void* stream);
+int vcnf_mvn_sample_bwd_f64(const double* eps, const double* gamma, const double* tri, const double* consts,
+                            const double* g_z, const double* g_lp, double* deps, double* dgamma, double* partials,
+                            int64_t batch, int32_t features, int family, void* stream);
+int vcnf_mvn_reduce_partials_f64(const double* partials, int64_t groups, int32_t features, double* d_loc, double* d_tri,
+                                 double* d_nu, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

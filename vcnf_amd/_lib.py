@@ -124,6 +124,7 @@ PROTOTYPES = {
     "vcnf_linear_probe_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _P, _P], _INT),
     "vcnf_gmm_bwd_groups": ([_I64, _I32, _I32], _I64),
     "vcnf_tail_bwd_groups": ([_I64, _I32], _I64),
+    "vcnf_mvn_bwd_groups": ([_I64, _I32], _I64),
 }
 
 # Entry points that exist as name_f32 and name_f64 (all return int), stated once with the fp32 argument types: the
@@ -164,6 +165,11 @@ _PAIRS = {
     "vcnf_tail_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
     "vcnf_tail_sample_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
     "vcnf_tail_reduce_partials": [_P, _I64, _I32, _P, _P, _P, _P],
+    "vcnf_mvn_log_prob": [_P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
+    "vcnf_mvn_sample": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
+    "vcnf_mvn_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
+    "vcnf_mvn_sample_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
+    "vcnf_mvn_reduce_partials": [_P, _I64, _I32, _P, _P, _P, _P],
 }
 _F64_TWIN = {_F32: _F64, _CFG: _CFG64}
 for _name, _args in _PAIRS.items():
@@ -1599,6 +1605,119 @@ def tail_sample_bwd(eps, gamma, loc, ls, shape, family, g_z=None, g_lp=None, row
                                _ptr(d_gamma), ws, b, d, int(family), _stream())
         sums = _tail_row_sums(launch, name, e2, b, d, rows)
     return (d_eps.view(eps.shape) if want_eps else None, d_gamma.view(eps.shape)) + sums
+
+
+MVN_GAUSSIAN, MVN_STUDENT_T = 0, 1
+MVN_MAX_DIM = 128
+
+
+def _mvn_operands(x, loc, tri, consts, what):
+    """Checked operands of the full-covariance base entry points: x [B, D], loc [D] (or None), tri [D, D], consts [2],
+    one dtype.  Returns (device, x, loc, tri, consts contiguous, B, D)."""
+    dev = require_device(x, loc, tri, consts, f64=True)
+    if any(u is not None and u.dtype != x.dtype for u in (loc, tri, consts)):
+        raise VcnfError(what + ": mixed dtypes")
+    if tri.dim() != 2 or tri.shape[0] != tri.shape[1] or tuple(consts.shape) != (2,):
+        raise VcnfError(what + ": tri must be [features, features] and consts [2]")
+    d = tri.shape[0]
+    if x.dim() != 2 or x.shape[1] != d or (loc is not None and loc.numel() != d):
+        raise VcnfError("%s: inputs %s for %d features" % (what, tuple(x.shape), d))
+    return (dev, x.contiguous(), None if loc is None else loc.reshape(-1).contiguous(), tri.contiguous(),
+            consts.contiguous(), x.shape[0], d)
+
+
+def _mvn_vector(t, b, dtype, what, name):
+    t = t.to(dtype).contiguous()
+    if tuple(t.shape) != (b,):
+        raise VcnfError("%s: %s must be [batch]" % (what, name))
+    return t
+
+
+def mvn_log_prob(z, loc, tri_inv, consts, family, logp=None, sign=1.0):
+    """vcnf_mvn_log_prob_*: log density [B] of z [B, D] under the multivariate Gaussian (family 0) or Student-t (1) with
+    location loc [D], inverse scale factor tri_inv [D, D] (lower triangle) and consts = (cst, nu); ``logp``: accumulate
+    into it."""
+    name = "vcnf_mvn_log_prob" + _sfx(z)
+    dev, z2, loc, tri_inv, consts, b, d = _mvn_operands(z, loc, tri_inv, consts, name)
+    logp, mode = _logp_out(logp, b, z, dev, name)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(tri_inv), _ptr(consts), _ptr(logp), b, d, int(family), mode,
+                                  float(sign), _stream())
+    _check(st, name)
+    return logp
+
+
+def mvn_sample(eps, gamma, loc, tri, consts, family):
+    """vcnf_mvn_sample_*: (z [B, D], log p(z) [B]) for the standard-normal draw eps [B, D] and, for the Student-t, the
+    gamma draw [B] (None for the Gaussian); tri [D, D] is the scale factor L."""
+    name = "vcnf_mvn_sample" + _sfx(eps)
+    dev, e2, loc, tri, consts, b, d = _mvn_operands(eps, loc, tri, consts, name)
+    require_device(gamma, f64=True)
+    if gamma is not None:
+        gamma = _mvn_vector(gamma, b, eps.dtype, name, "gamma")
+    z = torch.empty_like(e2)
+    logp = torch.empty(b, dtype=eps.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(e2), _ptr(gamma), _ptr(loc), _ptr(tri), _ptr(consts), _ptr(z), _ptr(logp), b, d,
+                                  int(family), _stream())
+    _check(st, name)
+    return z, logp
+
+
+def _mvn_block_sums(launch, what, like, b, d, sums):
+    """``launch`` and, with ``sums``, vcnf_mvn_reduce_partials_*: (d_loc [D], d_tri [D, D], d_nu [1]), or three None."""
+    outs = None
+    if sums:
+        outs = (torch.empty(d, dtype=like.dtype, device=like.device), torch.empty(d, d, dtype=like.dtype, device=like.device),
+                torch.empty(1, dtype=like.dtype, device=like.device))
+    return _block_sums(launch, what, outs, (d * d + d + 1,), ("vcnf_mvn_bwd_groups", (b, d)),
+                       ("vcnf_mvn_reduce_partials" + _sfx(like), (d,))) or (None, None, None)
+
+
+def mvn_log_prob_bwd(z, loc, tri_inv, consts, family, g, gz_in=None, sums=True):
+    """vcnf_mvn_log_prob_bwd_* and vcnf_mvn_reduce_partials_*: (dz [B, D], d_loc [D], Y = tril(sum_b c_b y_b y_b^T) [D, D]
+    with zeros above the diagonal, d_nu [1]) for the cotangent g [B] of the log density; the gradient of the scale factor
+    L = tri_inv^-1 is -tril(tri_inv^T (Y + strict(Y)^T)); d_nu is the part that does not go through cst,
+    ``gz_in`` [B, D] is added to dz.  ``sums`` false: dz only (the three others are None), no workspace, one launch."""
+    name = "vcnf_mvn_log_prob_bwd" + _sfx(z)
+    dev, z2, loc, tri_inv, consts, b, d = _mvn_operands(z, loc, tri_inv, consts, name)
+    require_device(g, gz_in, f64=True)
+    g = _mvn_vector(g, b, z.dtype, name, "g")
+    if gz_in is not None:
+        gz_in = gz_in.to(z.dtype).contiguous()
+        if gz_in.shape != z2.shape:
+            raise VcnfError(name + ": gz_in does not have the shape of z")
+    dz = torch.empty_like(z2)
+    with torch.cuda.device(dev):
+        fn = getattr(lib(), name)
+        launch = lambda ws: fn(_ptr(z2), _ptr(loc), _ptr(tri_inv), _ptr(consts), _ptr(g), _ptr(gz_in), _ptr(dz), ws, b, d,
+                               int(family), _stream())
+        out = _mvn_block_sums(launch, name, z2, b, d, sums)
+    return (dz,) + out
+
+
+def mvn_sample_bwd(eps, gamma, tri, consts, family, g_z=None, g_lp=None, sums=True, want_eps=True):
+    """vcnf_mvn_sample_bwd_* and vcnf_mvn_reduce_partials_*: (d_eps [B, D] or None, d_gamma [B] or None for the Gaussian,
+    d_loc [D], d_tri [D, D], d_nu [1]) for the cotangents g_z [B, D] and g_lp [B] of vcnf_mvn_sample_*; None is zero."""
+    name = "vcnf_mvn_sample_bwd" + _sfx(eps)
+    dev, e2, _, tri, consts, b, d = _mvn_operands(eps, None, tri, consts, name)
+    require_device(gamma, g_z, g_lp, f64=True)
+    if gamma is not None:
+        gamma = _mvn_vector(gamma, b, eps.dtype, name, "gamma")
+    if g_z is not None:
+        g_z = g_z.to(eps.dtype).contiguous()
+        if g_z.shape != e2.shape:
+            raise VcnfError(name + ": g_z does not have the shape of eps")
+    if g_lp is not None:
+        g_lp = _mvn_vector(g_lp, b, eps.dtype, name, "g_lp")
+    d_eps = torch.empty_like(e2) if want_eps else None
+    d_gamma = torch.empty(b, dtype=eps.dtype, device=dev) if gamma is not None else None
+    with torch.cuda.device(dev):
+        fn = getattr(lib(), name)
+        launch = lambda ws: fn(_ptr(e2), _ptr(gamma), _ptr(tri), _ptr(consts), _ptr(g_z), _ptr(g_lp), _ptr(d_eps),
+                               _ptr(d_gamma), ws, b, d, int(family), _stream())
+        out = _mvn_block_sums(launch, name, e2, b, d, sums)
+    return (d_eps, d_gamma) + out
 
 
 PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2

@@ -494,6 +494,64 @@ class HeavyTailSampleFn(torch.autograd.Function):
         return (d_eps, d_gamma if need[1] else None, d_loc if need[2] else None, d_ls if need[3] else None,
                 d_sh if need[4] else None, g_lp.sum().expand(shape.shape) if need[5] else None, None)
 
+
+def _mvn_d_consts(g, d_nu):
+    """Gradient of consts = (cst, nu): cst enters every sample's log density once."""
+    return torch.cat([g.sum().reshape(1), d_nu])
+
+
+class MultivariateLogProbFn(torch.autograd.Function):
+    """vcnf_mvn_log_prob_*: log density of z [B, D] under the multivariate Gaussian / Student-t with location loc [D],
+    scale factor tri = L [D, D], its inverse tri_inv (a constant here: the gradient goes to L) and consts = (cst, nu);
+    backward on vcnf_mvn_log_prob_bwd_* and vcnf_mvn_reduce_partials_*.  The kernels sum Y = tril(sum_b c_b y_b y_b^T);
+    the gradient of L is -tril(L^-T Y_sym), a [D, D] product in fp64 like the inverse itself.  The caller's autograd
+    carries it on to lower and log_diag, and d_consts to log_diag and log_df."""
+
+    @staticmethod
+    def forward(ctx, z, loc, tri, tri_inv, consts, family):
+        with torch.no_grad():
+            lp = _lib.mvn_log_prob(z, loc, tri_inv, consts, family)
+        ctx.save_for_backward(z, loc, tri_inv, consts)
+        ctx.family = family
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        z, loc, tri_inv, consts = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dz, d_loc, yy, d_nu = _lib.mvn_log_prob_bwd(z, loc, tri_inv, consts, ctx.family, g, sums=any(need[1:5]))
+        d_tri = None
+        if need[2]:
+            yy = yy.double()
+            d_tri = -torch.tril(tri_inv.double().t() @ (yy + yy.tril(-1).t())).to(z.dtype)
+        return (dz, d_loc if need[1] else None, d_tri, None, _mvn_d_consts(g, d_nu) if need[4] else None, None)
+
+
+class MultivariateSampleFn(torch.autograd.Function):
+    """vcnf_mvn_sample_*: (z, log p(z)) from the standard-normal draw eps [B, D] and, for the Student-t, the gamma draw
+    [B]; backward on vcnf_mvn_sample_bwd_* and vcnf_mvn_reduce_partials_*, with respect to both draws, loc, the scale
+    factor tri and consts (the gradient of gamma is what carries the pathwise share of log_df through torch's gamma
+    sampler)."""
+
+    @staticmethod
+    def forward(ctx, eps, gamma, loc, tri, consts, family):
+        with torch.no_grad():
+            z, lp = _lib.mvn_sample(eps, gamma, loc, tri, consts, family)
+        ctx.save_for_backward(eps, gamma, tri, consts)
+        ctx.family = family
+        return z, lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_z, g_lp):
+        eps, gamma, tri, consts = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_eps, d_gamma, d_loc, d_tri, d_nu = _lib.mvn_sample_bwd(eps, gamma, tri, consts, ctx.family, g_z, g_lp,
+                                                                 sums=any(need[2:5]), want_eps=need[0])
+        return (d_eps, d_gamma if need[1] else None, d_loc if need[2] else None, d_tri if need[3] else None,
+                _mvn_d_consts(g_lp, d_nu) if need[4] else None, None)
+
 # Matrix path of the conditioner's dense layers on the training path at large batches: 'fp16x3' - forward products, the
 # 128 -> 128 layers' input gradients (csrc/linear_f16x3.hip) and the weight gradients (csrc/linear_wgrad.hip, split-half
 # form) on fp16 split-half operands with fp32 accumulation (error against fp64 below the library's fp32 GEMM on every

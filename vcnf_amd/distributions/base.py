@@ -3,8 +3,10 @@ normflow/distributions/base.py:609-652) and the class-conditional bases of the
 reference's Glow, ClassCondDiagGaussian (:715-775) and GlowBase (:778-869), and the
 GaussianMixture of normflow 1.2.  Of the heavy-tailed bases the followed fork adds, the
 product Student-t (its T) and the generalised Gaussian (its GGD) are StudentT and
-GeneralizedGaussian here, with one trainable tail parameter per feature; its other
-research distributions (GenNormal, the multivariate t, ...) are out of scope."""
+GeneralizedGaussian here, with one trainable tail parameter per feature, and its
+full-covariance bases (its MultivariateGaussian and TMV) are MultivariateGaussian and
+MultivariateStudentT, parametrised by a lower-triangular scale factor; its other
+research distributions (GenNormal, ...) are out of scope."""
 import math
 
 import numpy as np
@@ -356,3 +358,139 @@ class GeneralizedGaussian(_HeavyTailBase):
         l64 = log_beta.double()
         cst = l64 - math.log(2.0) - torch.lgamma(torch.exp(-l64))
         return beta, cst, 1.0 / beta
+
+
+class _FullCovarianceBase(BaseDistribution):
+    """Shared end of the full-covariance bases over ``n_dim`` features: z = loc + s L eps with the lower-triangular
+    L = tril(lower, -1) + diag(exp(log_diag)), and a density cst + f(q), q = |L^-1 (z - loc)|^2.  Density, sampling and
+    their gradients run on the vcnf_mvn_* kernels (csrc/mvn_base.hip).  Everything of size [D, D] or smaller stays in
+    torch: building L and the scalar cst = normaliser - sum log_diag (fp64) with autograd, and the inverse of L (one
+    triangular solve against the identity, in fp64 whatever the module's dtype, cast once; computed afresh on every
+    call), whose gradient autograd.MultivariateLogProbFn hands to L in closed form.  The kernels never solve and never
+    call lgamma.  Parameters (buffers with ``trainable=False``): loc, log_diag
+    [1, D] and lower [D, D], of which only the strictly lower triangle is ever used: the rest is created zero, never
+    read, and receives exactly zero gradient."""
+    _family = None
+    MAX_DIM = _lib.MVN_MAX_DIM
+
+    def __init__(self, n_dim, loc, scale_tril, trainable, extra=()):
+        super().__init__()
+        self.n_dim = self.d = int(n_dim)
+        self.shape = (self.d,)
+        d = self.d
+        loc = np.zeros(d) if loc is None else np.array(loc, dtype=np.float64).reshape(-1)
+        tril = np.eye(d) if scale_tril is None else np.array(scale_tril, dtype=np.float64)
+        name = type(self).__name__
+        if loc.shape != (d,):
+            raise ValueError("%s: loc must have %d elements" % (name, d))
+        if tril.shape != (d, d) or np.any(np.triu(tril, 1) != 0) or not (np.diagonal(tril) > 0).all():
+            raise ValueError("%s: scale_tril must be [%d, %d] with a zero upper triangle and a positive diagonal" % (name, d, d))
+        dtype = torch.get_default_dtype()
+        tensors = (("loc", torch.tensor(loc, dtype=dtype).reshape(1, d)),
+                   ("log_diag", torch.tensor(np.log(np.diagonal(tril)), dtype=dtype).reshape(1, d)),
+                   ("lower", torch.tensor(np.tril(tril, -1), dtype=dtype))) + tuple(extra)
+        for key, t in tensors:
+            if trainable:
+                setattr(self, key, nn.Parameter(t))
+            else:
+                self.register_buffer(key, t)
+
+    @property
+    def scale_tril(self):
+        """L = tril(lower, -1) + diag(exp(log_diag))"""
+        return torch.tril(self.lower, -1) + torch.diag(torch.exp(self.log_diag[0]))
+
+    def _check_dim(self):
+        if self.d > self.MAX_DIM:
+            raise NotImplementedError("%s: n_dim = %d is beyond the kernels' limit of %d features"
+                                      % (type(self).__name__, self.d, self.MAX_DIM))
+
+    def _consts(self):
+        """consts [2] = (cst, nu) in the module's dtype, cst evaluated in fp64"""
+        norm, nu = self._normaliser()
+        cst = norm - self.log_diag.double().sum()
+        return torch.stack([cst.reshape(()), nu.double().reshape(())]).to(self.loc.dtype)
+
+    def _inverse(self, tri):
+        eye = torch.eye(self.d, dtype=torch.float64, device=tri.device)
+        return torch.linalg.solve_triangular(tri.double(), eye, upper=False).to(tri.dtype)
+
+    def _gamma(self, num_samples):
+        return None
+
+    def forward(self, num_samples=1):
+        """The draws on the device with torch, then one kernel for z and log p."""
+        self._check_dim()
+        _lib.require_device(self.loc, allow_grad=True, f64=True)
+        eps = torch.randn(num_samples, self.d, dtype=self.loc.dtype, device=self.loc.device)
+        return self.from_noise(eps)
+
+    def _from_noise(self, eps, gamma):
+        self._check_dim()
+        _lib.require_device(eps, self.loc, gamma, allow_grad=True, f64=True)
+        if gamma is None:
+            gamma = self._gamma(len(eps))
+        loc, tri, consts = self.loc.reshape(-1), self.scale_tril, self._consts()
+        if autograd.needs_grad(eps, gamma, loc, tri, consts):
+            return autograd.MultivariateSampleFn.apply(eps, gamma, loc, tri, consts, self._family)
+        return _lib.mvn_sample(eps, gamma, loc, tri, consts, self._family)
+
+    def log_prob(self, z, out=None):
+        """``out`` [B]: accumulate into it instead of allocating."""
+        self._check_dim()
+        _lib.require_device(z, self.loc, allow_grad=True, f64=True)
+        loc, tri, consts = self.loc.reshape(-1), self.scale_tril, self._consts()
+        with torch.no_grad():
+            tri_inv = self._inverse(tri)
+        if autograd.needs_grad(z, loc, tri, consts, out):
+            lp = autograd.MultivariateLogProbFn.apply(z, loc, tri, tri_inv, consts, self._family)
+            return lp if out is None else out.add_(lp)
+        return _lib.mvn_log_prob(z, loc.detach(), tri_inv, consts.detach(), self._family, logp=out)
+
+
+class MultivariateGaussian(_FullCovarianceBase):
+    """N(loc, L L^T) over ``n_dim`` <= 128 features: log p = -D/2 log 2 pi - sum log_diag - |L^-1 (z - loc)|^2 / 2, sampling
+    z = loc + L eps.  ``loc=None`` gives zeros, ``scale_tril=None`` the identity; a given ``scale_tril`` [D, D] must have
+    a zero upper triangle and a positive diagonal.  state_dict: loc, log_diag [1, D], lower [D, D]."""
+    _family = _lib.MVN_GAUSSIAN
+
+    def __init__(self, n_dim, loc=None, scale_tril=None, trainable=True):
+        super().__init__(n_dim, loc, scale_tril, trainable)
+
+    def _normaliser(self):
+        z = torch.zeros((), dtype=torch.float64, device=self.loc.device)
+        return z - 0.5 * self.d * math.log(2.0 * math.pi), z
+
+    def from_noise(self, eps):
+        """``forward`` with the standard-normal draw eps [B, D] supplied."""
+        return self._from_noise(eps, None)
+
+
+class MultivariateStudentT(_FullCovarianceBase):
+    """Multivariate Student-t over ``n_dim`` <= 128 features with nu = exp(log_df) degrees of freedom, location loc and
+    scale factor L: log p = lgamma((nu+D)/2) - lgamma(nu/2) - D/2 log(nu pi) - sum log_diag - (nu+D)/2 log1p(q/nu),
+    q = |L^-1 (z - loc)|^2.  Sampling: z = loc + s L eps with s = sqrt(nu / (2 gamma)) and one gamma ~ Gamma(nu/2, 1)
+    per sample; the density of a draw uses q = s^2 |eps|^2 directly.  The gamma draw is taken with autograd on, so
+    torch's implicit derivative carries the pathwise gradient to log_df.  state_dict: loc, log_diag [1, D], lower
+    [D, D], log_df [1]."""
+    _family = _lib.MVN_STUDENT_T
+
+    def __init__(self, n_dim, df=3.0, loc=None, scale_tril=None, trainable=True):
+        df = float(df)
+        if not df > 0:
+            raise ValueError("MultivariateStudentT: df must be positive")
+        super().__init__(n_dim, loc, scale_tril, trainable,
+                         extra=(("log_df", torch.tensor([math.log(df)], dtype=torch.get_default_dtype())),))
+
+    def _normaliser(self):
+        l64 = self.log_df.double()[0]
+        nu = torch.exp(l64)
+        norm = torch.lgamma(0.5 * (nu + self.d)) - torch.lgamma(0.5 * nu) - 0.5 * self.d * (l64 + math.log(math.pi))
+        return norm, nu
+
+    def _gamma(self, num_samples):
+        return torch._standard_gamma((0.5 * torch.exp(self.log_df)).expand(num_samples))
+
+    def from_noise(self, eps, gamma=None):
+        """``forward`` with the standard-normal draw eps [B, D] supplied, and optionally the gamma draw [B]."""
+        return self._from_noise(eps, gamma)
