@@ -144,6 +144,7 @@ __device__ __forceinline__ void rqs_lean_eval(float x, const float (&lg)[3 * K -
     const float rdd = hw_rcp(dd);
     const float n2 = 2.f * qc;
     float r = n2 * rdd; r = fmaf(fmaf(-dd, r, n2), rdd, r);
+    r = r > 1.f ? 1.f : r;                  // rqs_math.hpp::rqs_bin_eval: the root of a point of the bin, NaN kept
     const float omr = 1.f - r, rr = r * omr;
     const float den = fmaf(e, rr, s);
     const float dn = (s * s) * fmaf(D1 * r, r, fmaf(2.f * s, rr, (D0 * omr) * omr));

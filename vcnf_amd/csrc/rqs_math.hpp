@@ -95,7 +95,13 @@ __device__ __forceinline__ void rqs_bin_eval(float x, const RqsBin& b, float& y,
     const float perr = fmaf(fa, qc, -p);
     const float disc = rqs_rounding_level_zero(fmaf(qb, qb, -p) - perr, qb, p);    // :163
     bad = bad || !(disc >= 0.f);                   // :164 (the reference asserts)
-    const float r = div_nr(2.f * qc, -qb - hw_sqrt(disc));   // :166
+    float r = div_nr(2.f * qc, -qb - hw_sqrt(disc));   // :166
+    // Beside the upper edge of a steep bin the true discriminant (h d1)^2 is below the rounding of b^2 (see
+    // rqs_rounding_level_zero), so the root is only good to sqrt(rounding) / |b|: r = 1 + 2e-4 was seen for s ~ 1000.
+    // y takes that as (r - 1) w, a rounding of x; log|det| does not: 2 s r (1 - r) = -0.4 outweighs a floor-level
+    // d1 and the logarithm below is of a negative number.  A point of the bin (dy <= h; dy > h only extrapolates the
+    // last bin of a spline without tails) has its root in [0, 1]; a NaN root (counted above) stays a NaN.
+    r = (dy <= b.h && r > 1.f) ? 1.f : r;
     y = fmaf(r, b.w, b.xl);                        // :167
     const float omr = 1.f - r;
     const float rr = r * omr;
