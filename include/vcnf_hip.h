@@ -885,6 +885,64 @@ int vcnf_mvn_sample_bwd_f64(const double* eps, const double* gamma, const double
 int vcnf_mvn_reduce_partials_f64(const double* partials, int64_t groups, int32_t features, double* d_loc, double* d_tri,
                                  double* d_nu, void* stream);
 
+/* ---- A run of Planar and Radial layers (normflow/flows/planar.py, radial.py) in one launch, with its VJP
+ * (csrc/planar_radial.hip).  z / out [B, D] contiguous, D = features <= 256 (vcnf_planar_radial_supported), K =
+ * n_layers >= 1 without an upper limit.  The layers arrive in the order they are applied, as EFFECTIVE operands the
+ * caller computes (no parameter formula lives in a kernel):
+ *   kind [K] int32   0 planar tanh, 1 planar leaky_relu, 2 radial.  Given twice: `kind` in HOST memory, validated
+ *                    before anything is launched, and `kind_dev`, the same values on the device, read by the kernel.
+ *                    That the two agree is the CALLER'S contract and is not checked (checking would read device
+ *                    memory back): with differing copies the validation passes for layers other than those the kernel
+ *                    runs, e.g. the inverse on a kind it does not have, or a read of a NULL vb
+ *   va [K, D]        planar: u_hat = u + (log(1 + exp(w.u)) - 1 - w.u) w / |w|^2;  radial: z_0
+ *   vb [K, D]        planar: w;  radial rows are not read (NULL is accepted when every kind is 2)
+ *   sc [K, 2]        planar: (b, negative slope);  radial: (|alpha|, beta_eff = log(1 + exp(beta)) - |alpha|)
+ *   forward  planar: lin = w.z + b, z' = z + u_hat h(lin), ld = log|1 + (w.u_hat) h'(lin)|  (h = tanh, or leaky_relu)
+ *            radial: r = |z - z_0|, h = beta_eff / (|alpha| + r), h' = -beta_eff r / (|alpha| + r)^2,
+ *                    z' = z + h (z - z_0), ld = (D - 1) log(1 + h) + log(1 + h + h')
+ *   inverse != 0 (every kind must be 1): lin = w.z + b, a = 1 or the slope where lin < 0, s = a (w.u_hat),
+ *            z' = z - a u_hat lin / (1 + s), ld = -log|1 + s|
+ *   logdet[b] = ld_sign * (sum of the layers' ld), stored or accumulated (ld_mode).  trace [K, B] (may be NULL)
+ *   receives lin of a planar layer and r of a radial layer.  checkpoints [(K - 1) / C, B, D] with C =
+ *   vcnf_planar_radial_checkpoint_every(D) = max(ceil(D / 8), 4) (may be NULL) receives the row as it enters the layers C,
+ *   2 C, ...: at most 8 K elements per sample.
+ *   stack_bwd: VJP of the forward run from its output z_out, its trace and the cotangents g_out [B, D] and g_logdet
+ *            [B] of (out, sum of ld) - either may be NULL = zero; checkpoints as the forward run wrote them, or NULL
+ *            (then every layer's input is rebuilt, and the rounding of z_out grows across the moving direction of
+ *            contracting radial layers: by 1 / (1 + h) per layer): g_in [B, D], g_va [K, D], g_vb [K, D] (zero rows for
+ *            radial layers) and g_sc [K, 2] (the slope's entry is zero).  One launch walks the layers from last to
+ *            first, rebuilding each layer's input from its output and the trace; every workgroup adds its samples'
+ *            parameter terms into its own block of `workspace` (vcnf_planar_radial_bwd_groups(batch, D, K) blocks of
+ *            K (2 D + 2) elements, uninitialised on entry) and a second launch adds the blocks in a fixed order.
+ * vcnf_planar_radial_bwd_groups is a pure function of its arguments (no device query; 0 for an unsupported shape):
+ * at most 1024, and at most 2^22 workspace elements while one block fits in that.
+ * NULL required pointer -> VCNF_ERR_NULL; batch < 0, features outside 1 .. 256 or n_layers < 1 -> VCNF_ERR_SHAPE; a
+ * pointer not aligned to its element size -> VCNF_ERR_ALIGN; unknown kind or ld_mode, or inverse with a kind other than
+ * 1 -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch.  16-byte (8-byte) accesses are used when
+ * features % V == 0 and the [., D] buffers are aligned to them.  No atomics, no allocation, no host synchronisation:
+ * every call is bitwise reproducible and capturable. */
+int vcnf_planar_radial_supported(int32_t features);
+int32_t vcnf_planar_radial_checkpoint_every(int32_t features);
+int64_t vcnf_planar_radial_bwd_groups(int64_t batch, int32_t features, int32_t n_layers);
+int vcnf_planar_radial_stack_f32(const float* z, float* out, float* logdet, float* trace, float* checkpoints,
+                                 const int32_t* kind, const int32_t* kind_dev, const float* va, const float* vb,
+                                 const float* sc, int64_t batch, int32_t features, int32_t n_layers, int inverse,
+                                 int ld_mode, float ld_sign, void* stream);
+int vcnf_planar_radial_stack_bwd_f32(const float* z_out, const float* trace, const float* checkpoints,
+                                     const float* g_out, const float* g_logdet, const int32_t* kind,
+                                     const int32_t* kind_dev, const float* va, const float* vb, const float* sc,
+                                     float* g_in, float* g_va, float* g_vb, float* g_sc, float* workspace,
+                                     int64_t batch, int32_t features, int32_t n_layers, void* stream);
+int vcnf_planar_radial_stack_f64(const double* z, double* out, double* logdet, double* trace, double* checkpoints,
+                                 const int32_t* kind, const int32_t* kind_dev, const double* va, const double* vb,
+                                 const double* sc, int64_t batch, int32_t features, int32_t n_layers, int inverse,
+                                 int ld_mode, double ld_sign, void* stream);
+int vcnf_planar_radial_stack_bwd_f64(const double* z_out, const double* trace, const double* checkpoints,
+                                     const double* g_out, const double* g_logdet, const int32_t* kind,
+                                     const int32_t* kind_dev, const double* va, const double* vb, const double* sc,
+                                     double* g_in, double* g_va, double* g_vb, double* g_sc, double* workspace,
+                                     int64_t batch, int32_t features, int32_t n_layers, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

@@ -125,6 +125,9 @@ PROTOTYPES = {
     "vcnf_gmm_bwd_groups": ([_I64, _I32, _I32], _I64),
     "vcnf_tail_bwd_groups": ([_I64, _I32], _I64),
     "vcnf_mvn_bwd_groups": ([_I64, _I32], _I64),
+    "vcnf_planar_radial_supported": ([_I32], _INT),
+    "vcnf_planar_radial_checkpoint_every": ([_I32], _I32),
+    "vcnf_planar_radial_bwd_groups": ([_I64, _I32, _I32], _I64),
 }
 
 # Entry points that exist as name_f32 and name_f64 (all return int), stated once with the fp32 argument types: the
@@ -170,6 +173,8 @@ _PAIRS = {
     "vcnf_mvn_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
     "vcnf_mvn_sample_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
     "vcnf_mvn_reduce_partials": [_P, _I64, _I32, _P, _P, _P, _P],
+    "vcnf_planar_radial_stack": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F32, _P],
+    "vcnf_planar_radial_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
 }
 _F64_TWIN = {_F32: _F64, _CFG: _CFG64}
 for _name, _args in _PAIRS.items():
@@ -1718,6 +1723,90 @@ def mvn_sample_bwd(eps, gamma, tri, consts, family, g_z=None, g_lp=None, sums=Tr
                                _ptr(d_gamma), ws, b, d, int(family), _stream())
         out = _mvn_block_sums(launch, name, e2, b, d, sums)
     return (d_eps, d_gamma) + out
+
+
+PLANAR_TANH, PLANAR_LEAKY, RADIAL = 0, 1, 2
+
+
+def planar_radial_kinds(kinds, device):
+    """(host int32 array, device int32 tensor) of a run's layer kinds: the entry points validate the host copy before
+    they launch and the kernels read the device copy."""
+    kinds = [int(k) for k in kinds]
+    return (ctypes.c_int32 * len(kinds))(*kinds), torch.tensor(kinds, dtype=torch.int32, device=device)
+
+
+def _planar_radial_operands(x, kinds, va, vb, sc, what):
+    """Checked operands of vcnf_planar_radial_stack*: x [B, D], va / vb [K, D] and sc [K, 2] contiguous, of x's dtype and
+    on its device.  Returns (device, x, va, vb, sc, B, D, K)."""
+    dev = require_device(x, va, vb, sc, kinds[1], f64=True, allow_grad=True)
+    if x.dim() != 2:
+        raise VcnfError(what + ": expects [batch, features] inputs")
+    b, d = x.shape
+    k = len(kinds[0])
+    if kinds[1].dtype != torch.int32 or tuple(kinds[1].shape) != (k,):
+        raise VcnfError(what + ": kinds must be planar_radial_kinds(...) of the run")
+    for name, t, shape in (("va", va, (k, d)), ("vb", vb, (k, d)), ("sc", sc, (k, 2))):
+        if t.dtype != x.dtype or tuple(t.shape) != shape:
+            raise VcnfError("%s: %s must be a %s tensor of shape %s" % (what, name, x.dtype, list(shape)))
+    return dev, x.contiguous(), va.contiguous(), vb.contiguous(), sc.contiguous(), b, int(d), k
+
+
+def planar_radial_stack(z, kinds, va, vb, sc, inverse=False, logdet=None, sign=1.0, want_trace=False):
+    """vcnf_planar_radial_stack_*: a run of Planar / Radial layers over z [B, D] in one launch from the effective operands
+    described in include/vcnf_hip.h (``kinds`` from planar_radial_kinds).  Returns (out, logdet) - logdet a fresh [B]
+    tensor holding sign * log|det|, or the caller's with that added - and with ``want_trace`` what the VJP needs besides:
+    the trace [K, B] and the row checkpoints [(K - 1) / C, B, D] (None when there is none)."""
+    name = "vcnf_planar_radial_stack" + _sfx(z)
+    dev, z, va, vb, sc, b, d, k = _planar_radial_operands(z.detach(), kinds, va.detach(), vb.detach(), sc.detach(), name)
+    logdet, mode = _logp_out(logdet, b, z, dev, name)
+    out = torch.empty_like(z)
+    trace = ckpt = None
+    if want_trace:
+        trace = torch.empty((k, b), dtype=z.dtype, device=dev)
+        n_ck = (k - 1) // max(1, int(lib().vcnf_planar_radial_checkpoint_every(d)))
+        ckpt = torch.empty((n_ck, b, d), dtype=z.dtype, device=dev) if n_ck else None
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z), _ptr(out), _ptr(logdet), _ptr(trace), _ptr(ckpt), kinds[0], _ptr(kinds[1]), _ptr(va),
+                                  _ptr(vb), _ptr(sc), b, d, k, int(bool(inverse)), mode, float(sign), _stream())
+    _check(st, name)
+    return (out, logdet, trace, ckpt) if want_trace else (out, logdet)
+
+
+def planar_radial_stack_bwd(z_out, trace, ckpt, kinds, va, vb, sc, g_out=None, g_ld=None):
+    """vcnf_planar_radial_stack_bwd_*: (g_in [B, D], g_va [K, D], g_vb [K, D], g_sc [K, 2]) of the forward run for the
+    cotangents g_out [B, D] and g_ld [B] of (out, log|det|); None is zero.  ``trace`` and ``ckpt`` (or None) as the forward
+    run returned them.  Two launches, no atomics."""
+    name = "vcnf_planar_radial_stack_bwd" + _sfx(z_out)
+    dev, z_out, va, vb, sc, b, d, k = _planar_radial_operands(z_out, kinds, va, vb, sc, name)
+    require_device(trace, ckpt, g_out, g_ld, f64=True, allow_grad=True)
+    if ckpt is not None:
+        every = int(lib().vcnf_planar_radial_checkpoint_every(d))
+        if ckpt.dtype != z_out.dtype or tuple(ckpt.shape) != ((k - 1) // max(1, every), b, d) or not ckpt.is_contiguous():
+            raise VcnfError(name + ": ckpt must be the contiguous checkpoint tensor of the forward run")
+    if trace.dtype != z_out.dtype or tuple(trace.shape) != (k, b) or not trace.is_contiguous():
+        raise VcnfError(name + ": trace must be the contiguous [layers, batch] tensor of the forward run")
+    if g_out is not None:
+        if g_out.dtype != z_out.dtype or g_out.shape != z_out.shape:
+            raise VcnfError(name + ": g_out must be like the run's output")
+        g_out = g_out.contiguous()
+    if g_ld is not None:
+        if g_ld.dtype != z_out.dtype or tuple(g_ld.shape) != (b,):
+            raise VcnfError(name + ": g_ld must be a [batch] tensor of the run's dtype")
+        g_ld = g_ld.contiguous()
+    g_in = torch.empty_like(z_out)
+    if b == 0:
+        return g_in, torch.zeros_like(va), torch.zeros_like(vb), torch.zeros_like(sc)
+    g_va, g_vb, g_sc = torch.empty_like(va), torch.empty_like(vb), torch.empty_like(sc)
+    groups = int(lib().vcnf_planar_radial_bwd_groups(b, d, k))
+    if groups < 1:
+        _check(2, name)
+    work = torch.empty((groups, k, 2 * d + 2), dtype=z_out.dtype, device=dev)
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z_out), _ptr(trace), _ptr(ckpt), _ptr(g_out), _ptr(g_ld), kinds[0], _ptr(kinds[1]), _ptr(va),
+                                  _ptr(vb), _ptr(sc), _ptr(g_in), _ptr(g_va), _ptr(g_vb), _ptr(g_sc), _ptr(work), b, d, k,
+                                  _stream())
+    _check(st, name)
+    return g_in, g_va, g_vb, g_sc
 
 
 PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2

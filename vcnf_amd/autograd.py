@@ -495,6 +495,30 @@ class HeavyTailSampleFn(torch.autograd.Function):
                 d_sh if need[4] else None, g_lp.sum().expand(shape.shape) if need[5] else None, None)
 
 
+class PlanarRadialStackFn(torch.autograd.Function):
+    """vcnf_planar_radial_stack_*: (out, log|det| [B]) of a run of Planar / Radial layers from its effective operands va,
+    vb [K, D] and sc [K, 2] (vcnf_amd.fused_planar.operands) as ONE node.  Forward launches the kernel with the trace
+    [K, B] and the row checkpoints; backward is vcnf_planar_radial_stack_bwd_*, which rebuilds the layers' inputs from
+    the run's output, the trace and the checkpoints: the saved state is O(B K + B D)."""
+
+    @staticmethod
+    def forward(ctx, z, va, vb, sc, kinds):
+        with torch.no_grad():
+            out, ld, trace, ckpt = _lib.planar_radial_stack(z, kinds, va, vb, sc, want_trace=True)
+        ctx.save_for_backward(out, trace, ckpt, va, vb, sc)
+        ctx.kinds = kinds
+        ctx.set_materialize_grads(False)
+        return out, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_ld):
+        out, trace, ckpt, va, vb, sc = ctx.saved_tensors
+        g_in, g_va, g_vb, g_sc = _lib.planar_radial_stack_bwd(out, trace, ckpt, ctx.kinds, va.detach(), vb.detach(),
+                                                               sc.detach(), g_out, g_ld)
+        return g_in, g_va, g_vb, g_sc, None
+
+
 def _mvn_d_consts(g, d_nu):
     """Gradient of consts = (cst, nu): cst enters every sample's log density once."""
     return torch.cat([g.sum().reshape(1), d_nu])

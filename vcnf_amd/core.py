@@ -17,16 +17,19 @@ import torch
 from torch import nn
 
 from .flows.affine.coupling import AffineCouplingBlock, MaskedAffineFlow, AffineConstFlow
-from . import fused_affine, fused, fused_masked
+from . import fused_affine, fused, fused_masked, fused_planar
 from .flows.mixing import Permute
 from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
+from .flows.planar import Planar
+from .flows.radial import Radial
 from .fused import refresh_packed
 
 # The single-launch families, tried in this order at every position of a pass: (the model's switch, the flow types a
 # run can start with, the family's planner: None or (end, launch) with launch(z, log_q, sign) -> (z, log_q))
 _STACKS = (('fuse_affine_stacks', (Permute, AffineCouplingBlock), fused_affine.stack_run),
            ('fuse_masked_stacks', (MaskedAffineFlow, AffineConstFlow), fused_masked.stack_run),
-           ('fuse_rqs_stacks', (CoupledRationalQuadraticSpline,), fused.stack_run))
+           ('fuse_rqs_stacks', (CoupledRationalQuadraticSpline,), fused.stack_run),
+           ('fuse_planar_stacks', (Planar, Radial), fused_planar.stack_run))
 
 
 class _PackedWeightsMixin:
@@ -58,6 +61,7 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         self.fuse_affine_stacks = True           # runs of one-kernel affine layers in a single launch (fused_affine.run_stack)
         self.fuse_rqs_stacks = True              # runs of one-kernel RQS layers in a single launch at small batches (fused.run_stack)
         self.fuse_masked_stacks = True           # runs of MaskedAffineFlow (+ MLP conditioners) / ActNorm layers in a single launch
+        self.fuse_planar_stacks = True           # runs of Planar / Radial layers in a single launch (fused_planar.run)
 
     def _walk(self, z, log_q, context, density):
         """(z, log_q) after one pass over the flows: last to first through their inverses with the log-dets added
@@ -107,14 +111,31 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
     def _plain_walk(self, z, log_q, context, density, trace=None):
         """The pass of ``_walk`` through every flow's plain ``(z, log_det)`` contract, log-dets summed out of place;
         ``trace``: two lists that receive each layer's output and log-det as numpy arrays (the reference's
-        ``extended`` lists)."""
-        for flow in (reversed(self.flows) if density else self.flows):
+        ``extended`` lists).  Without a trace a family of _STACKS whose ``stack_run.differentiable`` is set - its run is one
+        autograd node and returns the log-dets out of place when given no log_q - still takes its runs in one launch:
+        reverse_kld trains through here."""
+        order = list(reversed(self.flows)) if density else list(self.flows)
+        i = 0
+        while i < len(order):
+            flow = order[i]
+            run = None
+            for switch, starts, stack_run in _STACKS:
+                if trace is None and getattr(stack_run, 'differentiable', False) and isinstance(flow, starts) and getattr(self, switch):
+                    run = stack_run(self, order, i, z, context, density)
+                    if run is not None:
+                        break
+            if run is not None:
+                i, launch = run
+                z, log_det = launch(z, None, 1.0 if density else -1.0)
+                log_q = log_q + log_det
+                continue
             ctx = {'context': context} if (context is not None and getattr(flow, 'takes_context', False)) else {}
             z, log_det = flow.inverse(z, **ctx) if density else flow(z, **ctx)
             if trace is not None:
                 trace[0].append(z.detach().cpu().numpy())
                 trace[1].append(torch.as_tensor(log_det).detach().cpu().numpy())
             log_q = log_q + log_det if density else log_q - log_det
+            i += 1
         return z, log_q
 
     # ------------------------------------------------------------ density
