@@ -943,6 +943,34 @@ int vcnf_planar_radial_stack_bwd_f64(const double* z_out, const double* trace, c
                                      double* g_in, double* g_va, double* g_vb, double* g_sc, double* workspace,
                                      int64_t batch, int32_t features, int32_t n_layers, void* stream);
 
+/* ---- Target densities: the 2-D targets of normflow 1.2 (distributions/target.py) with their score, one launch
+ * (csrc/target_density.hip).  z [B, 2] contiguous, logp [B], score [B, 2] = d logp / d z or NULL (then none of the
+ * score's arithmetic runs).  With r = sqrt(z0^2 + z1^2) and a = |z0|:
+ *   VCNF_TARGET_TWO_MOONS     logp = -((r - 2) / 0.2)^2 / 2 - ((a - 2) / 0.3)^2 / 2 + log1p(e),  e = exp(-4 a / 0.09)
+ *                             score0 = -(r - 2) / 0.04 z0 / r + sign(z0) ((2 - a) / 0.09 - (4 / 0.09) e / (1 + e))
+ *                             score1 = -(r - 2) / 0.04 z1 / r
+ *                             table, n_comp and scale are ignored (table may be NULL)
+ *   VCNF_TARGET_CIRCULAR_GMM  table [n_comp, 2] the centres c_i (upstream: 2 (sin, cos)(2 pi i / n)),
+ *                             d_i = |z - c_i|^2 / (2 scale^2),  logp = -log(2 pi scale^2 n_comp) + logsumexp_i(-d_i)
+ *                             score = sum_i softmax_i(-d) (c_i - z) / scale^2
+ *   VCNF_TARGET_RING_MIXTURE  table [n_comp] the radii t_i (upstream: 2 (i + 1) / n),
+ *                             d_i = (r - t_i)^2 / (2 scale^2),  logp = logsumexp_i(-d_i)
+ *                             score = sum_i softmax_i(-d) (t_i - r) / scale^2 z / r
+ * The caller computes the table.  Every z / r is 0 at r == 0 (torch's gradient of norm there) and sign(0) = 0; a
+ * non-finite z gives NaN logp and score.  The logsumexp subtracts its maximum in two passes over the components; no
+ * buffer of size [B, n_comp] exists and n_comp has no upper limit.  One sample per lane; a row moves as one 8-byte
+ * (16-byte) access when z and score are aligned to it, as two elements otherwise, with the same bits either way.
+ * logp does not depend on whether score is given, bit for bit.
+ * batch < 0, or n_comp < 1 for a mixture -> VCNF_ERR_SHAPE; unknown family -> VCNF_ERR_UNSUPPORTED; batch == 0 ->
+ * VCNF_OK without a launch; NULL z or logp, or NULL table for a mixture -> VCNF_ERR_NULL; a pointer not aligned to
+ * its element size -> VCNF_ERR_ALIGN.  No atomics, no allocation, no host synchronisation: every call is bitwise
+ * reproducible and capturable. */
+enum { VCNF_TARGET_TWO_MOONS = 0, VCNF_TARGET_CIRCULAR_GMM = 1, VCNF_TARGET_RING_MIXTURE = 2 };
+int vcnf_target_log_prob_f32(const float* z, const float* table, float* logp, float* score, int64_t batch,
+                             int32_t n_comp, int family, float scale, void* stream);
+int vcnf_target_log_prob_f64(const double* z, const double* table, double* logp, double* score, int64_t batch,
+                             int32_t n_comp, int family, double scale, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

@@ -175,6 +175,7 @@ _PAIRS = {
     "vcnf_mvn_reduce_partials": [_P, _I64, _I32, _P, _P, _P, _P],
     "vcnf_planar_radial_stack": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F32, _P],
     "vcnf_planar_radial_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
+    "vcnf_target_log_prob": [_P, _P, _P, _P, _I64, _I32, _INT, _F32, _P],
 }
 _F64_TWIN = {_F32: _F64, _CFG: _CFG64}
 for _name, _args in _PAIRS.items():
@@ -1807,6 +1808,38 @@ def planar_radial_stack_bwd(z_out, trace, ckpt, kinds, va, vb, sc, g_out=None, g
                                   _stream())
     _check(st, name)
     return g_in, g_va, g_vb, g_sc
+
+
+TARGET_TWO_MOONS, TARGET_CIRCULAR_GMM, TARGET_RING_MIXTURE = 0, 1, 2
+
+
+def target_log_prob(z, family, table=None, scale=0.0, want_score=False):
+    """vcnf_target_log_prob_*: (log density [B], score d logp / d z [B, 2] or None) of z [B, 2] under TwoMoons (family 0),
+    the circular Gaussian mixture with the centres ``table`` [n, 2] (1) or the ring mixture with the radii ``table`` [n]
+    (2), both of standard deviation ``scale``.  One launch; without ``want_score`` none of the score's arithmetic runs."""
+    name = "vcnf_target_log_prob" + _sfx(z)
+    dev = require_device(z, table, f64=True, allow_grad=True)
+    if z.dtype not in (torch.float32, torch.float64):
+        raise VcnfError("%s: z must be fp32 or fp64 (got %s)" % (name, z.dtype))
+    if z.dim() != 2 or z.shape[1] != 2:
+        raise VcnfError("%s: expects [batch, 2] inputs (got %s)" % (name, list(z.shape)))
+    n = 0
+    if family != TARGET_TWO_MOONS:
+        per = 2 if family == TARGET_CIRCULAR_GMM else 1
+        if table is None or table.dtype != z.dtype or table.device != dev or table.numel() % per:
+            raise VcnfError("%s: the component table must be a %s tensor on %s" % (name, z.dtype, dev))
+        table = table.detach().contiguous()
+        n = table.numel() // per
+    else:
+        table = None
+    z = z.detach().contiguous()
+    b = len(z)
+    logp = torch.empty(b, dtype=z.dtype, device=dev)
+    score = torch.empty_like(z) if want_score else None
+    with torch.cuda.device(dev):
+        st = getattr(lib(), name)(_ptr(z), _ptr(table), _ptr(logp), _ptr(score), b, n, int(family), float(scale), _stream())
+    _check(st, name)
+    return logp, score
 
 
 PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2

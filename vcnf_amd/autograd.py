@@ -519,6 +519,23 @@ class PlanarRadialStackFn(torch.autograd.Function):
         return g_in, g_va, g_vb, g_sc, None
 
 
+class TargetLogProbFn(torch.autograd.Function):
+    """vcnf_target_log_prob_*: log density of z [B, 2] under one of the 2-D targets as ONE node.  The forward launch also
+    writes the score d logp / d z, the only thing saved; backward is one multiply.  The targets have no parameters."""
+
+    @staticmethod
+    def forward(ctx, z, table, family, scale):
+        lp, score = _lib.target_log_prob(z, family, table, scale, want_score=True)
+        ctx.save_for_backward(score)
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        score, = ctx.saved_tensors
+        return g[:, None] * score, None, None, None
+
+
 def _mvn_d_consts(g, d_nu):
     """Gradient of consts = (cst, nu): cst enters every sample's log density once."""
     return torch.cat([g.sum().reshape(1), d_nu])

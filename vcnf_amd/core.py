@@ -211,11 +211,14 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         if dreg:
             w_const = torch.exp(log_p - log_q).detach()
             log_q = self._frozen_log_q(z, context)
-            w = torch.exp(log_p - log_q)
+            # log w = log p - log q as it stands, not log(exp(.)): where exp underflows (fp32 below e^-103; a sharp
+            # target such as RingMixture puts samples of an untrained flow there) the weight is 0, log(0) = -inf and
+            # the loss their product, NaN
+            log_w = log_p - log_q
             w_alpha = w_const ** alpha
             w_alpha = w_alpha / torch.mean(w_alpha)
             weights = (1 - alpha) * w_alpha + alpha * w_alpha ** 2
-            loss = -alpha * torch.mean(weights * torch.log(w))
+            loss = -alpha * torch.mean(weights * log_w)
         else:
             loss = np.sign(alpha - 1) * torch.logsumexp(alpha * (log_p - log_q), 0)
         if extended:
