@@ -4,6 +4,16 @@ and thin tensor-level wrappers around each entry point.
 There is no CPU implementation behind these wrappers: a CPU tensor, a missing
 library or a non-zero status raises.  PyTorch is used for device memory and the
 current HIP stream only.
+
+How a wrapper calls the library (copy this for a new entry point):
+
+* pointer arguments are declared ``_P`` in ``PROTOTYPES`` / ``_PAIRS`` and the wrapper passes the tensor itself (or
+  None for NULL); a ``vcnf_rqs_cfg`` argument is declared ``_CFG`` and the wrapper passes the struct (``_cfg_of``
+  picks the fp64 twin) - ctypes converts both during the call;
+* ``_call(name, dev, *args)`` enters the tensors' device, appends the current stream as the last argument, calls the
+  entry point ``name`` and raises on a non-zero status, naming ``name``; ``tag=`` brackets the launch for bench.py;
+* ``_ld_out`` gives the log-det / log-prob output and its ``LD_STORE | LD_ACCUM`` mode, ``_bad_if`` the inverse
+  spline's discriminant counter.
 """
 import ctypes
 import math
@@ -13,7 +23,18 @@ import torch
 
 from . import build as _build
 
-_P = ctypes.c_void_p
+
+class _P:
+    """``void*`` argument that takes the tensor itself.  ctypes calls ``from_param`` on each argument during the call:
+    a tensor becomes its ``data_ptr()``, None is NULL, and a plain int address, a ``c_void_p`` or a ctypes array pass
+    as they do for ``c_void_p``.  (A static method with its two globals bound as defaults: this runs once per pointer
+    of every launch, and a classmethod on a ``c_void_p`` subclass cost 1.3 us more per 26-argument call.)"""
+
+    @staticmethod
+    def from_param(value, _as_void_p=ctypes.c_void_p.from_param, _tensor=torch.Tensor):
+        return _as_void_p(value.data_ptr() if isinstance(value, _tensor) else value)
+
+
 _I32, _I64, _F32, _INT = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_int
 _F64 = ctypes.c_double
 
@@ -234,6 +255,7 @@ def _stream():
 
 
 def _ptr(t):
+    # what _P does with a tensor, for callers that bind entry points of their own (profiles/tools)
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
@@ -292,10 +314,15 @@ def make_cfg(num_bins, tails, tail_bound=1.0, left=0.0, right=1.0, bottom=0.0, t
     return cfg
 
 
+def _cfg_of(cfg, x):
+    """The spline constants in the precision of the inputs ``x``."""
+    return cfg.f64 if x.dtype == torch.float64 else cfg
+
+
 _BAD = {}
 
-# bench.py hook: when set to a list, rqs_coupling brackets its kernel launch with a
-# pair of HIP events on the launch stream and appends (start, end, batch) to it.
+# bench.py hook: when set to a list, the bracketed wrappers (``_timed``) put a pair of HIP events around their kernel
+# launch and append (start, end, tag) to it; the RQS coupling wrappers give their batch size as the tag.
 EVENT_SINK = None
 
 
@@ -335,10 +362,32 @@ class _timed:
         return False
 
 
+def _launch(name, *args):
+    """Status of the entry point ``name`` enqueued on the current stream of the current device."""
+    return getattr(lib(), name)(*args, _stream())
+
+
+def _call(name, dev, *args, tag=None):
+    """One checked launch: the entry point ``name`` with ``args`` and, as its last argument, the current stream of
+    ``dev``; raises on a non-zero status.  ``tag``: bracket the launch for bench.py (``_timed``)."""
+    with torch.cuda.device(dev):
+        if tag is None:
+            st = _launch(name, *args)
+        else:
+            with _timed(tag):
+                st = _launch(name, *args)
+    _check(st, name)
+
+
 def bad_discriminant_counter(device):
     """Device int32 that the inverse spline kernels bump when b^2-4ac < 0 (the
     reference asserts on the host, splines.py:164)."""
     return _counter(_BAD, device)
+
+
+def _bad_if(inverse, dev):
+    """The ``bad_count`` argument of the spline entry points: only the inverse direction has a discriminant."""
+    return bad_discriminant_counter(dev) if inverse else None
 
 
 _SAT = {}
@@ -401,6 +450,18 @@ def check_saturation(device="cuda", model=None):
     return n
 
 
+def _ld_out(out, b, dtype, dev, name=None):
+    """(tensor, ld_mode) of a log-det / log-prob output: a fresh [batch] tensor to store into, or the caller's to
+    accumulate into.  With ``name`` (the base distributions) the caller's tensor is checked first."""
+    if out is None:
+        return torch.empty(b, dtype=dtype, device=dev), LD_STORE
+    if name is not None:
+        require_device(out, f64=True)
+        if out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != (b,):
+            raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
+    return out, LD_ACCUM
+
+
 # ---------------------------------------------------------------- wrappers
 def rqs_elementwise(x, uw, uh, ud, cfg, inverse, allow_grad=False):
     """x [...]; uw, uh [..., K]; ud [..., K-1 | K+1] (last dim contiguous)."""
@@ -423,16 +484,10 @@ def rqs_elementwise(x, uw, uh, ud, cfg, inverse, allow_grad=False):
     d2, ldd = rows(ud, nd)
     y = torch.empty_like(xf)
     lad = torch.empty_like(xf)
-    f64 = xf.dtype == torch.float64
-    if f64 and not all(t.dtype == torch.float64 for t in (w2, h2, d2)):
+    if xf.dtype == torch.float64 and not all(t.dtype == torch.float64 for t in (w2, h2, d2)):
         raise VcnfError("fp64 spline: inputs and logits must all be fp64")
-    with torch.cuda.device(dev):
-        fn = lib().vcnf_rqs_elementwise_f64 if f64 else lib().vcnf_rqs_elementwise_f32
-        st = fn(_ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), ldw, ldh, ldd,
-                _ptr(y), _ptr(lad), xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg),
-                int(bool(inverse)),
-                _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-    _check(st, "vcnf_rqs_elementwise" + _sfx(xf))
+    _call("vcnf_rqs_elementwise" + _sfx(xf), dev, xf, w2, h2, d2, ldw, ldh, ldd, y, lad, xf.numel(), _cfg_of(cfg, xf),
+          bool(inverse), _bad_if(inverse, dev))
     return y.view(shape), lad.view(shape)
 
 
@@ -452,14 +507,10 @@ def rqs_elementwise_image(x, params, cfg, inverse, allow_grad=False):
     x = x.contiguous()
     params = params.contiguous()
     y, lad = torch.empty_like(x), torch.empty_like(x)
-    base, es = params.data_ptr(), params.element_size()
-    f64 = x.dtype == torch.float64
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_rqs_elementwise_strided" + _sfx(x))(
-            _ptr(x), base, base + es * k * inner, base + 2 * es * k * inner, p * inner, p * inner, p * inner,
-            inner, inner, 0, _ptr(y), _ptr(lad), x.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)),
-            _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-    _check(st, "vcnf_rqs_elementwise_strided" + _sfx(x))
+    base, es = params.data_ptr(), params.element_size()     # widths | heights | derivatives: addresses inside params
+    _call("vcnf_rqs_elementwise_strided" + _sfx(x), dev, x, base, base + es * k * inner, base + 2 * es * k * inner,
+          p * inner, p * inner, p * inner, inner, inner, 0, y, lad, x.numel(), _cfg_of(cfg, x), bool(inverse),
+          _bad_if(inverse, dev))
     return y, lad
 
 
@@ -477,11 +528,8 @@ def rqs_elementwise_shared(x, uw, uh, ud, cfg, inverse, allow_grad=False):
     y, lad = torch.empty_like(x), torch.empty_like(x)
     period = int(x[0].numel())
     tables = torch.empty(period * 3 * (k + 1), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = lib().vcnf_rqs_shared_f32(_ptr(x), _ptr(uw), _ptr(uh), _ptr(ud), period, _ptr(tables), _ptr(y), _ptr(lad),
-                                       x.numel(), ctypes.byref(cfg), int(bool(inverse)),
-                                       _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-    _check(st, "vcnf_rqs_shared_f32")
+    _call("vcnf_rqs_shared_f32", dev, x, uw, uh, ud, period, tables, y, lad, x.numel(), cfg, bool(inverse),
+          _bad_if(inverse, dev))
     return y, lad
 
 
@@ -496,12 +544,8 @@ def rqs_packed_bwd(x, params, gy, glad, cfg, inverse):
     gy, glad = gy.detach().contiguous(), glad.detach().contiguous()
     inner = int(x[0, 0].numel())
     gx, gp = torch.empty_like(x), torch.empty_like(params)
-    f64 = x.dtype == torch.float64
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_rqs_packed_bwd" + _sfx(x))(
-            _ptr(x), _ptr(params), inner, int(x[0].numel()), _ptr(gy), _ptr(glad), _ptr(gx), _ptr(gp), x.numel(),
-            ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)), _stream())
-    _check(st, "vcnf_rqs_packed_bwd" + _sfx(x))
+    _call("vcnf_rqs_packed_bwd" + _sfx(x), dev, x, params, inner, int(x[0].numel()), gy, glad, gx, gp, x.numel(),
+          _cfg_of(cfg, x), bool(inverse))
     return gx, gp
 
 
@@ -518,11 +562,8 @@ def rqs_shared_bwd(x, uw, uh, ud, gy, glad, cfg, inverse):
     groups = int(lib().vcnf_rqs_shared_bwd_groups(b, period))
     gx = torch.empty_like(x)
     partial = torch.empty(groups, period, 2 * k + nd, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = lib().vcnf_rqs_shared_bwd_f32(_ptr(x), _ptr(uw), _ptr(uh), _ptr(ud), b, period, period,
-                                           _ptr(gy), _ptr(glad), _ptr(gx), _ptr(partial), groups,
-                                           ctypes.byref(cfg), int(bool(inverse)), _stream())
-    _check(st, "vcnf_rqs_shared_bwd_f32")
+    _call("vcnf_rqs_shared_bwd_f32", dev, x, uw, uh, ud, b, period, period, gy, glad, gx, partial, groups, cfg,
+          bool(inverse))
     g = partial.sum(0)
     return gx, g[:, :k].reshape(uw.shape), g[:, k:2 * k].reshape(uh.shape), g[:, 2 * k:].reshape(ud.shape)
 
@@ -544,12 +585,8 @@ def rqs_elementwise_bwd(x, uw, uh, ud, gy, glad, cfg, inverse):
     glf = glad.detach().reshape(-1).contiguous()
     gx = torch.empty_like(xf)
     gw, gh, gd = torch.empty_like(w2), torch.empty_like(h2), torch.empty_like(d2)
-    with torch.cuda.device(dev):
-        fn = lib().vcnf_rqs_elementwise_bwd_f64 if f64 else lib().vcnf_rqs_elementwise_bwd_f32
-        st = fn(_ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), k, k, nd,
-                _ptr(gyf), _ptr(glf), _ptr(gx), _ptr(gw), _ptr(gh), _ptr(gd),
-                xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)), _stream())
-    _check(st, "vcnf_rqs_elementwise_bwd" + _sfx(xf))
+    _call("vcnf_rqs_elementwise_bwd" + _sfx(xf), dev, xf, w2, h2, d2, k, k, nd, gyf, glf, gx, gw, gh, gd, xf.numel(),
+          _cfg_of(cfg, xf), bool(inverse))
     return gx.view(shape), gw.view(shape + (k,)), gh.view(shape + (k,)), gd.view(shape + (nd,))
 
 
@@ -624,14 +661,8 @@ def rqs_elementwise_limits(x, uw, uh, ud, limits, cfg, inverse, allow_grad=False
     lay = _limit_layouts(limits, x, allow_grad)
     k = cfg.num_bins
     y, lad = torch.empty_like(xf), torch.empty_like(xf)
-    f64 = xf.dtype == torch.float64
-    bc = _bcast(lay)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_rqs_elementwise_limits" + _sfx(xf))(
-            _ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), k, k, k + 1, *[_ptr(l[0]) for l in lay], ctypes.byref(bc),
-            _ptr(y), _ptr(lad), xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)),
-            _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-    _check(st, "vcnf_rqs_elementwise_limits" + _sfx(xf))
+    _call("vcnf_rqs_elementwise_limits" + _sfx(xf), dev, xf, w2, h2, d2, k, k, k + 1, *[l[0] for l in lay], _bcast(lay),
+          y, lad, xf.numel(), _cfg_of(cfg, xf), bool(inverse), _bad_if(inverse, dev))
     return y.view(x.shape), lad.view(x.shape)
 
 
@@ -650,14 +681,8 @@ def rqs_elementwise_limits_bwd(x, uw, uh, ud, limits, gy, glad, cfg, inverse, wa
     gx = torch.empty_like(xf)
     gw, gh, gd = torch.empty_like(w2), torch.empty_like(h2), torch.empty_like(d2)
     glim = [torch.empty_like(xf) if w else None for w in want]
-    f64 = xf.dtype == torch.float64
-    bc = _bcast(lay)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_rqs_elementwise_limits_bwd" + _sfx(xf))(
-            _ptr(xf), _ptr(w2), _ptr(h2), _ptr(d2), k, k, k + 1, *[_ptr(l[0]) for l in lay], ctypes.byref(bc),
-            _ptr(gyf), _ptr(glf), _ptr(gx), _ptr(gw), _ptr(gh), _ptr(gd), *[_ptr(g) for g in glim],
-            xf.numel(), ctypes.byref(cfg.f64 if f64 else cfg), int(bool(inverse)), _stream())
-    _check(st, "vcnf_rqs_elementwise_limits_bwd" + _sfx(xf))
+    _call("vcnf_rqs_elementwise_limits_bwd" + _sfx(xf), dev, xf, w2, h2, d2, k, k, k + 1, *[l[0] for l in lay],
+          _bcast(lay), gyf, glf, gx, gw, gh, gd, *glim, xf.numel(), _cfg_of(cfg, xf), bool(inverse))
     out = []
     for g, t in zip(glim, limits):
         out.append(None if g is None else g.view(shape).sum_to_size(t.shape).to(t.device))
@@ -672,25 +697,10 @@ def rqs_coupling(x, params, tf_idx, id_idx, shared, cfg, inverse, logdet=None, s
     x = x.contiguous()
     params = params.contiguous()
     y = torch.empty_like(x)
-    mode = LD_ACCUM
-    if logdet is None:
-        logdet = torch.empty(b, dtype=torch.float32, device=dev)
-        mode = LD_STORE
+    logdet, mode = _ld_out(logdet, b, torch.float32, dev)
     sw, sh, sd = shared if shared is not None else (None, None, None)
-    sink = EVENT_SINK
-    with torch.cuda.device(dev):
-        if sink is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        st = lib().vcnf_rqs_coupling_f32(_ptr(x), _ptr(params), _ptr(tf_idx), tf_idx.numel(),
-                                         _ptr(id_idx), id_idx.numel(), _ptr(sw), _ptr(sh), _ptr(sd),
-                                         _ptr(y), _ptr(logdet), b, ctypes.byref(cfg), int(bool(inverse)),
-                                         mode, float(sign),
-                                         _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-        if sink is not None:
-            ev1.record()
-            sink.append((ev0, ev1, b))
-    _check(st, "vcnf_rqs_coupling_f32")
+    _call("vcnf_rqs_coupling_f32", dev, x, params, tf_idx, tf_idx.numel(), id_idx, id_idx.numel(), sw, sh, sd, y,
+          logdet, b, cfg, bool(inverse), mode, sign, _bad_if(inverse, dev), tag=b)
     return y, logdet
 
 
@@ -704,11 +714,8 @@ def rqs_conditioner_input(x, id_idx, context, shared, cfg, apply_inverse_shared)
         c = context.shape[1]
     out = torch.empty(b, id_idx.numel() + c, dtype=torch.float32, device=dev)
     sw, sh, sd = shared if shared is not None else (None, None, None)
-    with torch.cuda.device(dev):
-        st = lib().vcnf_rqs_conditioner_input_f32(_ptr(x), b, d, _ptr(id_idx), id_idx.numel(), _ptr(context), c,
-                                                  _ptr(sw), _ptr(sh), _ptr(sd), ctypes.byref(cfg),
-                                                  int(bool(apply_inverse_shared)), _ptr(out), _stream())
-    _check(st, "vcnf_rqs_conditioner_input_f32")
+    _call("vcnf_rqs_conditioner_input_f32", dev, x, b, d, id_idx, id_idx.numel(), context, c, sw, sh, sd, cfg,
+          bool(apply_inverse_shared), out)
     return out
 
 
@@ -737,6 +744,27 @@ def small_batch_rows(rows=None):
     return int(lib().vcnf_rqs_layer_fused_small_batch_rows(-1 if rows is None else int(rows)))
 
 
+def _range_safe_launches(name, dev, b, precision, first, second, launch):
+    """The launch protocol of the fused RQS layer entry points (``name``) on a batch of ``b`` samples.
+    ``launch(fn, operands, precision, counter, flags)`` makes one launch of the entry point ``fn`` and returns its
+    status; ``first`` are the operands of the requested ``precision``, ``second`` the exact fp32 ones or None.
+    precision 1 (fp16 split-half operands) with ``second`` is the range-safe pair: the split-half launch leaves tiles
+    (32 samples, one flag each) that hold a non-finite input or a value beyond +-65504 unwritten, flags them and counts
+    them in range_redo_counter; the fp32 launch behind it evaluates exactly the flagged tiles (normally none: it
+    returns at once).  Without ``second`` the split-half kernel clamps and counts in saturation_counter.  bench.py's
+    event bracket is around the first launch only."""
+    safe = precision == 1 and second is not None
+    fn = getattr(lib(), name)
+    with torch.cuda.device(dev):
+        flags = _redo_flags(dev, (b + 31) // 32) if safe and b > 0 else None
+        counter = (range_redo_counter(dev) if safe else saturation_counter(dev)) if precision == 1 else None
+        with _timed(b):
+            st = launch(fn, first, precision, counter, flags)
+        if st == OK and flags is not None:
+            st = launch(fn, second, 0, None, flags)
+    _check(st, name)
+
+
 def rqs_layer_fused(x, context, tf_idx, id_idx, ctx_dim, hidden, num_blocks, precision, wpack, shared, cfg,
                     inverse, logdet=None, sign=1.0, wpack_f32=None, cfg_f32=None):
     """Whole coupling layer (conditioner included) in one kernel; see csrc/fused_layer.hip.
@@ -750,35 +778,17 @@ def rqs_layer_fused(x, context, tf_idx, id_idx, ctx_dim, hidden, num_blocks, pre
     if context is not None:
         context = context.contiguous()
     y = torch.empty_like(x)
-    mode = LD_ACCUM
-    if logdet is None:
-        logdet = torch.empty(b, dtype=torch.float32, device=dev)
-        mode = LD_STORE
+    logdet, mode = _ld_out(logdet, b, torch.float32, dev)
     sw, sh, sd = shared if shared is not None else (None, None, None)
-    sink = EVENT_SINK
-    L = lib()
-    safe = precision == 1 and wpack_f32 is not None
+    n_tf, n_id, ctx_dim, hidden, num_blocks = tf_idx.numel(), id_idx.numel(), int(ctx_dim), int(hidden), int(num_blocks)
+    inverse, bad = bool(inverse), _bad_if(inverse, dev)
 
-    def launch(prec, pack, cf, sat, redo):
-        return L.vcnf_rqs_layer_fused_f32(_ptr(x), _ptr(context), _ptr(y), _ptr(logdet), b,
-                                          _ptr(tf_idx), tf_idx.numel(), _ptr(id_idx), id_idx.numel(),
-                                          int(ctx_dim), int(hidden), int(num_blocks), int(prec),
-                                          _ptr(pack), pack.numel(), _ptr(sw), _ptr(sh), _ptr(sd),
-                                          ctypes.byref(cf), int(bool(inverse)), mode, float(sign),
-                                          _ptr(bad_discriminant_counter(dev)) if inverse else None, sat, redo, _stream())
-    with torch.cuda.device(dev):
-        flags = _redo_flags(dev, (b + 31) // 32) if safe and b > 0 else None        # one flag per 32 samples
-        if sink is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        st = launch(precision, wpack, cfg, _ptr(range_redo_counter(dev) if safe else saturation_counter(dev)) if precision == 1 else None,
-                    _ptr(flags))
-        if sink is not None:
-            ev1.record()
-            sink.append((ev0, ev1, b))
-        if st == OK and flags is not None:
-            st = launch(0, wpack_f32, cfg_f32 if cfg_f32 is not None else cfg, None, _ptr(flags))
-    _check(st, "vcnf_rqs_layer_fused_f32")
+    def launch(fn, operands, prec, counter, flags):
+        pack, cf = operands
+        return fn(x, context, y, logdet, b, tf_idx, n_tf, id_idx, n_id, ctx_dim, hidden, num_blocks, prec, pack,
+                  pack.numel(), sw, sh, sd, cf, inverse, mode, sign, bad, counter, flags, _stream())
+    _range_safe_launches("vcnf_rqs_layer_fused_f32", dev, b, precision, (wpack, cfg),
+                         None if wpack_f32 is None else (wpack_f32, cfg_f32 if cfg_f32 is not None else cfg), launch)
     return y, logdet
 
 
@@ -794,32 +804,14 @@ def rqs_stack_fused(x, context, layers, layers_f32, pack_floats, d_t, d_id, ctx_
     if context is not None:
         context = context.contiguous()
     y = torch.empty_like(x)
-    mode = LD_ACCUM
-    if logdet is None:
-        logdet = torch.empty(b, dtype=torch.float32, device=dev)
-        mode = LD_STORE
-    L = lib()
-    safe = precision == 1 and layers_f32 is not None
+    logdet, mode = _ld_out(logdet, b, torch.float32, dev)
+    dims = (int(d_t), int(d_id), int(ctx_dim), int(hidden), int(num_blocks))
+    pack_floats, inverse, bad = int(pack_floats), bool(inverse), _bad_if(inverse, dev)
 
-    def launch(prec, lay, sat, redo):
-        return L.vcnf_rqs_stack_fused_f32(_ptr(x), _ptr(context), _ptr(y), _ptr(logdet), b, lay, len(lay),
-                                          int(d_t), int(d_id), int(ctx_dim), int(hidden), int(num_blocks), int(prec),
-                                          int(pack_floats), ctypes.byref(cfg), int(bool(inverse)), mode, float(sign),
-                                          _ptr(bad_discriminant_counter(dev)) if inverse else None, sat, redo, _stream())
-    with torch.cuda.device(dev):
-        flags = _redo_flags(dev, (b + 31) // 32) if safe and b > 0 else None
-        sink = EVENT_SINK
-        if sink is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        st = launch(precision, layers, _ptr(range_redo_counter(dev) if safe else saturation_counter(dev)) if precision == 1 else None,
-                    _ptr(flags))
-        if sink is not None:
-            ev1.record()
-            sink.append((ev0, ev1, b))
-        if st == OK and flags is not None:
-            st = launch(0, layers_f32, None, _ptr(flags))
-    _check(st, "vcnf_rqs_stack_fused_f32")
+    def launch(fn, lay, prec, counter, flags):
+        return fn(x, context, y, logdet, b, lay, len(lay), *dims, prec, pack_floats, cfg, inverse, mode, sign, bad,
+                  counter, flags, _stream())
+    _range_safe_launches("vcnf_rqs_stack_fused_f32", dev, b, precision, layers, layers_f32, launch)
     return y, logdet
 
 
@@ -834,16 +826,12 @@ def affine_coupling(z, param, t_off, d_t, scale_map, inverse, logdet=None, sign=
     b, c = z.shape[0], z.shape[1]
     inner = int(z[0, 0].numel()) if z.dim() > 2 else 1
     out = torch.empty_like(z)
-    mode = LD_ACCUM
-    if logdet is None:
+    if logdet is None and scale_map == SCALE_NONE:      # a pure shift: no log-det tensor at all
         mode = LD_STORE
-        if scale_map != SCALE_NONE:
-            logdet = torch.empty(b, dtype=z.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_affine_coupling" + _sfx(z))(
-            _ptr(z), _ptr(param), _ptr(out), _ptr(logdet), b, c, inner,
-            int(t_off), int(d_t), int(scale_map), int(bool(inverse)), mode, float(sign), _stream())
-    _check(st, "vcnf_affine_coupling" + _sfx(z))
+    else:
+        logdet, mode = _ld_out(logdet, b, z.dtype, dev)
+    _call("vcnf_affine_coupling" + _sfx(z), dev, z, param, out, logdet, b, c, inner, int(t_off), int(d_t),
+          int(scale_map), bool(inverse), mode, sign)
     return out, logdet
 
 
@@ -860,12 +848,9 @@ def rqs_final_fused(x, h, out, tf_idx, d_t, hidden, wpack, cfg, inverse, partial
         partial = torch.empty(rows, b, dtype=torch.float32, device=dev)
     elif partial.shape[0] < rows or partial.shape[1] != b or not partial.is_contiguous():
         raise VcnfError("partial log-det buffer %s too small for %d rows of %d" % (tuple(partial.shape), rows, b))
-    with torch.cuda.device(dev), _timed("rqs_final_fused"):
-        fn = lib().vcnf_rqs_final_fused_presplit_f32 if presplit else lib().vcnf_rqs_final_fused_f32
-        st = fn(_ptr(x), _ptr(h), _ptr(out), _ptr(partial), b, d, _ptr(tf_idx), int(d_t), int(hidden), _ptr(wpack),
-                wpack.numel(), ctypes.byref(cfg), int(bool(inverse)),
-                _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-    _check(st, "vcnf_rqs_final_fused_f32")
+    _call("vcnf_rqs_final_fused_presplit_f32" if presplit else "vcnf_rqs_final_fused_f32", dev, x, h, out, partial, b, d,
+          tf_idx, int(d_t), int(hidden), wpack, wpack.numel(), cfg, bool(inverse), _bad_if(inverse, dev),
+          tag="rqs_final_fused")
     return partial
 
 
@@ -890,15 +875,9 @@ def rqs_identity_half(x, out, id_idx, d_id, shared, cfg, inverse, partial=None, 
             raise VcnfError("rqs_identity_half needs a [rows, B] partial log-det buffer")
     else:
         sw = sh = sd = None
-    with torch.cuda.device(dev), _timed("rqs_identity_half"):
-        st = lib().vcnf_rqs_identity_half_f32(
-            _ptr(x), _ptr(out), _ptr(cond_in) if cond_in is not None else None,
-            _ptr(partial) if partial is not None else None, b, d, _ptr(id_idx), int(d_id),
-            _ptr(sw) if sw is not None else None, _ptr(sh) if sh is not None else None,
-            _ptr(sd) if sd is not None and sd.numel() else None,
-            ctypes.byref(cfg) if cfg is not None else None, int(bool(inverse)), int(bool(inverse)),
-            _ptr(bad_discriminant_counter(dev)) if inverse else None, _stream())
-    _check(st, "vcnf_rqs_identity_half_f32")
+    _call("vcnf_rqs_identity_half_f32", dev, x, out, cond_in, partial, b, d, id_idx, int(d_id), sw, sh,
+          sd if sd is not None and sd.numel() else None, cfg, bool(inverse), bool(inverse), _bad_if(inverse, dev),
+          tag="rqs_identity_half")
     return cond_in
 
 
@@ -908,15 +887,22 @@ def resnet_trunk(x, wpack, hidden, num_blocks, split=False):
     x = x.contiguous()
     b, d_in = x.shape
     h = torch.empty(b, hidden, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed("resnet_trunk"):
-        if split:       # h: per row 128 fp16 hi halves | 128 fp16 lo halves, for rqs_final_fused(..., presplit=True)
-            st = lib().vcnf_resnet_trunk_split_f32(_ptr(x), _ptr(h), b, int(d_in), int(hidden), int(num_blocks), _ptr(wpack),
-                                                   wpack.numel(), _ptr(saturation_counter(dev)), _stream())
-        else:
-            st = lib().vcnf_resnet_trunk_f32(_ptr(x), _ptr(h), b, int(d_in), int(hidden), int(num_blocks), _ptr(wpack),
-                                             wpack.numel(), _stream())
-    _check(st, "vcnf_resnet_trunk_f32")
+    args = (x, h, b, d_in, int(hidden), int(num_blocks), wpack, wpack.numel())
+    if split:       # h: per row 128 fp16 hi halves | 128 fp16 lo halves, for rqs_final_fused(..., presplit=True)
+        _call("vcnf_resnet_trunk_split_f32", dev, *args, saturation_counter(dev), tag="resnet_trunk")
+    else:
+        _call("vcnf_resnet_trunk_f32", dev, *args, tag="resnet_trunk")
     return h
+
+
+def _affine_ld_out(logdet, b, scale_map, dev):
+    """(logdet to return, logdet argument, ld_mode) of the fused affine wrappers: without a scale (a pure shift) the
+    kernels take no log-det pointer, and a fresh log-det is zero."""
+    if scale_map == SCALE_NONE:
+        return (torch.zeros(b, dtype=torch.float32, device=dev) if logdet is None else logdet), None, \
+            (LD_STORE if logdet is None else LD_ACCUM)
+    logdet, mode = _ld_out(logdet, b, torch.float32, dev)
+    return logdet, logdet, mode
 
 
 def affine_layer_fused(z, wpack, cond_off, c_in, t_off, d_t, hidden, slope, scale_map, inverse, logdet=None,
@@ -926,17 +912,10 @@ def affine_layer_fused(z, wpack, cond_off, c_in, t_off, d_t, hidden, slope, scal
     z = z.contiguous()
     b, d = z.shape
     out = torch.empty_like(z)
-    mode = LD_ACCUM
-    if logdet is None:
-        mode = LD_STORE
-        logdet = (torch.empty if scale_map != SCALE_NONE else torch.zeros)(b, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = lib().vcnf_affine_layer_fused_f32(_ptr(z), _ptr(out), _ptr(logdet) if scale_map != SCALE_NONE else None,
-                                               b, d, int(cond_off), int(c_in), int(t_off), int(d_t), int(hidden),
-                                               float(slope), int(scale_map), _ptr(wpack), wpack.numel(),
-                                               _ptr(in_gather), _ptr(out_gather),
-                                               int(bool(inverse)), mode, float(sign), _stream())
-    _check(st, "vcnf_affine_layer_fused_f32")
+    logdet, ld_arg, mode = _affine_ld_out(logdet, b, scale_map, dev)
+    _call("vcnf_affine_layer_fused_f32", dev, z, out, ld_arg, b, d, int(cond_off), int(c_in), int(t_off), int(d_t),
+          int(hidden), float(slope), int(scale_map), wpack, wpack.numel(), in_gather, out_gather, bool(inverse), mode,
+          sign)
     return out, logdet
 
 
@@ -956,27 +935,16 @@ def affine_stack_fused(z, wpack, layers, gather_after, gathers, c_in, hidden, sl
     z = z.contiguous()
     b, d = z.shape
     out = torch.empty_like(z)
-    mode = LD_ACCUM
-    if logdet is None:
-        mode = LD_STORE
-        logdet = (torch.empty if scale_map != SCALE_NONE else torch.zeros)(b, dtype=torch.float32, device=dev)
+    logdet, ld_arg, mode = _affine_ld_out(logdet, b, scale_map, dev)
     arr = (AffineStackLayer * len(layers))(*[AffineStackLayer(*map(int, l)) for l in layers])
-    with torch.cuda.device(dev), _timed("affine_stack_fused"):
-        if wpack_h3 is not None:
-            st = lib().vcnf_affine_stack_fused_f16x3_f32(
-                _ptr(z), _ptr(out), _ptr(logdet) if scale_map != SCALE_NONE else None,
-                b, d, len(layers), ctypes.cast(arr, ctypes.c_void_p), int(gather_after),
-                int(c_in), int(hidden), float(slope), int(scale_map), _ptr(wpack), wpack.numel(),
-                _ptr(wpack_h3), wpack_h3.numel(), _ptr(gathers), 0 if gathers is None else int(gathers.shape[0]),
-                int(bool(inverse)), mode, float(sign), _ptr(range_redo_counter(dev)), _stream())
-        else:
-            st = lib().vcnf_affine_stack_fused_f32(_ptr(z), _ptr(out), _ptr(logdet) if scale_map != SCALE_NONE else None,
-                                                   b, d, len(layers), ctypes.cast(arr, ctypes.c_void_p), int(gather_after),
-                                                   int(c_in), int(hidden), float(slope), int(scale_map),
-                                                   _ptr(wpack), wpack.numel(), _ptr(gathers),
-                                                   0 if gathers is None else int(gathers.shape[0]),
-                                                   int(bool(inverse)), mode, float(sign), _stream())
-    _check(st, "vcnf_affine_stack_fused_f32")
+    head = (z, out, ld_arg, b, d, len(layers), ctypes.cast(arr, ctypes.c_void_p), int(gather_after), int(c_in),
+            int(hidden), float(slope), int(scale_map), wpack, wpack.numel())
+    tail = (gathers, 0 if gathers is None else int(gathers.shape[0]), bool(inverse), mode, sign)
+    if wpack_h3 is not None:
+        _call("vcnf_affine_stack_fused_f16x3_f32", dev, *head, wpack_h3, wpack_h3.numel(), *tail,
+              range_redo_counter(dev), tag="affine_stack_fused")
+    else:
+        _call("vcnf_affine_stack_fused_f32", dev, *head, *tail, tag="affine_stack_fused")
     return out, logdet
 
 
@@ -989,14 +957,8 @@ def masked_affine(z, s, t, bmask, inverse, logdet=None, sign=1.0):
     t = t.contiguous() if t is not None else None
     b, d = z.shape
     out = torch.empty_like(z)
-    mode = LD_ACCUM
-    if logdet is None:
-        logdet = torch.empty(b, dtype=z.dtype, device=dev)
-        mode = LD_STORE
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_masked_affine" + _sfx(z))(_ptr(z), _ptr(s), _ptr(t), _ptr(bmask), _ptr(out), _ptr(logdet),
-                                                            b, d, int(bool(inverse)), mode, float(sign), _stream())
-    _check(st, "vcnf_masked_affine" + _sfx(z))
+    logdet, mode = _ld_out(logdet, b, z.dtype, dev)
+    _call("vcnf_masked_affine" + _sfx(z), dev, z, s, t, bmask, out, logdet, b, d, bool(inverse), mode, sign)
     return out, logdet
 
 
@@ -1012,10 +974,7 @@ def maf_affine(x, params, inverse):
         raise VcnfError("maf_affine: params %s do not match inputs %s" % (tuple(params.shape), tuple(x.shape)))
     out = torch.empty_like(x)
     ld = torch.empty(b, dtype=x.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_maf_affine" + _sfx(x))(_ptr(x), _ptr(params), _ptr(out), _ptr(ld), b, d,
-                                                          int(bool(inverse)), LD_STORE, 1.0, _stream())
-    _check(st, "vcnf_maf_affine" + _sfx(x))
+    _call("vcnf_maf_affine" + _sfx(x), dev, x, params, out, ld, b, d, bool(inverse), LD_STORE, 1.0)
     return out, ld
 
 
@@ -1027,10 +986,7 @@ def affine_const(z, s, t, inverse):
     b, c = z.shape[0], z.shape[1]
     inner = int(z[0, 0].numel()) if z.dim() > 2 else 1
     out = torch.empty_like(z)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_affine_const" + _sfx(z))(_ptr(z), _ptr(s), _ptr(t), _ptr(out), b, c, inner,
-                                                           int(bool(inverse)), _stream())
-    _check(st, "vcnf_affine_const" + _sfx(z))
+    _call("vcnf_affine_const" + _sfx(z), dev, z, s, t, out, b, c, inner, bool(inverse))
     return out
 
 
@@ -1042,12 +998,9 @@ def conv1x1_fused(x, wpack, c_out, in_bias=None, out_bias=None, in_slope=None, o
     b, c_in = x.shape[0], x.shape[1]
     inner = int(x[0, 0].numel())
     out = torch.empty((b, c_out) + tuple(x.shape[2:]), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed("conv1x1_fused"):
-        st = lib().vcnf_conv1x1_f16x3_f32(_ptr(x), _ptr(out), _ptr(wpack), wpack.numel(), _ptr(in_bias), _ptr(out_bias),
-                                          b, int(c_in), int(c_out), inner, int(in_slope is not None),
-                                          float(in_slope or 0.0), int(out_slope is not None), float(out_slope or 0.0),
-                                          _ptr(saturation_counter(dev)), _stream())
-    _check(st, "vcnf_conv1x1_f16x3_f32")
+    _call("vcnf_conv1x1_f16x3_f32", dev, x, out, wpack, wpack.numel(), in_bias, out_bias, b, c_in, int(c_out), inner,
+          in_slope is not None, float(in_slope or 0.0), out_slope is not None, float(out_slope or 0.0),
+          saturation_counter(dev), tag="conv1x1_fused")
     return out
 
 
@@ -1058,14 +1011,8 @@ def masked_affine_stack(z, table, n_layers, inverse, logdet=None, sign=1.0):
     z = z.contiguous()
     b, d = z.shape
     out = torch.empty_like(z)
-    mode = LD_ACCUM
-    if logdet is None:
-        logdet = torch.empty(b, dtype=z.dtype, device=dev)
-        mode = LD_STORE
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_masked_affine_stack" + _sfx(z))(_ptr(z), _ptr(out), _ptr(logdet), _ptr(table), b, int(d),
-                                                                  int(n_layers), int(bool(inverse)), mode, float(sign), _stream())
-    _check(st, "vcnf_masked_affine_stack" + _sfx(z))
+    logdet, mode = _ld_out(logdet, b, z.dtype, dev)
+    _call("vcnf_masked_affine_stack" + _sfx(z), dev, z, out, logdet, table, b, d, int(n_layers), bool(inverse), mode, sign)
     return out, logdet
 
 
@@ -1078,11 +1025,8 @@ def masked_affine_stack_bwd(z_out, g_out, g_ld, table, goff, n_layers, n_grad, i
     b, d = z_out.shape
     g_in = torch.empty_like(z_out)
     grads = torch.zeros(n_grad, dtype=z_out.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_masked_affine_stack_bwd" + _sfx(z_out))(
-            _ptr(z_out), _ptr(g_out), _ptr(g_ld), _ptr(g_in), _ptr(grads), _ptr(table), _ptr(goff), b, int(d), int(n_layers),
-            int(bool(inverse)), _stream())
-    _check(st, "vcnf_masked_affine_stack_bwd" + _sfx(z_out))
+    _call("vcnf_masked_affine_stack_bwd" + _sfx(z_out), dev, z_out, g_out, g_ld, g_in, grads, table, goff, b, d,
+          int(n_layers), bool(inverse))
     return g_in, grads
 
 
@@ -1104,15 +1048,14 @@ def linear_f16x3(x, weight, bias=None, input_grad=False, relu_in=False, relu_out
         n, ldn, ldk = n_out, n_in, 1
         assert k == n_in
     y = torch.empty(b, n, dtype=torch.float32, device=dev)
+    if bias is not None:
+        bias = bias.detach().contiguous()
     if mask is not None:
         mask = mask.detach().contiguous()
     if addend is not None:
         addend = addend.detach().contiguous()
-    with torch.cuda.device(dev), _timed("linear_f16x3"):
-        st = lib().vcnf_linear_f16x3_f32(_ptr(x), _ptr(weight), _ptr(bias.detach().contiguous() if bias is not None else None),
-                                         _ptr(y), b, int(k), int(n), int(ldn), int(ldk), int(bool(relu_in)), int(bool(relu_out)),
-                                         _ptr(mask), _ptr(addend), _ptr(saturation_counter(dev)), _stream())
-    _check(st, "vcnf_linear_f16x3_f32")
+    _call("vcnf_linear_f16x3_f32", dev, x, weight, bias, y, b, k, n, ldn, ldk, bool(relu_in), bool(relu_out), mask,
+          addend, saturation_counter(dev), tag="linear_f16x3")
     return y
 
 
@@ -1142,14 +1085,11 @@ def linear_wgrad(x, dy, want_bias=True, f16x3=False, relu_x=False):
         _WGRAD_WS[key] = ws
     dw = torch.empty(n_out, n_in, dtype=torch.float32, device=dev)
     db = torch.empty(n_out, dtype=torch.float32, device=dev) if want_bias else None
-    with torch.cuda.device(dev), _timed("linear_wgrad"):
-        if f16x3:
-            st = lib().vcnf_linear_wgrad_f16x3_f32(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), b, int(n_in),
-                                                   int(n_out), 0, int(bool(relu_x)), _ptr(saturation_counter(dev)), _stream())
-        else:
-            st = lib().vcnf_linear_wgrad_f32(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), b, int(n_in),
-                                             int(n_out), 0, _stream())
-    _check(st, "vcnf_linear_wgrad_f32")
+    args = (x, dy, dw, db, ws, ws.numel(), b, n_in, n_out, 0)
+    if f16x3:
+        _call("vcnf_linear_wgrad_f16x3_f32", dev, *args, bool(relu_x), saturation_counter(dev), tag="linear_wgrad")
+    else:
+        _call("vcnf_linear_wgrad_f32", dev, *args, tag="linear_wgrad")
     return dw, db
 
 
@@ -1160,11 +1100,8 @@ def conv3x3_1x1_fused(x, w1pack, w2pack, b1, b2, slope1, slope2):
     x = x.contiguous()
     b, c_in, h, w = x.shape
     out = torch.empty((b, 256, h, w), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed("conv3x3_1x1_fused"):
-        st = lib().vcnf_conv3x3_1x1_f16x3_f32(_ptr(x), _ptr(out), _ptr(w1pack), w1pack.numel(), _ptr(w2pack), w2pack.numel(),
-                                              _ptr(b1), _ptr(b2), b, int(c_in), int(h), int(w), float(slope1), float(slope2),
-                                              _ptr(saturation_counter(dev)), _stream())
-    _check(st, "vcnf_conv3x3_1x1_f16x3_f32")
+    _call("vcnf_conv3x3_1x1_f16x3_f32", dev, x, out, w1pack, w1pack.numel(), w2pack, w2pack.numel(), b1, b2, b, c_in, h, w,
+          float(slope1), float(slope2), saturation_counter(dev), tag="conv3x3_1x1_fused")
     return out
 
 
@@ -1176,15 +1113,14 @@ def convnet3_fused(x, w1pack, w2pack, w3pack, b1, b2, b3, c_out, slope1, slope2)
     b, c_in, h, w = x.shape
     z = torch.empty((b, 9 * c_out, h, w), dtype=torch.float32, device=dev)
     out = torch.empty((b, c_out, h, w), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev):        # two entry points under one device context: _call would enter it twice
         with _timed("convnet3_taps"):
-            st = lib().vcnf_convnet3_taps_f16x3_f32(_ptr(x), _ptr(z), _ptr(w1pack), w1pack.numel(), _ptr(w2pack), w2pack.numel(),
-                                                    _ptr(w3pack), w3pack.numel(), _ptr(b1), _ptr(b2), b, int(c_in), int(c_out),
-                                                    int(h), int(w), float(slope1), float(slope2),
-                                                    _ptr(saturation_counter(dev)), _stream())
+            st = _launch("vcnf_convnet3_taps_f16x3_f32", x, z, w1pack, w1pack.numel(), w2pack, w2pack.numel(), w3pack,
+                         w3pack.numel(), b1, b2, b, c_in, int(c_out), h, w, float(slope1), float(slope2),
+                         saturation_counter(dev))
         _check(st, "vcnf_convnet3_taps_f16x3_f32")
         with _timed("col2im3x3"):
-            st = lib().vcnf_col2im3x3_f32(_ptr(z), _ptr(b3), _ptr(out), b, int(c_out), int(h), int(w), _stream())
+            st = _launch("vcnf_col2im3x3_f32", z, b3, out, b, int(c_out), h, w)
     _check(st, "vcnf_col2im3x3_f32")
     return out
 
@@ -1196,10 +1132,7 @@ def resblock_op(op, a, b, c=None, two_outputs=False):
     c = c.detach().contiguous() if c is not None else None
     out0 = torch.empty_like(a)
     out1 = torch.empty_like(a) if two_outputs else None
-    with torch.cuda.device(dev):
-        st = lib().vcnf_resblock_elementwise_f32(int(op), _ptr(a), _ptr(b), _ptr(c), _ptr(out0), _ptr(out1), a.numel(),
-                                                 _stream())
-    _check(st, "vcnf_resblock_elementwise_f32")
+    _call("vcnf_resblock_elementwise_f32", dev, int(op), a, b, c, out0, out1, a.numel())
     return (out0, out1) if two_outputs else out0
 
 
@@ -1214,10 +1147,7 @@ def channel_mix(z, matrix, shift):
             tuple(matrix.shape), tuple(shift.shape), c))
     inner = int(z[0, 0].numel()) if z.dim() > 2 else 1
     out = torch.empty_like(z)
-    with torch.cuda.device(dev), _timed("channel_mix"):
-        st = lib().vcnf_channel_mix_f32(_ptr(z), _ptr(out), _ptr(matrix.contiguous()), _ptr(shift.contiguous()), b, c,
-                                        inner, _stream())
-    _check(st, "vcnf_channel_mix_f32")
+    _call("vcnf_channel_mix_f32", dev, z, out, matrix.contiguous(), shift.contiguous(), b, c, inner, tag="channel_mix")
     return out
 
 
@@ -1227,9 +1157,7 @@ def permute(z, idx32):
     b, c = z.shape[0], z.shape[1]
     inner = int(z[0, 0].numel()) if z.dim() > 2 else 1
     out = torch.empty_like(z)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_permute" + _sfx(z))(_ptr(z), _ptr(idx32), _ptr(out), b, c, inner, _stream())
-    _check(st, "vcnf_permute" + _sfx(z))
+    _call("vcnf_permute" + _sfx(z), dev, z, idx32, out, b, c, inner)
     return out
 
 
@@ -1242,9 +1170,7 @@ def split_columns(z, idx32, first):
         raise VcnfError("split_columns: index of %d entries / first part of %d columns for %d columns" % (idx32.numel(), first, c))
     pa = torch.empty(b, first, dtype=z.dtype, device=dev)
     pb = torch.empty(b, c - first, dtype=z.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_split_columns" + _sfx(z))(_ptr(z), _ptr(idx32), _ptr(pa), _ptr(pb), b, c, first, _stream())
-    _check(st, "vcnf_split_columns" + _sfx(z))
+    _call("vcnf_split_columns" + _sfx(z), dev, z, idx32, pa, pb, b, c, first)
     return pa, pb
 
 
@@ -1259,25 +1185,12 @@ def merge_columns(pa, pb, idx32):
     if idx32.numel() != c:
         raise VcnfError("merge_columns: index of %d entries for %d columns" % (idx32.numel(), c))
     out = torch.empty(b, c, dtype=pa.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_merge_columns" + _sfx(pa))(_ptr(pa), _ptr(pb), _ptr(idx32), _ptr(out), b, c, first, _stream())
-    _check(st, "vcnf_merge_columns" + _sfx(pa))
+    _call("vcnf_merge_columns" + _sfx(pa), dev, pa, pb, idx32, out, b, c, first)
     return out
 
 
 def _log_t(temperature):
     return 0.0 if temperature is None else math.log(temperature)
-
-
-def _logp_out(logp, b, like, dev, name):
-    """(logp, ld_mode) of a log_prob wrapper: a fresh [batch] tensor to store into, or the checked caller's tensor to
-    accumulate into."""
-    require_device(logp, f64=True)
-    if logp is None:
-        return torch.empty(b, dtype=like.dtype, device=dev), LD_STORE
-    if logp.dtype != like.dtype or not logp.is_contiguous() or tuple(logp.shape) != (b,):
-        raise VcnfError(name + ": logp must be a contiguous [batch] tensor of the input's dtype")
-    return logp, LD_ACCUM
 
 
 def _check_index(idx, b, what, contiguous=False):
@@ -1286,24 +1199,41 @@ def _check_index(idx, b, what, contiguous=False):
         raise VcnfError("%s must be %s int32 tensor [batch]" % (what, "a contiguous" if contiguous else "an"))
 
 
-def _block_sums(launch, what, outs, block, groups, reduce):
-    """Tail of the VJPs that sum over the batch.  ``launch`` (given the workspace pointer) writes one partial block of
-    shape ``block`` per workgroup; ``groups`` = (entry point that gives the number of workgroups, its arguments
-    (batch, ...)); ``reduce`` = (entry point that adds the blocks into the tensors ``outs`` in a fixed order, its size
-    arguments).  ``outs`` None: nobody wants the sums - one launch without a workspace, None."""
-    if outs is None:
-        _check(launch(None), what)
-        return None
-    (count, args), (red, dims) = groups, reduce
-    if args[0] == 0:
-        return tuple(t.zero_() for t in outs)
-    n = int(getattr(lib(), count)(*args))
-    if n < 1:
-        _check(2, what)
-    partials = torch.empty((n,) + tuple(block), dtype=outs[0].dtype, device=outs[0].device)
-    _check(launch(_ptr(partials)), what)
-    _check(getattr(lib(), red)(_ptr(partials), n, *dims, *map(_ptr, outs), _stream()), red)
-    return outs
+def _like_input(t, x2, what, name, of="the input"):
+    """Operand ``name`` of a base's entry point ``what`` that goes with the input rows ``x2`` [B, D] sample by sample
+    (a cotangent, a second draw): cast to the input's dtype, as contiguous [B, D] rows."""
+    if t.dim() < 1 or len(t) != len(x2) or t.numel() != x2.numel():
+        raise VcnfError("%s: %s does not have the shape of %s" % (what, name, of))
+    return t.to(x2.dtype).reshape(x2.shape).contiguous()
+
+
+def _batch_vector(t, b, dtype, what, name):
+    """Operand ``name`` of a base's entry point ``what`` with one value per sample: cast to ``dtype``, contiguous."""
+    if tuple(t.shape) != (b,):
+        raise VcnfError("%s: %s must be [batch]" % (what, name))
+    return t.to(dtype).contiguous()
+
+
+def _block_sums(dev, launch, what, outs, block, groups, reduce):
+    """Tail of the VJPs that sum over the batch, under one device context.  ``launch`` (given the workspace or None)
+    writes one partial block of shape ``block`` per workgroup and returns the status; ``groups`` = (entry point that
+    gives the number of workgroups, its arguments (batch, ...)); ``reduce`` = (entry point that adds the blocks into the
+    tensors ``outs`` in a fixed order, its size arguments).  ``outs`` None: nobody wants the sums - one launch without
+    a workspace, None."""
+    with torch.cuda.device(dev):
+        if outs is None:
+            _check(launch(None), what)
+            return None
+        (count, args), (red, dims) = groups, reduce
+        if args[0] == 0:
+            return tuple(t.zero_() for t in outs)
+        n = int(getattr(lib(), count)(*args))
+        if n < 1:
+            _check(2, what)
+        partials = torch.empty((n,) + tuple(block), dtype=outs[0].dtype, device=outs[0].device)
+        _check(launch(partials), what)
+        _check(_launch(red, partials, n, *dims, *outs), red)
+        return outs
 
 
 def diag_gaussian_log_prob(z, loc, log_scale, temperature=None, logp=None, sign=1.0):
@@ -1312,15 +1242,9 @@ def diag_gaussian_log_prob(z, loc, log_scale, temperature=None, logp=None, sign=
         raise VcnfError("diag_gaussian_log_prob: mixed dtypes")
     b = z.shape[0]
     z2 = z.reshape(b, -1).contiguous()
-    mode = LD_ACCUM
-    if logp is None:
-        logp = torch.empty(b, dtype=z.dtype, device=dev)
-        mode = LD_STORE
-    lt = _log_t(temperature)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_diag_gaussian_log_prob" + _sfx(z))(
-            _ptr(z2), _ptr(loc.contiguous()), _ptr(log_scale.contiguous()), lt, _ptr(logp), b, z2.shape[1], mode, float(sign), _stream())
-    _check(st, "vcnf_diag_gaussian_log_prob" + _sfx(z))
+    logp, mode = _ld_out(logp, b, z.dtype, dev)
+    _call("vcnf_diag_gaussian_log_prob" + _sfx(z), dev, z2, loc.contiguous(), log_scale.contiguous(),
+          _log_t(temperature), logp, b, z2.shape[1], mode, sign)
     return logp
 
 
@@ -1332,11 +1256,8 @@ def diag_gaussian_sample(eps, loc, log_scale, temperature=None):
     e2 = eps.reshape(b, -1).contiguous()
     z = torch.empty_like(e2)
     logp = torch.empty(b, dtype=eps.dtype, device=dev)
-    lt = _log_t(temperature)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), "vcnf_diag_gaussian_sample" + _sfx(eps))(
-            _ptr(e2), _ptr(loc.contiguous()), _ptr(log_scale.contiguous()), lt, _ptr(z), _ptr(logp), b, e2.shape[1], _stream())
-    _check(st, "vcnf_diag_gaussian_sample" + _sfx(eps))
+    _call("vcnf_diag_gaussian_sample" + _sfx(eps), dev, e2, loc.contiguous(), log_scale.contiguous(),
+          _log_t(temperature), z, logp, b, e2.shape[1])
     return z.view(eps.shape), logp
 
 
@@ -1365,11 +1286,9 @@ def cc_gaussian_log_prob(z, loc_rows, ls_rows, row_index, pixels, temperature=No
     the tables loc_rows / ls_rows [R, C]; ``logp``: accumulate into it."""
     name = "vcnf_cc_gaussian_log_prob" + _sfx(z)
     dev, z2, b, c, r = _cc_operands(z, loc_rows, ls_rows, row_index, pixels, name)
-    logp, mode = _logp_out(logp, b, z, dev, name)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z2), _ptr(loc_rows.contiguous()), _ptr(ls_rows.contiguous()), _ptr(row_index),
-                                  _log_t(temperature), _ptr(logp), b, c, pixels, r, mode, float(sign), _stream())
-    _check(st, name)
+    logp, mode = _ld_out(logp, b, z.dtype, dev, name)
+    _call(name, dev, z2, loc_rows.contiguous(), ls_rows.contiguous(), row_index, _log_t(temperature), logp, b, c, pixels,
+          r, mode, sign)
     return logp
 
 
@@ -1379,10 +1298,8 @@ def cc_gaussian_sample(eps, loc_rows, ls_rows, row_index, pixels, temperature=No
     dev, e2, b, c, r = _cc_operands(eps, loc_rows, ls_rows, row_index, pixels, name)
     z = torch.empty_like(e2)
     logp = torch.empty(b, dtype=eps.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(e2), _ptr(loc_rows.contiguous()), _ptr(ls_rows.contiguous()), _ptr(row_index),
-                                  _log_t(temperature), _ptr(z), _ptr(logp), b, c, pixels, r, _stream())
-    _check(st, name)
+    _call(name, dev, e2, loc_rows.contiguous(), ls_rows.contiguous(), row_index, _log_t(temperature), z, logp, b, c,
+          pixels, r)
     return z.view(eps.shape), logp
 
 
@@ -1394,11 +1311,8 @@ def cc_gaussian_log_prob_bwd(z, loc_rows, ls_rows, row_index, pixels, temperatur
     dz = torch.empty_like(z2)
     d_loc = torch.empty(b, c, dtype=z.dtype, device=dev)
     d_ls = torch.empty(b, c, dtype=z.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z2), _ptr(loc_rows.contiguous()), _ptr(ls_rows.contiguous()), _ptr(row_index),
-                                  _log_t(temperature), _ptr(g.to(z.dtype).contiguous()), _ptr(dz), _ptr(d_loc), _ptr(d_ls),
-                                  b, c, pixels, r, _stream())
-    _check(st, name)
+    _call(name, dev, z2, loc_rows.contiguous(), ls_rows.contiguous(), row_index, _log_t(temperature),
+          g.to(z.dtype).contiguous(), dz, d_loc, d_ls, b, c, pixels, r)
     return dz.view(z.shape), d_loc, d_ls
 
 
@@ -1414,11 +1328,8 @@ def cc_gaussian_sample_bwd(eps, ls_rows, row_index, pixels, temperature, g_z, g_
     d_eps = torch.empty_like(e2)
     d_loc = torch.empty(b, c, dtype=eps.dtype, device=dev)
     d_ls = torch.empty(b, c, dtype=eps.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(e2), _ptr(ls_rows.contiguous()), _ptr(row_index), _log_t(temperature), _ptr(gz2),
-                                  _ptr(g_logp.to(eps.dtype).contiguous()), _ptr(d_eps), _ptr(d_loc), _ptr(d_ls),
-                                  b, c, pixels, r, _stream())
-    _check(st, name)
+    _call(name, dev, e2, ls_rows.contiguous(), row_index, _log_t(temperature), gz2, g_logp.to(eps.dtype).contiguous(),
+          d_eps, d_loc, d_ls, b, c, pixels, r)
     return d_eps.view(eps.shape), d_loc, d_ls
 
 
@@ -1431,9 +1342,7 @@ def cc_gaussian_reduce_rows(per_sample, row_index, rows):
     b, c = per_sample.shape
     _check_index(row_index, b, name + ": row_index")
     out = torch.empty(rows, c, dtype=per_sample.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(per_sample), _ptr(row_index), _ptr(out), b, c, rows, _stream())
-    _check(st, name)
+    _call(name, dev, per_sample, row_index, out, b, c, rows)
     return out
 
 
@@ -1459,11 +1368,8 @@ def gmm_log_prob(z, loc, ls, log_w, logp=None, sign=1.0):
     log_w [M]; ``logp``: accumulate into it."""
     name = "vcnf_gmm_log_prob" + _sfx(z)
     dev, z2, loc, ls, log_w, b, d, m = _gmm_operands(z, loc, ls, log_w, name)
-    logp, mode = _logp_out(logp, b, z, dev, name)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(logp), b, d, m, mode, float(sign),
-                                  _stream())
-    _check(st, name)
+    logp, mode = _ld_out(logp, b, z.dtype, dev, name)
+    _call(name, dev, z2, loc, ls, log_w, logp, b, d, m, mode, sign)
     return logp
 
 
@@ -1475,10 +1381,7 @@ def gmm_sample(eps, mode, loc, ls, log_w):
     _check_index(mode, b, name + ": mode", contiguous=True)
     z = torch.empty_like(e2)
     logp = torch.empty(b, dtype=eps.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(e2), _ptr(mode), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(z), _ptr(logp), b, d, m,
-                                  _stream())
-    _check(st, name)
+    _call(name, dev, e2, mode, loc, ls, log_w, z, logp, b, d, m)
     return z, logp
 
 
@@ -1489,21 +1392,13 @@ def gmm_log_prob_bwd(z, loc, ls, log_w, lse, g, gz_in=None, tables=True):
     name = "vcnf_gmm_log_prob_bwd" + _sfx(z)
     dev, z2, loc, ls, log_w, b, d, m = _gmm_operands(z, loc, ls, log_w, name)
     require_device(lse, g, gz_in, f64=True)
-    lse, g = lse.to(z.dtype).contiguous(), g.to(z.dtype).contiguous()
-    if tuple(lse.shape) != (b,) or tuple(g.shape) != (b,):
-        raise VcnfError(name + ": lse and g must be [batch]")
+    lse, g = _batch_vector(lse, b, z.dtype, name, "lse"), _batch_vector(g, b, z.dtype, name, "g")
     if gz_in is not None:
-        gz_in = gz_in.to(z.dtype).contiguous()
-        if gz_in.shape != z2.shape:
-            raise VcnfError(name + ": gz_in does not have the shape of z")
+        gz_in = _like_input(gz_in, z2, name, "gz_in", "z")
     dz = torch.empty_like(z2)
     outs = (torch.empty_like(loc), torch.empty_like(ls), torch.empty_like(log_w)) if tables else None
-    with torch.cuda.device(dev):
-        fn = getattr(lib(), name)
-        launch = lambda ws: fn(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(log_w), _ptr(lse), _ptr(g), _ptr(gz_in), _ptr(dz), ws,
-                               b, d, m, _stream())
-        sums = _block_sums(launch, name, outs, (m, 2 * d + 1), ("vcnf_gmm_bwd_groups", (b, d, m)),
-                           ("vcnf_gmm_reduce_partials" + _sfx(z), (m, d)))
+    sums = _block_sums(dev, lambda ws: _launch(name, z2, loc, ls, log_w, lse, g, gz_in, dz, ws, b, d, m), name, outs,
+                       (m, 2 * d + 1), ("vcnf_gmm_bwd_groups", (b, d, m)), ("vcnf_gmm_reduce_partials" + _sfx(z), (m, d)))
     return (dz,) + (sums or (None, None, None))
 
 
@@ -1525,23 +1420,13 @@ def _tail_operands(x, rows, what):
     return dev, x.reshape(b, d).contiguous(), [u.reshape(-1).contiguous() for u in rows], b, d
 
 
-def _tail_like(t, x2, dtype, what, name):
-    t = t.to(dtype).reshape(len(x2), -1).contiguous()
-    if t.shape != x2.shape:
-        raise VcnfError("%s: %s does not have the shape of the input" % (what, name))
-    return t
-
-
 def tail_log_prob(z, loc, ls, shape, cst, family, logp=None, sign=1.0):
     """vcnf_tail_log_prob_*: log density [B] of z [B, ...] under the product of Student-t (family 0) or generalised
     Gaussian (1) factors with the rows loc / ls / shape / cst [D]; ``logp``: accumulate into it."""
     name = "vcnf_tail_log_prob" + _sfx(z)
     dev, z2, (loc, ls, shape, cst), b, d = _tail_operands(z, (loc, ls, shape, cst), name)
-    logp, mode = _logp_out(logp, b, z, dev, name)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(cst), _ptr(logp), b, d, int(family), mode,
-                                  float(sign), _stream())
-    _check(st, name)
+    logp, mode = _ld_out(logp, b, z.dtype, dev, name)
+    _call(name, dev, z2, loc, ls, shape, cst, logp, b, d, int(family), mode, sign)
     return logp
 
 
@@ -1552,20 +1437,17 @@ def tail_sample(eps, gamma, loc, ls, shape, cst, family):
     require_device(gamma, f64=True)
     if gamma.dtype != eps.dtype:
         raise VcnfError(name + ": mixed dtypes")
-    g2 = _tail_like(gamma, e2, eps.dtype, name, "gamma")
+    g2 = _like_input(gamma, e2, name, "gamma")
     z = torch.empty_like(e2)
     logp = torch.empty(b, dtype=eps.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(e2), _ptr(g2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(cst), _ptr(z), _ptr(logp), b, d,
-                                  int(family), _stream())
-    _check(st, name)
+    _call(name, dev, e2, g2, loc, ls, shape, cst, z, logp, b, d, int(family))
     return z.view(eps.shape), logp
 
 
-def _tail_row_sums(launch, what, like, b, d, rows):
+def _tail_row_sums(dev, launch, what, like, b, d, rows):
     """``launch`` and, with ``rows``, vcnf_tail_reduce_partials_*: (d_loc, d_log_scale, d_shape) [D], or three None."""
     outs = tuple(torch.empty(3, d, dtype=like.dtype, device=like.device)) if rows else None
-    return _block_sums(launch, what, outs, (3, d), ("vcnf_tail_bwd_groups", (b, d)),
+    return _block_sums(dev, launch, what, outs, (3, d), ("vcnf_tail_bwd_groups", (b, d)),
                        ("vcnf_tail_reduce_partials" + _sfx(like), (d,))) or (None, None, None)
 
 
@@ -1576,17 +1458,13 @@ def tail_log_prob_bwd(z, loc, ls, shape, family, g, gz_in=None, rows=True):
     name = "vcnf_tail_log_prob_bwd" + _sfx(z)
     dev, z2, (loc, ls, shape), b, d = _tail_operands(z, (loc, ls, shape), name)
     require_device(g, gz_in, f64=True)
-    g = g.to(z.dtype).contiguous()
-    if tuple(g.shape) != (b,):
-        raise VcnfError(name + ": g must be [batch]")
+    g = _batch_vector(g, b, z.dtype, name, "g")
     if gz_in is not None:
-        gz_in = _tail_like(gz_in, z2, z.dtype, name, "gz_in")
+        gz_in = _like_input(gz_in, z2, name, "gz_in")
     dz = torch.empty_like(z2)
-    with torch.cuda.device(dev):
-        fn = getattr(lib(), name)
-        launch = lambda ws: fn(_ptr(z2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(g), _ptr(gz_in), _ptr(dz), ws, b, d,
-                               int(family), _stream())
-        sums = _tail_row_sums(launch, name, z2, b, d, rows)
+    family = int(family)
+    sums = _tail_row_sums(dev, lambda ws: _launch(name, z2, loc, ls, shape, g, gz_in, dz, ws, b, d, family), name, z2,
+                          b, d, rows)
     return (dz.view(z.shape),) + sums
 
 
@@ -1596,20 +1474,16 @@ def tail_sample_bwd(eps, gamma, loc, ls, shape, family, g_z=None, g_lp=None, row
     name = "vcnf_tail_sample_bwd" + _sfx(eps)
     dev, e2, (loc, ls, shape), b, d = _tail_operands(eps, (loc, ls, shape), name)
     require_device(gamma, g_z, g_lp, f64=True)
-    g2 = _tail_like(gamma, e2, eps.dtype, name, "gamma")
+    g2 = _like_input(gamma, e2, name, "gamma")
     if g_z is not None:
-        g_z = _tail_like(g_z, e2, eps.dtype, name, "g_z")
+        g_z = _like_input(g_z, e2, name, "g_z")
     if g_lp is not None:
-        g_lp = g_lp.to(eps.dtype).contiguous()
-        if tuple(g_lp.shape) != (b,):
-            raise VcnfError(name + ": g_lp must be [batch]")
+        g_lp = _batch_vector(g_lp, b, eps.dtype, name, "g_lp")
     d_eps = torch.empty_like(e2) if want_eps else None
     d_gamma = torch.empty_like(e2)
-    with torch.cuda.device(dev):
-        fn = getattr(lib(), name)
-        launch = lambda ws: fn(_ptr(e2), _ptr(g2), _ptr(loc), _ptr(ls), _ptr(shape), _ptr(g_z), _ptr(g_lp), _ptr(d_eps),
-                               _ptr(d_gamma), ws, b, d, int(family), _stream())
-        sums = _tail_row_sums(launch, name, e2, b, d, rows)
+    family = int(family)
+    sums = _tail_row_sums(dev, lambda ws: _launch(name, e2, g2, loc, ls, shape, g_z, g_lp, d_eps, d_gamma, ws, b, d,
+                                                  family), name, e2, b, d, rows)
     return (d_eps.view(eps.shape) if want_eps else None, d_gamma.view(eps.shape)) + sums
 
 
@@ -1632,24 +1506,14 @@ def _mvn_operands(x, loc, tri, consts, what):
             consts.contiguous(), x.shape[0], d)
 
 
-def _mvn_vector(t, b, dtype, what, name):
-    t = t.to(dtype).contiguous()
-    if tuple(t.shape) != (b,):
-        raise VcnfError("%s: %s must be [batch]" % (what, name))
-    return t
-
-
 def mvn_log_prob(z, loc, tri_inv, consts, family, logp=None, sign=1.0):
     """vcnf_mvn_log_prob_*: log density [B] of z [B, D] under the multivariate Gaussian (family 0) or Student-t (1) with
     location loc [D], inverse scale factor tri_inv [D, D] (lower triangle) and consts = (cst, nu); ``logp``: accumulate
     into it."""
     name = "vcnf_mvn_log_prob" + _sfx(z)
     dev, z2, loc, tri_inv, consts, b, d = _mvn_operands(z, loc, tri_inv, consts, name)
-    logp, mode = _logp_out(logp, b, z, dev, name)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z2), _ptr(loc), _ptr(tri_inv), _ptr(consts), _ptr(logp), b, d, int(family), mode,
-                                  float(sign), _stream())
-    _check(st, name)
+    logp, mode = _ld_out(logp, b, z.dtype, dev, name)
+    _call(name, dev, z2, loc, tri_inv, consts, logp, b, d, int(family), mode, sign)
     return logp
 
 
@@ -1660,23 +1524,20 @@ def mvn_sample(eps, gamma, loc, tri, consts, family):
     dev, e2, loc, tri, consts, b, d = _mvn_operands(eps, loc, tri, consts, name)
     require_device(gamma, f64=True)
     if gamma is not None:
-        gamma = _mvn_vector(gamma, b, eps.dtype, name, "gamma")
+        gamma = _batch_vector(gamma, b, eps.dtype, name, "gamma")
     z = torch.empty_like(e2)
     logp = torch.empty(b, dtype=eps.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(e2), _ptr(gamma), _ptr(loc), _ptr(tri), _ptr(consts), _ptr(z), _ptr(logp), b, d,
-                                  int(family), _stream())
-    _check(st, name)
+    _call(name, dev, e2, gamma, loc, tri, consts, z, logp, b, d, int(family))
     return z, logp
 
 
-def _mvn_block_sums(launch, what, like, b, d, sums):
+def _mvn_block_sums(dev, launch, what, like, b, d, sums):
     """``launch`` and, with ``sums``, vcnf_mvn_reduce_partials_*: (d_loc [D], d_tri [D, D], d_nu [1]), or three None."""
     outs = None
     if sums:
         outs = (torch.empty(d, dtype=like.dtype, device=like.device), torch.empty(d, d, dtype=like.dtype, device=like.device),
                 torch.empty(1, dtype=like.dtype, device=like.device))
-    return _block_sums(launch, what, outs, (d * d + d + 1,), ("vcnf_mvn_bwd_groups", (b, d)),
+    return _block_sums(dev, launch, what, outs, (d * d + d + 1,), ("vcnf_mvn_bwd_groups", (b, d)),
                        ("vcnf_mvn_reduce_partials" + _sfx(like), (d,))) or (None, None, None)
 
 
@@ -1688,17 +1549,13 @@ def mvn_log_prob_bwd(z, loc, tri_inv, consts, family, g, gz_in=None, sums=True):
     name = "vcnf_mvn_log_prob_bwd" + _sfx(z)
     dev, z2, loc, tri_inv, consts, b, d = _mvn_operands(z, loc, tri_inv, consts, name)
     require_device(g, gz_in, f64=True)
-    g = _mvn_vector(g, b, z.dtype, name, "g")
+    g = _batch_vector(g, b, z.dtype, name, "g")
     if gz_in is not None:
-        gz_in = gz_in.to(z.dtype).contiguous()
-        if gz_in.shape != z2.shape:
-            raise VcnfError(name + ": gz_in does not have the shape of z")
+        gz_in = _like_input(gz_in, z2, name, "gz_in", "z")
     dz = torch.empty_like(z2)
-    with torch.cuda.device(dev):
-        fn = getattr(lib(), name)
-        launch = lambda ws: fn(_ptr(z2), _ptr(loc), _ptr(tri_inv), _ptr(consts), _ptr(g), _ptr(gz_in), _ptr(dz), ws, b, d,
-                               int(family), _stream())
-        out = _mvn_block_sums(launch, name, z2, b, d, sums)
+    family = int(family)
+    out = _mvn_block_sums(dev, lambda ws: _launch(name, z2, loc, tri_inv, consts, g, gz_in, dz, ws, b, d, family), name,
+                          z2, b, d, sums)
     return (dz,) + out
 
 
@@ -1709,20 +1566,16 @@ def mvn_sample_bwd(eps, gamma, tri, consts, family, g_z=None, g_lp=None, sums=Tr
     dev, e2, _, tri, consts, b, d = _mvn_operands(eps, None, tri, consts, name)
     require_device(gamma, g_z, g_lp, f64=True)
     if gamma is not None:
-        gamma = _mvn_vector(gamma, b, eps.dtype, name, "gamma")
+        gamma = _batch_vector(gamma, b, eps.dtype, name, "gamma")
     if g_z is not None:
-        g_z = g_z.to(eps.dtype).contiguous()
-        if g_z.shape != e2.shape:
-            raise VcnfError(name + ": g_z does not have the shape of eps")
+        g_z = _like_input(g_z, e2, name, "g_z", "eps")
     if g_lp is not None:
-        g_lp = _mvn_vector(g_lp, b, eps.dtype, name, "g_lp")
+        g_lp = _batch_vector(g_lp, b, eps.dtype, name, "g_lp")
     d_eps = torch.empty_like(e2) if want_eps else None
     d_gamma = torch.empty(b, dtype=eps.dtype, device=dev) if gamma is not None else None
-    with torch.cuda.device(dev):
-        fn = getattr(lib(), name)
-        launch = lambda ws: fn(_ptr(e2), _ptr(gamma), _ptr(tri), _ptr(consts), _ptr(g_z), _ptr(g_lp), _ptr(d_eps),
-                               _ptr(d_gamma), ws, b, d, int(family), _stream())
-        out = _mvn_block_sums(launch, name, e2, b, d, sums)
+    family = int(family)
+    out = _mvn_block_sums(dev, lambda ws: _launch(name, e2, gamma, tri, consts, g_z, g_lp, d_eps, d_gamma, ws, b, d,
+                                                  family), name, e2, b, d, sums)
     return (d_eps, d_gamma) + out
 
 
@@ -1759,17 +1612,14 @@ def planar_radial_stack(z, kinds, va, vb, sc, inverse=False, logdet=None, sign=1
     the trace [K, B] and the row checkpoints [(K - 1) / C, B, D] (None when there is none)."""
     name = "vcnf_planar_radial_stack" + _sfx(z)
     dev, z, va, vb, sc, b, d, k = _planar_radial_operands(z.detach(), kinds, va.detach(), vb.detach(), sc.detach(), name)
-    logdet, mode = _logp_out(logdet, b, z, dev, name)
+    logdet, mode = _ld_out(logdet, b, z.dtype, dev, name)
     out = torch.empty_like(z)
     trace = ckpt = None
     if want_trace:
         trace = torch.empty((k, b), dtype=z.dtype, device=dev)
         n_ck = (k - 1) // max(1, int(lib().vcnf_planar_radial_checkpoint_every(d)))
         ckpt = torch.empty((n_ck, b, d), dtype=z.dtype, device=dev) if n_ck else None
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z), _ptr(out), _ptr(logdet), _ptr(trace), _ptr(ckpt), kinds[0], _ptr(kinds[1]), _ptr(va),
-                                  _ptr(vb), _ptr(sc), b, d, k, int(bool(inverse)), mode, float(sign), _stream())
-    _check(st, name)
+    _call(name, dev, z, out, logdet, trace, ckpt, kinds[0], kinds[1], va, vb, sc, b, d, k, bool(inverse), mode, sign)
     return (out, logdet, trace, ckpt) if want_trace else (out, logdet)
 
 
@@ -1802,11 +1652,7 @@ def planar_radial_stack_bwd(z_out, trace, ckpt, kinds, va, vb, sc, g_out=None, g
     if groups < 1:
         _check(2, name)
     work = torch.empty((groups, k, 2 * d + 2), dtype=z_out.dtype, device=dev)
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z_out), _ptr(trace), _ptr(ckpt), _ptr(g_out), _ptr(g_ld), kinds[0], _ptr(kinds[1]), _ptr(va),
-                                  _ptr(vb), _ptr(sc), _ptr(g_in), _ptr(g_va), _ptr(g_vb), _ptr(g_sc), _ptr(work), b, d, k,
-                                  _stream())
-    _check(st, name)
+    _call(name, dev, z_out, trace, ckpt, g_out, g_ld, kinds[0], kinds[1], va, vb, sc, g_in, g_va, g_vb, g_sc, work, b, d, k)
     return g_in, g_va, g_vb, g_sc
 
 
@@ -1836,9 +1682,7 @@ def target_log_prob(z, family, table=None, scale=0.0, want_score=False):
     b = len(z)
     logp = torch.empty(b, dtype=z.dtype, device=dev)
     score = torch.empty_like(z) if want_score else None
-    with torch.cuda.device(dev):
-        st = getattr(lib(), name)(_ptr(z), _ptr(table), _ptr(logp), _ptr(score), b, n, int(family), float(scale), _stream())
-    _check(st, name)
+    _call(name, dev, z, table, logp, score, b, n, int(family), float(scale))
     return logp, score
 
 
@@ -1855,7 +1699,6 @@ def linear_probe(x, weight, bias, mode, relu_input=False):
     if weight.shape[1] != k or (bias is not None and bias.shape != (n,)):
         raise VcnfError("linear_probe: shapes %s %s" % (tuple(x.shape), tuple(weight.shape)))
     y = torch.empty(b, n, device=dev, dtype=torch.float32)
-    _check(lib().vcnf_linear_probe_f32(_ptr(x), _ptr(weight), _ptr(bias.contiguous() if bias is not None else None),
-                                       _ptr(y), b, k, n, int(mode), int(bool(relu_input)),
-                                       _ptr(saturation_counter(dev)), _stream()), "vcnf_linear_probe_f32")
+    _check(_launch("vcnf_linear_probe_f32", x, weight, bias.contiguous() if bias is not None else None, y, b, k, n,
+                   int(mode), bool(relu_input), saturation_counter(dev)), "vcnf_linear_probe_f32")
     return y
