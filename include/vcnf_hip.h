@@ -971,6 +971,72 @@ int vcnf_target_log_prob_f32(const float* z, const float* table, float* logp, fl
 int vcnf_target_log_prob_f64(const double* z, const double* table, double* logp, double* score, int64_t batch,
                              int32_t n_comp, int family, double scale, void* stream);
 
+/* ---- Stochastic layers of normflow 1.2 (flows/stochastic.py) against the targets above (csrc/stochastic.hip): a run
+ * of HamiltonianMonteCarlo layers in one launch with its VJP, and the walk of a MetropolisHastings layer with a diagonal
+ * Gaussian proposal.  z / z_out [B, 2] contiguous; family, table, n_comp and scale as for vcnf_target_log_prob_*, with
+ * its logp, score and its rule for a non-finite row.  Nothing random is drawn in a kernel: the draws are inputs.
+ *   hmc_stack: K = n_layers >= 1 layers of `steps` >= 0 leapfrog steps each, applied in order.  step, mass, sqrt_mass
+ *     [K, 2] are exp(log_step_size), exp(log_mass), exp(0.5 log_mass) of the layers (the caller computes them), noise
+ *     [K, B, 2] standard-normal and unif [K, B] uniform draws.  Per layer and sample:
+ *       p = noise sqrt_mass,  z_new = z,  p_new = p
+ *       steps times:  p_half = p_new - (step / 2) (-score(z_new)),  z_new = z_new + step (p_half / mass),
+ *                     p_new = p_half - (step / 2) (-score(z_new))
+ *       prob = exp(logp(z_new) - logp(z) - sum(p_new^2 / mass) / 2 + sum(p^2 / mass) / 2)
+ *       accept = unif < prob (a NaN prob rejects),  z_out = accept ? z_new : z (a rejected row keeps its bits)
+ *       log_det += logp(z) - logp(z_out)      (0 on a rejected finite row, NaN on a non-finite one)
+ *     K steps + 1 evaluations of (logp, score) per sample.  log_det [B] is stored.  trace [K, B, 2] (may be NULL)
+ *     receives the row as it enters each layer and accept [K, B] (bytes 0 / 1, may be NULL) each layer's decision:
+ *     what the VJP reads.
+ *   hmc_stack_bwd: VJP of the run for the cotangents g_out [B, 2] of z_out and g_logdet [B] of log_det (either may be
+ *     NULL = zero), with the score and the decision treated as constants, as the reference's detach does.  Per layer,
+ *     last to first, with a the decision, gz the running cotangent and gl = g_logdet:
+ *       G = a (gz - gl score(z_new)),  g_z = (1 - a) gz + G + a gl score(z)
+ *       g_step      = G sum_i [p_half_i / mass + (step / mass) ((steps - i) s_i + (steps - 1 - i) s_{i+1}) / 2]
+ *       g_mass      = -G step sum_i p_half_i / mass^2,      g_sqrt_mass = steps G (step / mass) noise
+ *     (s_i the score before step i) from the trajectory recomputed out of trace, accept and noise.  a enters as a
+ *     select on g_z and on each of the six terms: a rejected row hands gz on unchanged and adds exact zeros to the sums,
+ *     also where its row is non-finite or its trajectory ran off to inf / NaN (the reference's autograd gives NaN
+ *     parameter gradients for the whole batch there).  g_in
+ *     [B, 2]; g_step, g_mass, g_sqrt_mass [K, 2] summed over the batch: every workgroup adds its samples' terms into
+ *     its own block of `workspace` (`groups` blocks of 6 K elements, uninitialised on entry; 1 <= groups <=
+ *     min(1024, ceil(B / 256)), the number of workgroups) and a second launch adds the blocks in a fixed order.
+ *   mh_walk: `steps` >= 0 random-walk steps with eps [steps, B, 2] standard-normal and w [steps, B] uniform draws and
+ *     prop_scale [2] the proposal's standard deviations (device memory):  z_ = eps prop_scale + z,
+ *     accept = w <= min(exp(logp(z_) - logp(z)), 1) (NaN rejects),  z = accept ? z_ : z;  logp(z) is carried from step
+ *     to step.  accept [steps, B] (bytes, may be NULL) receives the decisions.  The layer's log_det is zero and it is
+ *     the identity under differentiation, so the caller provides both.
+ * batch < 0, n_layers < 1, steps < 0, n_comp < 1 for a mixture, or groups outside its range -> VCNF_ERR_SHAPE; unknown
+ * family, or n_layers (steps + 1) > 65536 (a mistaken argument must not become a launch that runs for minutes) ->
+ * VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a pointer not
+ * aligned to its element size -> VCNF_ERR_ALIGN, checked in this order.  One sample per lane; rows move as one 8-byte
+ * (16-byte) access when the [., 2] buffers are aligned to it, as two elements otherwise, with the same bits either way.
+ * Every loop is bounded by n_layers, steps or n_comp.  No atomics, no allocation, no host synchronisation: every call is
+ * bitwise reproducible and capturable. */
+int vcnf_hmc_stack_f32(const float* z, const float* noise, const float* unif, const float* step, const float* mass,
+                       const float* sqrt_mass, const float* table, float* z_out, float* log_det, float* trace,
+                       uint8_t* accept, int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, int family,
+                       float scale, void* stream);
+int vcnf_hmc_stack_bwd_f32(const float* trace, const uint8_t* accept, const float* noise, const float* step,
+                           const float* mass, const float* sqrt_mass, const float* table, const float* g_out,
+                           const float* g_logdet, float* g_in, float* g_step, float* g_mass, float* g_sqrt_mass,
+                           float* workspace, int64_t batch, int32_t n_layers, int32_t steps, int32_t groups,
+                           int32_t n_comp, int family, float scale, void* stream);
+int vcnf_mh_walk_f32(const float* z, const float* eps, const float* w, const float* prop_scale, const float* table,
+                     float* z_out, uint8_t* accept, int64_t batch, int32_t steps, int32_t n_comp, int family,
+                     float scale, void* stream);
+int vcnf_hmc_stack_f64(const double* z, const double* noise, const double* unif, const double* step, const double* mass,
+                       const double* sqrt_mass, const double* table, double* z_out, double* log_det, double* trace,
+                       uint8_t* accept, int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, int family,
+                       double scale, void* stream);
+int vcnf_hmc_stack_bwd_f64(const double* trace, const uint8_t* accept, const double* noise, const double* step,
+                           const double* mass, const double* sqrt_mass, const double* table, const double* g_out,
+                           const double* g_logdet, double* g_in, double* g_step, double* g_mass, double* g_sqrt_mass,
+                           double* workspace, int64_t batch, int32_t n_layers, int32_t steps, int32_t groups,
+                           int32_t n_comp, int family, double scale, void* stream);
+int vcnf_mh_walk_f64(const double* z, const double* eps, const double* w, const double* prop_scale, const double* table,
+                     double* z_out, uint8_t* accept, int64_t batch, int32_t steps, int32_t n_comp, int family,
+                     double scale, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

@@ -197,6 +197,10 @@ _PAIRS = {
     "vcnf_planar_radial_stack": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F32, _P],
     "vcnf_planar_radial_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
     "vcnf_target_log_prob": [_P, _P, _P, _P, _I64, _I32, _INT, _F32, _P],
+    "vcnf_hmc_stack": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _INT, _F32, _P],
+    "vcnf_hmc_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT,
+                           _F32, _P],
+    "vcnf_mh_walk": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F32, _P],
 }
 _F64_TWIN = {_F32: _F64, _CFG: _CFG64}
 for _name, _args in _PAIRS.items():
@@ -1684,6 +1688,117 @@ def target_log_prob(z, family, table=None, scale=0.0, want_score=False):
     score = torch.empty_like(z) if want_score else None
     _call(name, dev, z, table, logp, score, b, n, int(family), float(scale))
     return logp, score
+
+
+HMC_BLOCK, HMC_MAX_BWD_GROUPS = 256, 1024      # samples per workgroup and the cap on the workgroups of the HMC VJP
+
+
+def _stochastic_target(z, family, table, name):
+    """Checked (device, z, table, n_comp) of the stochastic entry points: z [B, 2] fp32 / fp64 contiguous and detached,
+    the mixture's table like z (None for TwoMoons)."""
+    dev = require_device(z, table, f64=True, allow_grad=True)
+    if z.dtype not in (torch.float32, torch.float64):
+        raise VcnfError("%s: z must be fp32 or fp64 (got %s)" % (name, z.dtype))
+    if z.dim() != 2 or z.shape[1] != 2:
+        raise VcnfError("%s: expects [batch, 2] inputs (got %s)" % (name, list(z.shape)))
+    if family not in (TARGET_TWO_MOONS, TARGET_CIRCULAR_GMM, TARGET_RING_MIXTURE):
+        raise VcnfError("%s: unknown target family %r" % (name, family))
+    n = 0
+    if family != TARGET_TWO_MOONS:
+        per = 2 if family == TARGET_CIRCULAR_GMM else 1
+        if table is None or table.dtype != z.dtype or table.device != dev or table.numel() % per or not table.numel():
+            raise VcnfError("%s: the component table must be a %s tensor on %s" % (name, z.dtype, dev))
+        table = table.detach().contiguous()
+        n = table.numel() // per
+    else:
+        table = None
+    return dev, z.detach().contiguous(), table, n
+
+
+def _stochastic_like(name, what, t, z, shape):
+    """``t`` detached and contiguous after the check that it is a ``shape`` tensor of z's dtype on z's device."""
+    if not torch.is_tensor(t) or t.dtype != z.dtype or t.device != z.device or tuple(t.shape) != tuple(shape):
+        raise VcnfError("%s: %s must be a %s tensor of shape %s on %s" % (name, what, z.dtype, list(shape), z.device))
+    return t.detach().contiguous()
+
+
+def hmc_stack(z, noise, unif, step, mass, sqrt_mass, steps, family, table=None, scale=0.0, want_trace=False):
+    """vcnf_hmc_stack_*: a run of K HamiltonianMonteCarlo layers of ``steps`` leapfrog steps over z [B, 2] in one launch
+    against the target ``family`` (``table`` and ``scale`` as for target_log_prob), from the operands described in
+    include/vcnf_hip.h: step, mass, sqrt_mass [K, 2] and the draws noise [K, B, 2], unif [K, B].  Returns (z_out, log_det)
+    - log_det a fresh [B] tensor holding the sum of the layers' log p(z) - log p(z_out) - and with ``want_trace`` what
+    the VJP needs besides: each layer's entrance row trace [K, B, 2] and its decision accept [K, B] (uint8)."""
+    name = "vcnf_hmc_stack" + _sfx(z)
+    dev, z, table, n = _stochastic_target(z, family, table, name)
+    b, steps = len(z), int(steps)
+    if step.dim() != 2 or step.shape[0] < 1:
+        raise VcnfError(name + ": step must be a [layers, 2] tensor")
+    k = step.shape[0]
+    if steps < 0:
+        raise VcnfError(name + ": steps must not be negative")
+    step, mass, sqrt_mass = (_stochastic_like(name, what, t, z, (k, 2))
+                             for what, t in (("step", step), ("mass", mass), ("sqrt_mass", sqrt_mass)))
+    noise = _stochastic_like(name, "noise", noise, z, (k, b, 2))
+    unif = _stochastic_like(name, "unif", unif, z, (k, b))
+    out = torch.empty_like(z)
+    log_det = torch.empty(b, dtype=z.dtype, device=dev)
+    trace = accept = None
+    if want_trace:
+        trace = torch.empty((k, b, 2), dtype=z.dtype, device=dev)
+        accept = torch.empty((k, b), dtype=torch.uint8, device=dev)
+    _call(name, dev, z, noise, unif, step, mass, sqrt_mass, table, out, log_det, trace, accept, b, k, steps, n, int(family),
+          float(scale))
+    return (out, log_det, trace, accept) if want_trace else (out, log_det)
+
+
+def hmc_stack_bwd(trace, accept, noise, step, mass, sqrt_mass, steps, family, table=None, scale=0.0, g_out=None, g_ld=None):
+    """vcnf_hmc_stack_bwd_*: (g_in [B, 2], g_step [K, 2], g_mass [K, 2], g_sqrt_mass [K, 2]) of the forward run for the
+    cotangents g_out [B, 2] and g_ld [B] of (z_out, log_det); None is zero.  ``trace`` and ``accept`` as the forward run
+    returned them, the other operands as it took them.  The score and the decisions are constants, as in the reference.
+    Two launches, no atomics."""
+    name = "vcnf_hmc_stack_bwd" + _sfx(trace)
+    if trace.dim() != 3:
+        raise VcnfError(name + ": trace must be the [layers, batch, 2] tensor of the forward run")
+    k, b = int(trace.shape[0]), int(trace.shape[1])
+    dev, z, table, n = _stochastic_target(trace.reshape(-1, 2), family, table, name)
+    require_device(accept, noise, step, mass, sqrt_mass, g_out, g_ld, f64=True, allow_grad=True)
+    if k < 1 or not torch.is_tensor(accept) or accept.dtype != torch.uint8 or tuple(accept.shape) != (k, b) or accept.device != dev:
+        raise VcnfError(name + ": accept must be the uint8 [layers, batch] tensor of the forward run")
+    step, mass, sqrt_mass = (_stochastic_like(name, what, t, z, (k, 2))
+                             for what, t in (("step", step), ("mass", mass), ("sqrt_mass", sqrt_mass)))
+    noise = _stochastic_like(name, "noise", noise, z, (k, b, 2))
+    g_out = None if g_out is None else _stochastic_like(name, "g_out", g_out, z, (b, 2))
+    g_ld = None if g_ld is None else _stochastic_like(name, "g_ld", g_ld, z, (b,))
+    g_in = torch.empty((b, 2), dtype=z.dtype, device=dev)
+    if b == 0:
+        return g_in, torch.zeros_like(step), torch.zeros_like(mass), torch.zeros_like(sqrt_mass)
+    g_step, g_mass, g_sqm = torch.empty_like(step), torch.empty_like(mass), torch.empty_like(sqrt_mass)
+    groups = min((b + HMC_BLOCK - 1) // HMC_BLOCK, HMC_MAX_BWD_GROUPS)
+    work = torch.empty((groups, k, 3, 2), dtype=z.dtype, device=dev)
+    _call(name, dev, z, accept.contiguous(), noise, step, mass, sqrt_mass, table, g_out, g_ld, g_in, g_step, g_mass, g_sqm,
+          work, b, k, int(steps), groups, n, int(family), float(scale))
+    return g_in, g_step, g_mass, g_sqm
+
+
+def mh_walk(z, eps, w, prop_scale, family, table=None, scale=0.0, want_accept=False):
+    """vcnf_mh_walk_*: the random walk of a MetropolisHastings layer with a diagonal Gaussian proposal over z [B, 2] in
+    one launch: eps [steps, B, 2] and w [steps, B] the draws, prop_scale [2] the proposal's standard deviations,
+    ``family``, ``table`` and ``scale`` the target as for target_log_prob.  Returns z_out, with ``want_accept``
+    (z_out, accept [steps, B] uint8).  The layer's log_det is zero and its derivative the identity: both are the
+    caller's."""
+    name = "vcnf_mh_walk" + _sfx(z)
+    dev, z, table, n = _stochastic_target(z, family, table, name)
+    b = len(z)
+    if not torch.is_tensor(eps) or eps.dim() != 3:
+        raise VcnfError(name + ": eps must be a [steps, batch, 2] tensor")
+    steps = int(eps.shape[0])
+    eps = _stochastic_like(name, "eps", eps, z, (steps, b, 2))
+    w = _stochastic_like(name, "w", w, z, (steps, b))
+    prop_scale = _stochastic_like(name, "prop_scale", prop_scale, z, (2,))
+    out = torch.empty_like(z)
+    accept = torch.empty((steps, b), dtype=torch.uint8, device=dev) if want_accept else None
+    _call(name, dev, z, eps, w, prop_scale, table, out, accept, b, steps, n, int(family), float(scale))
+    return (out, accept) if want_accept else out
 
 
 PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2

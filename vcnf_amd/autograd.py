@@ -536,6 +536,47 @@ class TargetLogProbFn(torch.autograd.Function):
         return g[:, None] * score, None, None, None
 
 
+class HmcStackFn(torch.autograd.Function):
+    """vcnf_hmc_stack_*: (z_out, log_det [B]) of a run of HamiltonianMonteCarlo layers from its operands step, mass,
+    sqrt_mass [K, 2] (vcnf_amd.fused_stochastic.operands) and the draws noise [K, B, 2], unif [K, B] as ONE node.  Forward
+    launches the kernel with the trace (each layer's entrance row) and the decisions; backward is
+    vcnf_hmc_stack_bwd_*, which recomputes each layer's trajectory: the saved state is O(B K).  The score and the
+    decisions are constants under differentiation, as the reference's detach makes them; the draws get no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, step, mass, sqrt_mass, noise, unif, steps, family, table, scale):
+        with torch.no_grad():
+            out, ld, trace, accept = _lib.hmc_stack(z, noise, unif, step, mass, sqrt_mass, steps, family, table, scale,
+                                                    want_trace=True)
+        ctx.save_for_backward(trace, accept, noise, step, mass, sqrt_mass, table)
+        ctx.target = (steps, family, scale)
+        ctx.set_materialize_grads(False)
+        return out, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_ld):
+        trace, accept, noise, step, mass, sqrt_mass, table = ctx.saved_tensors
+        steps, family, scale = ctx.target
+        g_in, g_step, g_mass, g_sqm = _lib.hmc_stack_bwd(trace, accept, noise, step.detach(), mass.detach(),
+                                                         sqrt_mass.detach(), steps, family, table, scale, g_out, g_ld)
+        return g_in, g_step, g_mass, g_sqm, None, None, None, None, None, None
+
+
+class MhWalkFn(torch.autograd.Function):
+    """vcnf_mh_walk_*: the Metropolis-Hastings walk of z [B, 2] as a node.  Every step is z or z + eps scale, chosen by a
+    decision that has no derivative: the walk is the identity under differentiation and backward hands gz through."""
+
+    @staticmethod
+    def forward(ctx, z, eps, w, prop_scale, family, table, scale):
+        return _lib.mh_walk(z, eps, w, prop_scale, family, table, scale)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return g, None, None, None, None, None, None
+
+
 def _mvn_d_consts(g, d_nu):
     """Gradient of consts = (cst, nu): cst enters every sample's log density once."""
     return torch.cat([g.sum().reshape(1), d_nu])

@@ -17,11 +17,12 @@ import torch
 from torch import nn
 
 from .flows.affine.coupling import AffineCouplingBlock, MaskedAffineFlow, AffineConstFlow
-from . import fused_affine, fused, fused_masked, fused_planar
+from . import fused_affine, fused, fused_masked, fused_planar, fused_stochastic
 from .flows.mixing import Permute
 from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
 from .flows.planar import Planar
 from .flows.radial import Radial
+from .flows.stochastic import HamiltonianMonteCarlo
 from .fused import refresh_packed
 
 # The single-launch families, tried in this order at every position of a pass: (the model's switch, the flow types a
@@ -29,7 +30,8 @@ from .fused import refresh_packed
 _STACKS = (('fuse_affine_stacks', (Permute, AffineCouplingBlock), fused_affine.stack_run),
            ('fuse_masked_stacks', (MaskedAffineFlow, AffineConstFlow), fused_masked.stack_run),
            ('fuse_rqs_stacks', (CoupledRationalQuadraticSpline,), fused.stack_run),
-           ('fuse_planar_stacks', (Planar, Radial), fused_planar.stack_run))
+           ('fuse_planar_stacks', (Planar, Radial), fused_planar.stack_run),
+           ('fuse_stochastic_stacks', (HamiltonianMonteCarlo,), fused_stochastic.stack_run))
 
 
 class _PackedWeightsMixin:
@@ -62,6 +64,7 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         self.fuse_rqs_stacks = True              # runs of one-kernel RQS layers in a single launch at small batches (fused.run_stack)
         self.fuse_masked_stacks = True           # runs of MaskedAffineFlow (+ MLP conditioners) / ActNorm layers in a single launch
         self.fuse_planar_stacks = True           # runs of Planar / Radial layers in a single launch (fused_planar.run)
+        self.fuse_stochastic_stacks = True       # runs of HamiltonianMonteCarlo layers in a single launch (fused_stochastic.run)
 
     def _walk(self, z, log_q, context, density):
         """(z, log_q) after one pass over the flows: last to first through their inverses with the log-dets added

@@ -1,0 +1,423 @@
+// The stochastic layers of normflow 1.2 (flows/stochastic.py) against the 2-D kernel targets for MI355X (gfx950,
+// wave64), fp32 and fp64 from one template: a run of HamiltonianMonteCarlo layers in ONE launch, its VJP, and the
+// random walk of a MetropolisHastings layer with a diagonal Gaussian proposal.  Written in torch one HMC layer of L
+// leapfrog steps is 2 L autograd.grad calls through target.log_prob, four more log_prob calls and some twenty
+// elementwise ops on a few kilobytes; here the sample's row, its momentum, log p and the score stay in the lane's
+// registers from the first layer to the last, and a leapfrog point is one fused (log p, score) evaluation of
+// target_math.hpp: steps + 1 per layer for the first layer of a run and steps for each later one, since the second
+// score of step i is the first of step i + 1 and log p of a layer's output is log p of the next layer's input.
+//
+// HMC layer k of a run, per sample (step, mass, sqrt_mass are rows [2] of the [K, 2] operands, noise [K, B, 2] and
+// unif [K, B] the draws; nothing random is drawn here):
+//   p = noise sqrt_mass,  z_new = z,  p_new = p
+//   steps times:  p_half = p_new - (step / 2) (-score(z_new)),  z_new = z_new + step (p_half / mass),
+//                 p_new = p_half - (step / 2) (-score(z_new))
+//   prob = exp(logp(z_new) - logp(z) - sum(p_new^2 / mass) / 2 + sum(p^2 / mass) / 2)
+//   accept = unif < prob (a NaN prob rejects),  z_out = accept ? z_new : z (a rejected row keeps its bits),
+//   log_det += logp(z) - logp(z_out)
+// A non-finite row has NaN log p and score (the targets' rule), so it is rejected and its log_det is NaN.
+//
+// VJP.  The reference detaches the score and the decision has no derivative, so given the scores the leapfrog is affine
+// in z and the cotangents have a closed form that needs no stored trajectory: with a the decision, gz and gl the
+// cotangents of z_out and log_det, G = a (gz - gl score(z_new)) is the cotangent of z_new and
+//   g_z = (1 - a) gz + G + a gl score(z)
+//   g_step      = G sum_i [p_half_i / mass + (step / mass) ((steps - i) s_i + (steps - 1 - i) s_{i+1}) / 2]
+//   g_mass      = -G step sum_i p_half_i / mass^2
+//   g_sqrt_mass = steps G (step / mass) noise
+// where s_i is the score before step i.  One launch walks the layers last to first: per layer it reads the layer's
+// entrance row (trace) and decision, recomputes the trajectory once in the forward direction with the sums above beside
+// it, and hands g_z on as the next layer's gz.  The layer's six parameter terms are summed over the lanes of a wave
+// (butterfly), over the waves through LDS in ascending order, and added to the workgroup's own block [K, 3, 2] of the
+// workspace; a second launch (reduce_partials) adds the blocks in a fixed order.
+//
+// MH walk, per step (eps [S, B, 2] and w [S, B] the draws, prop_scale [2] the proposal's standard deviations):
+//   z_ = eps prop_scale + z,  accept = w <= min(exp(logp(z_) - logp(z)), 1) (NaN rejects),  z = accept ? z_ : z
+// with logp(z) carried from step to step: steps + 1 evaluations.
+//
+// All kernels are streams over [B, 2] like target_density.hip: one sample per lane, a row one 8-byte (fp32) or 16-byte
+// (fp64) access when the row buffers are aligned to it and two element accesses otherwise, a grid-stride loop under a
+// capped grid.  Every loop is bounded by a host argument (n_layers, steps, n_comp) that the entry point validates;
+// none depends on data.  No atomics, no scratch; LDS only for the VJP's sums over the waves.  The same call twice gives
+// the same bits.  Contraction to fused multiply-adds is off, as in target_density.hip: log p at a point has the bits
+// that unit gives.
+#include "stream_common.hpp"
+
+#pragma clang fp contract(off)
+
+#include "target_math.hpp"
+
+namespace vcnf_stoch {
+
+using namespace vcnf_stream;
+using vcnf_target::is_family;
+using vcnf_target::is_mixture;
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kMaxBlocks = 2048;
+constexpr int kMaxBwdGroups = 1024;
+constexpr long long kMaxPoints = 1LL << 16;   // n_layers (steps + 1) of one call
+constexpr int kTerms = 6;                     // g_step, g_mass, g_sqrt_mass of a layer: [3, 2]
+
+typedef unsigned char byte_t;
+
+template <typename T>
+struct Target {
+  const T* table;
+  int n;
+  T scale;
+};
+
+// log p and, with SCORE, the score at (z0, z1) with the targets' rule for a non-finite row; without SCORE none of the
+// score's arithmetic is instantiated and s0, s1 are left alone (log p has the same bits either way)
+template <typename T, int F, bool SCORE>
+__device__ __forceinline__ T point(const Target<T>& t, T z0, T z1, T& s0, T& s1) {
+  if (SCORE) s0 = s1 = T(0);
+  T lp = F == VCNF_TARGET_TWO_MOONS ? vcnf_target::two_moons<T, SCORE>(z0, z1, s0, s1)
+                                    : vcnf_target::mixture<T, F, SCORE>(t.table, t.n, t.scale, z0, z1, s0, s1);
+  if (!(abs_(z0) < T(INFINITY) && abs_(z1) < T(INFINITY))) {
+    lp = T(NAN);
+    if (SCORE) s0 = s1 = T(NAN);
+  }
+  return lp;
+}
+
+template <typename T, bool ROW>
+__device__ __forceinline__ Pack<T, 2> load_row(const T* __restrict__ p, long long row) {
+  Pack<T, 2> x;
+  if (ROW) {
+    x = reinterpret_cast<const Pack<T, 2>*>(p)[row];
+  } else {
+    x.v[0] = p[2 * row];
+    x.v[1] = p[2 * row + 1];
+  }
+  return x;
+}
+
+template <typename T, bool ROW>
+__device__ __forceinline__ void store_row(T* __restrict__ p, long long row, const Pack<T, 2>& x) {
+  if (ROW) {
+    reinterpret_cast<Pack<T, 2>*>(p)[row] = x;
+  } else {
+    p[2 * row] = x.v[0];
+    p[2 * row + 1] = x.v[1];
+  }
+}
+
+// ------------------------------------------------------------------ HMC run, forward
+template <typename T>
+struct HmcArgs {
+  Target<T> t;
+  const T *z, *noise, *unif, *step, *mass, *sqm;
+  T *out, *logdet, *trace;
+  byte_t* accept;
+  long long B;
+  int K, steps;
+};
+
+template <typename T, int F, bool ROW>
+__global__ __launch_bounds__(kBlock) void hmc_fwd_kernel(const HmcArgs<T> a) {
+  for (long long b = (long long)blockIdx.x * kBlock + threadIdx.x; b < a.B; b += (long long)gridDim.x * kBlock) {
+    Pack<T, 2> z = load_row<T, ROW>(a.z, b);
+    T s0, s1;
+    T lp = point<T, F, true>(a.t, z.v[0], z.v[1], s0, s1);
+    T ld = T(0);
+    for (int k = 0; k < a.K; ++k) {
+      const long long at = (long long)k * a.B + b;
+      const T h0 = a.step[2 * k], h1 = a.step[2 * k + 1], m0 = a.mass[2 * k], m1 = a.mass[2 * k + 1];
+      const Pack<T, 2> e = load_row<T, ROW>(a.noise, at);
+      const T u = a.unif[at];
+      if (a.trace) store_row<T, ROW>(a.trace, at, z);
+      const T p0 = e.v[0] * a.sqm[2 * k], p1 = e.v[1] * a.sqm[2 * k + 1];
+      T x0 = z.v[0], x1 = z.v[1], r0 = p0, r1 = p1, t0 = s0, t1 = s1, lpn = lp;
+      for (int i = 0; i < a.steps; ++i) {
+        const T q0 = r0 - (h0 / T(2)) * -t0, q1 = r1 - (h1 / T(2)) * -t1;
+        x0 = x0 + h0 * (q0 / m0);
+        x1 = x1 + h1 * (q1 / m1);
+        lpn = point<T, F, true>(a.t, x0, x1, t0, t1);
+        r0 = q0 - (h0 / T(2)) * -t0;
+        r1 = q1 - (h1 / T(2)) * -t1;
+      }
+      const T prob = exp_(lpn - lp - T(0.5) * (r0 * r0 / m0 + r1 * r1 / m1) + T(0.5) * (p0 * p0 / m0 + p1 * p1 / m1));
+      const bool acc = u < prob;
+      const T lp_out = acc ? lpn : lp;
+      ld += lp - lp_out;
+      z.v[0] = acc ? x0 : z.v[0];
+      z.v[1] = acc ? x1 : z.v[1];
+      s0 = acc ? t0 : s0;
+      s1 = acc ? t1 : s1;
+      lp = lp_out;
+      if (a.accept) a.accept[at] = acc ? 1 : 0;
+    }
+    store_row<T, ROW>(a.out, b, z);
+    a.logdet[b] = ld;
+  }
+}
+
+// ------------------------------------------------------------------ HMC run, VJP
+template <typename T>
+struct HmcBwdArgs {
+  Target<T> t;
+  const T *trace, *noise, *step, *mass, *sqm, *gout, *gld;
+  const byte_t* accept;
+  T *gin, *partials;
+  long long B, tiles;
+  int K, steps;
+};
+
+template <typename T, int F, bool ROW>
+__global__ __launch_bounds__(kBlock) void hmc_bwd_kernel(const HmcBwdArgs<T> a) {
+  __shared__ T red[2][kWaves][kTerms];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  T* const block = a.partials + (long long)blockIdx.x * a.K * kTerms;
+  int it = 0;                                          // layers visited: its parity picks the LDS buffer
+  bool first = true;
+  // every lane of the workgroup walks every tile (barriers inside); a lane past the batch adds zeros
+  for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x, first = false) {
+    const long long b = tile * kBlock + threadIdx.x;
+    const bool live = b < a.B;
+    Pack<T, 2> gz;
+    gz.v[0] = gz.v[1] = T(0);
+    if (live && a.gout) gz = load_row<T, ROW>(a.gout, b);
+    const T gl = (live && a.gld) ? a.gld[b] : T(0);
+    for (int k = a.K - 1; k >= 0; --k, ++it) {
+      T v[kTerms];
+#pragma unroll
+      for (int j = 0; j < kTerms; ++j) v[j] = T(0);
+      if (live) {
+        const long long at = (long long)k * a.B + b;
+        const T h0 = a.step[2 * k], h1 = a.step[2 * k + 1], m0 = a.mass[2 * k], m1 = a.mass[2 * k + 1];
+        const T c0 = h0 / m0, c1 = h1 / m1;
+        const Pack<T, 2> z = load_row<T, ROW>(a.trace, at);
+        const Pack<T, 2> e = load_row<T, ROW>(a.noise, at);
+        const bool acc = a.accept[at] != 0;
+        T t0, t1;
+        point<T, F, true>(a.t, z.v[0], z.v[1], t0, t1);
+        const T sz0 = t0, sz1 = t1;                    // the score at the layer's entrance
+        // the forward pass's trajectory again, with the sums of the closed form beside it
+        T x0 = z.v[0], x1 = z.v[1], r0 = e.v[0] * a.sqm[2 * k], r1 = e.v[1] * a.sqm[2 * k + 1];
+        T w0 = T(0), w1 = T(0);                        // sum_i p_half_i
+        T f0 = T(0), f1 = T(0);                        // sum_i ((steps - i) s_i + (steps - 1 - i) s_{i+1}) / 2
+        for (int i = 0; i < a.steps; ++i) {
+          const T q0 = r0 - (h0 / T(2)) * -t0, q1 = r1 - (h1 / T(2)) * -t1;
+          const T n_half = T(a.steps - i), n_next = T(a.steps - 1 - i);
+          const T u0 = t0, u1 = t1;
+          x0 = x0 + h0 * (q0 / m0);
+          x1 = x1 + h1 * (q1 / m1);
+          point<T, F, true>(a.t, x0, x1, t0, t1);
+          r0 = q0 - (h0 / T(2)) * -t0;
+          r1 = q1 - (h1 / T(2)) * -t1;
+          w0 += q0;
+          w1 += q1;
+          f0 += (n_half * u0 + n_next * t0) / T(2);
+          f1 += (n_half * u1 + n_next * t1) / T(2);
+        }
+        // selects, not products with a: a rejected row - a non-finite one, or one whose leapfrog ran off to inf / NaN,
+        // has NaN sums - adds exact zeros to the parameter sums and hands its gz on as it is
+        const T G0 = acc ? gz.v[0] - gl * t0 : T(0), G1 = acc ? gz.v[1] - gl * t1 : T(0);
+        if (acc) {
+          v[0] = G0 * (w0 / m0 + c0 * f0);
+          v[1] = G1 * (w1 / m1 + c1 * f1);
+          v[2] = -(G0 * h0 * w0) / (m0 * m0);
+          v[3] = -(G1 * h1 * w1) / (m1 * m1);
+          v[4] = T(a.steps) * G0 * c0 * e.v[0];
+          v[5] = T(a.steps) * G1 * c1 * e.v[1];
+        }
+        gz.v[0] = acc ? G0 + gl * sz0 : gz.v[0];
+        gz.v[1] = acc ? G1 + gl * sz1 : gz.v[1];
+      }
+      // over the lanes of the wave, then over the waves
+#pragma unroll
+      for (int j = 0; j < kTerms; ++j) v[j] = lanes_sum(v[j], 1, 64);
+      if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < kTerms; ++j) red[it & 1][wave][j] = v[j];
+      }
+      __syncthreads();
+      if (threadIdx.x < kTerms) {
+        T s = red[it & 1][0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) s += red[it & 1][w][threadIdx.x];
+        T* const dst = block + (long long)k * kTerms + threadIdx.x;
+        *dst = first ? s : *dst + s;
+      }
+    }
+    if (live) store_row<T, ROW>(a.gin, b, gz);
+  }
+}
+
+// element e of the summed block [K, 3, 2] goes to g_step | g_mass | g_sqrt_mass, each [K, 2]
+template <typename T>
+struct ParamDest {
+  T *step, *mass, *sqm;
+  __device__ T* operator()(long long e) const {
+    const long long k = e / kTerms;
+    const int j = (int)(e - k * kTerms);
+    return (j < 2 ? step : j < 4 ? mass : sqm) + 2 * k + (j & 1);
+  }
+};
+
+// ------------------------------------------------------------------ MH walk
+template <typename T>
+struct MhArgs {
+  Target<T> t;
+  const T *z, *eps, *w, *prop;
+  T* out;
+  byte_t* accept;
+  long long B;
+  int steps;
+};
+
+template <typename T, int F, bool ROW>
+__global__ __launch_bounds__(kBlock) void mh_walk_kernel(const MhArgs<T> a) {
+  const T c0 = a.prop[0], c1 = a.prop[1];
+  for (long long b = (long long)blockIdx.x * kBlock + threadIdx.x; b < a.B; b += (long long)gridDim.x * kBlock) {
+    Pack<T, 2> z = load_row<T, ROW>(a.z, b);
+    T s0 = T(0), s1 = T(0);                          // not computed: the walk needs log p alone
+    T lp = point<T, F, false>(a.t, z.v[0], z.v[1], s0, s1);
+    for (int i = 0; i < a.steps; ++i) {
+      const long long at = (long long)i * a.B + b;
+      const Pack<T, 2> e = load_row<T, ROW>(a.eps, at);
+      const T x0 = e.v[0] * c0 + z.v[0], x1 = e.v[1] * c1 + z.v[1];
+      const T lpn = point<T, F, false>(a.t, x0, x1, s0, s1);
+      const T ratio = exp_(lpn - lp);
+      const bool acc = a.w[at] <= (ratio > T(1) ? T(1) : ratio);       // a NaN ratio stays NaN and rejects
+      z.v[0] = acc ? x0 : z.v[0];
+      z.v[1] = acc ? x1 : z.v[1];
+      lp = acc ? lpn : lp;
+      if (a.accept) a.accept[at] = acc ? 1 : 0;
+    }
+    store_row<T, ROW>(a.out, b, z);
+  }
+}
+
+// ------------------------------------------------------------------ host side
+// what every entry point checks before it looks at a pointer
+static int check_run(int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, int family) {
+  if (batch < 0 || n_layers < 1 || steps < 0) return VCNF_ERR_SHAPE;
+  if (!is_family(family)) return VCNF_ERR_UNSUPPORTED;
+  if (is_mixture(family) && n_comp < 1) return VCNF_ERR_SHAPE;
+  if ((long long)n_layers * ((long long)steps + 1) > kMaxPoints) return VCNF_ERR_UNSUPPORTED;
+  return VCNF_OK;
+}
+
+static long long sample_tiles(int64_t batch) { return (batch + kBlock - 1) / kBlock; }
+
+// family and row pack to template arguments
+#define VCNF_STOCH_LAUNCH(KERNEL, GRID, ST, ARGS)                                                  \
+  do {                                                                                             \
+    if (row)                                                                                       \
+      hipLaunchKernelGGL((KERNEL<T, F, true>), GRID, dim3(kBlock), 0, ST, ARGS);                   \
+    else                                                                                           \
+      hipLaunchKernelGGL((KERNEL<T, F, false>), GRID, dim3(kBlock), 0, ST, ARGS);                  \
+    return launched();                                                                             \
+  } while (0)
+
+#define VCNF_STOCH_FAMILY(FN, ...)                                                                 \
+  switch (family) {                                                                                \
+    case VCNF_TARGET_TWO_MOONS: return FN<T, VCNF_TARGET_TWO_MOONS>(__VA_ARGS__);                  \
+    case VCNF_TARGET_CIRCULAR_GMM: return FN<T, VCNF_TARGET_CIRCULAR_GMM>(__VA_ARGS__);            \
+    default: return FN<T, VCNF_TARGET_RING_MIXTURE>(__VA_ARGS__);                                  \
+  }
+
+template <typename T, int F>
+static int launch_hmc(const HmcArgs<T>& a, bool row, hipStream_t st) {
+  VCNF_STOCH_LAUNCH(hmc_fwd_kernel, grid_for(a.B, 1, kBlock, kMaxBlocks), st, a);
+}
+
+template <typename T, int F>
+static int launch_hmc_bwd(const HmcBwdArgs<T>& a, int32_t groups, bool row, hipStream_t st) {
+  VCNF_STOCH_LAUNCH(hmc_bwd_kernel, dim3((unsigned)groups), st, a);
+}
+
+template <typename T, int F>
+static int launch_mh(const MhArgs<T>& a, bool row, hipStream_t st) {
+  VCNF_STOCH_LAUNCH(mh_walk_kernel, grid_for(a.B, 1, kBlock, kMaxBlocks), st, a);
+}
+
+template <typename T>
+static Target<T> target_of(const T* table, int32_t n_comp, int family, T scale) {
+  return is_mixture(family) ? Target<T>{table, (int)n_comp, scale} : Target<T>{nullptr, 0, T(0)};
+}
+
+template <typename T>
+static int hmc_stack(const T* z, const T* noise, const T* unif, const T* step, const T* mass, const T* sqm, const T* table,
+                     T* out, T* logdet, T* trace, byte_t* accept, int64_t batch, int32_t n_layers, int32_t steps,
+                     int32_t n_comp, int family, T scale, void* stream) {
+  if (const int st = check_run(batch, n_layers, steps, n_comp, family)) return st;
+  if (batch == 0) return VCNF_OK;
+  if (!z || !noise || !unif || !step || !mass || !sqm || !out || !logdet || (is_mixture(family) && !table)) return VCNF_ERR_NULL;
+  if (!all_aligned({z, noise, unif, step, mass, sqm, table, out, logdet, trace}, sizeof(T))) return VCNF_ERR_ALIGN;
+  const HmcArgs<T> a{target_of(table, n_comp, family, scale), z, noise, unif, step, mass, sqm, out, logdet, trace, accept,
+                     batch, n_layers, steps};
+  const bool row = all_aligned({z, noise, out, trace}, 2 * sizeof(T));
+  hipStream_t st = (hipStream_t)stream;
+  VCNF_STOCH_FAMILY(launch_hmc, a, row, st)
+}
+
+template <typename T>
+static int hmc_stack_bwd(const T* trace, const byte_t* accept, const T* noise, const T* step, const T* mass, const T* sqm,
+                         const T* table, const T* gout, const T* gld, T* gin, T* g_step, T* g_mass, T* g_sqm, T* workspace,
+                         int64_t batch, int32_t n_layers, int32_t steps, int32_t groups, int32_t n_comp, int family, T scale,
+                         void* stream) {
+  if (const int st = check_run(batch, n_layers, steps, n_comp, family)) return st;
+  if (batch == 0) return VCNF_OK;
+  // one block of the workspace per workgroup, and every workgroup has a tile to write its block for
+  if (groups < 1 || groups > kMaxBwdGroups || groups > sample_tiles(batch)) return VCNF_ERR_SHAPE;
+  if (!trace || !accept || !noise || !step || !mass || !sqm || !gin || !g_step || !g_mass || !g_sqm || !workspace ||
+      (is_mixture(family) && !table))
+    return VCNF_ERR_NULL;
+  if (!all_aligned({trace, noise, step, mass, sqm, table, gout, gld, gin, g_step, g_mass, g_sqm, workspace}, sizeof(T)))
+    return VCNF_ERR_ALIGN;
+  const HmcBwdArgs<T> a{target_of(table, n_comp, family, scale), trace, noise, step, mass, sqm, gout, gld, accept, gin,
+                        workspace, batch, sample_tiles(batch), n_layers, steps};
+  const bool row = all_aligned({trace, noise, gout, gin}, 2 * sizeof(T));
+  hipStream_t st = (hipStream_t)stream;
+  auto kernel = [&]() -> int { VCNF_STOCH_FAMILY(launch_hmc_bwd, a, groups, row, st) };
+  if (const int rc = kernel()) return rc;
+  return launch_reduce_partials(workspace, (long long)groups, (long long)n_layers * kTerms, ParamDest<T>{g_step, g_mass, g_sqm},
+                                stream);
+}
+
+template <typename T>
+static int mh_walk(const T* z, const T* eps, const T* w, const T* prop, const T* table, T* out, byte_t* accept,
+                   int64_t batch, int32_t steps, int32_t n_comp, int family, T scale, void* stream) {
+  if (const int st = check_run(batch, 1, steps, n_comp, family)) return st;
+  if (batch == 0) return VCNF_OK;
+  if (!z || !prop || !out || (steps > 0 && (!eps || !w)) || (is_mixture(family) && !table)) return VCNF_ERR_NULL;
+  if (!all_aligned({z, eps, w, prop, table, out}, sizeof(T))) return VCNF_ERR_ALIGN;
+  const MhArgs<T> a{target_of(table, n_comp, family, scale), z, eps, w, prop, out, accept, batch, steps};
+  const bool row = all_aligned({z, eps, out}, 2 * sizeof(T));
+  hipStream_t st = (hipStream_t)stream;
+  VCNF_STOCH_FAMILY(launch_mh, a, row, st)
+}
+
+}  // namespace vcnf_stoch
+
+#define VCNF_STOCH_ENTRY_POINTS(T, SFX)                                                                                \
+  extern "C" int vcnf_hmc_stack_##SFX(const T* z, const T* noise, const T* unif, const T* step, const T* mass,         \
+                                      const T* sqrt_mass, const T* table, T* z_out, T* log_det, T* trace,              \
+                                      uint8_t* accept, int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, \
+                                      int family, T scale, void* stream) {                                             \
+    return vcnf_stoch::hmc_stack<T>(z, noise, unif, step, mass, sqrt_mass, table, z_out, log_det, trace, accept,       \
+                                    batch, n_layers, steps, n_comp, family, scale, stream);                            \
+  }                                                                                                                    \
+  extern "C" int vcnf_hmc_stack_bwd_##SFX(const T* trace, const uint8_t* accept, const T* noise, const T* step,        \
+                                          const T* mass, const T* sqrt_mass, const T* table, const T* g_out,           \
+                                          const T* g_logdet, T* g_in, T* g_step, T* g_mass, T* g_sqrt_mass,            \
+                                          T* workspace, int64_t batch, int32_t n_layers, int32_t steps,                \
+                                          int32_t groups, int32_t n_comp, int family, T scale, void* stream) {         \
+    return vcnf_stoch::hmc_stack_bwd<T>(trace, accept, noise, step, mass, sqrt_mass, table, g_out, g_logdet, g_in,     \
+                                        g_step, g_mass, g_sqrt_mass, workspace, batch, n_layers, steps, groups,        \
+                                        n_comp, family, scale, stream);                                                \
+  }                                                                                                                    \
+  extern "C" int vcnf_mh_walk_##SFX(const T* z, const T* eps, const T* w, const T* prop_scale, const T* table,         \
+                                    T* z_out, uint8_t* accept, int64_t batch, int32_t steps, int32_t n_comp,           \
+                                    int family, T scale, void* stream) {                                               \
+    return vcnf_stoch::mh_walk<T>(z, eps, w, prop_scale, table, z_out, accept, batch, steps, n_comp, family, scale,    \
+                                  stream);                                                                             \
+  }
+
+VCNF_STOCH_ENTRY_POINTS(float, f32)
+VCNF_STOCH_ENTRY_POINTS(double, f64)
+

@@ -3,7 +3,8 @@
 Constructor arguments, attribute names and state_dict keys are the reference's.  Density and score d log p / d z come
 from one launch of vcnf_target_log_prob_* (csrc/target_density.hip) in fp32 or fp64, picked by ``z``; under autograd
 ``log_prob`` is one node whose backward is a multiply by the score the forward launch wrote.  The targets have no
-parameters.  The fork's other targets (NealsFunnel, ...), priors and n_dims != 2 are out of scope."""
+parameters.  The stochastic layers (vcnf_amd.flows.stochastic) evaluate the same device functions inside their own
+kernels (csrc/target_math.hpp).  The fork's other targets (NealsFunnel, ...), priors and n_dims != 2 are out of scope."""
 import numpy as np
 import torch
 from torch import nn

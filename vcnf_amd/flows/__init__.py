@@ -4,6 +4,7 @@ from .mixing import Permute, Invertible1x1Conv, LULinearPermute                 
 from .normalization import ActNorm                                                # noqa: F401
 from .planar import Planar                                                        # noqa: F401
 from .radial import Radial                                                        # noqa: F401
+from .stochastic import MetropolisHastings, HamiltonianMonteCarlo                 # noqa: F401
 from .affine import (AffineConstFlow, AffineCoupling, MaskedAffineFlow,           # noqa: F401
                      AffineCouplingBlock)
 from .affine.glow import GlowBlock                                                # noqa: F401
