@@ -1,8 +1,8 @@
 """Plain-torch restatement of the stochastic layers of normflow 1.2 (normflows/flows/stochastic.py) as the reference
 writes them, with the draws as arguments: HamiltonianMonteCarlo (leapfrog with the detached score, the accept / reject
 decision, log_det = log p(z) - log p(z_out)) and MetropolisHastings with a diagonal Gaussian proposal (log_det 0).  The
-density and the score are target_ref's (the score autograd's unless another is passed).  It computes in the dtype of
-``z`` on the CPU; the tests run it in fp32 and fp64 and compare the kernels of csrc/stochastic.hip against it.
+density and the score are target_ref's (the score autograd's unless another is passed).  It computes in the dtype and on
+the device of ``z``; the tests run it in fp32 and fp64 and compare the kernels of csrc/stochastic.hip against it.
 
 Also here, because the CPU tests and the GPU tests share them: the cases, their inputs and draws, the near-tie bands,
 and the references computed once per case."""
@@ -81,7 +81,7 @@ def hmc_layer(family, n, z, noise, unif, log_step_size, log_mass, steps, score=r
 
 def hmc_run(family, n, z, noise, unif, params, steps, score=ref.score, accept=None):
     """A run of layers: (z_out, sum of the log_dets in layer order, accept [K, B], probabilities [K, B])."""
-    log_det = torch.zeros(len(z), dtype=z.dtype)
+    log_det = torch.zeros(len(z), dtype=z.dtype, device=z.device)
     masks, probs = [], []
     for k, (ls, lm) in enumerate(params):
         z, ld, mask, prob = hmc_layer(family, n, z, noise[k], unif[k], ls, lm, steps, score, None if accept is None else accept[k])
@@ -93,12 +93,12 @@ def hmc_run(family, n, z, noise, unif, params, steps, score=ref.score, accept=No
 
 def mh_walk(family, n, z, eps, w, scale):
     """(z_out, log_det = 0, accept [steps, B], min(exp(.), 1) [steps, B]) of the walk with the proposal z_ = eps scale + z."""
-    log_det = torch.zeros(len(z), dtype=z.dtype)
+    log_det = torch.zeros(len(z), dtype=z.dtype, device=z.device)
     log_p = ref.log_prob(family, n, z)
     masks, ratios = [], []
     for i in range(len(eps)):
         z_ = eps[i] * scale + z
-        log_p_diff = torch.zeros(len(z), dtype=z.dtype)
+        log_p_diff = torch.zeros(len(z), dtype=z.dtype, device=z.device)
         log_p_ = ref.log_prob(family, n, z_)
         log_w_accept = log_p_ - log_p + log_p_diff
         w_accept = torch.clamp(torch.exp(log_w_accept), max=1)
@@ -107,7 +107,7 @@ def mh_walk(family, n, z, eps, w, scale):
         log_p = torch.where(accept, log_p_, log_p)
         masks.append(accept)
         ratios.append(w_accept)
-    empty = torch.zeros((0, len(z)))
+    empty = torch.zeros((0, len(z)), device=z.device)
     return z, log_det, (torch.stack(masks) if masks else empty.bool()), (torch.stack(ratios) if ratios else empty.to(z.dtype))
 
 
@@ -122,7 +122,7 @@ def closed_form_score(family, n, z):
         k = -(r - 2) / 0.04
         return torch.stack([k * unit(z0, r) + torch.sign(z0) * ((2 - a) / 0.09 - (4 / 0.09) * e / (1 + e)), k * unit(z1, r)], 1)
     scale = float(ref.scale_of(family, n))
-    i = torch.arange(n, dtype=z.dtype)
+    i = torch.arange(n, dtype=z.dtype, device=z.device)
     if family == "circular":
         c = torch.stack([2 * torch.sin(2 * math.pi * i / n), 2 * torch.cos(2 * math.pi * i / n)], 1)
         diff = c[None] - z[:, None]
