@@ -1,5 +1,6 @@
 """Result bits of the matrix units (csrc/conv1x1.hip, conv3x3_1x1.hip and the fused RQS layer kernels fused_layer_v6.hip,
-fused_layer_v6s.hip, fused_layer.hip) for comparing two builds, modelled on stream_bits.py.
+fused_layer_v6s.hip, fused_layer.hip) and of the composed RQS coupling around them, for comparing two builds or two
+checkouts (VCNF_ROOT), modelled on stream_bits.py.
 
     python profiles/tools/matrix_bits.py --out DIR          # on a GPU: every output's raw bytes, one file each
     python profiles/tools/matrix_bits.py --compare DIR DIR  # anywhere: the two runs byte for byte
@@ -132,6 +133,61 @@ def fused_rqs(L):
         L.small_batch_rows(prev)
 
 
+# ---------------------------------------------------------------- composed RQS coupling (no fused kernel)
+def _composed_coupling(path, seed):
+    import vcnf_amd as nf
+    from vcnf_amd.flows.neural_spline.coupling import PiecewiseRationalQuadraticCoupling
+    torch.manual_seed(seed)
+    mask = nf.utils.masks.create_alternating_binary_mask(4, even=True)
+    if path == "image":
+        net = lambda i, o: nf.nets.ConvResidualNet(in_channels=i, out_channels=o, hidden_channels=16, context_channels=None,
+                                                   num_blocks=1, activation=torch.nn.functional.relu,
+                                                   dropout_probability=0.0, use_batch_norm=False)
+    else:
+        net = lambda i, o: nf.nets.ResidualNet(in_features=i, out_features=o, context_features=None, hidden_features=16,
+                                               num_blocks=1, activation=torch.nn.functional.relu, dropout_probability=0.0,
+                                               use_batch_norm=False)
+    cp = PiecewiseRationalQuadraticCoupling(
+        mask=mask, transform_net_create_fn=net, num_bins=8, tail_bound=3.0, apply_unconditional_transform=True,
+        tails=["linear", "circular", "circular", "linear"] if path == "per_feature" else "linear",
+        img_shape=[2, 2] if path == "image" else None)
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for p in cp.parameters():                  # the reference zero-initialises the last layer: move every parameter
+            p.add_(0.05 * torch.randn(p.shape, generator=g))
+    return cp.cuda()
+
+
+def composed_coupling(L):
+    """The three compositions of PiecewiseRationalQuadraticCoupling._run around the conditioner call, B = 33: the
+    training path (2-D inputs, autograd recording: SplitColumnsFn, rqs_packed, MergeColumnsFn), 4-D inputs, per-feature
+    tails; both directions, without autograd and with it (then the parameter gradients too)."""
+    for path, shape in (("train", (33, 4)), ("image", (33, 4, 2, 2)), ("per_feature", (33, 4))):
+        cp = _composed_coupling(path, 4100 + len(path))
+        x, w = rnd(*shape, scale=1.3), rnd(*shape)
+        if path == "per_feature":                  # circular tails: inside the interval
+            x = x.clamp(-2.9, 2.9)
+        for dirn, fn in (("fwd", cp.forward), ("inv", cp.inverse)):
+            if path != "train":                    # (without autograd the 2-D fp32 layer takes a fused or the three-step path)
+                save("coupling_%s_%s" % (path, dirn), *fn(x))
+            with torch.enable_grad():
+                cp.zero_grad(set_to_none=True)
+                xin = x.clone().requires_grad_(True)
+                out, lad = fn(xin)
+                ((out * w).sum() + lad.sum()).backward()
+                if path == "train":
+                    names = set()
+                    todo = [out.grad_fn]
+                    while todo:
+                        node = todo.pop()
+                        if node is not None and node not in names:
+                            names.add(node)
+                            todo += [n for n, _ in node.next_functions]
+                    names = {type(n).__name__ for n in names}
+                    assert {"SplitColumnsFnBackward", "RqsPackedFnBackward", "MergeColumnsFnBackward"} <= names, names
+            save("coupling_%s_%s_grad" % (path, dirn), out, lad, xin.grad, *[p.grad for p in cp.parameters()])
+
+
 def main():
     global OUT
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -147,7 +203,7 @@ def main():
     OUT = args.out
     os.makedirs(OUT, exist_ok=True)
     with torch.no_grad():
-        for part in (conv1x1, conv3x3, fused_rqs):
+        for part in (conv1x1, conv3x3, fused_rqs, composed_coupling):
             part(_lib)
     torch.cuda.synchronize()
     assert nf.check_saturation() == 0

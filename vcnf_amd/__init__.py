@@ -16,6 +16,6 @@ from . import utils, nets, flows, distributions                  # noqa: F401
 from .core import NormalizingFlow, ClassCondFlow, MultiscaleFlow  # noqa: F401
 from .sharded import ShardedEvaluator, shard_bounds              # noqa: F401
 from .graphs import GraphedFlow, GraphedTrainStep                # noqa: F401
-from .fused import refresh_packed                                # noqa: F401
+from .stacks import refresh_packed                               # noqa: F401
 
 __version__ = "0.1.0"

@@ -23,10 +23,10 @@ from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
 from .flows.planar import Planar
 from .flows.radial import Radial
 from .flows.stochastic import HamiltonianMonteCarlo
-from .fused import refresh_packed
+from .stacks import refresh_packed
 
 # The single-launch families, tried in this order at every position of a pass: (the model's switch, the flow types a
-# run can start with, the family's planner: None or (end, launch) with launch(z, log_q, sign) -> (z, log_q))
+# run can start with, the family's planner - the contract is the docstring of vcnf_amd.stacks)
 _STACKS = (('fuse_affine_stacks', (Permute, AffineCouplingBlock), fused_affine.stack_run),
            ('fuse_masked_stacks', (MaskedAffineFlow, AffineConstFlow), fused_masked.stack_run),
            ('fuse_rqs_stacks', (CoupledRationalQuadraticSpline,), fused.stack_run),
@@ -37,7 +37,7 @@ _STACKS = (('fuse_affine_stacks', (Permute, AffineCouplingBlock), fused_affine.s
 class _PackedWeightsMixin:
     """Keeps the packed weight copies of the fused kernels honest across the events that change parameters
     behind autograd's back: train() / eval() transitions and load_state_dict() drop the caches
-    (vcnf_amd.fused.refresh_packed); after a manual ``p.data`` edit call ``refresh_packed()`` yourself."""
+    (vcnf_amd.stacks.refresh_packed); after a manual ``p.data`` edit call ``refresh_packed()`` yourself."""
 
     def _install_pack_hooks(self):
         self.register_load_state_dict_post_hook(lambda module, incompatible: refresh_packed(module) and None)
@@ -66,6 +66,17 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         self.fuse_planar_stacks = True           # runs of Planar / Radial layers in a single launch (fused_planar.run)
         self.fuse_stochastic_stacks = True       # runs of HamiltonianMonteCarlo layers in a single launch (fused_stochastic.run)
 
+    def _stack_at(self, order, i, z, context, density, differentiable=False):
+        """(end, launch) of the first family of _STACKS that is switched on and plans a run from order[i], or None;
+        ``differentiable``: only the families whose planner is marked so (vcnf_amd.stacks)."""
+        for switch, starts, stack_run in _STACKS:
+            if isinstance(order[i], starts) and getattr(self, switch) and \
+                    (not differentiable or getattr(stack_run, 'differentiable', False)):
+                run = stack_run(self, order, i, z, context, density)
+                if run is not None:
+                    return run
+        return None
+
     def _walk(self, z, log_q, context, density):
         """(z, log_q) after one pass over the flows: last to first through their inverses with the log-dets added
         (``density``), or first to last with the log-dets subtracted (sampling).  At each position the first of these
@@ -78,12 +89,7 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         i = 0
         while i < n:
             flow = order[i]
-            run = None
-            for switch, starts, stack_run in _STACKS:
-                if isinstance(flow, starts) and getattr(self, switch):
-                    run = stack_run(self, order, i, z, context, density)
-                    if run is not None:
-                        break
+            run = self._stack_at(order, i, z, context, density)
             if run is not None:
                 i, launch = run
                 z, log_q = launch(z, log_q, sign)
@@ -121,12 +127,7 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
         i = 0
         while i < len(order):
             flow = order[i]
-            run = None
-            for switch, starts, stack_run in _STACKS:
-                if trace is None and getattr(stack_run, 'differentiable', False) and isinstance(flow, starts) and getattr(self, switch):
-                    run = stack_run(self, order, i, z, context, density)
-                    if run is not None:
-                        break
+            run = self._stack_at(order, i, z, context, density, True) if trace is None else None
             if run is not None:
                 i, launch = run
                 z, log_det = launch(z, None, 1.0 if density else -1.0)

@@ -6,7 +6,7 @@ Inference runs the 1x1 convolution and the ActNorm as ONE per-pixel channel map 
     density direction  (glow.py:67-73):  z -> W ((z - t) * exp(-s))            M = W diag(exp -s),    v = -W (t exp -s)
 with M, v composed in fp64 from the layer parameters (W = P L U or the dense W, mixing.py:71-95) and cached per
 direction, keyed on the parameters' (data_ptr, _version) like the packed conditioner weights and rewritten in place
-(fused.refresh_packed invalidates it)."""
+(stacks.refresh_packed invalidates it)."""
 import torch
 from torch import nn
 

@@ -267,93 +267,77 @@ class PiecewiseRationalQuadraticCoupling(Flow):
             return True
         return any(p.requires_grad for p in self.parameters())
 
-    def _run_differentiable(self, inputs, context, sampling):
-        """Training path (coupling.py:70-125 as written there): the channel partition and its
-        inverse are one pass each (autograd.SplitColumnsFn / MergeColumnsFn, each the other's VJP),
-        the conditioner is PyTorch ops over the training GEMM kernels; the two spline families and
-        their gradients are HIP kernels that read the conditioner output and the shared logits in
-        place (vcnf_amd.autograd)."""
-        gather, scatter = self._split_index(inputs.device)
-        xi, xt = autograd.SplitColumnsFn.apply(inputs, gather, scatter, self.num_identity_features)
+    def _composed(self, inputs, context, sampling, split, spline, merge):
+        """The coupling of coupling.py:70-125 as written there, composed from a channel partition (``split(inputs)`` ->
+        identity and transform halves, ``merge(inputs, xi, yt)`` its inverse) and the transform spline ``spline(xt, params)``
+        -> (yt, log|det| [B]); the conditioner and the unconditional spline of the identity half are the modules' own
+        calls.  _run picks the three."""
+        xi, xt = split(inputs)
         lad = 0.0
         uncond = self.unconditional_transform
         if sampling and uncond is not None:
             xi, lad = uncond.inverse(xi)
         params = self.transform_net(xi, context) if context is not None else self.transform_net(xi)
-        yt, lad_t = autograd.rqs_packed(xt, params, self._cfg(True), inverse=sampling)
+        yt, lad_t = spline(xt, params)
         lad = lad + lad_t
         if (not sampling) and uncond is not None:
             xi, lad_i = uncond.forward(xi)
             lad = lad + lad_i
-        out = autograd.MergeColumnsFn.apply(xi, yt, gather, scatter)
-        return out, lad
+        return merge(inputs, xi, yt), lad
 
-    def _run_image(self, inputs, context, sampling):
-        """4-D inputs [B, C, H, W], mask over channels (coupling.py:70-125 with :148-151): channel
-        gather / scatter and the convolutional conditioner are PyTorch-ROCm ops; the splines read
-        the conditioner output [B, C_t*P, H, W] in place through the strided elementwise kernel
-        (the reference reshapes and permutes it to [B, C_t, H, W, P] first)."""
-        k = self.num_bins
-        uncond = self.unconditional_transform
-        grad = self._needs_grad(inputs, context)
-        xi = inputs[:, self.identity_features]
-        xt = inputs[:, self.transform_features]
-        lad = 0.0
-        if sampling and uncond is not None:
-            xi, lad = uncond.inverse(xi)
-        params = self.transform_net(xi, context) if context is not None else self.transform_net(xi)
+    def _spline_image(self, xt, params, sampling, grad):
+        """The conditioner output [B, C_t*P, H, W] read in place through the strided elementwise kernel (the reference
+        reshapes and permutes it to [B, C_t, H, W, P] first); with a gradient, the packed spline and its VJP kernel."""
         if grad:
-            yt, le = autograd.rqs_packed(xt.contiguous(), params, self._cfg(True), inverse=sampling)
-            lad = lad + le
-        else:
-            yt, le = _lib.rqs_elementwise_image(xt, params, self._cfg(True), sampling)
-            lad = lad + le.sum(dim=(1, 2, 3))
-        if (not sampling) and uncond is not None:
-            xi, l2 = uncond.forward(xi)
-            lad = lad + l2
-        out = torch.empty_like(inputs)
-        out[:, self.identity_features] = xi
-        out[:, self.transform_features] = yt
-        return out, lad
+            return autograd.rqs_packed(xt.contiguous(), params, self._cfg(True), inverse=sampling)
+        yt, le = _lib.rqs_elementwise_image(xt, params, self._cfg(True), sampling)
+        return yt, le.sum(dim=(1, 2, 3))
 
-    def _run_per_feature(self, inputs, context, sampling):
-        """Per-feature tails / bounds (the circular NSF layers, wrapper.py:90-187): the coupling of
-        coupling.py:70-125 with both spline families evaluated group by group
-        (utils.splines.feature_groups)."""
-        if inputs.dim() != 2:
-            raise NotImplementedError("per-feature tails / tail bounds cover [B, features] inputs")
+    def _spline_per_feature(self, xt, params, sampling):
+        """Per-feature tails / bounds (the circular NSF layers, wrapper.py:90-187): the transform spline evaluated group
+        by group (utils.splines.feature_groups)."""
         k = self.num_bins
-        uncond = self.unconditional_transform
-        xi = inputs[:, self.identity_features]
-        xt = inputs[:, self.transform_features]
-        lad = 0.0
-        if sampling and uncond is not None:
-            xi, lad = uncond.inverse(xi)
-        params = self.transform_net(xi, context) if context is not None else self.transform_net(xi)
-        p = params.reshape(inputs.shape[0], self.num_transform_features, -1)
+        p = params.reshape(xt.shape[0], self.num_transform_features, -1)
         scale = self._logit_scale()
         yt, le = splines.unconstrained_rational_quadratic_spline(
             xt, p[..., :k] * scale, p[..., k:2 * k] * scale, p[..., 2 * k:], inverse=sampling, tails=self.tails,
             tail_bound=self.tail_bound, min_bin_width=self.min_bin_width, min_bin_height=self.min_bin_height,
             min_derivative=self.min_derivative)
-        lad = lad + le.sum(1)
-        if (not sampling) and uncond is not None:
-            xi, l2 = uncond.forward(xi)
-            lad = lad + l2
+        return yt, le.sum(1)
+
+    def _split_indexed(self, inputs):
+        return inputs[:, self.identity_features], inputs[:, self.transform_features]
+
+    def _merge_indexed(self, inputs, xi, yt):
         out = torch.empty_like(inputs)
         out[:, self.identity_features] = xi
         out[:, self.transform_features] = yt
-        return out, lad
+        return out
 
     def _run(self, inputs, context, sampling, log_q=None, sign=1.0):
         self._check(inputs)
+        path = None
         if self.per_feature or (inputs.dtype == torch.float64 and inputs.dim() == 2):
             # fp64: the plain structure of coupling.py:70-125 over the fp64 elementwise spline (csrc/rqs_f64.hip)
-            return fold_log_det(*self._run_per_feature(inputs, context, sampling), log_q, sign)
-        if inputs.dim() == 4:
-            return fold_log_det(*self._run_image(inputs, context, sampling), log_q, sign)
-        if self._needs_grad(inputs, context):
-            return fold_log_det(*self._run_differentiable(inputs, context, sampling), log_q, sign)
+            if inputs.dim() != 2:
+                raise NotImplementedError("per-feature tails / tail bounds cover [B, features] inputs")
+            path = (self._split_indexed, lambda xt, params: self._spline_per_feature(xt, params, sampling), self._merge_indexed)
+        elif inputs.dim() == 4:
+            # [B, C, H, W], mask over channels (coupling.py:148-151), convolutional conditioner: channel gather / scatter
+            # are PyTorch-ROCm indexing ops
+            grad = self._needs_grad(inputs, context)
+            path = (self._split_indexed, lambda xt, params: self._spline_image(xt, params, sampling, grad), self._merge_indexed)
+        elif self._needs_grad(inputs, context):
+            # training path: the channel partition and its inverse are one pass each (autograd.SplitColumnsFn /
+            # MergeColumnsFn, each the other's VJP), the conditioner is PyTorch ops over the training GEMM kernels; the two
+            # spline families and their gradients are HIP kernels that read the conditioner output and the shared logits
+            # in place (vcnf_amd.autograd)
+            gather, scatter = self._split_index(inputs.device)
+            path = (lambda x: autograd.SplitColumnsFn.apply(x, gather, scatter, self.num_identity_features),
+                    lambda xt, params: autograd.rqs_packed(xt, params, self._cfg(True), inverse=sampling),
+                    lambda x, xi, yt: autograd.MergeColumnsFn.apply(xi, yt, gather, scatter))
+        if path is not None:
+            return fold_log_det(*self._composed(inputs, context, sampling, *path), log_q, sign)
         if self.fused and fused.eligible(self, context):
             # conditioner + splines in one kernel (csrc/fused_layer.hip)
             return fused.run(self, inputs, context, sampling, log_q, sign)

@@ -17,6 +17,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _lib
+from .stacks import memo_plan, refresh_packed, run_cache           # noqa: F401  (both memo names stay importable from here)
 
 
 def _frag_index(n_rows_blocks, n_s4, chained, device):
@@ -316,26 +317,6 @@ def plan_stack(order, start, z, context):
     return start + len(run), run, sig
 
 
-def memo_plan(owner, attr, key, order, start, make, stamp, seen=None):
-    """``make()`` - a run plan (end, ...) or None - memoised in the dict ``owner.<attr>`` under ``key``.  An entry is
-    reused while the modules the plan has seen - the run and the flow that ended it, narrowed by ``seen`` - are the
-    same objects at the same positions of ``order`` with the same ``stamp``."""
-    plans = owner.__dict__.setdefault(attr, {})
-    hit = plans.get(key)
-    if hit is not None:
-        plan, mods, stamps = hit
-        if all(a is b for a, b in zip(order[start:start + len(mods)], mods)) and stamps == tuple(map(stamp, mods)):
-            return plan
-    plan = make()
-    mods = order[start:(start if plan is None else plan[0]) + 1]
-    if seen is not None:
-        mods = seen(mods)
-    if len(plans) > 64:
-        plans.clear()
-    plans[key] = (plan, mods, tuple(map(stamp, mods)))
-    return plan
-
-
 def _stack_stamp(flow):
     cp = flow.prqct
     return (cp.fused, cp.fused_precision, getattr(cp, 'range_safe', True), cp.tails, cp.num_bins, cp.per_feature,
@@ -366,12 +347,12 @@ def cached_plan_stack(owner, order, start, z, context):
 
 
 def stack_run(owner, order, start, z, context, density):
-    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS)."""
+    """NormalizingFlow's planner for this family (the contract: vcnf_amd.stacks)."""
     plan = cached_plan_stack(owner, order, start, z, context)
     if plan is None:
         return None
     end, run, sig = plan
-    return end, lambda z, log_q, sign: (run_stack(run, sig, z, context, not density, log_q, sign)[0], log_q)
+    return end, lambda z, log_q, sign: run_stack(run, sig, z, context, not density, log_q, sign)
 
 
 def run_stack(run, sig, z, context, sampling, log_q, sign):
@@ -380,11 +361,8 @@ def run_stack(run, sig, z, context, sampling, log_q, sign):
     refilled with the current addresses on every call (packed buffers are rewritten in place, so they rarely change)."""
     d_id, d_t, ctx_dim, hidden, blocks, prec, safe = sig[:7]
     first = run[0]
-    cache = first.__dict__.setdefault('_fused_rqs_stack', {})
-    ids = (tuple(id(c) for c in run), bool(sampling))
-    if cache.get('ids') != ids:
-        cache.clear()
-        cache['ids'] = ids
+    cache = run_cache(first, '_fused_rqs_stack', (tuple(id(c) for c in run), bool(sampling)))
+    if 'tab' not in cache:
         cache['tab'] = (_lib.RqsStackLayer * len(run))()
         cache['tab32'] = (_lib.RqsStackLayer * len(run))()
     want32 = prec == PREC_F16X3 and safe
@@ -407,38 +385,3 @@ def run_stack(run, sig, z, context, sampling, log_q, sign):
                                blocks, prec, first._cfg(True), sampling, logdet=log_q, sign=sign)
     del keep
     return out
-
-
-def refresh_packed(module):
-    """Invalidate every packed / derived weight cache under ``module``: the fused kernels read re-ordered copies of
-    the conditioner weights (this file, fused_affine.py, fused_final.py) and ``_LULinear`` a cached L.U product,
-    all keyed on (data_ptr, _version) of the parameters (likewise a GlowBlock's composed 1x1 convolution + ActNorm map).  An in-place update through ``.data`` (``p.data.copy_(ema)``,
-    initialisation on ``.data`` - an idiom of the reference API) does NOT bump ``_version``: call this afterwards.
-    ``NormalizingFlow`` / ``MultiscaleFlow`` call it on train() / eval() transitions and after load_state_dict().
-    Buffers are rewritten in place at the next use, so a captured HIP graph keeps its addresses."""
-    for m in module.modules():
-        d = m.__dict__
-        d.pop('_fused_slots', None)
-        d.pop('_init_done_host', None)              # ActNorm: re-read the device flag (a loaded state dict may reset it)
-        d.pop('_masked_stack', None)
-        d.pop('_masked_stack_plans', None)
-        d.pop('_fused_rqs_stack', None)
-        d.pop('_rqs_stack_plans', None)
-        if isinstance(d.get('_fused_pack'), dict):
-            for prec, (key, buf) in list(d['_fused_pack'].items()):
-                d['_fused_pack'][prec] = (None, buf)
-        for name in ('_fused_affine_pack', '_fused_affine_stack', '_fused_final_pack', '_fused_trunk_pack', '_fused_conv_pack',
-                     '_fused_conv3_pack', '_fused_taps_pack'):
-            if isinstance(d.get(name), dict):
-                d[name]['key'] = None
-                d[name].pop('desc', None)                   # stack launch descriptors (permutation rows)
-        if isinstance(d.get('_stack_plans'), dict):         # NormalizingFlow: memoised stack plans
-            d['_stack_plans'].clear()
-        if isinstance(d.get('_mats'), dict):
-            d['_mats'].clear()
-        if isinstance(d.get('_mix_cache'), dict):           # GlowBlock: composed 1x1 convolution + ActNorm per direction
-            for k, v in d['_mix_cache'].items():
-                if isinstance(v, dict):
-                    v['key'] = None
-            d['_mix_cache']['norm_ready'] = False
-    return module

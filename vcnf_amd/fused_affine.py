@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .stacks import memo_plan, run_cache
 
 
 def _linears(mlp):
@@ -223,41 +224,48 @@ def _struct_key(f):
     return None
 
 
+def _stamp(f):
+    return getattr(f, 'fused', None), _struct_key(f)
+
+
 def cached_plan(owner, order, start, z, inverse):
-    """plan_stack memoised on the calling model for evaluations without autograd: the plan depends only on the
-    modules in ``order`` (identity, their ``fused`` switches), the position, the direction and the feature count."""
+    """plan_stack memoised on the calling model (vcnf_amd.stacks.memo_plan) for evaluations without autograd: the plan
+    depends only on the modules it has read (identity, their ``fused`` switches, _struct_key), the position, the
+    direction and the feature count."""
     if torch.is_grad_enabled():
         return plan_stack(order, start, z, inverse)
-    key = (start, bool(inverse), z.dim(), z.shape[-1], z.dtype, tuple(map(id, order)),
-           tuple(getattr(f, 'fused', None) for f in order), tuple(_struct_key(f) for f in order))
-    plans = owner.__dict__.setdefault('_stack_plans', {})
-    if key not in plans:
-        if len(plans) > 32:
-            plans.clear()
-        plans[key] = plan_stack(order, start, z, inverse)
-    return plans[key]
+
+    def make():
+        # without a run plan_stack has read no further than [Permute, block, Permute, the flow that stopped it]: an end
+        # alone (mapped back to None below) has the memo watch those four, where its None would watch order[start] only
+        return plan_stack(order, start, z, inverse) or (start + 3,)
+    key = (start, bool(inverse), z.dim(), z.shape[-1], z.dtype, len(order), id(order[start]))
+    plan = memo_plan(owner, '_stack_plans', key, order, start, make, _stamp)
+    return plan if len(plan) > 1 else None
 
 
 def stack_run(owner, order, start, z, context, density):
-    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS)."""
+    """NormalizingFlow's planner for this family (the contract: vcnf_amd.stacks)."""
     plan = cached_plan(owner, order, start, z, density)
     if plan is None:
         return None
     end, steps, trailing = plan
     core = steps[0][0].flows[1]
     code = _lib.scale_code(core.scale, core.scale_map)
-    return end, lambda z, log_q, sign: (run_stack(steps, trailing, z, code, density, log_q, sign)[0], log_q)
+    return end, lambda z, log_q, sign: run_stack(steps, trailing, z, code, density, log_q, sign)
 
 
 def run_stack(steps, trailing, z, code, inverse, log_q, sign):
     """Execute a planned run (see plan_stack) in one launch."""
     first = steps[0][0]
-    cache = first.__dict__.setdefault('_fused_affine_stack', {})
-    # validity of everything cached below: the run's blocks and the (address, version) of their conditioner parameters
-    ids = tuple(id(b) for b, _ in steps)
-    if cache.get('ids') != ids:
-        cache.clear()
-        cache['ids'] = ids
+    # validity of everything cached below: the run's blocks, their structure (a swapped param_map brings other parameters)
+    # and the (address, version) of their conditioners' parameters
+    cache = run_cache(first, '_fused_affine_stack', tuple(id(b) for b, _ in steps))
+    struct = tuple((_struct_key(b), None if p is None else (id(p), _struct_key(p))) for b, p in steps)
+    if cache.get('struct') != struct:
+        cache['struct'] = struct
+        cache.pop('params', None)
+    if 'params' not in cache:
         cache['params'] = [p for b, _ in steps for lin in _linears(b.flows[1].param_map)[0] for p in (lin.weight, lin.bias)]
     key = tuple((p.data_ptr(), p._version) for p in cache['params'])
     if cache.get('key') != key:
@@ -279,8 +287,7 @@ def run_stack(steps, trailing, z, code, inverse, log_q, sign):
         else:
             cache['wpack_h3'] = new3
         cache['key'] = key
-    dkey = (bool(inverse), z.shape[1], str(z.device), None if trailing is None else (id(trailing), _struct_key(trailing)),
-            tuple((_struct_key(b), None if p is None else (id(p), _struct_key(p))) for b, p in steps))
+    dkey = (bool(inverse), z.shape[1], str(z.device), None if trailing is None else (id(trailing), _struct_key(trailing)), struct)
     desc = cache.setdefault('desc', {}).get(bool(inverse))
     if desc is None or desc[0] != dkey:
         (l1, _, l3), slope = _linears(first.flows[1].param_map)

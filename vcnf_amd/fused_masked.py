@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .fused import memo_plan
+from .stacks import add_log_det, memo_plan, run_cache
 
 MAX_LAYERS = 4096
 
@@ -123,8 +123,8 @@ def cached_plan(owner, order, start, z):
 
 
 def stack_run(owner, order, start, z, context, density):
-    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS); the launch returns a
-    new log_q when autograd records the run."""
+    """NormalizingFlow's planner for this family (the contract: vcnf_amd.stacks); the launch returns a new log_q
+    when autograd records the run."""
     p = cached_plan(owner, order, start, z)
     if p is None:
         return None
@@ -136,11 +136,7 @@ def run(steps, z, inverse, log_q, sign):
     """Execute a planned run in one launch.  The table of parameter addresses lives on the first layer of the run and is
     rebuilt when an address changes (parameters are read in place: in-place updates need nothing)."""
     first = steps[0][0]
-    cache = first.__dict__.setdefault('_masked_stack', {})
-    ids = tuple(id(f) for f, _ in steps)
-    if cache.get('ids') != ids:
-        cache.clear()
-        cache['ids'] = ids
+    cache = run_cache(first, '_masked_stack', tuple(id(f) for f, _ in steps))
     # the tensors behind the table (parameters and the mask buffers; re-read from the modules: a re-assigned Parameter is seen)
     tens = []
     for flow, (kind, h, slope, ts) in steps:
@@ -168,9 +164,7 @@ def run(steps, z, inverse, log_q, sign):
             cache['goff_key'] = key
         params = [t for flow, (kind, h, slope, _) in steps for t in _layer_tensors(flow, kind)[1:] if t is not None]
         out, ld = MaskedStackFn.apply(z, cache['table'], cache['goff'], cache['n'], cache['n_grad'], bool(inverse), *params)
-        if log_q is not None:
-            return out, log_q + sign * ld
-        return out, (ld if sign == 1.0 else sign * ld)
+        return add_log_det(out, ld, log_q, sign)
     return _lib.masked_affine_stack(z, cache['table'], cache['n'], inverse, logdet=log_q, sign=sign)
 
 

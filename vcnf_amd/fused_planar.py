@@ -18,6 +18,7 @@ from . import _lib
 from .autograd import PlanarRadialStackFn, needs_grad
 from .flows.planar import NEGATIVE_SLOPE, Planar
 from .flows.radial import Radial
+from .stacks import add_log_det
 
 _STRUCTURE = {}               # (kinds, device, dtype) -> see _structure; insertion order is the order of last use
 _STRUCTURE_LIMIT = 64
@@ -75,7 +76,7 @@ def plan(order, start, z, density):
 
 
 def stack_run(owner, order, start, z, context, density):
-    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS).  The inverse has no
+    """NormalizingFlow's planner for this family (the contract: vcnf_amd.stacks).  The inverse has no
     differentiable kernel path: a density pass that autograd records takes the layers one by one."""
     p = plan(order, start, z, density)
     if p is None:
@@ -145,8 +146,6 @@ def run(flows, z, density, log_q, sign):
         if density:
             raise _lib.VcnfError("the leaky_relu inverse has no differentiable kernel path")
         out, ld = PlanarRadialStackFn.apply(z2, va, vb, sc, codes)
-        if log_q is not None:
-            return out.reshape(z.shape), log_q + sign * ld
-        return out.reshape(z.shape), (ld if sign == 1.0 else sign * ld)
+        return add_log_det(out.reshape(z.shape), ld, log_q, sign)
     out, log_q = _lib.planar_radial_stack(z2, codes, va, vb, sc, inverse=density, logdet=log_q, sign=sign)
     return out.reshape(z.shape), log_q

@@ -18,6 +18,7 @@ from .distributions.mh_proposal import DiagGaussianProposal
 from .distributions.target import CircularGaussianMixture, RingMixture, TwoMoons
 from .flows.base import fold_log_det
 from .flows.stochastic import HamiltonianMonteCarlo
+from .stacks import add_log_det
 
 MAX_POINTS = 1 << 16          # n_layers (steps + 1) of one launch: the entry point's limit
 
@@ -66,7 +67,7 @@ def plan(order, start, z):
 
 
 def stack_run(owner, order, start, z, context, density):
-    """NormalizingFlow's planner for this family (the contract is at vcnf_amd.core._STACKS); the same in both pass
+    """NormalizingFlow's planner for this family (the contract: vcnf_amd.stacks); the same in both pass
     directions."""
     p = plan(order, start, z)
     if p is None:
@@ -104,9 +105,7 @@ def run(flows, z, log_q, sign):
     noise, unif = draws(z, len(flows))
     if needs_grad(z, step, mass, sqrt_mass):
         out, ld = HmcStackFn.apply(z, step, mass, sqrt_mass, noise, unif, flows[0].steps, target._family, table, scale)
-        if log_q is not None:
-            return out, log_q + sign * ld
-        return out, (ld if sign == 1.0 else sign * ld)
+        return add_log_det(out, ld, log_q, sign)
     out, ld = _lib.hmc_stack(z, noise, unif, step, mass, sqrt_mass, flows[0].steps, target._family, table, scale)
     return fold_log_det(out, ld, log_q, sign)
 

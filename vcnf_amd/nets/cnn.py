@@ -56,7 +56,7 @@ class ConvNet2d(nn.Module):
         return bool(_lib.lib().vcnf_conv1x1_supported(c2.in_channels, c2.out_channels))
 
     def _packed(self, slot, weight, make):
-        """``make()``'s packed buffer of ``weight``, kept in ``self.__dict__[slot]`` as {'key', 'buf'} (fused.refresh_packed
+        """``make()``'s packed buffer of ``weight``, kept in ``self.__dict__[slot]`` as {'key', 'buf'} (stacks.refresh_packed
         clears the key) and rebuilt when the parameter's storage, version or device changes."""
         key = (weight.data_ptr(), weight._version, str(weight.device))
         cache = self.__dict__.setdefault(slot, {})
