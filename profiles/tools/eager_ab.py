@@ -5,7 +5,7 @@ loaded under another name.  Device code is the same library in both when only ho
     python profiles/tools/eager_ab.py OTHER_CHECKOUT [BATCH]
 
 Rows: C3 on the three-step path (host-bound, one planner call per layer), C3 fp16x3 (12 layers in one launch), C2 (the
-affine family's run).  Ten alternating rounds each; minimum, median and maximum per side."""
+affine family's run), Glow (one GlowBlock(24, 32) on [B, 24, 8, 8]: the composed mixer and the packed 1x1 convolution).  Ten alternating rounds each; minimum, median and maximum per side."""
 import importlib.util
 import os
 import sys
@@ -45,6 +45,12 @@ def c2(nf):
     return nf.NormalizingFlow(nf.distributions.DiagGaussian(32), flows).cuda()
 
 
+def glow(nf):
+    torch.manual_seed(0)
+    m = nf.NormalizingFlow(nf.distributions.DiagGaussian((24, 8, 8)), [nf.flows.GlowBlock(24, 32, init_zeros=False)]).cuda()
+    return m.eval()         # (the first of the warm-up calls initialises the ActNorm)
+
+
 def timeit(fn, n):
     torch.cuda.synchronize()
     t = time.perf_counter()
@@ -58,9 +64,9 @@ def main():
     old = load_as("vcnf_other", sys.argv[1])
     b = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
     rows = (("C3 split (three-step)", lambda nf: c3(nf, fused=False), 64, 16, 100), ("C3 fp16x3", c3, 64, 16, 500),
-            ("C2", c2, 32, None, 500))
+            ("C2", c2, 32, None, 500), ("Glow", glow, (24, 8, 8), None, 500))
     for name, mk, d, c, n in rows:
-        x = torch.randn(b, d, device="cuda")
+        x = torch.randn(b, d, device="cuda") if isinstance(d, int) else torch.randn(b, *d, device="cuda")
         kw = {"context": torch.randn(b, c, device="cuda")} if c else {}
         models = {"other": mk(old), "this": mk(new)}
         res = {k: [] for k in models}

@@ -542,7 +542,9 @@ def test_affine_stack_single_launch_matches_per_layer(hip, d, widths, mode, spli
     with torch.no_grad():
         model.fuse_affine_stacks = True
         model.log_prob(x)
-        addr = model.flows[0].__dict__['_fused_affine_stack']['wpack'].data_ptr()
+        from vcnf_amd import derived
+        addr = [(id(m), slot, t.data_ptr()) for m, slot, t in derived.buffers(model)]      # the run's buffers and each block's
+        assert any(m is model.flows[0] and slot == 'affine_run' for m, slot, _ in derived.buffers(model))
         for step in range(2):
             for p in model.parameters():
                 if step == 0:
@@ -554,7 +556,7 @@ def test_affine_stack_single_launch_matches_per_layer(hip, d, widths, mode, spli
             model.fuse_affine_stacks = True
             lp1 = model.log_prob(x)
             z1, _ = model.sample_from(eps)
-            assert model.flows[0].__dict__['_fused_affine_stack']['wpack'].data_ptr() == addr
+            assert [(id(m), slot, t.data_ptr()) for m, slot, t in derived.buffers(model)] == addr
             model.fuse_affine_stacks = False
             assert_close(lp1, model.log_prob(x).cpu(), rtol=2e-6, atol=2e-5, what="stack after weight update %d" % step)
             assert torch.equal(z1, model.sample_from(eps)[0])

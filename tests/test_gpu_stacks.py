@@ -9,7 +9,7 @@ from torch import nn
 import stochastic_ref as sref
 import vcnf_amd as nf
 from helpers import assert_close
-from vcnf_amd import fused, fused_affine, fused_masked, fused_planar, fused_stochastic
+from vcnf_amd import derived, fused, fused_affine, fused_masked, fused_planar, fused_stochastic
 
 pytestmark = pytest.mark.gpu
 
@@ -81,10 +81,10 @@ def test_affine_plan_memo_follows_structural_edits(hip):
         with torch.no_grad():
             return (m.log_prob(x),) + tuple(m.sample_from(eps))
     first = both(model)
-    plans = dict(model.__dict__["_stack_plans"])
+    plans = dict(derived.plans(model, "_stack_plans"))
     assert len(plans) == 2 and all(hit[0][0] == 16 for hit in plans.values())           # one run per direction, all 16 flows
     again = both(model)
-    assert all(model.__dict__["_stack_plans"][k] is v for k, v in plans.items()), "the second call planned again"
+    assert all(derived.plans(model, "_stack_plans")[k] is v for k, v in plans.items()), "the second call planned again"
     assert all(torch.equal(a, b) for a, b in zip(first, again))
     for what, edit in AFFINE_EDITS:
         edit(model)

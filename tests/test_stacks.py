@@ -4,7 +4,7 @@ import pytest
 import torch
 
 import vcnf_amd as nf
-from vcnf_amd import fused_affine
+from vcnf_amd import derived, fused_affine
 from vcnf_amd.stacks import add_log_det
 
 
@@ -63,7 +63,7 @@ def test_affine_cached_plan_reuses_a_plan_per_position(planner):
         fused_affine.cached_plan(owner, order, 0, z, False)              # the other direction is another plan
         fused_affine.cached_plan(owner, order, 0, z.double(), True)      # so is another dtype
         assert planner == [0, 4, 0, 0]
-    assert "_stack_plans" in owner.__dict__
+    assert len(derived.plans(owner, "_stack_plans")) == 4              # on the shared plan memo, one per key
     with torch.enable_grad():                                           # autograd on: every call plans
         for _ in range(3):
             fused_affine.cached_plan(owner, order, 0, z, True)

@@ -5,8 +5,7 @@ Inference runs the 1x1 convolution and the ActNorm as ONE per-pixel channel map 
     sampling direction (glow.py:59-65):  z -> exp(s) * (W^-1 z) + t            M = diag(exp s) W^-1,  v = t
     density direction  (glow.py:67-73):  z -> W ((z - t) * exp(-s))            M = W diag(exp -s),    v = -W (t exp -s)
 with M, v composed in fp64 from the layer parameters (W = P L U or the dense W, mixing.py:71-95) and cached per
-direction, keyed on the parameters' (data_ptr, _version) like the packed conditioner weights and rewritten in place
-(stacks.refresh_packed invalidates it)."""
+direction: a derived slot (vcnf_amd.derived) keyed on the parameters like the packed conditioner weights."""
 import torch
 from torch import nn
 
@@ -15,6 +14,7 @@ from .coupling import AffineCouplingBlock
 from ..mixing import Invertible1x1Conv
 from ..normalization import ActNorm
 from ... import nets, _lib, autograd
+from ...derived import packed, tensor_key
 
 
 class GlowBlock(Flow):
@@ -46,11 +46,8 @@ class GlowBlock(Flow):
         conv, norm = self._mixer_parts()
         if not self.fused_mixers or conv is None or z.dim() != 4 or not z.is_cuda or z.dtype != torch.float32:
             return False
-        cache = self.__dict__.setdefault('_mix_cache', {})
-        if not cache.get('norm_ready'):           # the first batch initialises the ActNorm on the plain path
-            if not bool(norm.data_dep_init_done > 0.):
-                return False
-            cache['norm_ready'] = True            # (one host read per block and refresh_packed, not one per call)
+        if not norm._initialised():               # the first batch initialises the ActNorm on the plain path
+            return False                          # (one host read per block and refresh_packed, not one per call)
         if norm.s.numel() != z.shape[1] or norm.t.numel() != z.shape[1]:
             return False
         if autograd.needs_grad(z, *conv.parameters(), *norm.parameters()):
@@ -60,42 +57,34 @@ class GlowBlock(Flow):
     def _mixer(self, sampling):
         """(M, v, log|det| per pixel) of conv + ActNorm in the given direction, cached."""
         conv, norm = self._mixer_parts()
-        params = list(conv.parameters()) + [norm.s, norm.t]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in params)
-        cache = self.__dict__.setdefault('_mix_cache', {})
-        hit = cache.get(sampling)
-        if hit is not None and hit['key'] == key:
-            return hit['out']
-        with torch.no_grad():
-            c = conv.num_channels
+        key = tensor_key(list(conv.parameters()) + [norm.s, norm.t])
+        return packed(self, 'mixer_sampling' if sampling else 'mixer_density', key, lambda _: self._compose(sampling))
+
+    def _compose(self, sampling):
+        conv, norm = self._mixer_parts()
+        c = conv.num_channels
+        if conv.use_lu:
+            lower = torch.tril(conv.L, diagonal=-1).double() + torch.eye(c, dtype=torch.float64, device=conv.L.device)
+            upper = torch.triu(conv.U, diagonal=1).double() + torch.diag((conv.sign_S * torch.exp(conv.log_S)).double())
+            ld_w = torch.sum(conv.log_S)
+        else:
+            ld_w = torch.slogdet(conv.W)[1]
+        s, t = norm.s.reshape(c).double(), norm.t.reshape(c).double()
+        if sampling:
+            # the reference inverts in fp64 and rounds W^-1 to fp32 before the convolution (mixing.py:90-95, :104-106)
             if conv.use_lu:
-                lower = torch.tril(conv.L, diagonal=-1).double() + torch.eye(c, dtype=torch.float64, device=conv.L.device)
-                upper = torch.triu(conv.U, diagonal=1).double() + torch.diag((conv.sign_S * torch.exp(conv.log_S)).double())
-                ld_w = torch.sum(conv.log_S)
+                w_inv = (torch.inverse(upper) @ torch.inverse(lower)).float().double() @ conv.P.t().double()
             else:
-                ld_w = torch.slogdet(conv.W)[1]
-            s, t = norm.s.reshape(c).double(), norm.t.reshape(c).double()
-            if sampling:
-                # the reference inverts in fp64 and rounds W^-1 to fp32 before the convolution (mixing.py:90-95, :104-106)
-                if conv.use_lu:
-                    w_inv = (torch.inverse(upper) @ torch.inverse(lower)).float().double() @ conv.P.t().double()
-                else:
-                    w_inv = torch.inverse(conv.W.double()).float().double()
-                mat = torch.exp(s).view(c, 1) * w_inv
-                vec = t
-                ld = torch.sum(norm.s) - ld_w
-            else:
-                w = (conv.P.double() @ lower @ upper) if conv.use_lu else conv.W.double()
-                mat = w * torch.exp(-s).view(1, c)
-                vec = -(w @ (t * torch.exp(-s)))
-                ld = ld_w - torch.sum(norm.s)
-            out = (mat.float().contiguous(), vec.float().contiguous(), ld.float())
-            if hit is not None and hit['out'][0].device == out[0].device:
-                for old, new in zip(hit['out'], out):      # in place: a captured HIP graph keeps reading these addresses
-                    old.copy_(new)
-                out = hit['out']
-        cache[sampling] = {'key': key, 'out': out}
-        return out
+                w_inv = torch.inverse(conv.W.double()).float().double()
+            mat = torch.exp(s).view(c, 1) * w_inv
+            vec = t
+            ld = torch.sum(norm.s) - ld_w
+        else:
+            w = (conv.P.double() @ lower @ upper) if conv.use_lu else conv.W.double()
+            mat = w * torch.exp(-s).view(1, c)
+            vec = -(w @ (t * torch.exp(-s)))
+            ld = ld_w - torch.sum(norm.s)
+        return mat.float().contiguous(), vec.float().contiguous(), ld.float()
 
     def _mix(self, z, sampling):
         mat, vec, ld = self._mixer(sampling)

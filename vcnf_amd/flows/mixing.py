@@ -10,6 +10,7 @@ from torch.nn import functional as F
 
 from .base import Flow
 from .. import _lib, autograd
+from ..derived import memo, tensor_key
 
 
 class Permute(Flow):
@@ -28,7 +29,6 @@ class Permute(Flow):
             inv_perm[perm] = torch.arange(num_channels)
             self.register_buffer("perm", perm)
             self.register_buffer("inv_perm", inv_perm)
-        self._idx_cache = {}
 
     def gather_index(self, inverse):
         """int64 CPU/any-device index vector such that out[:, j] = z[:, idx[j]]."""
@@ -42,16 +42,10 @@ class Permute(Flow):
         raise NotImplementedError('The mode ' + self.mode + ' is not implemented.')
 
     def _idx32(self, inverse, device):
-        src = self.gather_index(inverse)
-        key = (bool(inverse), str(device), src.data_ptr() if self.mode == 'shuffle' else 0,
-               src._version if self.mode == 'shuffle' else 0)
-        hit = self._idx_cache.get(key)
-        if hit is None:
-            if len(self._idx_cache) > 8:
-                self._idx_cache.clear()
-            hit = src.to(device=device, dtype=torch.int32).contiguous()
-            self._idx_cache[key] = hit
-        return hit
+        key = (bool(inverse), str(device)) + (tensor_key((self.gather_index(inverse),), device=False)
+                                              if self.mode == 'shuffle' else ())
+        return memo(self, 'idx32', key,
+                    lambda _: self.gather_index(inverse).to(device=device, dtype=torch.int32).contiguous(), 8)
 
     def _gather(self, z, inverse):
         if torch.is_grad_enabled() and z.requires_grad:
@@ -124,19 +118,12 @@ class _RandomPermutation(Flow):
     def __init__(self, features):
         super().__init__()
         self.register_buffer('_permutation', torch.randperm(features))
-        self._idx_cache = {}
 
     def _idx32(self, inverse, device):
         src = self._permutation
-        key = (bool(inverse), str(device), src.data_ptr(), src._version)
-        hit = self._idx_cache.get(key)
-        if hit is None:
-            if len(self._idx_cache) > 8:
-                self._idx_cache.clear()
-            idx = torch.argsort(src) if inverse else src
-            hit = idx.to(device=device, dtype=torch.int32).contiguous()
-            self._idx_cache[key] = hit
-        return hit
+        key = (bool(inverse), str(device)) + tensor_key((src,), device=False)
+        return memo(self, 'idx32', key, lambda _: (torch.argsort(src) if inverse else src).to(
+            device=device, dtype=torch.int32).contiguous(), 8)
 
     def _gather(self, z, inverse):
         if z.dim() != 2 or z.shape[1] != len(self._permutation):
@@ -185,7 +172,6 @@ class _LULinear(Flow):
             stdv = 1.0 / np.sqrt(features)
             for p in (self.lower_entries, self.upper_entries, self.unconstrained_upper_diag):
                 nn.init.uniform_(p, -stdv, stdv)
-        self._mats = {}
 
     @property
     def upper_diag(self):
@@ -217,38 +203,29 @@ class _LULinear(Flow):
     def _matrix(self, inverse, col_index=None):
         """W^T (or W^-T) with an optional permutation folded in, cached when no grad is needed."""
         params = (self.lower_entries, self.upper_entries, self.unconstrained_upper_diag)
-        grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        key = (bool(inverse), None if col_index is None else (col_index.data_ptr(), col_index._version),
-               str(params[0].device)) + tuple((p.data_ptr(), p._version) for p in params)
-        if not grad and key in self._mats:
-            return self._mats[key]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return self._build_matrix(inverse, col_index)
+        key = (bool(inverse), str(params[0].device)) + tensor_key((col_index,) + params, device=False)
+        return memo(self, 'mats', key, lambda _: self._build_matrix(inverse, col_index), 4)
+
+    def _build_matrix(self, inverse, col_index):
         m = (self.weight_inverse() if inverse else self.weight()).t()
         if col_index is not None:
             # forward map then gather columns: (x M)[:, idx] = x M[:, idx];
             # gather columns then forward map: x[:, idx] M = x M[argsort(idx), :]
             m = m[:, col_index] if inverse else m[torch.argsort(col_index), :]
-        m = m.contiguous()
-        if not grad:
-            if len(self._mats) > 4:
-                self._mats.clear()
-            self._mats[key] = m.detach()
-        return m
+        return m.contiguous()
 
     def _mix_operands(self, inverse, col_index):
         """(M, v) of csrc/channel_mix.hip for this direction: out = x M^T + v, cached like ``_matrix``."""
         params = (self.lower_entries, self.upper_entries, self.unconstrained_upper_diag, self.bias)
-        key = ('mix', bool(inverse), None if col_index is None else (col_index.data_ptr(), col_index._version),
-               str(params[0].device)) + tuple((p.data_ptr(), p._version) for p in params)
-        hit = self._mats.get(key)
-        if hit is None:
-            with torch.no_grad():
-                m = self._matrix(inverse, col_index)                   # out = (x - bias) m   or   x m + bias
-                vec = -(self.bias.double() @ m.double()).float() if inverse else self.bias.detach().clone()
-                hit = (m.t().contiguous(), vec.contiguous())
-            if len(self._mats) > 8:
-                self._mats.clear()
-            self._mats[key] = hit
-        return hit
+        key = ('mix', bool(inverse), str(params[0].device)) + tensor_key((col_index,) + params, device=False)
+
+        def make(_):
+            m = self._matrix(inverse, col_index)                   # out = (x - bias) m   or   x m + bias
+            vec = -(self.bias.double() @ m.double()).float() if inverse else self.bias.detach().clone()
+            return m.t().contiguous(), vec.contiguous()
+        return memo(self, 'mats', key, make, 8)
 
     def _apply_linear(self, inputs, inverse, col_index=None):
         params = (self.lower_entries, self.upper_entries, self.unconstrained_upper_diag, self.bias)

@@ -20,6 +20,7 @@ from torch import nn
 
 from ..base import Flow, fold_log_det
 from ... import _lib, fused, fused_final, autograd
+from ...derived import memo, tensor_key
 from ...utils import splines
 
 
@@ -125,6 +126,11 @@ class PiecewiseRationalQuadraticCDF(Flow):
         return self._spline(inputs, True)
 
 
+# _index32: (memo slot, builder) of the int32 copy of either index buffer
+_INDEX32 = {'id': ('id32', lambda coupling: coupling.identity_features.to(torch.int32).contiguous()),
+            'tf': ('tf32', lambda coupling: coupling.transform_features.to(torch.int32).contiguous())}
+
+
 class PiecewiseRationalQuadraticCoupling(Flow):
     """``mask[i] > 0``: feature i is transformed by a spline whose logits come
     from ``transform_net(identity_features[, context])``; other features pass
@@ -179,7 +185,6 @@ class PiecewiseRationalQuadraticCoupling(Flow):
                 min_bin_height=min_bin_height, min_derivative=min_derivative)
         else:
             self.unconditional_transform = None
-        self._i32 = {}
         # use the single-kernel layer when shape and conditioner qualify (fused.eligible);
         # set False to force the three-step path (gather kernel, torch GEMMs, spline kernel)
         self.fused = True
@@ -205,15 +210,8 @@ class PiecewiseRationalQuadraticCoupling(Flow):
 
     # ------------------------------------------------------------ helpers
     def _index32(self, which):
-        src = self.identity_features if which == 'id' else self.transform_features
-        key = (which, src.device, src.data_ptr(), src._version)
-        hit = self._i32.get(key)
-        if hit is None:
-            if len(self._i32) > 8:
-                self._i32.clear()
-            hit = src.to(torch.int32).contiguous()
-            self._i32[key] = hit
-        return hit
+        slot, make = _INDEX32[which]
+        return memo(self, slot, tensor_key((self.identity_features if which == 'id' else self.transform_features,)), make, 8)
 
     def _logit_scale(self):
         # coupling.py:314-321: width/height logits are divided by sqrt(hidden width)
@@ -252,13 +250,10 @@ class PiecewiseRationalQuadraticCoupling(Flow):
         lists the identity features first, then the transform features; scattered = parts[:, s]
         puts them back.  Both directions are the HIP column-gather kernel (and each is the
         other's VJP), instead of two advanced-indexing gathers and two index_put scatters."""
-        key = ('split', str(device), self.identity_features.data_ptr(), self.identity_features._version)
-        hit = self._i32.get(key)
-        if hit is None:
+        def make(_):
             g = torch.cat([self.identity_features, self.transform_features]).to(device)
-            hit = (g.to(torch.int32).contiguous(), torch.argsort(g).to(torch.int32).contiguous())
-            self._i32[key] = hit
-        return hit
+            return g.to(torch.int32).contiguous(), torch.argsort(g).to(torch.int32).contiguous()
+        return memo(self, 'split32', (str(device),) + tensor_key((self.identity_features,), device=False), make, 8)
 
     def _needs_grad(self, inputs, context):
         if not torch.is_grad_enabled():

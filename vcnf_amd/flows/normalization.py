@@ -4,6 +4,7 @@ are plain torch reductions.  Reference: normflow/flows/normalization.py:8-38."""
 import torch
 
 from .affine.coupling import AffineConstFlow
+from ..derived import memos
 
 
 class ActNorm(AffineConstFlow):
@@ -29,12 +30,12 @@ class ActNorm(AffineConstFlow):
         """normalization.py:29 / :40 test the device flag on every call (a host synchronisation per layer and call,
         and not capturable into a HIP graph).  The flag only ever goes from 0 to 1, so the first positive answer is
         remembered on the host; load_state_dict() / refresh_packed() forget it."""
-        if self.__dict__.get('_init_done_host', False):
-            return True
-        done = bool(self.data_dep_init_done > 0.)
-        if done:
-            self.__dict__['_init_done_host'] = True
-        return done
+        seen = memos(self, 'init_done')           # empty until the flag was read as set (vcnf_amd.derived: host-side state)
+        if not seen:
+            if not bool(self.data_dep_init_done > 0.):
+                return False
+            seen[()] = True
+        return True
 
     def forward(self, z):
         if not self._initialised():

@@ -17,6 +17,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _lib
+from .derived import memo, packed
 from .stacks import memo_plan, refresh_packed, run_cache           # noqa: F401  (both memo names stay importable from here)
 
 
@@ -218,46 +219,40 @@ def precision_of(coupling):
     return PREC_F16X3 if mode == 'fp16x3' else PREC_F32
 
 
+def _param_slots(coupling):
+    return [(mod, name) for mod in coupling.transform_net.modules() for name in mod._parameters
+            if mod._parameters[name] is not None]
+
+
 def _param_key(coupling):
     """(data_ptr, _version) of every conditioner parameter.  ``net.parameters()`` walks the module tree on every call
     (half of the host time of an eager log_prob at small batches); the walk is done once and remembered as
     (owner module, name) slots, which are read through ``_parameters`` - a re-assigned Parameter is still seen;
     refresh_packed() forgets the slots (needed only after sub-MODULES were replaced)."""
-    slots = coupling.__dict__.get('_fused_slots')
-    if slots is None:
-        slots = [(mod, name) for mod in coupling.transform_net.modules() for name in mod._parameters
-                 if mod._parameters[name] is not None]
-        coupling.__dict__['_fused_slots'] = slots
     key = []
-    for mod, name in slots:
+    for mod, name in memo(coupling, 'param_slots', (), _param_slots, 1):
         p = mod._parameters[name]
         key.append((p.data_ptr(), p._version))
     return tuple(key)
 
 
+def _pack_f32(coupling):
+    return pack_layer(coupling.transform_net, coupling.num_transform_features, coupling._transform_dim_multiplier())
+
+
+def _pack_f16x3(coupling):
+    return pack_layer_h3(coupling.transform_net, coupling.num_transform_features, coupling._transform_dim_multiplier(),
+                         coupling._cfg(True).wh_scale, coupling.num_bins)
+
+
+_PACKS = {PREC_F32: ('rqs_f32', _pack_f32), PREC_F16X3: ('rqs_f16x3', _pack_f16x3)}
+
+
 def packed_weights(coupling, prec=None, key=None):
-    """Cached packed buffer of one matrix path; refreshed when any conditioner parameter changed.  A refresh of the
-    same size rewrites the existing device buffer in place, so a captured HIP graph that holds its address
-    (vcnf_amd.graphs) sees the new weights."""
-    net = coupling.transform_net
-    prec = precision_of(coupling) if prec is None else prec
-    if key is None:
-        key = _param_key(coupling)
-    packs = coupling.__dict__.setdefault('_fused_pack', {})
-    cache = packs.get(prec)
-    if cache is None or cache[0] != key:
-        with torch.no_grad():
-            if prec == PREC_F16X3:
-                buf = pack_layer_h3(net, coupling.num_transform_features, coupling._transform_dim_multiplier(),
-                                    coupling._cfg(True).wh_scale, coupling.num_bins)
-            else:
-                buf = pack_layer(net, coupling.num_transform_features, coupling._transform_dim_multiplier())
-            if cache is not None and cache[1].shape == buf.shape and cache[1].device == buf.device:
-                cache[1].copy_(buf)
-                buf = cache[1]
-        cache = (key, buf)
-        packs[prec] = cache
-    return cache[1]
+    """Packed buffer of one matrix path, a derived slot keyed on ``_param_key`` (vcnf_amd.derived: rebuilt when any
+    conditioner parameter changed, in place, so a captured HIP graph that holds its address sees the new weights)."""
+    slot, make = _PACKS[precision_of(coupling) if prec is None else prec]
+    return packed(coupling, slot, _param_key(coupling) if key is None else key, make)
 
 
 def run(coupling, inputs, context, sampling, log_q=None, sign=1.0):

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from .derived import packed, tensor_key
 from .stacks import memo_plan, run_cache
 
 
@@ -136,18 +137,8 @@ def h3_ok(block):
 
 def packed_weights(block):
     (l1, l2, l3), slope = _linears(block.flows[1].param_map)
-    params = (l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
-    key = tuple((p.data_ptr(), p._version, str(p.device)) for p in params)
-    cache = block.__dict__.setdefault('_fused_affine_pack', {})
-    if cache.get('key') != key:
-        cache['key'] = key
-        buf = pack(l1, l2, l3)
-        old = cache.get('buf')
-        if old is not None and old.shape == buf.shape and old.device == buf.device:
-            old.copy_(buf)           # in place: a captured HIP graph keeps reading this address
-        else:
-            cache['buf'] = buf
-    return cache['buf'], (l1, l2, l3), slope
+    key = tensor_key((l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias))
+    return packed(block, 'affine', key, lambda _: pack(l1, l2, l3)), (l1, l2, l3), slope
 
 
 def run(block, z, code, inverse, log_q=None, sign=1.0, in_gather=None, out_gather=None):
@@ -220,7 +211,7 @@ def _struct_key(f):
     perm = getattr(f, 'perm', None)
     if torch.is_tensor(perm):
         inv = getattr(f, 'inv_perm', perm)
-        return (perm.data_ptr(), perm._version, inv.data_ptr(), inv._version)
+        return tensor_key((perm, inv), device=False)
     return None
 
 
@@ -255,38 +246,31 @@ def stack_run(owner, order, start, z, context, density):
     return end, lambda z, log_q, sign: run_stack(steps, trailing, z, code, density, log_q, sign)
 
 
+def _pack_run(steps):
+    """(wpack, wpack_h3) of a run: the blocks' packs concatenated, and the split-half fragments of their second / third
+    dense layers (None when the hidden width is no multiple of 32)."""
+    wpack = torch.cat([packed_weights(b)[0] for b, _ in steps]).contiguous()
+    linears = [_linears(b.flows[1].param_map)[0] for b, _ in steps]
+    if linears[0][0].out_features % 32:
+        return wpack, None
+    return wpack, torch.cat([pack_h3(l2, l3) for _, l2, l3 in linears]).contiguous()
+
+
 def run_stack(steps, trailing, z, code, inverse, log_q, sign):
     """Execute a planned run (see plan_stack) in one launch."""
     first = steps[0][0]
     # validity of everything cached below: the run's blocks, their structure (a swapped param_map brings other parameters)
     # and the (address, version) of their conditioners' parameters
-    cache = run_cache(first, '_fused_affine_stack', tuple(id(b) for b, _ in steps))
+    ids = tuple(id(b) for b, _ in steps)
+    cache = run_cache(first, '_fused_affine_stack', ids)
     struct = tuple((_struct_key(b), None if p is None else (id(p), _struct_key(p))) for b, p in steps)
     if cache.get('struct') != struct:
         cache['struct'] = struct
-        cache.pop('params', None)
-    if 'params' not in cache:
         cache['params'] = [p for b, _ in steps for lin in _linears(b.flows[1].param_map)[0] for p in (lin.weight, lin.bias)]
-    key = tuple((p.data_ptr(), p._version) for p in cache['params'])
-    if cache.get('key') != key:
-        # one weight buffer for the run, shared by both directions and rewritten IN PLACE when a layer's pack changes: a
-        # captured HIP graph keeps reading the same address (GraphedFlow.refresh)
-        new = torch.cat([packed_weights(b)[0] for b, _ in steps]).contiguous()
-        old = cache.get('wpack')
-        if old is not None and old.shape == new.shape and old.device == new.device:
-            old.copy_(new)
-        else:
-            cache['wpack'] = new
-        # ... and the split-half fragments of the second / third dense layers (same in-place rule)
-        with torch.no_grad():
-            new3 = torch.cat([pack_h3(*_linears(b.flows[1].param_map)[0][1:]) for b, _ in steps]).contiguous() \
-                if _linears(first.flows[1].param_map)[0][0].out_features % 32 == 0 else None
-        old3 = cache.get('wpack_h3')
-        if new3 is not None and old3 is not None and old3.shape == new3.shape and old3.device == new3.device:
-            old3.copy_(new3)
-        else:
-            cache['wpack_h3'] = new3
-        cache['key'] = key
+    # one weight buffer for the run (and one of split-half fragments), shared by both directions: a derived slot on the
+    # first block, rewritten IN PLACE when a layer's pack changes (a captured HIP graph keeps reading the same address)
+    wpack, wpack_h3 = packed(first, 'affine_run', (ids, struct, tensor_key(cache['params'], device=False)),
+                             lambda _: _pack_run(steps))
     dkey = (bool(inverse), z.shape[1], str(z.device), None if trailing is None else (id(trailing), _struct_key(trailing)), struct)
     desc = cache.setdefault('desc', {}).get(bool(inverse))
     if desc is None or desc[0] != dkey:
@@ -308,6 +292,6 @@ def run_stack(steps, trailing, z, code, inverse, log_q, sign):
         cache['desc'][bool(inverse)] = desc
     _, layers, ga, gathers, c_in, hidden, slope = desc
     # (the split-half form keeps 32-row strips: two per wave = 1 KB x D of LDS per workgroup, D <= 64)
-    use_h3 = cache.get('wpack_h3') is not None and z.shape[1] <= 64 and all(h3_ok(b) for b, _ in steps)
-    return _lib.affine_stack_fused(z, cache['wpack'], layers, ga, gathers, c_in, hidden, slope, code,
-                                   inverse, logdet=log_q, sign=sign, wpack_h3=cache['wpack_h3'] if use_h3 else None)
+    use_h3 = wpack_h3 is not None and z.shape[1] <= 64 and all(h3_ok(b) for b, _ in steps)
+    return _lib.affine_stack_fused(z, wpack, layers, ga, gathers, c_in, hidden, slope, code,
+                                   inverse, logdet=log_q, sign=sign, wpack_h3=wpack_h3 if use_h3 else None)

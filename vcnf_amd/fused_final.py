@@ -11,6 +11,7 @@ scale and the log2(e) factors of the spline's exponentials (see pack).
 import torch
 
 from . import _lib
+from .derived import packed, tensor_key
 from .flows.base import fold_log_det
 from .fused import _split_halves, _as_floats
 
@@ -70,22 +71,13 @@ def pack(weight, bias, d_t, k, wh_scale):
 
 def packed_weights(coupling):
     lin = coupling.transform_net.final_layer
-    key = tuple((t.data_ptr(), t._version, str(t.device)) for t in (lin.weight, lin.bias))
-    cache = coupling.__dict__.setdefault('_fused_final_pack', {})
-    if cache.get('key') != key:
-        cache['key'] = key
-        with torch.no_grad():
-            buf = pack(lin.weight.detach(), lin.bias.detach(), coupling.num_transform_features, coupling.num_bins,
-                       float(coupling._cfg(True).wh_scale))
-        old = cache.get('buf')
-        if old is not None and old.shape == buf.shape and old.device == buf.device:
-            old.copy_(buf)
-        else:
-            cache['buf'] = buf
+    buf = packed(coupling, 'final', tensor_key((lin.weight, lin.bias)),
+                 lambda _: pack(lin.weight.detach(), lin.bias.detach(), coupling.num_transform_features, coupling.num_bins,
+                                float(coupling._cfg(True).wh_scale)))
     want = int(_lib.lib().vcnf_rqs_final_fused_pack_floats(coupling.num_transform_features,
                                                            coupling.transform_net.hidden_features, coupling.num_bins))
-    assert cache['buf'].numel() == want, (cache['buf'].numel(), want)
-    return cache['buf']
+    assert buf.numel() == want, (buf.numel(), want)
+    return buf
 
 
 def trunk_eligible(net, first_in, context):
@@ -117,18 +109,7 @@ def packed_trunk(coupling):
     net = coupling.transform_net
     params = [net.initial_layer.weight, net.initial_layer.bias] + [p for b in net.blocks for l in b.linear_layers
                                                                    for p in (l.weight, l.bias)]
-    key = tuple((t.data_ptr(), t._version, str(t.device)) for t in params)
-    cache = coupling.__dict__.setdefault('_fused_trunk_pack', {})
-    if cache.get('key') != key:
-        cache['key'] = key
-        with torch.no_grad():
-            buf = pack_trunk(net)
-        old = cache.get('buf')
-        if old is not None and old.shape == buf.shape and old.device == buf.device:
-            old.copy_(buf)
-        else:
-            cache['buf'] = buf
-    return cache['buf']
+    return packed(coupling, 'trunk', tensor_key(params), lambda _: pack_trunk(net))
 
 
 def _identity_kernel_ok(coupling):

@@ -6,6 +6,8 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from ..derived import packed, tensor_key
+
 
 class ConvNet2d(nn.Module):
     def __init__(self, channels, kernel_size, leaky=0.0, init_zeros=True, actnorm=False, weight_std=None):
@@ -55,32 +57,16 @@ class ConvNet2d(nn.Module):
             return False
         return bool(_lib.lib().vcnf_conv1x1_supported(c2.in_channels, c2.out_channels))
 
-    def _packed(self, slot, weight, make):
-        """``make()``'s packed buffer of ``weight``, kept in ``self.__dict__[slot]`` as {'key', 'buf'} (stacks.refresh_packed
-        clears the key) and rebuilt when the parameter's storage, version or device changes."""
-        key = (weight.data_ptr(), weight._version, str(weight.device))
-        cache = self.__dict__.setdefault(slot, {})
-        if cache.get('key') != key:
-            with torch.no_grad():
-                buf = make()
-            old = cache.get('buf')
-            if old is not None and old.shape == buf.shape and old.device == buf.device:
-                old.copy_(buf)           # in place: a captured HIP graph keeps reading this address
-            else:
-                cache['buf'] = buf
-            cache['key'] = key
-        return cache['buf']
-
     def _packed_conv1x1(self):
         c2 = self.net[2]
-        return self._packed('_fused_conv_pack', c2.weight,
-                            lambda: pack_conv1x1(c2.weight.detach().view(c2.out_channels, c2.in_channels)))
+        return packed(self, 'conv1x1', tensor_key((c2.weight,)),
+                      lambda _: pack_conv1x1(c2.weight.detach().view(c2.out_channels, c2.in_channels)))
 
     def _packed_conv3x3(self):
         c1 = self.net[0]
         k1 = c1.in_channels * 9              # k = ci * 9 + ky * 3 + kx, padded to whole k-steps
-        return self._packed('_fused_conv3_pack', c1.weight,
-                            lambda: pack_conv1x1(F.pad(c1.weight.detach().reshape(c1.out_channels, k1), (0, (-k1) % 16))))
+        return packed(self, 'conv3x3', tensor_key((c1.weight,)),
+                      lambda _: pack_conv1x1(F.pad(c1.weight.detach().reshape(c1.out_channels, k1), (0, (-k1) % 16))))
 
     def _first_two_fusable(self):
         """3x3 convolution (padding 1, stride 1) into 256 channels followed by the 256 -> 256 1x1 convolution: both on
@@ -96,9 +82,9 @@ class ConvNet2d(nn.Module):
     def _packed_taps(self):
         c3 = self.net[4]
         co = c3.out_channels                 # row t * c_out + o
-        return self._packed('_fused_taps_pack', c3.weight,
-                            lambda: pack_conv1x1(c3.weight.detach().permute(2, 3, 0, 1).reshape(9 * co, c3.in_channels),
-                                                 row_blocks=(9 * co + 31) // 32))
+        return packed(self, 'taps', tensor_key((c3.weight,)),
+                      lambda _: pack_conv1x1(c3.weight.detach().permute(2, 3, 0, 1).reshape(9 * co, c3.in_channels),
+                                             row_blocks=(9 * co + 31) // 32))
 
     def _all_three_fusable(self):
         """... followed by a 3x3 convolution (padding 1) to at most 56 channels: its nine taps run as one more matrix

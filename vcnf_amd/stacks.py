@@ -26,18 +26,20 @@ Plans
 Run caches
     What a launch needs besides the plan (tables of addresses, concatenated packs, descriptors) lives on the run's first
     module in the dict ``run_cache`` returns, emptied when the run's modules are no longer the ones it was filled for.
-    Packed weights keep their own (data_ptr, _version) keys and are rewritten in place: a captured HIP graph holds their
-    addresses.
+    Weights a run packs or concatenates are derived buffers: slots of ``vcnf_amd.derived`` (keyed, rewritten in place -
+    the contract is that module's docstring), not entries of the run cache.
 
-``refresh_packed`` invalidates all of it after parameters changed behind autograd's back.
+Plan memos and run caches live in the containers of ``vcnf_amd.derived``, whose ``refresh_packed`` empties them along
+with every derived buffer's key after parameters changed behind autograd's back.
 """
+from .derived import plans as _plans, refresh_packed, runs as _runs           # noqa: F401  (refresh_packed stays importable from here)
 
 
 def memo_plan(owner, attr, key, order, start, make, stamp, seen=None):
-    """``make()`` - a run plan (end, ...) or None - memoised in the dict ``owner.<attr>`` under ``key``.  An entry is
+    """``make()`` - a run plan (end, ...) or None - memoised on ``owner`` in the plan memo ``attr`` under ``key``.  An entry is
     reused while the modules the plan has seen - the run and the flow that ended it, narrowed by ``seen`` - are the
     same objects at the same positions of ``order`` with the same ``stamp``."""
-    plans = owner.__dict__.setdefault(attr, {})
+    plans = _plans(owner, attr)
     hit = plans.get(key)
     if hit is not None:
         plan, mods, stamps = hit
@@ -54,9 +56,9 @@ def memo_plan(owner, attr, key, order, start, make, stamp, seen=None):
 
 
 def run_cache(first, name, ids):
-    """The dict ``first.<name>`` of a run whose identity is ``ids``, emptied (but for ``'ids'``) when it was filled for
-    another run."""
-    cache = first.__dict__.setdefault(name, {})
+    """The run cache ``name`` on ``first`` of a run whose identity is ``ids``, emptied (but for ``'ids'``) when it was
+    filled for another run."""
+    cache = _runs(first, name)
     if cache.get('ids') != ids:
         cache.clear()
         cache['ids'] = ids
@@ -69,37 +71,3 @@ def add_log_det(out, log_det, log_q, sign):
     if log_q is not None:
         return out, log_q + sign * log_det
     return out, (log_det if sign == 1.0 else sign * log_det)
-
-
-def refresh_packed(module):
-    """Invalidate every packed / derived weight cache under ``module``: the fused kernels read re-ordered copies of
-    the conditioner weights (fused.py, fused_affine.py, fused_final.py) and ``_LULinear`` a cached L.U product,
-    all keyed on (data_ptr, _version) of the parameters (likewise a GlowBlock's composed 1x1 convolution + ActNorm map).  An in-place update through ``.data`` (``p.data.copy_(ema)``,
-    initialisation on ``.data`` - an idiom of the reference API) does NOT bump ``_version``: call this afterwards.
-    ``NormalizingFlow`` / ``MultiscaleFlow`` call it on train() / eval() transitions and after load_state_dict().
-    Buffers are rewritten in place at the next use, so a captured HIP graph keeps its addresses."""
-    for m in module.modules():
-        d = m.__dict__
-        d.pop('_fused_slots', None)
-        d.pop('_init_done_host', None)              # ActNorm: re-read the device flag (a loaded state dict may reset it)
-        d.pop('_masked_stack', None)
-        d.pop('_fused_rqs_stack', None)
-        for name in ('_stack_plans', '_masked_stack_plans', '_rqs_stack_plans'):    # NormalizingFlow: the plan memos
-            if isinstance(d.get(name), dict):
-                d[name].clear()
-        if isinstance(d.get('_fused_pack'), dict):
-            for prec, (key, buf) in list(d['_fused_pack'].items()):
-                d['_fused_pack'][prec] = (None, buf)
-        for name in ('_fused_affine_pack', '_fused_affine_stack', '_fused_final_pack', '_fused_trunk_pack', '_fused_conv_pack',
-                     '_fused_conv3_pack', '_fused_taps_pack'):
-            if isinstance(d.get(name), dict):
-                d[name]['key'] = None
-                d[name].pop('desc', None)                   # stack launch descriptors (permutation rows)
-        if isinstance(d.get('_mats'), dict):
-            d['_mats'].clear()
-        if isinstance(d.get('_mix_cache'), dict):           # GlowBlock: composed 1x1 convolution + ActNorm per direction
-            for k, v in d['_mix_cache'].items():
-                if isinstance(v, dict):
-                    v['key'] = None
-            d['_mix_cache']['norm_ready'] = False
-    return module
