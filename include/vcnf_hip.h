@@ -503,11 +503,12 @@ int vcnf_affine_coupling_f32(const float* z, const float* param, float* out, flo
  * vcnf_affine_layer_fused_f32) and the column permutations between them in a single launch:
  * the reference's loop over [AffineCouplingBlock, Permute] pairs of NormalizingFlow.log_prob /
  * .sample (core.py:150-155, :176-183; flows/affine/coupling.py:225-258; flows/mixing.py:32-54)
- * for config C1 / C2 style stacks.  ``layers`` (HOST array, at most 16) is in EXECUTION order of the
- * requested direction; gather_before = row of ``gathers`` [n_gather_rows][features] (device int32) whose
+ * for config C1 / C2 style stacks.  ``layers`` (HOST array, at most VCNF_AFFINE_STACK_MAX_LAYERS) is in EXECUTION
+ * order of the requested direction; gather_before = row of ``gathers`` [n_gather_rows][features] (device int32) whose
  * permutation the layer's input columns go through (the layer sees z[:, row]), -1 for none;
  * gather_after likewise for the result.  wpack = the layers' vcnf_affine_layer_fused_pack_floats
  * buffers back to back, in the same order.  log|det| of all layers is added to / stored in logdet. */
+enum { VCNF_AFFINE_STACK_MAX_LAYERS = 16 };
 typedef struct {
   int32_t cond_off, t_off, d_t;
   int32_t gather_before;
@@ -734,11 +735,13 @@ int vcnf_cc_gaussian_reduce_rows_f64(const double* per_sample, const int32_t* ro
  *              is written in full.  partials == NULL: only dz is computed (no table needs a gradient)
  *   reduce_partials: d_loc, d_log_scale [M, D] and d_log_w [M] = the sum of `groups` blocks in a fixed order
  * vcnf_gmm_bwd_groups is a pure function of its arguments (no device query; 0 for an unsupported shape).
- * Supported: features >= 1, modes >= 1, features * modes <= 8192, else VCNF_ERR_SHAPE (groups < 1 as well); unknown
- * ld_mode -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a
- * pointer not aligned to its element size -> VCNF_ERR_ALIGN.  The tables are staged in LDS once per workgroup;
+ * Supported: features >= 1, modes >= 1, features * modes <= VCNF_GMM_MAX_TABLE, else VCNF_ERR_SHAPE (groups < 1 as
+ * well); unknown ld_mode -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer ->
+ * VCNF_ERR_NULL; a pointer not aligned to its element size -> VCNF_ERR_ALIGN.  The tables are staged in LDS once per
+ * workgroup;
  * 16-byte (8-byte) accesses are used when features % V == 0 and the row buffers are aligned to them.  No atomics,
  * no allocation, no host synchronisation: every call is bitwise reproducible and capturable. */
+enum { VCNF_GMM_MAX_TABLE = 8192 };
 int64_t vcnf_gmm_bwd_groups(int64_t batch, int32_t features, int32_t modes);
 int vcnf_gmm_log_prob_f32(const float* z, const float* loc, const float* log_scale, const float* log_w, float* logp,
                           int64_t batch, int32_t features, int32_t modes, int ld_mode, float sign, void* stream);
@@ -852,12 +855,14 @@ int vcnf_tail_reduce_partials_f64(const double* partials, int64_t groups, int32_
  * vcnf_mvn_bwd_groups is a pure function of its arguments (no device query; 0 for an unsupported shape): one workgroup
  * per 64 samples, at most 256, and at most 2^22 elements of partial blocks in all (16 MiB in fp32, 32 MiB in fp64).
  * Workgroup k takes the sample tiles k, k + groups, ...: every sum's order is fixed by the shape alone.
- * 1 <= features <= 128 and batch >= 0, else VCNF_ERR_SHAPE (groups < 1 as well); unknown family or ld_mode ->
- * VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a pointer not
- * aligned to its element size -> VCNF_ERR_ALIGN.  16-byte (8-byte) accesses are used when features % V == 0 and the
+ * 1 <= features <= VCNF_MVN_MAX_DIM and batch >= 0, else VCNF_ERR_SHAPE (groups < 1 as well); unknown family or
+ * ld_mode -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a
+ * pointer not aligned to its element size -> VCNF_ERR_ALIGN.
+ * 16-byte (8-byte) accesses are used when features % V == 0 and the
  * [B, D] buffers are aligned to them.  No atomics, no allocation, no host synchronisation: every call is bitwise
  * reproducible and capturable. */
 enum { VCNF_MVN_GAUSSIAN = 0, VCNF_MVN_STUDENT_T = 1 };
+enum { VCNF_MVN_MAX_DIM = 128 };
 int64_t vcnf_mvn_bwd_groups(int64_t batch, int32_t features);
 int vcnf_mvn_log_prob_f32(const float* z, const float* loc, const float* tri_inv, const float* consts, float* logp,
                           int64_t batch, int32_t features, int family, int ld_mode, float sign, void* stream);
@@ -889,8 +894,9 @@ int vcnf_mvn_reduce_partials_f64(const double* partials, int64_t groups, int32_t
  * (csrc/planar_radial.hip).  z / out [B, D] contiguous, D = features <= 256 (vcnf_planar_radial_supported), K =
  * n_layers >= 1 without an upper limit.  The layers arrive in the order they are applied, as EFFECTIVE operands the
  * caller computes (no parameter formula lives in a kernel):
- *   kind [K] int32   0 planar tanh, 1 planar leaky_relu, 2 radial.  Given twice: `kind` in HOST memory, validated
- *                    before anything is launched, and `kind_dev`, the same values on the device, read by the kernel.
+ *   kind [K] int32   VCNF_PLANAR_TANH, VCNF_PLANAR_LEAKY (leaky_relu) or VCNF_RADIAL.  Given twice: `kind` in HOST
+ *                    memory, validated before anything is launched, and `kind_dev`, the same values on the device,
+ *                    read by the kernel.
  *                    That the two agree is the CALLER'S contract and is not checked (checking would read device
  *                    memory back): with differing copies the validation passes for layers other than those the kernel
  *                    runs, e.g. the inverse on a kind it does not have, or a read of a NULL vb
@@ -921,6 +927,7 @@ int vcnf_mvn_reduce_partials_f64(const double* partials, int64_t groups, int32_t
  * 1 -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch.  16-byte (8-byte) accesses are used when
  * features % V == 0 and the [., D] buffers are aligned to them.  No atomics, no allocation, no host synchronisation:
  * every call is bitwise reproducible and capturable. */
+enum { VCNF_PLANAR_TANH = 0, VCNF_PLANAR_LEAKY = 1, VCNF_RADIAL = 2 };
 int vcnf_planar_radial_supported(int32_t features);
 int32_t vcnf_planar_radial_checkpoint_every(int32_t features);
 int64_t vcnf_planar_radial_bwd_groups(int64_t batch, int32_t features, int32_t n_layers);
@@ -999,19 +1006,23 @@ int vcnf_target_log_prob_f64(const double* z, const double* table, double* logp,
  *     parameter gradients for the whole batch there).  g_in
  *     [B, 2]; g_step, g_mass, g_sqrt_mass [K, 2] summed over the batch: every workgroup adds its samples' terms into
  *     its own block of `workspace` (`groups` blocks of 6 K elements, uninitialised on entry; 1 <= groups <=
- *     min(1024, ceil(B / 256)), the number of workgroups) and a second launch adds the blocks in a fixed order.
+ *     min(VCNF_HMC_MAX_BWD_GROUPS, ceil(B / VCNF_HMC_BLOCK)), the number of workgroups) and a second launch adds the
+ *     blocks in a fixed order.
  *   mh_walk: `steps` >= 0 random-walk steps with eps [steps, B, 2] standard-normal and w [steps, B] uniform draws and
  *     prop_scale [2] the proposal's standard deviations (device memory):  z_ = eps prop_scale + z,
  *     accept = w <= min(exp(logp(z_) - logp(z)), 1) (NaN rejects),  z = accept ? z_ : z;  logp(z) is carried from step
  *     to step.  accept [steps, B] (bytes, may be NULL) receives the decisions.  The layer's log_det is zero and it is
  *     the identity under differentiation, so the caller provides both.
  * batch < 0, n_layers < 1, steps < 0, n_comp < 1 for a mixture, or groups outside its range -> VCNF_ERR_SHAPE; unknown
- * family, or n_layers (steps + 1) > 65536 (a mistaken argument must not become a launch that runs for minutes) ->
- * VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a pointer not
- * aligned to its element size -> VCNF_ERR_ALIGN, checked in this order.  One sample per lane; rows move as one 8-byte
+ * family, or n_layers (steps + 1) > VCNF_STOCH_MAX_POINTS (a mistaken argument must not become a launch that runs for
+ * minutes) -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a
+ * pointer not aligned to its element size -> VCNF_ERR_ALIGN, checked in this order.
+ * One sample per lane; rows move as one 8-byte
  * (16-byte) access when the [., 2] buffers are aligned to it, as two elements otherwise, with the same bits either way.
  * Every loop is bounded by n_layers, steps or n_comp.  No atomics, no allocation, no host synchronisation: every call is
  * bitwise reproducible and capturable. */
+/* samples per workgroup, the cap on the workgroups of the HMC VJP, and the limit on n_layers (steps + 1) */
+enum { VCNF_HMC_BLOCK = 256, VCNF_HMC_MAX_BWD_GROUPS = 1024, VCNF_STOCH_MAX_POINTS = 65536 };
 int vcnf_hmc_stack_f32(const float* z, const float* noise, const float* unif, const float* step, const float* mass,
                        const float* sqrt_mass, const float* table, float* z_out, float* log_det, float* trace,
                        uint8_t* accept, int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, int family,

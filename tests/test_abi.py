@@ -4,11 +4,12 @@ documented status codes.  No GPU needed: nothing is launched."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
 import vcnf_amd
-from vcnf_amd import _lib
+from vcnf_amd import _abi, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,8 +30,85 @@ def test_header_symbols_exported_and_bound():
     assert vcnf_amd.lib().vcnf_abi_version() == 1
 
 
-def test_struct_layout_matches_header():
-    assert ctypes.sizeof(_lib.RqsCfg) == 40     # 2 x int32 + 8 x float
+def _c_check(abi, decls):
+    """A C11 file that includes the header and asserts, declaration by declaration, what vcnf_amd/_abi.py read from it:
+    ``decls`` (the functions as the reader spells them) against the compiler's own view of each prototype, the derived
+    ctypes structures member by member, every constant, and the C-to-ctypes type map by size and kind."""
+    out = ["#include <stddef.h>", "#include <stdio.h>", '#include "vcnf_hip.h"']
+    check = lambda cond, what: out.append('_Static_assert(%s, "%s");' % (cond, what))
+    for c, t in _abi.type_map(_lib._P).items():
+        size = ctypes.sizeof(ctypes.c_void_p if t is _lib._P else t)
+        check("sizeof(%s) == %d" % (c, size), "size of " + c)
+        if not c.endswith("*"):
+            real = t in (ctypes.c_float, ctypes.c_double)
+            check("((%s)0.5 != 0) == %d && (%s)-1 < 0" % (c, real, c), "kind of " + c)
+    for name, (ret, args) in decls.items():
+        check("__builtin_types_compatible_p(__typeof__(%s), %s(%s))" % (name, ret, ", ".join(args) or "void"), name)
+    for name, struct in abi.structs.items():
+        check("sizeof(%s) == %d" % (name, ctypes.sizeof(struct)), "sizeof " + name)
+        assert [m[1] for m in abi.members[name]] == [f[0] for f in struct._fields_]
+        for ctype, member, length in abi.members[name]:
+            field = getattr(struct, member)
+            check("offsetof(%s, %s) == %d && sizeof(((%s*)0)->%s) == %d" % (name, member, field.offset, name, member,
+                                                                           field.size), "%s.%s" % (name, member))
+            check("__builtin_types_compatible_p(__typeof__(((%s*)0)->%s), %s%s)" % (
+                name, member, ctype, "[%d]" % length if length else ""), "type of %s.%s" % (name, member))
+    for name, value in abi.constants.items():
+        check("%s == %d" % (name, value), name)
+    out.append('int main(void) { printf("abi_check ok %%d %%d %%d\\n", %d, %d, %d); return 0; }' % (
+        len(decls), len(abi.structs), len(abi.constants)))
+    return "\n".join(out) + "\n"
+
+
+def _compile_check(tmp_path, source, tag):
+    src, exe = tmp_path / (tag + ".c"), tmp_path / tag
+    src.write_text(source)
+    done = subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                          capture_output=True, text=True)
+    return done, exe
+
+
+def test_compiler_agrees_with_what_the_reader_parsed(tmp_path):
+    """gcc judges the reader (nothing is linked against the library, nothing launched): every prototype, struct layout
+    and constant that _lib binds is asserted in C against the real header.  ``_lib.RqsCfg`` and its four siblings are the
+    reader's classes, so this covers their layout."""
+    abi = _lib._ABI
+    assert abi.functions is _lib.PROTOTYPES and len(abi.decls) == len(abi.functions) >= 144
+    assert abi.structs["vcnf_rqs_cfg"] is _lib.RqsCfg and abi.structs["vcnf_affine_stack_layer"] is _lib.AffineStackLayer
+    done, exe = _compile_check(tmp_path, _c_check(abi, abi.decls), "abi_check")
+    assert done.returncode == 0, done.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.split() == ["abi_check", "ok", str(len(abi.decls)), "5",
+                                                          str(len(abi.constants))]
+    # a wrong read does not get past the compiler: one int32_t argument taken for an int64_t
+    name = "vcnf_gmm_bwd_groups"
+    ret, args = abi.decls[name]
+    assert args[1] == "int32_t"
+    wrong = dict(abi.decls)
+    wrong[name] = (ret, [args[0], "int64_t"] + args[2:])
+    done, exe = _compile_check(tmp_path, _c_check(abi, wrong), "abi_wrong")
+    assert done.returncode != 0 and name in done.stderr
+
+
+@pytest.mark.parametrize("text, named", [
+    ("int vcnf_f(size_t n);", "size_t"),
+    ("int vcnf_f(void (*done)(int), int n);", "vcnf_f"),
+    ("int vcnf_f(int n)\nint vcnf_g(int n);", "vcnf_f"),
+    ("int vcnf_g(int n);\nint vcnf_f(int n)", "vcnf_f"),
+    ("typedef struct vcnf_s { int32_t a; size_t n; } vcnf_s;", "size_t"),
+    ("typedef struct vcnf_s { int32_t a } vcnf_s;", "vcnf_s"),
+    ("enum { VCNF_A = 0, VCNF_B };", "VCNF_B"),
+    ("#define VCNF_TWICE(x) (2 * (x))", "VCNF_TWICE"),
+    ("unsigned int vcnf_f(void);", "vcnf_f"),
+])
+def test_reader_raises_on_what_it_does_not_understand(tmp_path, text, named):
+    """Never a skipped declaration and never a guess: the error names the declaration."""
+    path = tmp_path / "bad.h"
+    path.write_text("#include <stdint.h>\nint vcnf_ok(const float* x, int64_t n);\n" + text + "\n")
+    with pytest.raises(_abi.HeaderError, match=re.escape(named)):
+        _abi.read(str(path))
+    path.write_text("#include <stdint.h>\nint vcnf_ok(const float* x, int64_t n);\n")
+    assert list(_abi.read(str(path)).functions) == ["vcnf_ok"]
 
 
 def test_status_strings():
@@ -183,5 +261,5 @@ def test_validation_status_codes_of_the_round2_entry_points():
     assert L.vcnf_maf_affine_f32(fake, fake, fake, None, 4, 7, 0, 0, 1.0, None) == 1
     # affine stack: at most 16 layers
     layers = (_lib.AffineStackLayer * 17)()
-    assert L.vcnf_affine_stack_fused_f32(fake, fake, fake, 4, 32, 17, ctypes.cast(layers, ctypes.c_void_p), -1, 16, 64, 0.0, 0,
+    assert L.vcnf_affine_stack_fused_f32(fake, fake, fake, 4, 32, 17, layers, -1, 16, 64, 0.0, 0,
                                          fake, 100, None, 0, 0, 0, 1.0, None) in (2, 5)

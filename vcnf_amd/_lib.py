@@ -7,7 +7,7 @@ current HIP stream only.
 
 How a wrapper calls the library (copy this for a new entry point):
 
-* pointer arguments are declared ``_P`` in ``PROTOTYPES`` / ``_PAIRS`` and the wrapper passes the tensor itself (or
+* pointer arguments are declared ``_P`` in ``PROTOTYPES`` (read from the header) and the wrapper passes the tensor itself (or
   None for NULL); a ``vcnf_rqs_cfg`` argument is declared ``_CFG`` and the wrapper passes the struct (``_cfg_of``
   picks the fp64 twin) - ctypes converts both during the call;
 * ``_call(name, dev, *args)`` enters the tensors' device, appends the current stream as the last argument, calls the
@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from . import build as _build
+from . import _abi, build as _build
 
 
 class _P:
@@ -35,13 +35,12 @@ class _P:
         return _as_void_p(value.data_ptr() if isinstance(value, _tensor) else value)
 
 
-_I32, _I64, _F32, _INT = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_int
-_F64 = ctypes.c_double
+_ABI = _abi.read(_build.HEADER, pointer=_P)
 
-OK = 0
-LD_STORE, LD_ACCUM = 0, 1
-TAILS_NONE, TAILS_LINEAR, TAILS_CIRCULAR = 0, 1, 2
-SCALE_EXP, SCALE_SIGMOID, SCALE_SIGMOID_INV, SCALE_NONE = 0, 1, 2, 3
+# every VCNF_* constant of the header under its name without the prefix: OK, ERR_*, LD_*, TAILS_*, PREC_*, SCALE_*, TAIL_*,
+# MVN_* (MVN_MAX_DIM among them), GMM_MAX_TABLE, PLANAR_TANH / PLANAR_LEAKY / RADIAL, TARGET_*, HMC_BLOCK,
+# HMC_MAX_BWD_GROUPS, STOCH_MAX_POINTS, AFFINE_STACK_MAX_LAYERS, PROBE_*
+globals().update({name[len("VCNF_"):]: value for name, value in _ABI.constants.items()})
 SCALE_MAPS = {"exp": SCALE_EXP, "sigmoid": SCALE_SIGMOID, "sigmoid_inv": SCALE_SIGMOID_INV}
 
 
@@ -54,158 +53,14 @@ def scale_code(scale, scale_map):
     return SCALE_MAPS[scale_map]
 
 
-class RqsCfg(ctypes.Structure):
-    """struct vcnf_rqs_cfg"""
-    _fields_ = [("num_bins", _I32), ("tails", _I32), ("left", _F32), ("right", _F32),
-                ("bottom", _F32), ("top", _F32), ("min_bin_width", _F32),
-                ("min_bin_height", _F32), ("min_derivative", _F32), ("wh_scale", _F32)]
-
-
-class RqsCfg64(ctypes.Structure):
-    """struct vcnf_rqs_cfg_f64"""
-    _fields_ = [("num_bins", _I32), ("tails", _I32), ("left", _F64), ("right", _F64),
-                ("bottom", _F64), ("top", _F64), ("min_bin_width", _F64),
-                ("min_bin_height", _F64), ("min_derivative", _F64), ("wh_scale", _F64)]
-
-
-class RqsLimitBcast(ctypes.Structure):
-    """struct vcnf_rqs_limit_bcast: limit j of element i is lim_j[(i // inner[j]) % period[j]]"""
-    _fields_ = [("period", _I64 * 4), ("inner", _I64 * 4)]
-
-
-class RqsStackLayer(ctypes.Structure):
-    """struct vcnf_rqs_stack_layer"""
-    _fields_ = [("transform_idx", ctypes.c_void_p), ("identity_idx", ctypes.c_void_p), ("wpack", ctypes.c_void_p),
-                ("shared_w", ctypes.c_void_p), ("shared_h", ctypes.c_void_p), ("shared_d", ctypes.c_void_p)]
-
-
+RqsCfg, RqsCfg64 = _ABI.structs["vcnf_rqs_cfg"], _ABI.structs["vcnf_rqs_cfg_f64"]
+RqsLimitBcast = _ABI.structs["vcnf_rqs_limit_bcast"]       # limit j of element i is lim_j[(i // inner[j]) % period[j]]
+RqsStackLayer, AffineStackLayer = _ABI.structs["vcnf_rqs_stack_layer"], _ABI.structs["vcnf_affine_stack_layer"]
 _CFG, _CFG64 = ctypes.POINTER(RqsCfg), ctypes.POINTER(RqsCfg64)
+_I64 = ctypes.c_int64
 
-# name -> argtypes, exactly the prototypes of include/vcnf_hip.h
-PROTOTYPES = {
-    "vcnf_abi_version": ([], _INT),
-    "vcnf_status_string": ([_INT], ctypes.c_char_p),
-    "vcnf_affine_layer_fused_supported": ([_I32, _I32, _I32, _I32], _INT),
-    "vcnf_affine_stack_fused_supported": ([_I32, _I32, _I32, _I32], _INT),
-    "vcnf_affine_layer_fused_pack_floats": ([_I32, _I32, _I32], _I64),
-    "vcnf_affine_layer_fused_f32": ([_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _INT, _P, _I64, _P,
-                                     _P, _INT, _INT, _F32, _P], _INT),
-    "vcnf_rqs_shared_f32": ([_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _CFG, _INT, _P, _P], _INT),
-    "vcnf_rqs_final_fused_supported": ([_I32, _I32, _I32, _I32], _INT),
-    "vcnf_rqs_final_fused_pack_floats": ([_I32, _I32, _I32], _I64),
-    "vcnf_rqs_final_fused_partial_rows": ([_I32, _I32], _I64),
-    "vcnf_rqs_final_fused_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _CFG, _INT, _P, _P], _INT),
-    "vcnf_rqs_shared_bwd_groups": ([_I64, _I64], _I64),
-    "vcnf_rqs_shared_bwd_f32": ([_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _CFG, _INT, _P], _INT),
-    "vcnf_rqs_coupling_f32": ([_P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _I64, _CFG, _INT, _INT, _F32, _P, _P], _INT),
-    "vcnf_rqs_conditioner_input_f32": ([_P, _I64, _I32, _P, _I32, _P, _I32, _P, _P, _P, _CFG, _INT, _P, _P], _INT),
-    "vcnf_conv1x1_supported": ([_I32, _I32], _INT),
-    "vcnf_conv1x1_pack_floats": ([_I32, _I32], _I64),
-    "vcnf_conv1x1_f16x3_f32": ([_P, _P, _P, _I64, _P, _P, _I64, _I32, _I32, _I64, _INT, _F32, _INT, _F32, _P, _P], _INT),
-    "vcnf_linear_wgrad_supported": ([_I32, _I32], _INT),
-    "vcnf_linear_wgrad_slices": ([_I64, _I32, _I32], _I64),
-    "vcnf_linear_wgrad_f32": ([_P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _INT, _P], _INT),
-    "vcnf_linear_wgrad_f16x3_f32": ([_P, _P, _P, _P, _P, _I64, _I64, _I32, _I32, _INT, _INT, _P, _P], _INT),
-    "vcnf_conv3x3_1x1_supported": ([_I32, _I32, _I32], _INT),
-    "vcnf_conv3x3_1x1_pack_floats": ([_I32], _I64),
-    "vcnf_conv3x3_1x1_f16x3_f32": ([_P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _F32, _F32, _P, _P], _INT),
-    "vcnf_convnet3_supported": ([_I32, _I32, _I32], _INT),
-    "vcnf_convnet3_w3_pack_floats": ([_I32], _I64),
-    "vcnf_convnet3_taps_f16x3_f32": ([_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I32, _F32,
-                                      _F32, _P, _P], _INT),
-    "vcnf_col2im3x3_f32": ([_P, _P, _P, _I64, _I32, _I32, _I32, _P], _INT),
-    "vcnf_resblock_elementwise_f32": ([_INT, _P, _P, _P, _P, _P, _I64, _P], _INT),
-    "vcnf_channel_mix_supported": ([_I32], _INT),
-    "vcnf_channel_mix_f32": ([_P, _P, _P, _P, _I64, _I32, _I64, _P], _INT),
-    "vcnf_rqs_identity_half_supported": ([_I32, _I32], _INT),
-    "vcnf_rqs_identity_half_partial_rows": ([_I32], _I64),
-    "vcnf_rqs_identity_half_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _CFG, _INT, _INT, _P, _P], _INT),
-    "vcnf_rqs_layer_fused_pack_floats": ([_I32, _I32, _I32, _I32], _I64),
-    "vcnf_rqs_layer_fused_supported": ([_I32, _I32, _I32, _I32, _I32, _I32, _I32], _INT),
-    "vcnf_rqs_layer_fused_tile_rows": ([], _I32),
-    "vcnf_rqs_layer_fused_small_batch_rows": ([_I64], _I64),
-    "vcnf_masked_affine_stack_supported": ([_I32, _I32], _INT),
-    "vcnf_linear_f16x3_supported": ([_I32, _I32], _INT),
-    "vcnf_linear_f16x3_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _I64, _I64, _INT, _INT, _P, _P, _P, _P], _INT),
-    "vcnf_rqs_stack_fused_max_layers": ([], _I32),
-    "vcnf_rqs_stack_fused_f32": ([_P, _P, _P, _P, _I64, ctypes.POINTER(RqsStackLayer), _I32, _I32, _I32, _I32, _I32,
-                                  _I32, _I32, _I64, _CFG, _INT, _INT, _F32, _P, _P, _P, _P], _INT),
-    "vcnf_rqs_layer_fused_f32": ([_P, _P, _P, _P, _I64, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P,
-                                  _P, _CFG, _INT, _INT, _F32, _P, _P, _P, _P], _INT),
-    "vcnf_resnet_trunk_supported": ([_I32, _I32, _I32], _INT),
-    "vcnf_resnet_trunk_pack_floats": ([_I32, _I32, _I32], _I64),
-    "vcnf_resnet_trunk_f32": ([_P, _P, _I64, _I32, _I32, _I32, _P, _I64, _P], _INT),
-    "vcnf_resnet_trunk_split_f32": ([_P, _P, _I64, _I32, _I32, _I32, _P, _I64, _P, _P], _INT),
-    "vcnf_rqs_final_fused_presplit_f32": ([_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _I64, _CFG, _INT, _P, _P], _INT),
-    "vcnf_affine_stack_fused_f32": ([_P, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _F32, _INT, _P, _I64, _P,
-                                     _I32, _INT, _INT, _F32, _P], _INT),
-    "vcnf_affine_layer_fused_h3_pack_floats": ([_I32, _I32, _I32], _I64),
-    "vcnf_affine_stack_fused_f16x3_f32": ([_P, _P, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _F32, _INT, _P, _I64,
-                                           _P, _I64, _P, _I32, _INT, _INT, _F32, _P, _P], _INT),
-    "vcnf_linear_probe_f32": ([_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _P, _P], _INT),
-    "vcnf_gmm_bwd_groups": ([_I64, _I32, _I32], _I64),
-    "vcnf_tail_bwd_groups": ([_I64, _I32], _I64),
-    "vcnf_mvn_bwd_groups": ([_I64, _I32], _I64),
-    "vcnf_planar_radial_supported": ([_I32], _INT),
-    "vcnf_planar_radial_checkpoint_every": ([_I32], _I32),
-    "vcnf_planar_radial_bwd_groups": ([_I64, _I32, _I32], _I64),
-}
-
-# Entry points that exist as name_f32 and name_f64 (all return int), stated once with the fp32 argument types: the
-# fp64 twin takes double for float and vcnf_rqs_cfg_f64 for vcnf_rqs_cfg
-_PAIRS = {
-    "vcnf_rqs_elementwise": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _CFG, _INT, _P, _P],
-    "vcnf_rqs_elementwise_strided": [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _CFG, _INT, _P,
-                                     _P],
-    "vcnf_rqs_elementwise_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _CFG, _INT, _P],
-    "vcnf_rqs_packed_bwd": [_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, _CFG, _INT, _P],
-    "vcnf_masked_affine_stack": [_P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F32, _P],
-    "vcnf_masked_affine_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _P],
-    "vcnf_affine_coupling": [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT, _INT, _INT, _F32, _P],
-    "vcnf_maf_affine": [_P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
-    "vcnf_masked_affine": [_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
-    "vcnf_affine_const": [_P, _P, _P, _P, _I64, _I32, _I32, _INT, _P],
-    "vcnf_permute": [_P, _P, _P, _I64, _I32, _I32, _P],
-    "vcnf_split_columns": [_P, _P, _P, _P, _I64, _I32, _I32, _P],
-    "vcnf_merge_columns": [_P, _P, _P, _P, _I64, _I32, _I32, _P],
-    "vcnf_diag_gaussian_log_prob": [_P, _P, _P, _F32, _P, _I64, _I32, _INT, _F32, _P],
-    "vcnf_diag_gaussian_sample": [_P, _P, _P, _F32, _P, _P, _I64, _I32, _P],
-    "vcnf_rqs_elementwise_limits": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, ctypes.POINTER(RqsLimitBcast),
-                                    _P, _P, _I64, _CFG, _INT, _P, _P],
-    "vcnf_rqs_elementwise_limits_bwd": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P,
-                                        ctypes.POINTER(RqsLimitBcast), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64,
-                                        _CFG, _INT, _P],
-    "vcnf_cc_gaussian_log_prob": [_P, _P, _P, _P, _F32, _P, _I64, _I32, _I32, _I64, _INT, _F32, _P],
-    "vcnf_cc_gaussian_sample": [_P, _P, _P, _P, _F32, _P, _P, _I64, _I32, _I32, _I64, _P],
-    "vcnf_cc_gaussian_log_prob_bwd": [_P, _P, _P, _P, _F32, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P],
-    "vcnf_cc_gaussian_sample_bwd": [_P, _P, _P, _F32, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I64, _P],
-    "vcnf_cc_gaussian_reduce_rows": [_P, _P, _P, _I64, _I32, _I64, _P],
-    "vcnf_gmm_log_prob": [_P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F32, _P],
-    "vcnf_gmm_sample": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
-    "vcnf_gmm_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
-    "vcnf_gmm_reduce_partials": [_P, _I64, _I32, _I32, _P, _P, _P, _P],
-    "vcnf_tail_log_prob": [_P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
-    "vcnf_tail_sample": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
-    "vcnf_tail_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
-    "vcnf_tail_sample_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
-    "vcnf_tail_reduce_partials": [_P, _I64, _I32, _P, _P, _P, _P],
-    "vcnf_mvn_log_prob": [_P, _P, _P, _P, _P, _I64, _I32, _INT, _INT, _F32, _P],
-    "vcnf_mvn_sample": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
-    "vcnf_mvn_log_prob_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
-    "vcnf_mvn_sample_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _INT, _P],
-    "vcnf_mvn_reduce_partials": [_P, _I64, _I32, _P, _P, _P, _P],
-    "vcnf_planar_radial_stack": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _INT, _F32, _P],
-    "vcnf_planar_radial_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P],
-    "vcnf_target_log_prob": [_P, _P, _P, _P, _I64, _I32, _INT, _F32, _P],
-    "vcnf_hmc_stack": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _INT, _F32, _P],
-    "vcnf_hmc_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _INT,
-                           _F32, _P],
-    "vcnf_mh_walk": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _INT, _F32, _P],
-}
-_F64_TWIN = {_F32: _F64, _CFG: _CFG64}
-for _name, _args in _PAIRS.items():
-    PROTOTYPES[_name + "_f32"] = (_args, _INT)
-    PROTOTYPES[_name + "_f64"] = ([_F64_TWIN.get(a, a) for a in _args], _INT)
+# name -> (argtypes, restype): the prototypes of include/vcnf_hip.h, as vcnf_amd/_abi.py reads them
+PROTOTYPES = _ABI.functions
 
 _LIB = None
 
@@ -923,12 +778,6 @@ def affine_layer_fused(z, wpack, cond_off, c_in, t_off, d_t, hidden, slope, scal
     return out, logdet
 
 
-class AffineStackLayer(ctypes.Structure):
-    """vcnf_affine_stack_layer of include/vcnf_hip.h."""
-    _fields_ = [("cond_off", ctypes.c_int32), ("t_off", ctypes.c_int32), ("d_t", ctypes.c_int32),
-                ("gather_before", ctypes.c_int32)]
-
-
 def affine_stack_fused(z, wpack, layers, gather_after, gathers, c_in, hidden, slope, scale_map, inverse, logdet=None,
                        sign=1.0, wpack_h3=None):
     """A run of AffineCouplingBlocks + the permutations between them in one kernel; csrc/fused_affine.hip.
@@ -941,8 +790,8 @@ def affine_stack_fused(z, wpack, layers, gather_after, gathers, c_in, hidden, sl
     out = torch.empty_like(z)
     logdet, ld_arg, mode = _affine_ld_out(logdet, b, scale_map, dev)
     arr = (AffineStackLayer * len(layers))(*[AffineStackLayer(*map(int, l)) for l in layers])
-    head = (z, out, ld_arg, b, d, len(layers), ctypes.cast(arr, ctypes.c_void_p), int(gather_after), int(c_in),
-            int(hidden), float(slope), int(scale_map), wpack, wpack.numel())
+    head = (z, out, ld_arg, b, d, len(layers), arr, int(gather_after), int(c_in), int(hidden),
+            float(slope), int(scale_map), wpack, wpack.numel())
     tail = (gathers, 0 if gathers is None else int(gathers.shape[0]), bool(inverse), mode, sign)
     if wpack_h3 is not None:
         _call("vcnf_affine_stack_fused_f16x3_f32", dev, *head, wpack_h3, wpack_h3.numel(), *tail,
@@ -1350,9 +1199,6 @@ def cc_gaussian_reduce_rows(per_sample, row_index, rows):
     return out
 
 
-GMM_MAX_TABLE = 8192
-
-
 def _gmm_operands(x, loc, ls, log_w, what):
     """Checked operands of the Gaussian mixture entry points: x [B, D], tables loc / ls [M, D], log_w [M], one dtype.
     Returns (device, x, loc, ls, log_w contiguous, B, D, M)."""
@@ -1404,9 +1250,6 @@ def gmm_log_prob_bwd(z, loc, ls, log_w, lse, g, gz_in=None, tables=True):
     sums = _block_sums(dev, lambda ws: _launch(name, z2, loc, ls, log_w, lse, g, gz_in, dz, ws, b, d, m), name, outs,
                        (m, 2 * d + 1), ("vcnf_gmm_bwd_groups", (b, d, m)), ("vcnf_gmm_reduce_partials" + _sfx(z), (m, d)))
     return (dz,) + (sums or (None, None, None))
-
-
-TAIL_STUDENT_T, TAIL_GEN_GAUSSIAN = 0, 1
 
 
 def _tail_operands(x, rows, what):
@@ -1489,10 +1332,6 @@ def tail_sample_bwd(eps, gamma, loc, ls, shape, family, g_z=None, g_lp=None, row
     sums = _tail_row_sums(dev, lambda ws: _launch(name, e2, g2, loc, ls, shape, g_z, g_lp, d_eps, d_gamma, ws, b, d,
                                                   family), name, e2, b, d, rows)
     return (d_eps.view(eps.shape) if want_eps else None, d_gamma.view(eps.shape)) + sums
-
-
-MVN_GAUSSIAN, MVN_STUDENT_T = 0, 1
-MVN_MAX_DIM = 128
 
 
 def _mvn_operands(x, loc, tri, consts, what):
@@ -1583,9 +1422,6 @@ def mvn_sample_bwd(eps, gamma, tri, consts, family, g_z=None, g_lp=None, sums=Tr
     return (d_eps, d_gamma) + out
 
 
-PLANAR_TANH, PLANAR_LEAKY, RADIAL = 0, 1, 2
-
-
 def planar_radial_kinds(kinds, device):
     """(host int32 array, device int32 tensor) of a run's layer kinds: the entry points validate the host copy before
     they launch and the kernels read the device copy."""
@@ -1660,9 +1496,6 @@ def planar_radial_stack_bwd(z_out, trace, ckpt, kinds, va, vb, sc, g_out=None, g
     return g_in, g_va, g_vb, g_sc
 
 
-TARGET_TWO_MOONS, TARGET_CIRCULAR_GMM, TARGET_RING_MIXTURE = 0, 1, 2
-
-
 def target_log_prob(z, family, table=None, scale=0.0, want_score=False):
     """vcnf_target_log_prob_*: (log density [B], score d logp / d z [B, 2] or None) of z [B, 2] under TwoMoons (family 0),
     the circular Gaussian mixture with the centres ``table`` [n, 2] (1) or the ring mixture with the radii ``table`` [n]
@@ -1688,9 +1521,6 @@ def target_log_prob(z, family, table=None, scale=0.0, want_score=False):
     score = torch.empty_like(z) if want_score else None
     _call(name, dev, z, table, logp, score, b, n, int(family), float(scale))
     return logp, score
-
-
-HMC_BLOCK, HMC_MAX_BWD_GROUPS = 256, 1024      # samples per workgroup and the cap on the workgroups of the HMC VJP
 
 
 def _stochastic_target(z, family, table, name):
@@ -1799,9 +1629,6 @@ def mh_walk(z, eps, w, prop_scale, family, table=None, scale=0.0, want_accept=Fa
     accept = torch.empty((steps, b), dtype=torch.uint8, device=dev) if want_accept else None
     _call(name, dev, z, eps, w, prop_scale, table, out, accept, b, steps, n, int(family), float(scale))
     return (out, accept) if want_accept else out
-
-
-PROBE_F32, PROBE_F16X3, PROBE_F16X3_LL = 0, 1, 2
 
 
 def linear_probe(x, weight, bias, mode, relu_input=False):

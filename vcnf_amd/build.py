@@ -10,6 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libvcnf_hip.so")
+HEADER = os.path.normpath(os.path.join(CSRC, "..", "..", "include", "vcnf_hip.h"))    # the C ABI; vcnf_amd/_abi.py reads it
 SOURCES = ["rqs_kernels.hip", "affine_kernels.hip", "fused_layer.hip",
            "fused_layer_v6.hip", "fused_affine.hip", "fused_final.hip", "resnet_trunk.hip", "channel_mix.hip", "conv1x1.hip", "conv3x3_1x1.hip", "linear_wgrad.hip", "resblock_ops.hip",
            "rqs_backward.hip", "gemm_probe.hip", "rqs_f64.hip", "linear_f16x3.hip", "masked_affine_stack.hip", "class_cond_gaussian.hip",

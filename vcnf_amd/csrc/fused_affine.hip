@@ -375,7 +375,7 @@ __global__ __launch_bounds__(kFABlock) void fused_affine_layer_kernel(const Fuse
 // the wave's 16 rows stay in its LDS strip from the first layer to the last (x is read once, y written once; a
 // per-layer launch streams [B, D] through HBM and pays a launch gap per layer).  A permutation is a copy between the
 // wave's two strips through its index row.
-constexpr int kFAStackMax = 16;
+constexpr int kFAStackMax = VCNF_AFFINE_STACK_MAX_LAYERS;
 struct FusedAffineStackArgs {
   FusedAffineArgs base;          // x, y, logdet, wpack, B, D, KI, OB, scale_map, inverse, ld_*, slope, weight offsets
   const int32_t* gathers;        // [rows][D] column index rows

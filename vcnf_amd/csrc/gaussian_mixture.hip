@@ -28,7 +28,7 @@ constexpr int kFwdBlock = 256;
 constexpr int kBwdBlock = 64;                 // one wave: the cross-sample sums are shuffles, no barrier in the loop
 constexpr int kRegPacks = 4;                  // packs of a row a lane keeps in registers
 constexpr int kMaxFwdBlocks = 2048;
-constexpr int kMaxTable = 8192;               // M * D
+constexpr int kMaxTable = VCNF_GMM_MAX_TABLE; // M * D
 constexpr size_t kLdsBytes = 160 * 1024;
 
 // Every sum over lanes in this unit is the ascending lanes_sum: inside a lane group (1, G), across the groups (G, 64).

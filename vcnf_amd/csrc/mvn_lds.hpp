@@ -11,9 +11,11 @@
 
 #include <stddef.h>
 
+#include "../../include/vcnf_hip.h"
+
 namespace vcnf_mvn {
 
-constexpr int kMaxD = 128;                    // features: VCNF_ERR_SHAPE beyond
+constexpr int kMaxD = VCNF_MVN_MAX_DIM;       // features: VCNF_ERR_SHAPE beyond
 constexpr int kBlock = 256;                   // threads per workgroup
 constexpr int kMaxBlocksOwned = 3;            // 4 x 4 blocks of the outer-product sum a thread keeps in registers
 

@@ -51,7 +51,7 @@ constexpr int kMaxFwdBlocks = 4096;
 constexpr long long kMaxWsElems = 1LL << 22;  // elements of the VJP's workspace (while one block per K fits)
 constexpr long long kMaxBwdGroups = 1024;
 
-enum { kTanh = 0, kLeaky = 1, kRadial = 2 };
+enum { kTanh = VCNF_PLANAR_TANH, kLeaky = VCNF_PLANAR_LEAKY, kRadial = VCNF_RADIAL };
 
 __device__ __forceinline__ float tanh_(float v) { return tanhf(v); }
 __device__ __forceinline__ double tanh_(double v) { return tanh(v); }

@@ -56,7 +56,10 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kMaxBlocks = 2048;
 constexpr int kMaxBwdGroups = 1024;
-constexpr long long kMaxPoints = 1LL << 16;   // n_layers (steps + 1) of one call
+// the two above are what the caller sizes the VJP's workspace by: the header states them (tests/grid_caps.py reads the
+// numerals here, so they stay numerals and the compiler holds them to the header's names)
+static_assert(kBlock == VCNF_HMC_BLOCK && kMaxBwdGroups == VCNF_HMC_MAX_BWD_GROUPS, "include/vcnf_hip.h states these");
+constexpr long long kMaxPoints = VCNF_STOCH_MAX_POINTS;   // n_layers (steps + 1) of one call
 constexpr int kTerms = 6;                     // g_step, g_mass, g_sqrt_mass of a layer: [3, 2]
 
 typedef unsigned char byte_t;

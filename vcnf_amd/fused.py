@@ -69,7 +69,7 @@ def _pack_final(weight, bias, d_t, p):
     return wf.reshape(-1), bf.reshape(-1)
 
 
-PREC_F32, PREC_F16X3 = 0, 1
+PREC_F32, PREC_F16X3 = _lib.PREC_F32, _lib.PREC_F16X3
 LO_SCALE = 2048.0
 # Matrix path used when a module does not set ``fused_precision`` itself.  'fp16x3' (fp16 split-half operands, fp32
 # accumulation) is the default because (a) GEMM by GEMM its error against an fp64 product is at or below the exact

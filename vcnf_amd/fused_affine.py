@@ -155,7 +155,7 @@ def run(block, z, code, inverse, log_q=None, sign=1.0, in_gather=None, out_gathe
                                    inverse, logdet=log_q, sign=sign, in_gather=in_gather, out_gather=out_gather)
 
 
-STACK_MAX = 16
+STACK_MAX = _lib.AFFINE_STACK_MAX_LAYERS
 
 
 def _geometry(block, c):

@@ -20,7 +20,7 @@ from .flows.base import fold_log_det
 from .flows.stochastic import HamiltonianMonteCarlo
 from .stacks import add_log_det
 
-MAX_POINTS = 1 << 16          # n_layers (steps + 1) of one launch: the entry point's limit
+MAX_POINTS = _lib.STOCH_MAX_POINTS          # n_layers (steps + 1) of one launch: the entry point's limit
 
 
 def kernel_target(target):
