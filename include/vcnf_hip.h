@@ -1008,6 +1008,19 @@ int vcnf_target_log_prob_f64(const double* z, const double* table, double* logp,
  *     its own block of `workspace` (`groups` blocks of 6 K elements, uninitialised on entry; 1 <= groups <=
  *     min(VCNF_HMC_MAX_BWD_GROUPS, ceil(B / VCNF_HMC_BLOCK)), the number of workgroups) and a second launch adds the
  *     blocks in a fixed order.
+ *   hmc_annealed_stack, hmc_annealed_stack_bwd: the same run and its VJP for the layers of Hamiltonian annealed
+ *     importance sampling (normflow's sampling/hais.py): layer k's density is the LinearInterpolation of the target and a
+ *     2-D diagonal Gaussian prior with the weight beta[k].  beta [K], prior_loc [2] and prior_log_scale [2] are device
+ *     memory of the run's type, all required.  At a point x, with (lt, st) the target's logp and score there:
+ *       sig_j = exp(ls_j),  u_j = (x_j - loc_j) / sig_j
+ *       l0 = -log(2 pi) - (ls_0 + ls_1) - 0.5 (u_0^2 + u_1^2),   s0_j = -u_j / sig_j
+ *       logp_k = beta_k lt + (1 - beta_k) l0,   score_k = beta_k st + (1 - beta_k) s0
+ *     and the leapfrog, the decision, log_det, trace, accept and the VJP's closed form are hmc_stack's with logp_k and
+ *     score_k in place of logp and score (a non-finite row: NaN logp_k and score_k).  Only (lt, st) is carried from layer
+ *     to layer and the prior's part recomputed, so the run costs K steps + 1 target evaluations per sample as the plain
+ *     one does.  logp_target [B] (may be NULL) receives lt at z_out, the last term of the sampler's log weights.  beta and
+ *     the prior's parameters are constants of the VJP; workspace, groups and the reduction are hmc_stack_bwd's.  With
+ *     beta = 1 in every layer the run has the bits of hmc_stack on finite rows.
  *   mh_walk: `steps` >= 0 random-walk steps with eps [steps, B, 2] standard-normal and w [steps, B] uniform draws and
  *     prop_scale [2] the proposal's standard deviations (device memory):  z_ = eps prop_scale + z,
  *     accept = w <= min(exp(logp(z_) - logp(z)), 1) (NaN rejects),  z = accept ? z_ : z;  logp(z) is carried from step
@@ -1032,6 +1045,17 @@ int vcnf_hmc_stack_bwd_f32(const float* trace, const uint8_t* accept, const floa
                            const float* g_logdet, float* g_in, float* g_step, float* g_mass, float* g_sqrt_mass,
                            float* workspace, int64_t batch, int32_t n_layers, int32_t steps, int32_t groups,
                            int32_t n_comp, int family, float scale, void* stream);
+int vcnf_hmc_annealed_stack_f32(const float* z, const float* noise, const float* unif, const float* step, const float* mass,
+                                const float* sqrt_mass, const float* beta, const float* prior_loc,
+                                const float* prior_log_scale, const float* table, float* z_out, float* log_det,
+                                float* logp_target, float* trace, uint8_t* accept, int64_t batch, int32_t n_layers,
+                                int32_t steps, int32_t n_comp, int family, float scale, void* stream);
+int vcnf_hmc_annealed_stack_bwd_f32(const float* trace, const uint8_t* accept, const float* noise, const float* step,
+                                    const float* mass, const float* sqrt_mass, const float* beta, const float* prior_loc,
+                                    const float* prior_log_scale, const float* table, const float* g_out,
+                                    const float* g_logdet, float* g_in, float* g_step, float* g_mass, float* g_sqrt_mass,
+                                    float* workspace, int64_t batch, int32_t n_layers, int32_t steps, int32_t groups,
+                                    int32_t n_comp, int family, float scale, void* stream);
 int vcnf_mh_walk_f32(const float* z, const float* eps, const float* w, const float* prop_scale, const float* table,
                      float* z_out, uint8_t* accept, int64_t batch, int32_t steps, int32_t n_comp, int family,
                      float scale, void* stream);
@@ -1044,6 +1068,17 @@ int vcnf_hmc_stack_bwd_f64(const double* trace, const uint8_t* accept, const dou
                            const double* g_logdet, double* g_in, double* g_step, double* g_mass, double* g_sqrt_mass,
                            double* workspace, int64_t batch, int32_t n_layers, int32_t steps, int32_t groups,
                            int32_t n_comp, int family, double scale, void* stream);
+int vcnf_hmc_annealed_stack_f64(const double* z, const double* noise, const double* unif, const double* step, const double* mass,
+                                const double* sqrt_mass, const double* beta, const double* prior_loc,
+                                const double* prior_log_scale, const double* table, double* z_out, double* log_det,
+                                double* logp_target, double* trace, uint8_t* accept, int64_t batch, int32_t n_layers,
+                                int32_t steps, int32_t n_comp, int family, double scale, void* stream);
+int vcnf_hmc_annealed_stack_bwd_f64(const double* trace, const uint8_t* accept, const double* noise, const double* step,
+                                    const double* mass, const double* sqrt_mass, const double* beta, const double* prior_loc,
+                                    const double* prior_log_scale, const double* table, const double* g_out,
+                                    const double* g_logdet, double* g_in, double* g_step, double* g_mass, double* g_sqrt_mass,
+                                    double* workspace, int64_t batch, int32_t n_layers, int32_t steps, int32_t groups,
+                                    int32_t n_comp, int family, double scale, void* stream);
 int vcnf_mh_walk_f64(const double* z, const double* eps, const double* w, const double* prop_scale, const double* table,
                      double* z_out, uint8_t* accept, int64_t batch, int32_t steps, int32_t n_comp, int family,
                      double scale, void* stream);

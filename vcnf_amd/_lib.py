@@ -1558,7 +1558,29 @@ def hmc_stack(z, noise, unif, step, mass, sqrt_mass, steps, family, table=None, 
     include/vcnf_hip.h: step, mass, sqrt_mass [K, 2] and the draws noise [K, B, 2], unif [K, B].  Returns (z_out, log_det)
     - log_det a fresh [B] tensor holding the sum of the layers' log p(z) - log p(z_out) - and with ``want_trace`` what
     the VJP needs besides: each layer's entrance row trace [K, B, 2] and its decision accept [K, B] (uint8)."""
-    name = "vcnf_hmc_stack" + _sfx(z)
+    return _hmc_stack("vcnf_hmc_stack", z, noise, unif, step, mass, sqrt_mass, None, steps, family, table, scale, want_trace)
+
+
+def _annealing(name, prior, z, k):
+    """The checked (beta [K], prior_loc [2], prior_log_scale [2]) of an annealed run."""
+    beta, loc, log_scale = prior
+    return (_stochastic_like(name, "beta", beta, z, (k,)), _stochastic_like(name, "prior_loc", loc, z, (2,)),
+            _stochastic_like(name, "prior_log_scale", log_scale, z, (2,)))
+
+
+def hmc_annealed_stack(z, noise, unif, step, mass, sqrt_mass, beta, prior_loc, prior_log_scale, steps, family, table=None,
+                       scale=0.0, want_trace=False, want_logp=False):
+    """vcnf_hmc_annealed_stack_*: ``hmc_stack`` for the layers of Hamiltonian annealed importance sampling: layer k's
+    density is beta[k] log p + (1 - beta[k]) log N(prior_loc, exp(prior_log_scale)^2), beta [K] and the prior's
+    parameters [2] device tensors of z's dtype.  Returns what ``hmc_stack`` returns and, with ``want_logp``, as the last
+    element the target's log p [B] at z_out, which the kernel carries anyway."""
+    return _hmc_stack("vcnf_hmc_annealed_stack", z, noise, unif, step, mass, sqrt_mass, (beta, prior_loc, prior_log_scale),
+                      steps, family, table, scale, want_trace, want_logp)
+
+
+def _hmc_stack(base, z, noise, unif, step, mass, sqrt_mass, prior, steps, family, table, scale, want_trace, want_logp=False):
+    """The plain (``prior`` None) or annealed forward run: one statement of the operands' checks and outputs."""
+    name = base + _sfx(z)
     dev, z, table, n = _stochastic_target(z, family, table, name)
     b, steps = len(z), int(steps)
     if step.dim() != 2 or step.shape[0] < 1:
@@ -1576,9 +1598,12 @@ def hmc_stack(z, noise, unif, step, mass, sqrt_mass, steps, family, table=None, 
     if want_trace:
         trace = torch.empty((k, b, 2), dtype=z.dtype, device=dev)
         accept = torch.empty((k, b), dtype=torch.uint8, device=dev)
-    _call(name, dev, z, noise, unif, step, mass, sqrt_mass, table, out, log_det, trace, accept, b, k, steps, n, int(family),
+    logp = torch.empty(b, dtype=z.dtype, device=dev) if want_logp else None
+    extra, outs = ((), (out, log_det)) if prior is None else (_annealing(name, prior, z, k), (out, log_det, logp))
+    _call(name, dev, z, noise, unif, step, mass, sqrt_mass, *extra, table, *outs, trace, accept, b, k, steps, n, int(family),
           float(scale))
-    return (out, log_det, trace, accept) if want_trace else (out, log_det)
+    result = (out, log_det, trace, accept) if want_trace else (out, log_det)
+    return result + (logp,) if want_logp else result
 
 
 def hmc_stack_bwd(trace, accept, noise, step, mass, sqrt_mass, steps, family, table=None, scale=0.0, g_out=None, g_ld=None):
@@ -1586,7 +1611,21 @@ def hmc_stack_bwd(trace, accept, noise, step, mass, sqrt_mass, steps, family, ta
     cotangents g_out [B, 2] and g_ld [B] of (z_out, log_det); None is zero.  ``trace`` and ``accept`` as the forward run
     returned them, the other operands as it took them.  The score and the decisions are constants, as in the reference.
     Two launches, no atomics."""
-    name = "vcnf_hmc_stack_bwd" + _sfx(trace)
+    return _hmc_stack_bwd("vcnf_hmc_stack_bwd", trace, accept, noise, step, mass, sqrt_mass, None, steps, family, table, scale,
+                          g_out, g_ld)
+
+
+def hmc_annealed_stack_bwd(trace, accept, noise, step, mass, sqrt_mass, beta, prior_loc, prior_log_scale, steps, family,
+                           table=None, scale=0.0, g_out=None, g_ld=None):
+    """vcnf_hmc_annealed_stack_bwd_*: ``hmc_stack_bwd`` for the annealed run; beta and the prior's parameters are
+    constants and get no gradient."""
+    return _hmc_stack_bwd("vcnf_hmc_annealed_stack_bwd", trace, accept, noise, step, mass, sqrt_mass,
+                          (beta, prior_loc, prior_log_scale), steps, family, table, scale, g_out, g_ld)
+
+
+def _hmc_stack_bwd(base, trace, accept, noise, step, mass, sqrt_mass, prior, steps, family, table, scale, g_out, g_ld):
+    """The VJP of the plain (``prior`` None) or annealed run."""
+    name = base + _sfx(trace)
     if trace.dim() != 3:
         raise VcnfError(name + ": trace must be the [layers, batch, 2] tensor of the forward run")
     k, b = int(trace.shape[0]), int(trace.shape[1])
@@ -1597,6 +1636,7 @@ def hmc_stack_bwd(trace, accept, noise, step, mass, sqrt_mass, steps, family, ta
     step, mass, sqrt_mass = (_stochastic_like(name, what, t, z, (k, 2))
                              for what, t in (("step", step), ("mass", mass), ("sqrt_mass", sqrt_mass)))
     noise = _stochastic_like(name, "noise", noise, z, (k, b, 2))
+    prior = None if prior is None else _annealing(name, prior, z, k)
     g_out = None if g_out is None else _stochastic_like(name, "g_out", g_out, z, (b, 2))
     g_ld = None if g_ld is None else _stochastic_like(name, "g_ld", g_ld, z, (b,))
     g_in = torch.empty((b, 2), dtype=z.dtype, device=dev)
@@ -1605,8 +1645,9 @@ def hmc_stack_bwd(trace, accept, noise, step, mass, sqrt_mass, steps, family, ta
     g_step, g_mass, g_sqm = torch.empty_like(step), torch.empty_like(mass), torch.empty_like(sqrt_mass)
     groups = min((b + HMC_BLOCK - 1) // HMC_BLOCK, HMC_MAX_BWD_GROUPS)
     work = torch.empty((groups, k, 3, 2), dtype=z.dtype, device=dev)
-    _call(name, dev, z, accept.contiguous(), noise, step, mass, sqrt_mass, table, g_out, g_ld, g_in, g_step, g_mass, g_sqm,
-          work, b, k, int(steps), groups, n, int(family), float(scale))
+    extra = () if prior is None else prior
+    _call(name, dev, z, accept.contiguous(), noise, step, mass, sqrt_mass, *extra, table, g_out, g_ld, g_in, g_step, g_mass,
+          g_sqm, work, b, k, int(steps), groups, n, int(family), float(scale))
     return g_in, g_step, g_mass, g_sqm
 
 

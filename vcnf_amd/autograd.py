@@ -563,6 +563,33 @@ class HmcStackFn(torch.autograd.Function):
         return g_in, g_step, g_mass, g_sqm, None, None, None, None, None, None
 
 
+class HmcAnnealedStackFn(torch.autograd.Function):
+    """vcnf_hmc_annealed_stack_*: HmcStackFn for a run of annealed layers, whose densities are the LinearInterpolation
+    of the target and a 2-D diagonal Gaussian prior (prior_loc, prior_log_scale [2]) with the weights beta [K].  beta and
+    the prior's parameters are constants of the run: they get no gradient, and the caller sends a prior that trains to
+    the torch composition.  Backward is vcnf_hmc_annealed_stack_bwd_*."""
+
+    @staticmethod
+    def forward(ctx, z, step, mass, sqrt_mass, noise, unif, beta, prior_loc, prior_log_scale, steps, family, table, scale):
+        with torch.no_grad():
+            out, ld, trace, accept = _lib.hmc_annealed_stack(z, noise, unif, step, mass, sqrt_mass, beta, prior_loc,
+                                                             prior_log_scale, steps, family, table, scale, want_trace=True)
+        ctx.save_for_backward(trace, accept, noise, step, mass, sqrt_mass, beta, prior_loc, prior_log_scale, table)
+        ctx.target = (steps, family, scale)
+        ctx.set_materialize_grads(False)
+        return out, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_ld):
+        trace, accept, noise, step, mass, sqrt_mass, beta, prior_loc, prior_log_scale, table = ctx.saved_tensors
+        steps, family, scale = ctx.target
+        g_in, g_step, g_mass, g_sqm = _lib.hmc_annealed_stack_bwd(trace, accept, noise, step.detach(), mass.detach(),
+                                                                  sqrt_mass.detach(), beta, prior_loc, prior_log_scale,
+                                                                  steps, family, table, scale, g_out, g_ld)
+        return (g_in, g_step, g_mass, g_sqm) + (None,) * 9
+
+
 class MhWalkFn(torch.autograd.Function):
     """vcnf_mh_walk_*: the Metropolis-Hastings walk of z [B, 2] as a node.  Every step is z or z + eps scale, chosen by a
     decision that has no derivative: the walk is the identity under differentiation and backward hands gz through."""

@@ -30,6 +30,16 @@
 // (butterfly), over the waves through LDS in ascending order, and added to the workgroup's own block [K, 3, 2] of the
 // workspace; a second launch (reduce_partials) adds the blocks in a fixed order.
 //
+// Annealed run (Hamiltonian annealed importance sampling): layer k's density is the LinearInterpolation of the target
+// and a 2-D diagonal Gaussian prior, beta [K] the layers' weights and loc, log_scale [2] the prior's parameters:
+//   sig = exp(log_scale),  u = (x - loc) / sig,  l0 = -log(2 pi) - (ls_0 + ls_1) - (u_0^2 + u_1^2) / 2,  s0 = -u / sig
+//   logp_k = beta_k logp + (1 - beta_k) l0,   score_k = beta_k score + (1 - beta_k) s0
+// The same kernels with another policy (Plain, Annealed below): the leapfrog, the decision, log_det and the VJP's sums
+// are stated once and read logp_k, score_k where the plain run reads the target's.  What a lane carries from layer to
+// layer is the target's (logp, score) alone - the prior's part is a handful of flops, recomputed at the layer's entrance
+// - so a run of K layers still costs K steps + 1 target evaluations per sample; the carried logp at z_out is an output
+// (logp_target), the last term of the sampler's weights.  beta and the prior's parameters are constants of the VJP.
+//
 // MH walk, per step (eps [S, B, 2] and w [S, B] the draws, prop_scale [2] the proposal's standard deviations):
 //   z_ = eps prop_scale + z,  accept = w <= min(exp(logp(z_) - logp(z)), 1) (NaN rejects),  z = accept ? z_ : z
 // with logp(z) carried from step to step: steps + 1 evaluations.
@@ -107,10 +117,51 @@ __device__ __forceinline__ void store_row(T* __restrict__ p, long long row, cons
   }
 }
 
-// ------------------------------------------------------------------ HMC run, forward
+// ------------------------------------------------------------------ the density of a layer
+// The policy of an HMC kernel says what layer k's (log p, score) are at a point where the target's are known.  Its Mix
+// is made once per lane, set to a layer with layer(k), and turns the target's values at (x0, x1) into the layer's in
+// place; logp_target(b, lt) receives the target's log p at a sample's last row.
 template <typename T>
+struct Plain {                              // the target's own: nothing is instantiated
+  struct Mix {
+    __device__ explicit Mix(const Plain&) {}
+    __device__ void layer(const Plain&, int) {}
+    __device__ void operator()(T, T, T&, T&, T&) const {}
+  };
+  __device__ void logp_target(long long, T) const {}
+};
+
+template <typename T>
+struct Annealed {                           // the LinearInterpolation of the target and a diagonal Gaussian prior
+  const T *beta, *loc, *log_scale;          // [K], [2], [2]
+  T* lt_out;                                // [B] or NULL (the VJP has none)
+  struct Mix {
+    T loc0, loc1, ls, sig0, sig1, beta, rest;
+    __device__ explicit Mix(const Annealed& p)
+        : loc0(p.loc[0]), loc1(p.loc[1]), ls(p.log_scale[0] + p.log_scale[1]), sig0(exp_(p.log_scale[0])),
+          sig1(exp_(p.log_scale[1])), beta(T(1)), rest(T(0)) {}
+    __device__ void layer(const Annealed& p, int k) {
+      beta = p.beta[k];
+      rest = T(1) - beta;
+    }
+    __device__ void operator()(T x0, T x1, T& lp, T& s0, T& s1) const {
+      const T u0 = (x0 - loc0) / sig0, u1 = (x1 - loc1) / sig1;
+      const T l0 = T(-1.8378770664093454836) - ls - T(0.5) * (u0 * u0 + u1 * u1);       // -log(2 pi)
+      lp = beta * lp + rest * l0;           // a non-finite row's NaN log p and score stay NaN
+      s0 = beta * s0 + rest * (-u0 / sig0);
+      s1 = beta * s1 + rest * (-u1 / sig1);
+    }
+  };
+  __device__ void logp_target(long long b, T lt) const {
+    if (lt_out) lt_out[b] = lt;
+  }
+};
+
+// ------------------------------------------------------------------ HMC run, forward
+template <typename T, typename P>
 struct HmcArgs {
   Target<T> t;
+  P policy;
   const T *z, *noise, *unif, *step, *mass, *sqm;
   T *out, *logdet, *trace;
   byte_t* accept;
@@ -118,12 +169,15 @@ struct HmcArgs {
   int K, steps;
 };
 
-template <typename T, int F, bool ROW>
-__global__ __launch_bounds__(kBlock) void hmc_fwd_kernel(const HmcArgs<T> a) {
+// lt, c0, c1: the target's log p and score at the sample's row, carried from layer to layer; lp, s0, s1 the layer's
+// own there (the same registers under Plain)
+template <typename T, int F, bool ROW, typename P>
+__global__ __launch_bounds__(kBlock) void hmc_fwd_kernel(const HmcArgs<T, P> a) {
+  typename P::Mix mix(a.policy);
   for (long long b = (long long)blockIdx.x * kBlock + threadIdx.x; b < a.B; b += (long long)gridDim.x * kBlock) {
     Pack<T, 2> z = load_row<T, ROW>(a.z, b);
-    T s0, s1;
-    T lp = point<T, F, true>(a.t, z.v[0], z.v[1], s0, s1);
+    T c0, c1;
+    T lt = point<T, F, true>(a.t, z.v[0], z.v[1], c0, c1);
     T ld = T(0);
     for (int k = 0; k < a.K; ++k) {
       const long long at = (long long)k * a.B + b;
@@ -131,36 +185,43 @@ __global__ __launch_bounds__(kBlock) void hmc_fwd_kernel(const HmcArgs<T> a) {
       const Pack<T, 2> e = load_row<T, ROW>(a.noise, at);
       const T u = a.unif[at];
       if (a.trace) store_row<T, ROW>(a.trace, at, z);
+      mix.layer(a.policy, k);
+      T lp = lt, s0 = c0, s1 = c1;
+      mix(z.v[0], z.v[1], lp, s0, s1);
       const T p0 = e.v[0] * a.sqm[2 * k], p1 = e.v[1] * a.sqm[2 * k + 1];
       T x0 = z.v[0], x1 = z.v[1], r0 = p0, r1 = p1, t0 = s0, t1 = s1, lpn = lp;
+      T ltn = lt, d0 = c0, d1 = c1;                    // the target's at the trajectory's point
       for (int i = 0; i < a.steps; ++i) {
         const T q0 = r0 - (h0 / T(2)) * -t0, q1 = r1 - (h1 / T(2)) * -t1;
         x0 = x0 + h0 * (q0 / m0);
         x1 = x1 + h1 * (q1 / m1);
-        lpn = point<T, F, true>(a.t, x0, x1, t0, t1);
+        ltn = point<T, F, true>(a.t, x0, x1, d0, d1);
+        lpn = ltn, t0 = d0, t1 = d1;
+        mix(x0, x1, lpn, t0, t1);
         r0 = q0 - (h0 / T(2)) * -t0;
         r1 = q1 - (h1 / T(2)) * -t1;
       }
       const T prob = exp_(lpn - lp - T(0.5) * (r0 * r0 / m0 + r1 * r1 / m1) + T(0.5) * (p0 * p0 / m0 + p1 * p1 / m1));
       const bool acc = u < prob;
-      const T lp_out = acc ? lpn : lp;
-      ld += lp - lp_out;
+      ld += lp - (acc ? lpn : lp);
       z.v[0] = acc ? x0 : z.v[0];
       z.v[1] = acc ? x1 : z.v[1];
-      s0 = acc ? t0 : s0;
-      s1 = acc ? t1 : s1;
-      lp = lp_out;
+      c0 = acc ? d0 : c0;
+      c1 = acc ? d1 : c1;
+      lt = acc ? ltn : lt;
       if (a.accept) a.accept[at] = acc ? 1 : 0;
     }
     store_row<T, ROW>(a.out, b, z);
     a.logdet[b] = ld;
+    a.policy.logp_target(b, lt);
   }
 }
 
 // ------------------------------------------------------------------ HMC run, VJP
-template <typename T>
+template <typename T, typename P>
 struct HmcBwdArgs {
   Target<T> t;
+  P policy;
   const T *trace, *noise, *step, *mass, *sqm, *gout, *gld;
   const byte_t* accept;
   T *gin, *partials;
@@ -168,9 +229,10 @@ struct HmcBwdArgs {
   int K, steps;
 };
 
-template <typename T, int F, bool ROW>
-__global__ __launch_bounds__(kBlock) void hmc_bwd_kernel(const HmcBwdArgs<T> a) {
+template <typename T, int F, bool ROW, typename P>
+__global__ __launch_bounds__(kBlock) void hmc_bwd_kernel(const HmcBwdArgs<T, P> a) {
   __shared__ T red[2][kWaves][kTerms];
+  typename P::Mix mix(a.policy);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   T* const block = a.partials + (long long)blockIdx.x * a.K * kTerms;
   int it = 0;                                          // layers visited: its parity picks the LDS buffer
@@ -194,9 +256,11 @@ __global__ __launch_bounds__(kBlock) void hmc_bwd_kernel(const HmcBwdArgs<T> a) 
         const Pack<T, 2> z = load_row<T, ROW>(a.trace, at);
         const Pack<T, 2> e = load_row<T, ROW>(a.noise, at);
         const bool acc = a.accept[at] != 0;
+        mix.layer(a.policy, k);
         T t0, t1;
-        point<T, F, true>(a.t, z.v[0], z.v[1], t0, t1);
-        const T sz0 = t0, sz1 = t1;                    // the score at the layer's entrance
+        T lpx = point<T, F, true>(a.t, z.v[0], z.v[1], t0, t1);      // log p: the policy's mix writes it, nothing reads it
+        mix(z.v[0], z.v[1], lpx, t0, t1);
+        const T sz0 = t0, sz1 = t1;                    // the layer's score at its entrance
         // the forward pass's trajectory again, with the sums of the closed form beside it
         T x0 = z.v[0], x1 = z.v[1], r0 = e.v[0] * a.sqm[2 * k], r1 = e.v[1] * a.sqm[2 * k + 1];
         T w0 = T(0), w1 = T(0);                        // sum_i p_half_i
@@ -207,7 +271,8 @@ __global__ __launch_bounds__(kBlock) void hmc_bwd_kernel(const HmcBwdArgs<T> a) 
           const T u0 = t0, u1 = t1;
           x0 = x0 + h0 * (q0 / m0);
           x1 = x1 + h1 * (q1 / m1);
-          point<T, F, true>(a.t, x0, x1, t0, t1);
+          lpx = point<T, F, true>(a.t, x0, x1, t0, t1);
+          mix(x0, x1, lpx, t0, t1);
           r0 = q0 - (h0 / T(2)) * -t0;
           r1 = q1 - (h1 / T(2)) * -t1;
           w0 += q0;
@@ -323,13 +388,13 @@ static long long sample_tiles(int64_t batch) { return (batch + kBlock - 1) / kBl
     default: return FN<T, VCNF_TARGET_RING_MIXTURE>(__VA_ARGS__);                                  \
   }
 
-template <typename T, int F>
-static int launch_hmc(const HmcArgs<T>& a, bool row, hipStream_t st) {
+template <typename T, int F, typename P>
+static int launch_hmc(const HmcArgs<T, P>& a, bool row, hipStream_t st) {
   VCNF_STOCH_LAUNCH(hmc_fwd_kernel, grid_for(a.B, 1, kBlock, kMaxBlocks), st, a);
 }
 
-template <typename T, int F>
-static int launch_hmc_bwd(const HmcBwdArgs<T>& a, int32_t groups, bool row, hipStream_t st) {
+template <typename T, int F, typename P>
+static int launch_hmc_bwd(const HmcBwdArgs<T, P>& a, int32_t groups, bool row, hipStream_t st) {
   VCNF_STOCH_LAUNCH(hmc_bwd_kernel, dim3((unsigned)groups), st, a);
 }
 
@@ -343,36 +408,49 @@ static Target<T> target_of(const T* table, int32_t n_comp, int family, T scale) 
   return is_mixture(family) ? Target<T>{table, (int)n_comp, scale} : Target<T>{nullptr, 0, T(0)};
 }
 
+// a policy's part of the entry points' checks: its required pointers, and all of its pointers' alignment
 template <typename T>
-static int hmc_stack(const T* z, const T* noise, const T* unif, const T* step, const T* mass, const T* sqm, const T* table,
-                     T* out, T* logdet, T* trace, byte_t* accept, int64_t batch, int32_t n_layers, int32_t steps,
-                     int32_t n_comp, int family, T scale, void* stream) {
+static bool complete(const Plain<T>&) { return true; }
+template <typename T>
+static bool complete(const Annealed<T>& p) { return p.beta && p.loc && p.log_scale; }
+template <typename T>
+static bool policy_aligned(const Plain<T>&) { return true; }
+template <typename T>
+static bool policy_aligned(const Annealed<T>& p) { return all_aligned({p.beta, p.loc, p.log_scale, p.lt_out}, sizeof(T)); }
+
+template <typename T, typename P>
+static int hmc_stack(const P& policy, const T* z, const T* noise, const T* unif, const T* step, const T* mass, const T* sqm,
+                     const T* table, T* out, T* logdet, T* trace, byte_t* accept, int64_t batch, int32_t n_layers,
+                     int32_t steps, int32_t n_comp, int family, T scale, void* stream) {
   if (const int st = check_run(batch, n_layers, steps, n_comp, family)) return st;
   if (batch == 0) return VCNF_OK;
-  if (!z || !noise || !unif || !step || !mass || !sqm || !out || !logdet || (is_mixture(family) && !table)) return VCNF_ERR_NULL;
-  if (!all_aligned({z, noise, unif, step, mass, sqm, table, out, logdet, trace}, sizeof(T))) return VCNF_ERR_ALIGN;
-  const HmcArgs<T> a{target_of(table, n_comp, family, scale), z, noise, unif, step, mass, sqm, out, logdet, trace, accept,
-                     batch, n_layers, steps};
+  if (!z || !noise || !unif || !step || !mass || !sqm || !out || !logdet || (is_mixture(family) && !table) || !complete(policy))
+    return VCNF_ERR_NULL;
+  if (!all_aligned({z, noise, unif, step, mass, sqm, table, out, logdet, trace}, sizeof(T)) || !policy_aligned(policy))
+    return VCNF_ERR_ALIGN;
+  const HmcArgs<T, P> a{target_of(table, n_comp, family, scale), policy, z, noise, unif, step, mass, sqm, out, logdet, trace,
+                        accept, batch, n_layers, steps};
   const bool row = all_aligned({z, noise, out, trace}, 2 * sizeof(T));
   hipStream_t st = (hipStream_t)stream;
   VCNF_STOCH_FAMILY(launch_hmc, a, row, st)
 }
 
-template <typename T>
-static int hmc_stack_bwd(const T* trace, const byte_t* accept, const T* noise, const T* step, const T* mass, const T* sqm,
-                         const T* table, const T* gout, const T* gld, T* gin, T* g_step, T* g_mass, T* g_sqm, T* workspace,
-                         int64_t batch, int32_t n_layers, int32_t steps, int32_t groups, int32_t n_comp, int family, T scale,
-                         void* stream) {
+template <typename T, typename P>
+static int hmc_stack_bwd(const P& policy, const T* trace, const byte_t* accept, const T* noise, const T* step, const T* mass,
+                         const T* sqm, const T* table, const T* gout, const T* gld, T* gin, T* g_step, T* g_mass, T* g_sqm,
+                         T* workspace, int64_t batch, int32_t n_layers, int32_t steps, int32_t groups, int32_t n_comp,
+                         int family, T scale, void* stream) {
   if (const int st = check_run(batch, n_layers, steps, n_comp, family)) return st;
   if (batch == 0) return VCNF_OK;
   // one block of the workspace per workgroup, and every workgroup has a tile to write its block for
   if (groups < 1 || groups > kMaxBwdGroups || groups > sample_tiles(batch)) return VCNF_ERR_SHAPE;
   if (!trace || !accept || !noise || !step || !mass || !sqm || !gin || !g_step || !g_mass || !g_sqm || !workspace ||
-      (is_mixture(family) && !table))
+      (is_mixture(family) && !table) || !complete(policy))
     return VCNF_ERR_NULL;
-  if (!all_aligned({trace, noise, step, mass, sqm, table, gout, gld, gin, g_step, g_mass, g_sqm, workspace}, sizeof(T)))
+  if (!all_aligned({trace, noise, step, mass, sqm, table, gout, gld, gin, g_step, g_mass, g_sqm, workspace}, sizeof(T)) ||
+      !policy_aligned(policy))
     return VCNF_ERR_ALIGN;
-  const HmcBwdArgs<T> a{target_of(table, n_comp, family, scale), trace, noise, step, mass, sqm, gout, gld, accept, gin,
+  const HmcBwdArgs<T, P> a{target_of(table, n_comp, family, scale), policy, trace, noise, step, mass, sqm, gout, gld, accept, gin,
                         workspace, batch, sample_tiles(batch), n_layers, steps};
   const bool row = all_aligned({trace, noise, gout, gin}, 2 * sizeof(T));
   hipStream_t st = (hipStream_t)stream;
@@ -402,17 +480,36 @@ static int mh_walk(const T* z, const T* eps, const T* w, const T* prop, const T*
                                       const T* sqrt_mass, const T* table, T* z_out, T* log_det, T* trace,              \
                                       uint8_t* accept, int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, \
                                       int family, T scale, void* stream) {                                             \
-    return vcnf_stoch::hmc_stack<T>(z, noise, unif, step, mass, sqrt_mass, table, z_out, log_det, trace, accept,       \
-                                    batch, n_layers, steps, n_comp, family, scale, stream);                            \
+    return vcnf_stoch::hmc_stack(vcnf_stoch::Plain<T>{}, z, noise, unif, step, mass, sqrt_mass, table, z_out, log_det, \
+                                 trace, accept, batch, n_layers, steps, n_comp, family, scale, stream);                \
+  }                                                                                                                    \
+  extern "C" int vcnf_hmc_annealed_stack_##SFX(                                                                        \
+      const T* z, const T* noise, const T* unif, const T* step, const T* mass, const T* sqrt_mass, const T* beta,      \
+      const T* prior_loc, const T* prior_log_scale, const T* table, T* z_out, T* log_det, T* logp_target, T* trace,    \
+      uint8_t* accept, int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, int family, T scale,            \
+      void* stream) {                                                                                                  \
+    return vcnf_stoch::hmc_stack(vcnf_stoch::Annealed<T>{beta, prior_loc, prior_log_scale, logp_target}, z, noise,     \
+                                 unif, step, mass, sqrt_mass, table, z_out, log_det, trace, accept, batch, n_layers,   \
+                                 steps, n_comp, family, scale, stream);                                                \
   }                                                                                                                    \
   extern "C" int vcnf_hmc_stack_bwd_##SFX(const T* trace, const uint8_t* accept, const T* noise, const T* step,        \
                                           const T* mass, const T* sqrt_mass, const T* table, const T* g_out,           \
                                           const T* g_logdet, T* g_in, T* g_step, T* g_mass, T* g_sqrt_mass,            \
                                           T* workspace, int64_t batch, int32_t n_layers, int32_t steps,                \
                                           int32_t groups, int32_t n_comp, int family, T scale, void* stream) {         \
-    return vcnf_stoch::hmc_stack_bwd<T>(trace, accept, noise, step, mass, sqrt_mass, table, g_out, g_logdet, g_in,     \
-                                        g_step, g_mass, g_sqrt_mass, workspace, batch, n_layers, steps, groups,        \
-                                        n_comp, family, scale, stream);                                                \
+    return vcnf_stoch::hmc_stack_bwd(vcnf_stoch::Plain<T>{}, trace, accept, noise, step, mass, sqrt_mass, table,       \
+                                     g_out, g_logdet, g_in, g_step, g_mass, g_sqrt_mass, workspace, batch, n_layers,   \
+                                     steps, groups, n_comp, family, scale, stream);                                    \
+  }                                                                                                                    \
+  extern "C" int vcnf_hmc_annealed_stack_bwd_##SFX(                                                                    \
+      const T* trace, const uint8_t* accept, const T* noise, const T* step, const T* mass, const T* sqrt_mass,         \
+      const T* beta, const T* prior_loc, const T* prior_log_scale, const T* table, const T* g_out, const T* g_logdet,  \
+      T* g_in, T* g_step, T* g_mass, T* g_sqrt_mass, T* workspace, int64_t batch, int32_t n_layers, int32_t steps,     \
+      int32_t groups, int32_t n_comp, int family, T scale, void* stream) {                                             \
+    return vcnf_stoch::hmc_stack_bwd(vcnf_stoch::Annealed<T>{beta, prior_loc, prior_log_scale, nullptr}, trace,        \
+                                     accept, noise, step, mass, sqrt_mass, table, g_out, g_logdet, g_in, g_step,       \
+                                     g_mass, g_sqrt_mass, workspace, batch, n_layers, steps, groups, n_comp, family,   \
+                                     scale, stream);                                                                   \
   }                                                                                                                    \
   extern "C" int vcnf_mh_walk_##SFX(const T* z, const T* eps, const T* w, const T* prop_scale, const T* table,         \
                                     T* z_out, uint8_t* accept, int64_t batch, int32_t steps, int32_t n_comp,           \

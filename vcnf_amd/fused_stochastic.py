@@ -9,11 +9,23 @@ differentiable, so autograd carries the kernel's operand gradients on to the par
 random numbers from torch's generator in the reference's order, layer by layer into preallocated buffers: ``randn`` of
 the layer's [B, 2], then ``rand`` of its [B]; a seed gives the chain that the layers give one by one, on the kernel or
 in torch.
+
+Annealed layers - the layers of ``vcnf_amd.sampling.HAIS``, whose target is the ``LinearInterpolation`` of a kernel target
+and a ``DiagGaussian`` prior over (2,) with a weight ``alpha`` - form runs of their own: consecutive layers that share the
+target object, the prior object and the step count go to vcnf_hmc_annealed_stack_*, with their alphas as the operand
+``beta`` [K] (``betas``) and the prior's parameters as constants.  A run never mixes plain and annealed layers.  The kernel
+has no gradient for the prior, so while autograd records, a prior whose parameters require grad sends the layer to its
+torch composition.  ``launch`` can also return the target's log p at the run's output, which the kernel carries anyway:
+the last term of the sampler's log weights.
 """
+import numbers
+
 import torch
 
 from . import _lib
-from .autograd import HmcStackFn, MhWalkFn, needs_grad
+from .autograd import HmcAnnealedStackFn, HmcStackFn, MhWalkFn, needs_grad
+from .distributions.base import DiagGaussian
+from .distributions.linear_interpolation import LinearInterpolation
 from .distributions.mh_proposal import DiagGaussianProposal
 from .distributions.target import CircularGaussianMixture, RingMixture, TwoMoons
 from .flows.base import fold_log_det
@@ -28,6 +40,29 @@ def kernel_target(target):
     return type(target) in (TwoMoons, CircularGaussianMixture, RingMixture)
 
 
+def annealed(target):
+    """Whether ``target`` is the bridge of an annealed layer: exactly a LinearInterpolation."""
+    return type(target) is LinearInterpolation
+
+
+def _kernel_bridge(bridge, z):
+    """Whether the kernel evaluates the LinearInterpolation ``bridge`` on the kernel inputs ``z``: a kernel target against
+    exactly a DiagGaussian over (2,) without a temperature whose parameters are like z - and are constants while autograd
+    records, since the kernel has no gradient for them - with a weight that is a number or a one-element tensor that
+    does not require grad."""
+    prior, alpha = bridge.dist2, bridge.alpha
+    if not (kernel_target(bridge.dist1) and type(prior) is DiagGaussian and tuple(prior.shape) == (2,) and prior.temperature is None):
+        return False
+    if torch.is_tensor(alpha):
+        if alpha.numel() != 1 or alpha.requires_grad or not alpha.is_floating_point():
+            return False
+    elif isinstance(alpha, bool) or not isinstance(alpha, numbers.Real):
+        return False
+    recording = torch.is_grad_enabled()
+    return all(p.dtype == z.dtype and p.device == z.device and not (recording and p.requires_grad)
+               for p in (prior.loc, prior.log_scale))
+
+
 def _kernel_inputs(z):
     return torch.is_tensor(z) and z.is_cuda and z.dim() == 2 and z.shape[1] == 2 and z.dtype in (torch.float32, torch.float64)
 
@@ -40,7 +75,10 @@ def _steps(flow):
 def covers(flow, z):
     """Whether the kernel evaluates the HMC layer ``flow`` on inputs like ``z``; otherwise the layer takes its torch
     composition."""
-    return (type(flow) is HamiltonianMonteCarlo and kernel_target(flow.target) and _kernel_inputs(z) and _steps(flow)
+    if not (type(flow) is HamiltonianMonteCarlo and _kernel_inputs(z) and _steps(flow)):
+        return False
+    target = flow.target
+    return ((_kernel_bridge(target, z) if annealed(target) else kernel_target(target))
             and all(p.dtype == z.dtype and p.device == z.device and p.numel() in (1, 2)
                     for p in (flow.log_step_size, flow.log_mass)))
 
@@ -54,16 +92,23 @@ def covers_walk(flow, z):
 
 
 def plan(order, start, z):
-    """(end, flows): the longest run order[start:end] one launch evaluates, or None."""
+    """(end, flows): the longest run order[start:end] one launch evaluates, or None.  The layers of a run share the step
+    count and the target object - annealed layers the two objects their bridges join - so a run is plain or annealed."""
     if not covers(order[start], z):
         return None
     first = order[start]
     most = MAX_POINTS // (first.steps + 1)           # >= 1: covers() holds steps + 1 to the limit
     end = start + 1
-    while end < len(order) and end - start < most and covers(order[end], z) and order[end].target is first.target \
+    while end < len(order) and end - start < most and covers(order[end], z) and _same_target(order[end].target, first.target) \
             and order[end].steps == first.steps:
         end += 1
     return end, order[start:end]
+
+
+def _same_target(a, b):
+    if annealed(a) or annealed(b):
+        return annealed(a) and annealed(b) and a.dist1 is b.dist1 and a.dist2 is b.dist2
+    return a is b
 
 
 def stack_run(owner, order, start, z, context, density):
@@ -96,18 +141,42 @@ def draws(z, n_layers):
     return noise, unif
 
 
-def run(flows, z, log_q, sign):
-    """One launch for the run: (z', log_q + sign * log_det), or (z', sign * log_det) without a log_q.  With autograd
-    recording the run is one node, HmcStackFn, and log_q is not written in place."""
+def betas(flows, z):
+    """beta [K] of an annealed run: the layers' alphas in z's dtype on z's device.  Alphas that are tensors on that
+    device are stacked there, without a host synchronisation; numbers and host tensors make one host tensor."""
+    alphas = [f.target.alpha for f in flows]
+    if all(torch.is_tensor(a) and a.device == z.device for a in alphas):
+        return torch.stack([a.detach().reshape(()) for a in alphas]).to(z.dtype)
+    return torch.tensor([float(a) for a in alphas], dtype=torch.float64).to(device=z.device, dtype=z.dtype)
+
+
+def launch(flows, z, want_logp=False):
+    """One launch for the run: (z', log_det, recorded) and with ``want_logp`` - an annealed run outside autograd - also the
+    target's log p at z'.  ``recorded``: the run is one autograd node (HmcStackFn, HmcAnnealedStackFn)."""
     target = flows[0].target
-    table, scale = target._operands(z)
+    bridge = annealed(target)
+    kernel = target.dist1 if bridge else target
+    table, scale = kernel._operands(z)
     step, mass, sqrt_mass = operands(flows)
     noise, unif = draws(z, len(flows))
-    if needs_grad(z, step, mass, sqrt_mass):
-        out, ld = HmcStackFn.apply(z, step, mass, sqrt_mass, noise, unif, flows[0].steps, target._family, table, scale)
-        return add_log_det(out, ld, log_q, sign)
-    out, ld = _lib.hmc_stack(z, noise, unif, step, mass, sqrt_mass, flows[0].steps, target._family, table, scale)
-    return fold_log_det(out, ld, log_q, sign)
+    steps, family = flows[0].steps, kernel._family
+    recorded = needs_grad(z, step, mass, sqrt_mass)
+    if not bridge:
+        if recorded:
+            return HmcStackFn.apply(z, step, mass, sqrt_mass, noise, unif, steps, family, table, scale) + (True,)
+        return _lib.hmc_stack(z, noise, unif, step, mass, sqrt_mass, steps, family, table, scale) + (False,)
+    prior = (betas(flows, z), target.dist2.loc.detach().reshape(-1), target.dist2.log_scale.detach().reshape(-1))
+    if recorded:
+        return HmcAnnealedStackFn.apply(z, step, mass, sqrt_mass, noise, unif, *prior, steps, family, table, scale) + (True,)
+    got = _lib.hmc_annealed_stack(z, noise, unif, step, mass, sqrt_mass, *prior, steps, family, table, scale, want_logp=want_logp)
+    return got[:2] + (False,) + got[2:]
+
+
+def run(flows, z, log_q, sign):
+    """One launch for the run: (z', log_q + sign * log_det), or (z', sign * log_det) without a log_q.  With autograd
+    recording the run is one node and log_q is not written in place."""
+    out, ld, recorded = launch(flows, z)
+    return add_log_det(out, ld, log_q, sign) if recorded else fold_log_det(out, ld, log_q, sign)
 
 
 def walk(flow, z):
