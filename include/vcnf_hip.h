@@ -825,6 +825,64 @@ int vcnf_tail_sample_bwd_f64(const double* eps, const double* gamma, const doubl
 int vcnf_tail_reduce_partials_f64(const double* partials, int64_t groups, int32_t features, double* d_loc,
                                   double* d_log_scale, double* d_shape, void* stream);
 
+/* ---- End caps of the flow VAE (NormalizingFlowVAE): the amortised diagonal Gaussian encoder and the Gaussian /
+ * Bernoulli decoders.  rows = batch * samples rows of `features` = D columns, all buffers contiguous; row n belongs to
+ * data item n / samples.  A parameter row is h = [mean (D) | lv (D)], 2 D contiguous values with lv the log variance
+ * (for a net output [., 2 C, H, W] that is the contiguous row, D = C H W).  An operand that the rows of an item share
+ * is read through its divisor (row n reads its row n / div) and never repeated in memory.
+ *   encode (h [batch, 2 D], eps [rows, D]):  z = mean + exp(lv / 2) eps [rows, D],
+ *              logq[n] = -D/2 log 2 pi - sum_j (lv / 2 + eps^2 / 2)       (log std is lv / 2 as it stands)
+ *   encode_bwd (cotangents g_z [rows, D] and g_lq [rows], either may be NULL = zero, not both): d_h [batch, 2 D] with
+ *              d_mean[b, j] = sum_s g_z[n, j],  d_lv[b, j] = sum_s (exp(lv / 2) eps g_z / 2 - g_lq[n] / 2); eps gets no
+ *              gradient
+ *   gauss_log_prob (v [rows / v_div, D], h [rows / h_div, 2 D]):
+ *              logp[n] = -D/2 log 2 pi - 1/2 sum_j (lv + (v - mean)^2 exp(-lv))
+ *              the encoder's log_prob(z, x) is v_div = 1, h_div = samples; the Gaussian decoder v_div = samples,
+ *              h_div = 1.  Both divisors >= 1, min(v_div, h_div) == 1 and rows divisible by both, else VCNF_ERR_SHAPE
+ *   gauss_log_prob_bwd (cotangent g_lp [rows]; d_v and d_h shaped like v and h, either may be NULL, not both): with
+ *              r = (v - mean) exp(-lv):  d_v = -g r,  d_mean = g r,  d_lv = g (r (v - mean) / 2 - 1 / 2); the operand
+ *              with divisor 1 is written row by row, the other is summed over its rows
+ *   bernoulli_log_prob (x [rows / x_div, D] with values in [0, 1], score [rows, D]):
+ *              logp[n] = sum_j (x ls(a) + (1 - x) ls(-a)),  ls(a) = -max(-a, 0) - log1p(exp(-|a|))
+ *   bernoulli_log_prob_bwd: d_score [rows, D] = g (x - sigmoid(a)), the sigmoid in the form that never exponentiates a
+ *              positive number; x gets no gradient
+ * Forward: a lane group per row, the row in chunks of 16 bytes' worth of columns strided over the group; 16-byte
+ * (8-byte) accesses when features % V == 0 and the [., D] / [., 2 D] buffers are aligned to them, scalar otherwise,
+ * with the same bits either way.  VJPs: a lane per (item, column) walks the item's rows in ascending order, the shared
+ * operand's gradient in a register: a fixed-order sum, no atomics, no workspace, no allocation, no host
+ * synchronisation - every call is bitwise reproducible and capturable.  No kernel loops over the grid: a shape that
+ * needs more than 2^31 - 1 workgroups -> VCNF_ERR_SHAPE.
+ * Checked in this order: NULL required pointer -> VCNF_ERR_NULL; features < 1, samples < 1, a negative count or the
+ * divisor rules -> VCNF_ERR_SHAPE; batch == 0 / rows == 0 -> VCNF_OK without a launch; a pointer not aligned to its
+ * element size -> VCNF_ERR_ALIGN; in the _bwd entry points samples (the divisor) > VCNF_VAE_MAX_SAMPLES ->
+ * VCNF_ERR_UNSUPPORTED (one lane walks them: a mistaken argument must not become a launch that runs for minutes).  The
+ * forward entry points take any divisor. */
+enum { VCNF_VAE_MAX_SAMPLES = 4096 };
+int vcnf_vae_encode_f32(const float* h, const float* eps, float* z, float* logq, int64_t batch, int32_t samples,
+                        int32_t features, void* stream);
+int vcnf_vae_encode_bwd_f32(const float* h, const float* eps, const float* g_z, const float* g_lq, float* d_h,
+                            int64_t batch, int32_t samples, int32_t features, void* stream);
+int vcnf_vae_gauss_log_prob_f32(const float* v, const float* h, float* logp, int64_t rows, int32_t v_div, int32_t h_div,
+                                int32_t features, void* stream);
+int vcnf_vae_gauss_log_prob_bwd_f32(const float* v, const float* h, const float* g_lp, float* d_v, float* d_h,
+                                    int64_t rows, int32_t v_div, int32_t h_div, int32_t features, void* stream);
+int vcnf_vae_bernoulli_log_prob_f32(const float* x, const float* score, float* logp, int64_t rows, int32_t x_div,
+                                    int32_t features, void* stream);
+int vcnf_vae_bernoulli_log_prob_bwd_f32(const float* x, const float* score, const float* g_lp, float* d_score,
+                                        int64_t rows, int32_t x_div, int32_t features, void* stream);
+int vcnf_vae_encode_f64(const double* h, const double* eps, double* z, double* logq, int64_t batch, int32_t samples,
+                        int32_t features, void* stream);
+int vcnf_vae_encode_bwd_f64(const double* h, const double* eps, const double* g_z, const double* g_lq, double* d_h,
+                            int64_t batch, int32_t samples, int32_t features, void* stream);
+int vcnf_vae_gauss_log_prob_f64(const double* v, const double* h, double* logp, int64_t rows, int32_t v_div,
+                                int32_t h_div, int32_t features, void* stream);
+int vcnf_vae_gauss_log_prob_bwd_f64(const double* v, const double* h, const double* g_lp, double* d_v, double* d_h,
+                                    int64_t rows, int32_t v_div, int32_t h_div, int32_t features, void* stream);
+int vcnf_vae_bernoulli_log_prob_f64(const double* x, const double* score, double* logp, int64_t rows, int32_t x_div,
+                                    int32_t features, void* stream);
+int vcnf_vae_bernoulli_log_prob_bwd_f64(const double* x, const double* score, const double* g_lp, double* d_score,
+                                        int64_t rows, int32_t x_div, int32_t features, void* stream);
+
 /* ---- Full-covariance base distributions: the multivariate Gaussian and the multivariate Student-t over D = features
  * <= 128.  z / eps [B, D] contiguous, gamma [B], loc [D]; tri [D, D] row-major is a lower-triangular matrix of which
  * only the lower triangle including the diagonal is ever read: the scale L for sampling, its inverse M = L^-1 for the

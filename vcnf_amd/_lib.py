@@ -39,7 +39,7 @@ _ABI = _abi.read(_build.HEADER, pointer=_P)
 
 # every VCNF_* constant of the header under its name without the prefix: OK, ERR_*, LD_*, TAILS_*, PREC_*, SCALE_*, TAIL_*,
 # MVN_* (MVN_MAX_DIM among them), GMM_MAX_TABLE, PLANAR_TANH / PLANAR_LEAKY / RADIAL, TARGET_*, HMC_BLOCK,
-# HMC_MAX_BWD_GROUPS, STOCH_MAX_POINTS, AFFINE_STACK_MAX_LAYERS, PROBE_*
+# HMC_MAX_BWD_GROUPS, STOCH_MAX_POINTS, VAE_MAX_SAMPLES, AFFINE_STACK_MAX_LAYERS, PROBE_*
 globals().update({name[len("VCNF_"):]: value for name, value in _ABI.constants.items()})
 SCALE_MAPS = {"exp": SCALE_EXP, "sigmoid": SCALE_SIGMOID, "sigmoid_inv": SCALE_SIGMOID_INV}
 
@@ -1332,6 +1332,120 @@ def tail_sample_bwd(eps, gamma, loc, ls, shape, family, g_z=None, g_lp=None, row
     sums = _tail_row_sums(dev, lambda ws: _launch(name, e2, g2, loc, ls, shape, g_z, g_lp, d_eps, d_gamma, ws, b, d,
                                                   family), name, e2, b, d, rows)
     return (d_eps.view(eps.shape) if want_eps else None, d_gamma.view(eps.shape)) + sums
+
+
+def _vae_rows(name, dtype, *operands):
+    """Operands of a vcnf_vae_* entry point given as (tensor or None, rows, columns, what): each as contiguous
+    [rows, columns] of ``dtype`` (None stays None).  Returns (device, the operands)."""
+    dev = require_device(*[t for t, _, _, _ in operands], f64=True)
+    out = []
+    for t, rows, cols, what in operands:
+        if t is not None:
+            if t.dtype != dtype:
+                raise VcnfError(name + ": mixed dtypes")
+            if t.numel() != rows * cols:
+                raise VcnfError("%s: %s %s is not [%d, %d]" % (name, what, tuple(t.shape), rows, cols))
+            t = t.reshape(rows, cols).contiguous()
+        out.append(t)
+    return dev, out
+
+
+def _vae_encode_sizes(name, h, eps):
+    """(B, S, D) of h [B, 2 D elements] and eps [B, S, D elements]."""
+    if h.dim() < 2 or eps.dim() < 2 or len(h) != len(eps) or h[0].numel() % 2:
+        raise VcnfError("%s: h %s and eps %s are not [B, 2 D] and [B, S, D]" % (name, tuple(h.shape), tuple(eps.shape)))
+    return len(h), eps.shape[1], h[0].numel() // 2
+
+
+def vae_encode(h, eps):
+    """vcnf_vae_encode_*: (z like eps, log q [B, S]) of the draw eps [B, S, ...] under the Gaussian whose parameter rows
+    h [B, ...] hold [mean | log variance], D elements each."""
+    name = "vcnf_vae_encode" + _sfx(eps)
+    b, s, d = _vae_encode_sizes(name, h, eps)
+    dev, (h2, e2) = _vae_rows(name, eps.dtype, (h, b, 2 * d, "h"), (eps, b * s, d, "eps"))
+    z = torch.empty_like(e2)
+    logq = torch.empty(b * s, dtype=eps.dtype, device=dev)
+    if b * s:
+        _call(name, dev, h2, e2, z, logq, b, s, d)
+    return z.view(eps.shape), logq.view(b, s)
+
+
+def vae_encode_bwd(h, eps, g_z=None, g_lq=None):
+    """vcnf_vae_encode_bwd_*: d_h like h for the cotangents g_z (like eps) and g_lq [B, S] of vcnf_vae_encode_*; None is
+    zero (not both).  At most VAE_MAX_SAMPLES samples per item."""
+    name = "vcnf_vae_encode_bwd" + _sfx(eps)
+    b, s, d = _vae_encode_sizes(name, h, eps)
+    dev, (h2, e2, g_z, g_lq) = _vae_rows(name, eps.dtype, (h, b, 2 * d, "h"), (eps, b * s, d, "eps"),
+                                         (g_z, b * s, d, "g_z"), (g_lq, b * s, 1, "g_lq"))
+    d_h = torch.empty_like(h2)
+    if b:
+        _call(name, dev, h2, e2, g_z, g_lq, d_h, b, s, d)
+    return d_h.view(h.shape)
+
+
+def _vae_gauss_sizes(name, v, h, v_div, h_div):
+    """(N, D) of v [N / v_div, D elements] and h [N / h_div, 2 D elements]."""
+    n = len(v) * v_div
+    if v.dim() < 2 or h.dim() < 2 or len(h) * h_div != n or h[0].numel() != 2 * v[0].numel():
+        raise VcnfError("%s: v %s (divisor %d) and h %s (divisor %d) do not go together" % (
+            name, tuple(v.shape), v_div, tuple(h.shape), h_div))
+    return n, v[0].numel()
+
+
+def vae_gauss_log_prob(v, h, v_div=1, h_div=1):
+    """vcnf_vae_gauss_log_prob_*: log density [N] of the values v [N / v_div, ...] under the Gaussians with the parameter
+    rows h [N / h_div, ...] = [mean | log variance]; row n reads v[n // v_div] and h[n // h_div]."""
+    name = "vcnf_vae_gauss_log_prob" + _sfx(v)
+    n, d = _vae_gauss_sizes(name, v, h, v_div, h_div)
+    dev, (v2, h2) = _vae_rows(name, v.dtype, (v, n // v_div, d, "v"), (h, n // h_div, 2 * d, "h"))
+    logp = torch.empty(n, dtype=v.dtype, device=dev)
+    if n:
+        _call(name, dev, v2, h2, logp, n, v_div, h_div, d)
+    return logp
+
+
+def vae_gauss_log_prob_bwd(v, h, g, v_div=1, h_div=1, want_v=True, want_h=True):
+    """vcnf_vae_gauss_log_prob_bwd_*: (d_v like v or None, d_h like h or None) for the cotangent g [N]; the operand with
+    the divisor is summed over its rows (at most VAE_MAX_SAMPLES of them)."""
+    name = "vcnf_vae_gauss_log_prob_bwd" + _sfx(v)
+    n, d = _vae_gauss_sizes(name, v, h, v_div, h_div)
+    dev, (v2, h2, g) = _vae_rows(name, v.dtype, (v, n // v_div, d, "v"), (h, n // h_div, 2 * d, "h"), (g, n, 1, "g"))
+    d_v = torch.empty_like(v2) if want_v else None
+    d_h = torch.empty_like(h2) if want_h else None
+    if n:
+        _call(name, dev, v2, h2, g, d_v, d_h, n, v_div, h_div, d)
+    return d_v.view(v.shape) if want_v else None, d_h.view(h.shape) if want_h else None
+
+
+def _vae_bernoulli_sizes(name, x, score, x_div):
+    if x.dim() < 2 or score.dim() < 2 or len(x) * x_div != len(score) or x[0].numel() != score[0].numel():
+        raise VcnfError("%s: x %s (divisor %d) and the scores %s do not go together" % (
+            name, tuple(x.shape), x_div, tuple(score.shape)))
+    return len(score), x[0].numel()
+
+
+def vae_bernoulli_log_prob(x, score, x_div=1):
+    """vcnf_vae_bernoulli_log_prob_*: log likelihood [N] of the data x [N / x_div, ...] (values in [0, 1]) under the
+    Bernoulli scores (logits) [N, ...]; row n reads x[n // x_div]."""
+    name = "vcnf_vae_bernoulli_log_prob" + _sfx(score)
+    n, d = _vae_bernoulli_sizes(name, x, score, x_div)
+    dev, (x2, s2) = _vae_rows(name, score.dtype, (x, n // x_div, d, "x"), (score, n, d, "score"))
+    logp = torch.empty(n, dtype=score.dtype, device=dev)
+    if n:
+        _call(name, dev, x2, s2, logp, n, x_div, d)
+    return logp
+
+
+def vae_bernoulli_log_prob_bwd(x, score, g, x_div=1):
+    """vcnf_vae_bernoulli_log_prob_bwd_*: d_score like the scores for the cotangent g [N]; x gets no gradient.  At most
+    VAE_MAX_SAMPLES rows per data item."""
+    name = "vcnf_vae_bernoulli_log_prob_bwd" + _sfx(score)
+    n, d = _vae_bernoulli_sizes(name, x, score, x_div)
+    dev, (x2, s2, g) = _vae_rows(name, score.dtype, (x, n // x_div, d, "x"), (score, n, d, "score"), (g, n, 1, "g"))
+    d_score = torch.empty_like(s2)
+    if n:
+        _call(name, dev, x2, s2, g, d_score, n, x_div, d)
+    return d_score.view(score.shape)
 
 
 def _mvn_operands(x, loc, tri, consts, what):

@@ -495,6 +495,70 @@ class HeavyTailSampleFn(torch.autograd.Function):
                 d_sh if need[4] else None, g_lp.sum().expand(shape.shape) if need[5] else None, None)
 
 
+class VaeEncodeFn(torch.autograd.Function):
+    """vcnf_vae_encode_*: (z like eps, log q [B, S]) of the draw eps [B, S, ...] under the Gaussian of the parameter rows
+    h [B, ...] = [mean | log variance] as ONE node that saves only its inputs; backward is vcnf_vae_encode_bwd_*.  eps
+    gets no gradient (a caller whose eps requires grad takes the torch composition).  Not double-differentiable."""
+
+    @staticmethod
+    def forward(ctx, h, eps):
+        with torch.no_grad():
+            z, lq = _lib.vae_encode(h, eps)
+        ctx.save_for_backward(h, eps)
+        ctx.set_materialize_grads(False)
+        return z, lq
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_z, g_lq):
+        h, eps = ctx.saved_tensors
+        if g_z is None and g_lq is None:
+            return None, None
+        return _lib.vae_encode_bwd(h, eps, g_z, g_lq), None
+
+
+class VaeGaussLogProbFn(torch.autograd.Function):
+    """vcnf_vae_gauss_log_prob_*: log density [N] of v [N / v_div, ...] under the Gaussians of the parameter rows
+    h [N / h_div, ...] as ONE node that saves only its inputs; backward is vcnf_vae_gauss_log_prob_bwd_*, for whichever
+    of v and h needs a gradient.  Not double-differentiable."""
+
+    @staticmethod
+    def forward(ctx, v, h, v_div, h_div):
+        with torch.no_grad():
+            lp = _lib.vae_gauss_log_prob(v, h, v_div, h_div)
+        ctx.save_for_backward(v, h)
+        ctx.divs = (v_div, h_div)
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        v, h = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_v, d_h = _lib.vae_gauss_log_prob_bwd(v, h, g, *ctx.divs, want_v=need[0], want_h=need[1])
+        return d_v, d_h, None, None
+
+
+class VaeBernoulliLogProbFn(torch.autograd.Function):
+    """vcnf_vae_bernoulli_log_prob_*: log likelihood [N] of the data x [N / x_div, ...] under the scores [N, ...] as ONE
+    node that saves only its inputs; backward is vcnf_vae_bernoulli_log_prob_bwd_*.  x gets no gradient (a caller whose
+    x requires grad takes the torch composition).  Not double-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, score, x_div):
+        with torch.no_grad():
+            lp = _lib.vae_bernoulli_log_prob(x, score, x_div)
+        ctx.save_for_backward(x, score)
+        ctx.x_div = x_div
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, score = ctx.saved_tensors
+        return None, _lib.vae_bernoulli_log_prob_bwd(x, score, g, ctx.x_div), None
+
+
 class PlanarRadialStackFn(torch.autograd.Function):
     """vcnf_planar_radial_stack_*: (out, log|det| [B]) of a run of Planar / Radial layers from its effective operands va,
     vb [K, D] and sc [K, 2] (vcnf_amd.fused_planar.operands) as ONE node.  Forward launches the kernel with the trace

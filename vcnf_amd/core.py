@@ -17,7 +17,8 @@ import torch
 from torch import nn
 
 from .flows.affine.coupling import AffineCouplingBlock, MaskedAffineFlow, AffineConstFlow
-from . import fused_affine, fused, fused_masked, fused_planar, fused_stochastic
+from . import fused_affine, fused, fused_masked, fused_planar, fused_stochastic, vae_ends
+from .distributions.encoder import Dirac
 from .flows.mixing import Permute
 from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
 from .flows.planar import Planar
@@ -50,16 +51,11 @@ class _PackedWeightsMixin:
         return refresh_packed(self)
 
 
-class NormalizingFlow(_PackedWeightsMixin, nn.Module):
-    def __init__(self, q0, flows, p=None, categoricals=None, catlevels=None, catvdeqs=None):
-        super().__init__()
-        self._install_pack_hooks()
-        if categoricals is not None:
-            raise NotImplementedError("variational dequantisation of categorical columns is out of scope")
-        self.q0 = q0
-        self.flows = nn.ModuleList(flows)
-        self.p = p
-        self.categoricals = None
+class _FlowWalks:
+    """The passes over ``self.flows`` that NormalizingFlow and NormalizingFlowVAE share, and the switches of the
+    single-launch families they consult."""
+
+    def _init_stack_switches(self):
         self.fuse_affine_stacks = True           # runs of one-kernel affine layers in a single launch (fused_affine.run_stack)
         self.fuse_rqs_stacks = True              # runs of one-kernel RQS layers in a single launch at small batches (fused.run_stack)
         self.fuse_masked_stacks = True           # runs of MaskedAffineFlow (+ MLP conditioners) / ActNorm layers in a single launch
@@ -141,6 +137,19 @@ class NormalizingFlow(_PackedWeightsMixin, nn.Module):
             log_q = log_q + log_det if density else log_q - log_det
             i += 1
         return z, log_q
+
+
+class NormalizingFlow(_PackedWeightsMixin, _FlowWalks, nn.Module):
+    def __init__(self, q0, flows, p=None, categoricals=None, catlevels=None, catvdeqs=None):
+        super().__init__()
+        self._install_pack_hooks()
+        if categoricals is not None:
+            raise NotImplementedError("variational dequantisation of categorical columns is out of scope")
+        self.q0 = q0
+        self.flows = nn.ModuleList(flows)
+        self.p = p
+        self.categoricals = None
+        self._init_stack_switches()
 
     # ------------------------------------------------------------ density
     def log_prob(self, x, context=None):
@@ -262,6 +271,42 @@ class ClassCondFlow(NormalizingFlow):
         """``sample`` with the standard-normal base draw given."""
         z, log_q = self.q0.from_noise(eps, y)
         return self._walk(z, log_q, None, False)
+
+
+class NormalizingFlowVAE(_PackedWeightsMixin, _FlowWalks, nn.Module):
+    """VAE with normalizing flows on the latent (normflow/core.py:402-454): an encoder ``q0(x, num_samples)``, flows in
+    the sampling direction, a ``prior`` (any object with ``log_prob``: a base distribution of this package or a
+    ``torch.distributions`` object) and an optional ``decoder``.  The flows go through NormalizingFlow's plain walk, so a
+    stretch of Planar / Radial layers is one launch and one autograd node between the end-cap kernels of
+    ``distributions.NNDiagGaussian`` and the decoders (csrc/vae_ends.hip).  Tensors the kernels do not compute on (CPU,
+    half precision) take the torch composition of every layer and of the prior that has one."""
+
+    def __init__(self, prior, q0=None, flows=None, decoder=None):
+        super().__init__()
+        self._install_pack_hooks()
+        self.prior = prior
+        self.decoder = decoder
+        self.flows = nn.ModuleList(flows if flows is not None else [])
+        self.q0 = q0 if q0 is not None else Dirac()
+        self._init_stack_switches()
+
+    def forward(self, x, num_samples=1):
+        """(z [B, S, ...], log q(z | x) [B, S], log p(x, z) [B, S]) for S = num_samples latents per item of x [B, ...]."""
+        z, log_q = self.q0(x, num_samples=num_samples)
+        z = z.reshape((-1,) + tuple(z.shape[2:]))
+        log_q = log_q.reshape(-1)
+        if vae_ends.on_kernels(z):
+            z, log_q = self._plain_walk(z, log_q, None, False)
+            log_p = self.prior.log_prob(z)
+        else:
+            for flow in self.flows:
+                z, log_det = getattr(flow, '_torch_forward', flow)(z)
+                log_q = log_q - log_det
+            log_p = getattr(self.prior, '_torch_log_prob', self.prior.log_prob)(z)
+        if self.decoder is not None:
+            log_p = log_p + self.decoder.log_prob(x, z)
+        return (z.reshape((-1, num_samples) + tuple(z.shape[1:])), log_q.reshape(-1, num_samples),
+                log_p.reshape(-1, num_samples))
 
 
 class MultiscaleFlow(_PackedWeightsMixin, nn.Module):

@@ -68,6 +68,13 @@ class DiagGaussian(BaseDistribution):
             return lp if out is None else out.add_(lp)
         return _lib.diag_gaussian_log_prob(z, loc, ls, self.temperature, logp=out)
 
+    def _torch_log_prob(self, z):
+        """base.py:644-652 as the reference composes it, for the callers that serve tensors the kernels do not compute
+        on (NormalizingFlowVAE off the device); ``log_prob`` itself refuses those."""
+        log_scale = self.log_scale if self.temperature is None else self.log_scale + np.log(self.temperature)
+        return -0.5 * self.d * np.log(2 * np.pi) - torch.sum(
+            log_scale + 0.5 * torch.pow((z - self.loc) / torch.exp(log_scale), 2), list(range(1, self.n_dim + 1)))
+
 
 class _ClassCondBase(BaseDistribution):
     """Shared end of the class-conditional bases: labels to kernel operands, and the calls of the
