@@ -1021,16 +1021,44 @@ int vcnf_planar_radial_stack_bwd_f64(const double* z_out, const double* trace, c
  *   VCNF_TARGET_RING_MIXTURE  table [n_comp] the radii t_i (upstream: 2 (i + 1) / n),
  *                             d_i = (r - t_i)^2 / (2 scale^2),  logp = logsumexp_i(-d_i)
  *                             score = sum_i softmax_i(-d) (t_i - r) / scale^2 z / r
+ * The energy densities of normflow 1.2's distributions/prior.py (the test energies of Rezende & Mohamed) are families
+ * of the same entry points.  `scale` is the density's scale s and `table` holds its other constants, device memory of
+ * the call's type read at fixed indices.  With q = (20 s)^4, om = 2 pi / period, w1 = sin(om z0), w1' = om cos(om z0),
+ * d = z1 - w1 and u(z) = z / r:
+ *   VCNF_TARGET_TWO_MODES     table {loc} (n_comp >= 1); eps = |loc|, c1 = 2 s, c2 = 3 s, e = exp(-2 a eps / c2^2)
+ *                             logp = -((r - loc) / c1)^2 / 2 - ((a - eps) / c2)^2 / 2 + log1p(e)
+ *                             score0 = -(r - loc) / c1^2 u(z0) + sign(z0) ((eps - a) / c2^2 - (2 eps / c2^2) e / (1 + e))
+ *                             score1 = -(r - loc) / c1^2 u(z1)
+ *   VCNF_TARGET_SINUSOIDAL    table {period} (n_comp >= 1)
+ *                             logp = -(d / s)^2 / 2 - (z0^4 + z1^4) / (2 q)
+ *                             score0 = d w1' / s^2 - 2 z0^3 / q,   score1 = -d / s^2 - 2 z1^3 / q
+ *   VCNF_TARGET_SINUSOIDAL_GAP    table {period, amp, mu, width} (n_comp >= 4; upstream: amp 3, mu 1, width 0.6)
+ *                             w = amp exp(-((z0 - mu) / width)^2 / 2),  w' = -w (z0 - mu) / width^2
+ *                             a = -(d / s)^2 / 2,  b = -((d + w) / s)^2 / 2,  pb = sigmoid(b - a),  pa = 1 - pb
+ *                             logp = logaddexp(a, b) - (z0^4 + z1^4) / (2 q)
+ *                             score0 = (pa d w1' + pb (d + w) (w1' - w')) / s^2 - 2 z0^3 / q
+ *                             score1 = -(pa d + pb (d + w)) / s^2 - 2 z1^3 / q
+ *   VCNF_TARGET_SINUSOIDAL_SPLIT  the same with w = amp sigmoid((z0 - mu) / width),  w' = w (1 - w / amp) / width
+ *                             (upstream: amp 3, mu 1, width 0.3)
+ *   VCNF_TARGET_SMILEY        c = 2 s,  t = |z1 + 0.8|;  table and n_comp are ignored (table may be NULL)
+ *                             logp = -((r - 2) / c)^2 / 2 - ((t - 1.2) / c)^2 / 2
+ *                             score0 = -(r - 2) / c^2 u(z0),   score1 = -(r - 2) / c^2 u(z1) - sign(z1 + 0.8) (t - 1.2) / c^2
+ * The logaddexp subtracts its larger branch and pb comes from the same exp(-|b - a|): finite wherever a and b are,
+ * where log(exp a + exp b) is -inf in fp32 a few |d| / s out.  scale == 0 and period == 0 are the caller's business.
  * The caller computes the table.  Every z / r is 0 at r == 0 (torch's gradient of norm there) and sign(0) = 0; a
  * non-finite z gives NaN logp and score.  The logsumexp subtracts its maximum in two passes over the components; no
  * buffer of size [B, n_comp] exists and n_comp has no upper limit.  One sample per lane; a row moves as one 8-byte
  * (16-byte) access when z and score are aligned to it, as two elements otherwise, with the same bits either way.
  * logp does not depend on whether score is given, bit for bit.
- * batch < 0, or n_comp < 1 for a mixture -> VCNF_ERR_SHAPE; unknown family -> VCNF_ERR_UNSUPPORTED; batch == 0 ->
- * VCNF_OK without a launch; NULL z or logp, or NULL table for a mixture -> VCNF_ERR_NULL; a pointer not aligned to
- * its element size -> VCNF_ERR_ALIGN.  No atomics, no allocation, no host synchronisation: every call is bitwise
- * reproducible and capturable. */
-enum { VCNF_TARGET_TWO_MOONS = 0, VCNF_TARGET_CIRCULAR_GMM = 1, VCNF_TARGET_RING_MIXTURE = 2 };
+ * batch < 0, or n_comp below what the family reads (1 for a mixture) -> VCNF_ERR_SHAPE; unknown family ->
+ * VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL z or logp, or NULL table for a family that reads
+ * one -> VCNF_ERR_NULL; a pointer not aligned to its element size -> VCNF_ERR_ALIGN.  No atomics, no allocation, no
+ * host synchronisation: every call is bitwise reproducible and capturable. */
+enum {
+  VCNF_TARGET_TWO_MOONS = 0, VCNF_TARGET_CIRCULAR_GMM = 1, VCNF_TARGET_RING_MIXTURE = 2,
+  VCNF_TARGET_TWO_MODES = 16, VCNF_TARGET_SINUSOIDAL = 17, VCNF_TARGET_SINUSOIDAL_GAP = 18,
+  VCNF_TARGET_SINUSOIDAL_SPLIT = 19, VCNF_TARGET_SMILEY = 20
+};
 int vcnf_target_log_prob_f32(const float* z, const float* table, float* logp, float* score, int64_t batch,
                              int32_t n_comp, int family, float scale, void* stream);
 int vcnf_target_log_prob_f64(const double* z, const double* table, double* logp, double* score, int64_t batch,
@@ -1084,9 +1112,9 @@ int vcnf_target_log_prob_f64(const double* z, const double* table, double* logp,
  *     accept = w <= min(exp(logp(z_) - logp(z)), 1) (NaN rejects),  z = accept ? z_ : z;  logp(z) is carried from step
  *     to step.  accept [steps, B] (bytes, may be NULL) receives the decisions.  The layer's log_det is zero and it is
  *     the identity under differentiation, so the caller provides both.
- * batch < 0, n_layers < 1, steps < 0, n_comp < 1 for a mixture, or groups outside its range -> VCNF_ERR_SHAPE; unknown
- * family, or n_layers (steps + 1) > VCNF_STOCH_MAX_POINTS (a mistaken argument must not become a launch that runs for
- * minutes) -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a
+ * batch < 0, n_layers < 1, steps < 0, n_comp below what the family reads, or groups outside its range ->
+ * VCNF_ERR_SHAPE; unknown family, or n_layers (steps + 1) > VCNF_STOCH_MAX_POINTS (a mistaken argument must not become
+ * a launch that runs for minutes) -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; NULL required pointer -> VCNF_ERR_NULL; a
  * pointer not aligned to its element size -> VCNF_ERR_ALIGN, checked in this order.
  * One sample per lane; rows move as one 8-byte
  * (16-byte) access when the [., 2] buffers are aligned to it, as two elements otherwise, with the same bits either way.

@@ -1610,25 +1610,37 @@ def planar_radial_stack_bwd(z_out, trace, ckpt, kinds, va, vb, sc, g_out=None, g
     return g_in, g_va, g_vb, g_sc
 
 
+# what ``table`` holds per family: (entries per component, least number of components); a mixture has any number of
+# components, an energy's constants are one component of 1 or 4 entries.  _TABLE_FREE: families without a table.
+_TABLE_FREE = (TARGET_TWO_MOONS, TARGET_SMILEY)
+_TABLE_ENTRIES = {TARGET_CIRCULAR_GMM: (2, 0), TARGET_RING_MIXTURE: (1, 0), TARGET_TWO_MODES: (1, 1), TARGET_SINUSOIDAL: (1, 1),
+                  TARGET_SINUSOIDAL_GAP: (1, 4), TARGET_SINUSOIDAL_SPLIT: (1, 4)}
+
+
+def _target_table(name, z, dev, family, table):
+    """(table detached and contiguous, n_comp) of a target entry point, (None, 0) for a family that reads no table (an
+    unknown family is the entry point's to refuse)."""
+    if family not in _TABLE_ENTRIES:
+        return None, 0
+    per, least = _TABLE_ENTRIES[family]
+    if table is None or table.dtype != z.dtype or table.device != dev or table.numel() % per or table.numel() // per < least:
+        raise VcnfError("%s: the %s table must be a %s tensor on %s" % (name, "constant" if least else "component", z.dtype, dev))
+    return table.detach().contiguous(), table.numel() // per
+
+
 def target_log_prob(z, family, table=None, scale=0.0, want_score=False):
     """vcnf_target_log_prob_*: (log density [B], score d logp / d z [B, 2] or None) of z [B, 2] under TwoMoons (family 0),
     the circular Gaussian mixture with the centres ``table`` [n, 2] (1) or the ring mixture with the radii ``table`` [n]
-    (2), both of standard deviation ``scale``.  One launch; without ``want_score`` none of the score's arithmetic runs."""
+    (2), both of standard deviation ``scale``, or one of the energy densities of include/vcnf_hip.h of scale ``scale``:
+    TwoModes with ``table`` {loc}, Sinusoidal {period}, Sinusoidal_gap / Sinusoidal_split {period, amp, mu, width}, Smiley
+    (no table).  One launch; without ``want_score`` none of the score's arithmetic runs."""
     name = "vcnf_target_log_prob" + _sfx(z)
     dev = require_device(z, table, f64=True, allow_grad=True)
     if z.dtype not in (torch.float32, torch.float64):
         raise VcnfError("%s: z must be fp32 or fp64 (got %s)" % (name, z.dtype))
     if z.dim() != 2 or z.shape[1] != 2:
         raise VcnfError("%s: expects [batch, 2] inputs (got %s)" % (name, list(z.shape)))
-    n = 0
-    if family != TARGET_TWO_MOONS:
-        per = 2 if family == TARGET_CIRCULAR_GMM else 1
-        if table is None or table.dtype != z.dtype or table.device != dev or table.numel() % per:
-            raise VcnfError("%s: the component table must be a %s tensor on %s" % (name, z.dtype, dev))
-        table = table.detach().contiguous()
-        n = table.numel() // per
-    else:
-        table = None
+    table, n = _target_table(name, z, dev, family, table)
     z = z.detach().contiguous()
     b = len(z)
     logp = torch.empty(b, dtype=z.dtype, device=dev)
@@ -1639,23 +1651,17 @@ def target_log_prob(z, family, table=None, scale=0.0, want_score=False):
 
 def _stochastic_target(z, family, table, name):
     """Checked (device, z, table, n_comp) of the stochastic entry points: z [B, 2] fp32 / fp64 contiguous and detached,
-    the mixture's table like z (None for TwoMoons)."""
+    the family's table like z (None for TwoMoons and Smiley)."""
     dev = require_device(z, table, f64=True, allow_grad=True)
     if z.dtype not in (torch.float32, torch.float64):
         raise VcnfError("%s: z must be fp32 or fp64 (got %s)" % (name, z.dtype))
     if z.dim() != 2 or z.shape[1] != 2:
         raise VcnfError("%s: expects [batch, 2] inputs (got %s)" % (name, list(z.shape)))
-    if family not in (TARGET_TWO_MOONS, TARGET_CIRCULAR_GMM, TARGET_RING_MIXTURE):
+    if family not in _TABLE_FREE and family not in _TABLE_ENTRIES:
         raise VcnfError("%s: unknown target family %r" % (name, family))
-    n = 0
-    if family != TARGET_TWO_MOONS:
-        per = 2 if family == TARGET_CIRCULAR_GMM else 1
-        if table is None or table.dtype != z.dtype or table.device != dev or table.numel() % per or not table.numel():
-            raise VcnfError("%s: the component table must be a %s tensor on %s" % (name, z.dtype, dev))
-        table = table.detach().contiguous()
-        n = table.numel() // per
-    else:
-        table = None
+    table, n = _target_table(name, z, dev, family, table)
+    if table is not None and not n:
+        raise VcnfError("%s: the component table must be a %s tensor on %s" % (name, z.dtype, dev))
     return dev, z.detach().contiguous(), table, n
 
 

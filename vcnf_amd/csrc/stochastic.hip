@@ -60,7 +60,8 @@ namespace vcnf_stoch {
 
 using namespace vcnf_stream;
 using vcnf_target::is_family;
-using vcnf_target::is_mixture;
+using vcnf_target::has_table;
+using vcnf_target::table_min;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
@@ -86,8 +87,7 @@ struct Target {
 template <typename T, int F, bool SCORE>
 __device__ __forceinline__ T point(const Target<T>& t, T z0, T z1, T& s0, T& s1) {
   if (SCORE) s0 = s1 = T(0);
-  T lp = F == VCNF_TARGET_TWO_MOONS ? vcnf_target::two_moons<T, SCORE>(z0, z1, s0, s1)
-                                    : vcnf_target::mixture<T, F, SCORE>(t.table, t.n, t.scale, z0, z1, s0, s1);
+  T lp = vcnf_target::density<T, F, SCORE>(t.table, t.n, t.scale, z0, z1, s0, s1);
   if (!(abs_(z0) < T(INFINITY) && abs_(z1) < T(INFINITY))) {
     lp = T(NAN);
     if (SCORE) s0 = s1 = T(NAN);
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(kBlock) void mh_walk_kernel(const MhArgs<T> a) {
 static int check_run(int64_t batch, int32_t n_layers, int32_t steps, int32_t n_comp, int family) {
   if (batch < 0 || n_layers < 1 || steps < 0) return VCNF_ERR_SHAPE;
   if (!is_family(family)) return VCNF_ERR_UNSUPPORTED;
-  if (is_mixture(family) && n_comp < 1) return VCNF_ERR_SHAPE;
+  if (has_table(family) && n_comp < table_min(family)) return VCNF_ERR_SHAPE;
   if ((long long)n_layers * ((long long)steps + 1) > kMaxPoints) return VCNF_ERR_UNSUPPORTED;
   return VCNF_OK;
 }
@@ -385,7 +385,13 @@ static long long sample_tiles(int64_t batch) { return (batch + kBlock - 1) / kBl
   switch (family) {                                                                                \
     case VCNF_TARGET_TWO_MOONS: return FN<T, VCNF_TARGET_TWO_MOONS>(__VA_ARGS__);                  \
     case VCNF_TARGET_CIRCULAR_GMM: return FN<T, VCNF_TARGET_CIRCULAR_GMM>(__VA_ARGS__);            \
-    default: return FN<T, VCNF_TARGET_RING_MIXTURE>(__VA_ARGS__);                                  \
+    case VCNF_TARGET_RING_MIXTURE: return FN<T, VCNF_TARGET_RING_MIXTURE>(__VA_ARGS__);            \
+    case VCNF_TARGET_TWO_MODES: return FN<T, VCNF_TARGET_TWO_MODES>(__VA_ARGS__);                  \
+    case VCNF_TARGET_SINUSOIDAL: return FN<T, VCNF_TARGET_SINUSOIDAL>(__VA_ARGS__);                \
+    case VCNF_TARGET_SINUSOIDAL_GAP: return FN<T, VCNF_TARGET_SINUSOIDAL_GAP>(__VA_ARGS__);        \
+    case VCNF_TARGET_SINUSOIDAL_SPLIT: return FN<T, VCNF_TARGET_SINUSOIDAL_SPLIT>(__VA_ARGS__);    \
+    case VCNF_TARGET_SMILEY: return FN<T, VCNF_TARGET_SMILEY>(__VA_ARGS__);                        \
+    default: return VCNF_ERR_UNSUPPORTED; /* check_run has refused it */                           \
   }
 
 template <typename T, int F, typename P>
@@ -405,7 +411,7 @@ static int launch_mh(const MhArgs<T>& a, bool row, hipStream_t st) {
 
 template <typename T>
 static Target<T> target_of(const T* table, int32_t n_comp, int family, T scale) {
-  return is_mixture(family) ? Target<T>{table, (int)n_comp, scale} : Target<T>{nullptr, 0, T(0)};
+  return has_table(family) ? Target<T>{table, (int)n_comp, scale} : Target<T>{nullptr, 0, scale};
 }
 
 // a policy's part of the entry points' checks: its required pointers, and all of its pointers' alignment
@@ -424,7 +430,7 @@ static int hmc_stack(const P& policy, const T* z, const T* noise, const T* unif,
                      int32_t steps, int32_t n_comp, int family, T scale, void* stream) {
   if (const int st = check_run(batch, n_layers, steps, n_comp, family)) return st;
   if (batch == 0) return VCNF_OK;
-  if (!z || !noise || !unif || !step || !mass || !sqm || !out || !logdet || (is_mixture(family) && !table) || !complete(policy))
+  if (!z || !noise || !unif || !step || !mass || !sqm || !out || !logdet || (has_table(family) && !table) || !complete(policy))
     return VCNF_ERR_NULL;
   if (!all_aligned({z, noise, unif, step, mass, sqm, table, out, logdet, trace}, sizeof(T)) || !policy_aligned(policy))
     return VCNF_ERR_ALIGN;
@@ -445,7 +451,7 @@ static int hmc_stack_bwd(const P& policy, const T* trace, const byte_t* accept, 
   // one block of the workspace per workgroup, and every workgroup has a tile to write its block for
   if (groups < 1 || groups > kMaxBwdGroups || groups > sample_tiles(batch)) return VCNF_ERR_SHAPE;
   if (!trace || !accept || !noise || !step || !mass || !sqm || !gin || !g_step || !g_mass || !g_sqm || !workspace ||
-      (is_mixture(family) && !table) || !complete(policy))
+      (has_table(family) && !table) || !complete(policy))
     return VCNF_ERR_NULL;
   if (!all_aligned({trace, noise, step, mass, sqm, table, gout, gld, gin, g_step, g_mass, g_sqm, workspace}, sizeof(T)) ||
       !policy_aligned(policy))
@@ -465,7 +471,7 @@ static int mh_walk(const T* z, const T* eps, const T* w, const T* prop, const T*
                    int64_t batch, int32_t steps, int32_t n_comp, int family, T scale, void* stream) {
   if (const int st = check_run(batch, 1, steps, n_comp, family)) return st;
   if (batch == 0) return VCNF_OK;
-  if (!z || !prop || !out || (steps > 0 && (!eps || !w)) || (is_mixture(family) && !table)) return VCNF_ERR_NULL;
+  if (!z || !prop || !out || (steps > 0 && (!eps || !w)) || (has_table(family) && !table)) return VCNF_ERR_NULL;
   if (!all_aligned({z, eps, w, prop, table, out}, sizeof(T))) return VCNF_ERR_ALIGN;
   const MhArgs<T> a{target_of(table, n_comp, family, scale), z, eps, w, prop, out, accept, batch, steps};
   const bool row = all_aligned({z, eps, out}, 2 * sizeof(T));

@@ -32,6 +32,14 @@ __device__ __forceinline__ float sqrt_(float v) { return sqrtf(v); }
 __device__ __forceinline__ double sqrt_(double v) { return sqrt(v); }
 __device__ __forceinline__ float abs_(float v) { return fabsf(v); }
 __device__ __forceinline__ double abs_(double v) { return fabs(v); }
+__device__ __forceinline__ void sincos_(float v, float& s, float& c) { sincosf(v, &s, &c); }
+__device__ __forceinline__ void sincos_(double v, double& s, double& c) { sincos(v, &s, &c); }
+// 1 / (1 + exp(-v)) without an overflowing exp
+template <typename T>
+__device__ __forceinline__ T sigmoid_(T v) {
+  const T e = exp_(-abs_(v));
+  return v >= T(0) ? T(1) / (T(1) + e) : e / (T(1) + e);
+}
 
 // ld[b] = v (VCNF_LD_STORE) or ld[b] + v (VCNF_LD_ACCUM)
 template <typename T>

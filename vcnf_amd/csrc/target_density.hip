@@ -4,8 +4,11 @@
 //   TwoMoons          logp = -((r - 2) / 0.2)^2 / 2 - ((a - 2) / 0.3)^2 / 2 + log1p(exp(-4 a / 0.09))
 //   circular mixture  d_i = |z - c_i|^2 / (2 s^2),  logp = -log(2 pi s^2 n) + logsumexp_i(-d_i),  c = table [n, 2]
 //   ring mixture      d_i = (r - t_i)^2 / (2 s^2),  logp = logsumexp_i(-d_i),                     t = table [n]
-// The caller computes the table (no sin / cos in a kernel).  The targets' device functions are target_math.hpp's,
-// shared with stochastic.hip.
+// The caller computes a mixture's table (no sin / cos in a mixture's kernel).  The same kernel evaluates the five energy
+// densities of distributions/prior.py - TwoModes, Sinusoidal, Sinusoidal_gap, Sinusoidal_split, Smiley - whose table
+// holds their constants ({loc}, {period}, {period, amp, mu, width}, none) and whose formulas stand in target_math.hpp;
+// the Sinusoidal trio calls sincos once per point.  The device functions are target_math.hpp's, shared with
+// stochastic.hip.
 //
 // The kernel is a stream over [B, 2]: one sample per lane, its row one 8-byte (fp32) or 16-byte (fp64) access when the
 // buffers are aligned to it and two element accesses otherwise, a grid-stride loop under a capped grid.  Every lane
@@ -45,8 +48,7 @@ __global__ __launch_bounds__(kBlock) void target_log_prob_kernel(const T* __rest
     }
     RowT s;
     s.v[0] = s.v[1] = T(0);
-    T lp = F == VCNF_TARGET_TWO_MOONS ? two_moons<T, SCORE>(x.v[0], x.v[1], s.v[0], s.v[1])
-                                      : mixture<T, F, SCORE>(table, n, scale, x.v[0], x.v[1], s.v[0], s.v[1]);
+    T lp = density<T, F, SCORE>(table, n, scale, x.v[0], x.v[1], s.v[0], s.v[1]);
     // a non-finite z has no density: NaN, where the formulas alone give -inf for some infinite rows
     if (!(abs_(x.v[0]) < T(INFINITY) && abs_(x.v[1]) < T(INFINITY))) lp = s.v[0] = s.v[1] = T(NAN);
     logp[b] = lp;
@@ -88,17 +90,27 @@ template <typename T>
 static int log_prob(const T* z, const T* table, T* logp, T* score, int64_t batch, int32_t n, int family, T scale,
                     void* stream) {
   if (batch < 0) return VCNF_ERR_SHAPE;
-  if (family != VCNF_TARGET_TWO_MOONS && !is_mixture(family)) return VCNF_ERR_UNSUPPORTED;
-  if (is_mixture(family) && n < 1) return VCNF_ERR_SHAPE;
+  if (!is_family(family)) return VCNF_ERR_UNSUPPORTED;
+  if (has_table(family) && n < table_min(family)) return VCNF_ERR_SHAPE;
   if (batch == 0) return VCNF_OK;
-  if (!z || !logp || (is_mixture(family) && !table)) return VCNF_ERR_NULL;
+  if (!z || !logp || (has_table(family) && !table)) return VCNF_ERR_NULL;
   if (!all_aligned({z, table, logp, score}, sizeof(T))) return VCNF_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
+  if (!has_table(family)) table = nullptr, n = 0;      // ignored by the family: never read
+#define VCNF_TARGET_CASE(F) \
+  case F: return launch<T, F>(z, table, logp, score, batch, n, scale, st)
   switch (family) {
-    case VCNF_TARGET_TWO_MOONS: return launch<T, VCNF_TARGET_TWO_MOONS>(z, nullptr, logp, score, batch, 0, T(0), st);
-    case VCNF_TARGET_CIRCULAR_GMM: return launch<T, VCNF_TARGET_CIRCULAR_GMM>(z, table, logp, score, batch, n, scale, st);
-    default: return launch<T, VCNF_TARGET_RING_MIXTURE>(z, table, logp, score, batch, n, scale, st);
+    VCNF_TARGET_CASE(VCNF_TARGET_TWO_MOONS);
+    VCNF_TARGET_CASE(VCNF_TARGET_CIRCULAR_GMM);
+    VCNF_TARGET_CASE(VCNF_TARGET_RING_MIXTURE);
+    VCNF_TARGET_CASE(VCNF_TARGET_TWO_MODES);
+    VCNF_TARGET_CASE(VCNF_TARGET_SINUSOIDAL);
+    VCNF_TARGET_CASE(VCNF_TARGET_SINUSOIDAL_GAP);
+    VCNF_TARGET_CASE(VCNF_TARGET_SINUSOIDAL_SPLIT);
+    VCNF_TARGET_CASE(VCNF_TARGET_SMILEY);
+    default: return VCNF_ERR_UNSUPPORTED;              // is_family has refused it
   }
+#undef VCNF_TARGET_CASE
 }
 
 }  // namespace vcnf_target

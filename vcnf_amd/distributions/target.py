@@ -4,7 +4,8 @@ Constructor arguments, attribute names and state_dict keys are the reference's. 
 from one launch of vcnf_target_log_prob_* (csrc/target_density.hip) in fp32 or fp64, picked by ``z``; under autograd
 ``log_prob`` is one node whose backward is a multiply by the score the forward launch wrote.  The targets have no
 parameters.  The stochastic layers (vcnf_amd.flows.stochastic) evaluate the same device functions inside their own
-kernels (csrc/target_math.hpp).  The fork's other targets (NealsFunnel, ...), priors and n_dims != 2 are out of scope."""
+kernels (csrc/target_math.hpp).  The energy densities of the reference's prior.py are in prior.py, on the same kernels.
+The fork's other targets (NealsFunnel, ...) and n_dims != 2 are out of scope."""
 import numpy as np
 import torch
 from torch import nn
@@ -47,11 +48,45 @@ class Target(nn.Module):
         return z
 
 
-class _KernelTarget(Target):
-    """Shared end of the three targets: ``z`` checked, the component table cast once per dtype and device, and the call of
-    the kernel with or without autograd.  A subclass sets ``_family`` and, for a mixture, the non-persistent fp64 buffer
-    ``table`` and ``scale``."""
+class _KernelDensity:
+    """What the densities of csrc/target_math.hpp share on the host - the targets here and the energy densities of
+    prior.py: ``z`` checked, the constant table cast once per dtype and device, and the call of the kernel with or without
+    autograd.  A class sets ``_family`` and provides ``_constants``; ``_cast`` is its dict."""
     _family = None
+
+    def _constants(self):
+        """(key, table or None, scale): the table (an fp64 tensor or a tuple of numbers) and the scale of the kernel's
+        operands, and what they were computed from - a cast is served again while the key compares equal."""
+        raise NotImplementedError
+
+    def _operands(self, z):
+        """(table or None, scale) in z's dtype on z's device."""
+        _lib.require_device(z, f64=True, allow_grad=True)
+        if z.dtype not in (torch.float32, torch.float64):
+            raise _lib.VcnfError("%s.log_prob takes fp32 or fp64 inputs (got %s)" % (type(self).__name__, z.dtype))
+        key, table, scale = self._constants()
+        if table is None:
+            return None, float(scale)
+        slot = (z.dtype, z.device)
+        if slot not in self._cast or self._cast[slot][0] != key:
+            table = torch.as_tensor(table, dtype=torch.float64).to(device=z.device, dtype=z.dtype).contiguous()
+            self._cast[slot] = (key, table, float(scale))
+        return self._cast[slot][1:]
+
+    def _kernel_log_prob(self, z):
+        table, scale = self._operands(z)
+        if autograd.needs_grad(z):
+            return autograd.TargetLogProbFn.apply(z, table, self._family, scale)
+        return _lib.target_log_prob(z, self._family, table, scale)[0]
+
+    def _kernel_score(self, z):
+        table, scale = self._operands(z)
+        return _lib.target_log_prob(z, self._family, table, scale, want_score=True)[1]
+
+
+class _KernelTarget(_KernelDensity, Target):
+    """Shared end of the three targets.  A subclass sets ``_family`` and, for a mixture, the non-persistent fp64 buffer
+    ``table`` and ``scale``; whatever replaces a buffer clears the casts."""
 
     def __init__(self):
         super().__init__()
@@ -62,30 +97,17 @@ class _KernelTarget(Target):
         self._cast = {}                     # .to() / .double() / .cuda() replace the buffers the casts came from
         return super()._apply(fn, *args, **kwargs)
 
-    def _operands(self, z):
-        """(table or None, scale) in z's dtype on z's device."""
-        _lib.require_device(z, f64=True, allow_grad=True)
-        if z.dtype not in (torch.float32, torch.float64):
-            raise _lib.VcnfError("%s.log_prob takes fp32 or fp64 inputs (got %s)" % (type(self).__name__, z.dtype))
+    def _constants(self):
         table = getattr(self, "table", None)
-        if table is None:
-            return None, 0.0
-        key = (z.dtype, z.device)
-        if key not in self._cast:
-            self._cast[key] = (table.to(device=z.device, dtype=z.dtype).contiguous(), float(self.scale))
-        return self._cast[key]
+        return None, table, 0.0 if table is None else self.scale
 
     def log_prob(self, z):
         """log p(z) [B] of z [B, 2] on the device; differentiable in z (once)."""
-        table, scale = self._operands(z)
-        if autograd.needs_grad(z):
-            return autograd.TargetLogProbFn.apply(z, table, self._family, scale)
-        return _lib.target_log_prob(z, self._family, table, scale)[0]
+        return self._kernel_log_prob(z)
 
     def score(self, z):
         """d log p / d z [B, 2] from the launch that evaluates log p; no autograd."""
-        table, scale = self._operands(z)
-        return _lib.target_log_prob(z, self._family, table, scale, want_score=True)[1]
+        return self._kernel_score(z)
 
 
 class TwoMoons(_KernelTarget):

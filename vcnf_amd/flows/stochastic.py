@@ -2,8 +2,9 @@
 with a learnable step size and mass.  Names, arguments and parameter names are the reference's; both layers are their
 own inverses.
 
-Two paths, chosen per call.  With one of the kernel targets (TwoMoons, CircularGaussianMixture, RingMixture), ``z``
-[B, 2] fp32 or fp64 on the device and - for the walk - a DiagGaussianProposal over (2,), the layer is one launch of
+Two paths, chosen per call.  With one of the kernel densities (TwoMoons, CircularGaussianMixture, RingMixture, or the
+energies TwoModes, Sinusoidal, Sinusoidal_gap, Sinusoidal_split, Smiley of distributions/prior.py), ``z`` [B, 2] fp32 or
+fp64 on the device and - for the walk - a DiagGaussianProposal over (2,), the layer is one launch of
 csrc/stochastic.hip (vcnf_amd.fused_stochastic); NormalizingFlow takes consecutive HMC layers of one target and step
 count in one launch.  Anything else - another Target subclass, another proposal, other shapes - evaluates the
 reference's composition in torch, HMC with its score through ``autograd.grad`` on ``target.log_prob``.  Both paths draw

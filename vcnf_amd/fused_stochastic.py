@@ -27,6 +27,7 @@ from .autograd import HmcAnnealedStackFn, HmcStackFn, MhWalkFn, needs_grad
 from .distributions.base import DiagGaussian
 from .distributions.linear_interpolation import LinearInterpolation
 from .distributions.mh_proposal import DiagGaussianProposal
+from .distributions.prior import Sinusoidal, Sinusoidal_gap, Sinusoidal_split, Smiley, TwoModes
 from .distributions.target import CircularGaussianMixture, RingMixture, TwoMoons
 from .flows.base import fold_log_det
 from .flows.stochastic import HamiltonianMonteCarlo
@@ -36,8 +37,10 @@ MAX_POINTS = _lib.STOCH_MAX_POINTS          # n_layers (steps + 1) of one launch
 
 
 def kernel_target(target):
-    """One of the three targets of csrc/target_math.hpp; a subclass is not (what it overrides is unknown here)."""
-    return type(target) in (TwoMoons, CircularGaussianMixture, RingMixture)
+    """One of the densities of csrc/target_math.hpp - the three targets of distributions/target.py or the five energies
+    of distributions/prior.py; a subclass is not (what it overrides is unknown here)."""
+    return type(target) in (TwoMoons, CircularGaussianMixture, RingMixture,
+                            TwoModes, Sinusoidal, Sinusoidal_gap, Sinusoidal_split, Smiley)
 
 
 def annealed(target):
