@@ -10,7 +10,9 @@ module (a plain helper, not a conftest) holds
     so that every workgroup makes two full trips and the third one is ragged: r = per_block / 2 + 1 rows (5 where a
     workgroup takes one row), which ends inside a workgroup and, where lanes are grouped, inside a wave.
     "narrow" cases have 2 - 5 features and a batch sized for one lane per row (B > 2 * cap * block: past the cap
-    whatever lane count the launcher picks); "wide" cases have rows for which the restated rule gives 64 lanes.
+    whatever lane count the launcher picks); "wide" cases have rows for which the restated rule gives 64 lanes;
+    "tile" cases belong to the matrix kernels (conv1x1, conv3x3_1x1, channel_mix, fused_affine), whose workgroups take
+    a fixed tile of pixels or rows per trip whatever the shape: B holds 2 x cap + 1 tiles, the last one ragged.
 test_grid_caps_table.py checks the table on the CPU, test_gpu_grid_caps.py runs the cases."""
 import glob
 import os
@@ -38,6 +40,8 @@ def _value(expr):
 def _constexpr(name):
     return r"constexpr\s+(?:int|long long)\s+%s\s*=\s*([^;]+);" % name
 
+
+_LOCAL_CAP = r"const long long cap = ([^;]+);"          # the matrix kernels' launchers
 
 # name -> (file, pattern with one group, occurrences expected).  Every occurrence must give the same value.
 CONSTANTS = {
@@ -88,6 +92,17 @@ CONSTANTS = {
     "rqs.bwd_lds": ("rqs_backward.hip", r"\(size_t\)kBwdBlock \* P \* sizeof\(float\) <= (48 \* 1024);", 1),
     "rqs.shared_bwd_threads": ("rqs_backward.hip", r"long long g = (\(256LL \* 1024\)) / period;", 1),
     "rqs64.cap": ("rqs_f64.hip", r"grid64\(int64_t n\) \{ return dim3\(elem_blocks\(n, 256, ([^)]+)\)\); \}", 1),
+    # the matrix kernels: a local ``cap`` in the launcher
+    "conv1.pix": ("conv1x1.hip", _constexpr("kC1Pix"), 1),
+    "conv1.cap": ("conv1x1.hip", _LOCAL_CAP, 1),
+    "conv31.pix": ("conv3x3_1x1.hip", _constexpr("kC31Pix"), 1),
+    "conv31.cap": ("conv3x3_1x1.hip", _LOCAL_CAP, 1),
+    "mix.block": ("channel_mix.hip", _constexpr("kMixBlock"), 1),
+    "mix.cap": ("channel_mix.hip", _LOCAL_CAP, 1),
+    "mix.pix": ("channel_mix.hip", r"const long long blocks = \(a\.npix \+ \d+\) / (\d+);", 1),
+    "faffine.block": ("fused_affine.hip", _constexpr("kFABlock"), 1),
+    "faffine.cap": ("fused_affine.hip", _LOCAL_CAP, 2),
+    "trunk.cap": ("resnet_trunk.hip", _LOCAL_CAP, 1),
 }
 
 
@@ -110,21 +125,26 @@ def looping_files():
 
 
 # files whose looping kernels have cases here
-COVERED = ("affine_kernels.hip", "class_cond_gaussian.hip", "gaussian_mixture.hip", "heavy_tail.hip",
-           "masked_affine_stack.hip", "mvn_base.hip", "planar_radial.hip", "resblock_ops.hip", "rqs_backward.hip",
-           "rqs_f64.hip", "rqs_kernels.hip", "stochastic.hip", "target_density.hip")
-# looping files without a case, and why: the fused / matrix and the conv kernels.  A new looping file has to be entered in COVERED, with cases, or here, with a reason.
-_FUSED = "fused matrix kernel: the full-size C1 - C3 tests run the fused layers at 1 M rows"
-_CONV = "conv / image kernel: out of scope here with the other conv kernels"
+COVERED = ("affine_kernels.hip", "channel_mix.hip", "class_cond_gaussian.hip", "conv1x1.hip", "conv3x3_1x1.hip",
+           "fused_affine.hip", "gaussian_mixture.hip", "heavy_tail.hip", "masked_affine_stack.hip", "mvn_base.hip",
+           "planar_radial.hip", "resblock_ops.hip", "rqs_backward.hip", "rqs_f64.hip", "rqs_kernels.hip",
+           "stochastic.hip", "target_density.hip")
+# looping files without a case, and why.  A new looping file has to be entered in COVERED, with cases, or here, with a reason.
+_RQS_LAYER = ("fused RQS layer kernel: its tile walk is covered by tests/test_gpu_fused_handover.py, which runs the "
+              "128-sample-tile kernel (fused_layer_v6.hip, 256 workgroups) over 769 tiles - three full trips and a "
+              "ragged fourth - bitwise against the 32-sample-tile kernel (fused_layer_v6s.hip) walking the same rows, "
+              "and flagged tiles in the first, a middle and the last place of a workgroup's walk against the exact "
+              "fp32 kernel (fused_layer.hip)")
 EXCLUDED = {
-    "channel_mix.hip": _CONV + " (MFMA channel mixing of Glow)",
-    "conv1x1.hip": _CONV,
-    "conv3x3_1x1.hip": _CONV,
-    "fused_affine.hip": _FUSED,
-    "fused_layer.hip": _FUSED,
-    "fused_layer_v6.hip": _FUSED,
-    "fused_layer_v6s.hip": _FUSED,
-    "resnet_trunk.hip": _FUSED,
+    "fused_layer.hip": _RQS_LAYER,
+    "fused_layer_v6.hip": _RQS_LAYER,
+    "fused_layer_v6s.hip": _RQS_LAYER,
+    "resnet_trunk.hip": ("a workgroup takes two 16-row tiles per wave (128 rows) once B >= 65 536, so two trips of the "
+                         "2048 workgroups and a ragged third need B = 524 353 rows, whose [B, 128] output is 67 M elements "
+                         "against MAX_ELEMENTS = 12 M here (one tile per wave below 65 536 rows is at most 1024 workgroups: "
+                         "no second trip either).  test_gpu_parity.py::test_resnet_trunk_kernel_vs_torch runs the "
+                         "two-tile instance at B = 65 557: 513 workgroups, a ragged last one, every one on its first trip "
+                         "- a later trip of this kernel is not run by any test"),
 }
 
 
@@ -300,6 +320,38 @@ def rule_rqs_shared_bwd(period):
     return Rule(1, max(1, constant("rqs.shared_bwd_threads") // period), 1, 1)
 
 
+def _tiles(per_block, cap, lanes):
+    """A workgroup takes ``per_block`` consecutive items per trip whatever the shape: kind "tile"."""
+    return Rule(per_block, cap, lanes, per_block)
+
+
+def rule_conv_tile(unit):
+    """conv1x1.hip ("conv1") and conv3x3_1x1.hip ("conv31"): an item is a pixel of the batch (items_per_row = H W); an
+    8-wave workgroup takes one pass of 64 consecutive pixels per trip, tile = blockIdx + trip * gridDim."""
+    return _tiles(constant(unit + ".pix"), constant(unit + ".cap"), 8)
+
+
+def rule_channel_mix():
+    """channel_mix.hip: an item is a pixel (a row of a [B, C] matrix); wave w of workgroup g takes the pass
+    4 g + w + trip * 4 gridDim of 2 tiles x 16 pixels, so a workgroup takes 4 waves x 2 x 16 = 128 consecutive pixels
+    per trip - the divisor of the launcher's ``blocks`` line."""
+    waves = constant("mix.block") // 64
+    per_block = waves * 2 * 16
+    assert per_block == constant("mix.pix"), "channel_mix.hip: the grid is no longer sized for 2 tiles of 16 pixels per wave"
+    return _tiles(per_block, constant("mix.cap"), 2)
+
+
+def rule_fused_affine():
+    """fused_affine.hip (layer and stack kernels; one 16-row column block per wave, VCNF_FA_NCB = 1): an item is a batch
+    row.  The four waves of workgroup g do NOT take neighbouring wave-tiles: with G = gridDim they take the 16-row
+    wave-tiles g + G (w + 4 trip), w = 0 .. 3, i.e. g, g + G, g + 2 G, g + 3 G on the first trip.  A trip of the whole
+    grid still covers 4 G consecutive wave-tiles = 64 G consecutive rows, so per_block = 64 rows and rows_per_trip =
+    64 cap hold, while "the rows of workgroup g" are four runs of 16 rows G wave-tiles apart.  The remainder of 33 rows
+    makes three wave-tiles of the third trip, the last one with a single row."""
+    waves = constant("faffine.block") // 64
+    return _tiles(waves * 16, constant("faffine.cap"), 4)
+
+
 # ---------------------------------------------------------------- cases
 class Case(namedtuple("Case", "name rule kind items_per_row row_elements shape")):
     """One shape past a cap.  ``items_per_row``: items of the kernel's loop per batch row (1 for the row kernels);
@@ -439,6 +491,27 @@ def _build():
     f32 = lambda name, *a, **kw: cases.append(_case(name + ".f32", *a, f64=False, **kw))
     f32("rqs.shared.narrow", rule_rqs_elem(), "narrow", 32, items_per_row=32, period=32, bins=8)
     f32("rqs.shared_bwd.narrow", rule_rqs_shared_bwd(32), "narrow", 32, period=32, bins=8)
+    # ---- the matrix kernels (fp32 only): the smallest shapes that still reach the cap, 2 x cap + 1 tiles each
+    def image(name, rule, c_widest, h, w, **shape):
+        f32(name, rule, "tile", c_widest * h * w, items_per_row=h * w, H=h, W=w, **shape)
+    # conv1x1: KS = c_in / 16 k-steps.  2 x 2 images in torch's aligned buffers take the DMA staging (inner % 4 == 0),
+    # 1 x 3 and 1 x 1 images the register staging; 33 output channels leave the second row block partial
+    image("conv1x1.dma", rule_conv_tile("conv1"), 16, 2, 2, c_in=16, c_out=7, dma=True)
+    image("conv1x1.dma_odd", rule_conv_tile("conv1"), 48, 2, 2, c_in=48, c_out=33, dma=True)
+    image("conv1x1.regs", rule_conv_tile("conv1"), 16, 1, 3, c_in=16, c_out=7, dma=False)
+    image("conv1x1.regs_rows", rule_conv_tile("conv1"), 48, 1, 1, c_in=48, c_out=33, dma=False)
+    # conv3x3 + conv1x1 (256 hidden / output channels): every pixel of a 2 x 3 image is on a border, a pass of 64
+    # pixels holds ten images and two parts; convnet3 adds the nine taps (its widest tensor is z [B, 9 c_out, H, W])
+    image("conv3x3_1x1", rule_conv_tile("conv31"), 256, 2, 3, c_in=2)
+    image("convnet3", rule_conv_tile("conv31"), 9 * 5, 2, 3, c_in=3, c_out=5)
+    # channel mixing: [B, C] matrices (the ROWS instances, 16-byte stores) and an image whose pixel count is odd
+    f32("mix.rows", rule_channel_mix(), "tile", 4, C=4, rows=True)
+    f32("mix.rows8", rule_channel_mix(), "tile", 8, C=8, rows=True)
+    image("mix.image", rule_channel_mix(), 4, 1, 3, C=4, rows=False)
+    # fused affine coupling: one layer (D = 33: scalar strip copies, 16 + 1 output rows) and C1's stack of four
+    f32("faffine.layer", rule_fused_affine(), "tile", 4, D=4, hidden=32, mode="channel", scale_map="exp")
+    f32("faffine.layer_odd", rule_fused_affine(), "tile", 33, D=33, hidden=32, mode="channel_inv", scale_map="sigmoid_inv")
+    f32("faffine.stack", rule_fused_affine(), "tile", 2, D=2, widths=(1, 32, 32, 2), layers=4)
     return {c.name: c for c in cases}
 
 

@@ -12,6 +12,8 @@ fp32.  Per case:
      the last (but the first) set to zero against the reference's sums over that trip's rows alone - an overwrite
      instead of an add, or a dropped trip, fails one of the two outright;
   d. HMC / MH decisions on the rows outside the near-tie band, whose share is asserted under stochastic_ref.BAND_CAP.
+The matrix kernels (conv1x1, conv3x3 + conv1x1, channel mixing, fused affine layer and stack) follow at the end with
+(a), (b) and the fp16 saturation / range counters.
 Each test prints the figures that profiles/grid_caps.md records."""
 import copy
 import math
@@ -1272,4 +1274,280 @@ def test_resblock_ops(hip, which, op):
         else:
             check(case, "op %d output %d" % (op, j), o, r32[j], RESBLOCK[op](a.double(), b_.double(), c.double())[j], F32)
     rows_again(case, call, [(a, 0), (b_, 0), (c, 0)], [(o, 0) for o in got])
+    print("GRIDCAP %-34s wall %.2f s" % (case.name, time.time() - t0))
+
+
+# ================================================================ the matrix kernels: conv1x1, conv3x3 + conv1x1, channel mixing, fused affine
+# A "tile" case of grid_caps.py holds 2 x cap + 1 tiles: every workgroup of the capped grid makes two trips and the
+# first one a ragged third.  These kernels keep weights in registers for the whole launch, reuse LDS fragments from
+# pass to pass and (conv1x1) request the next pass's rows one pass ahead: what a later trip starts from is what the
+# earlier one left.  (a) - (c) as above, with the references and acceptance rules of each kernel's own test in
+# test_gpu_parity.py.
+SLOPES = (0.1, 0.2)                                               # both LeakyReLUs on: the masked paths run
+
+
+def by_trip(case, what, got, r32, r64):
+    """The GRIDCAP line of the whole batch and one per trip: a trip that is merely worse shows in the log."""
+    report(case, what, got, r32, r64)
+    assert case.trips == 3
+    for t in range(case.trips):
+        lo, hi = case.trip_rows(t)
+        assert lo < hi
+        report(case, "%s, trip %d" % (what, t), got[lo:hi], None if r32 is None else r32[lo:hi], r64[lo:hi])
+
+
+def accept_matrix(case, what, got, r32, r64, floor):
+    """The rule of the conv and channel-mix kernels' own tests: e_got <= 2 e_ref + floor * scale over every element,
+    e_ref being torch's fp32 composition against the fp64 one."""
+    assert got.shape == r64.shape and got.dtype == F32, (case.name, what, tuple(got.shape), tuple(r64.shape))
+    by_trip(case, what, got, r32, r64)
+    scale = float(r64.abs().max())
+    e_got, e_ref = float((got.double() - r64).abs().max()), float((r32.double() - r64).abs().max())
+    assert bool(torch.isfinite(got).all()) and e_got <= 2.0 * e_ref + floor * scale, (case.name, what, e_got, e_ref, scale)
+
+
+def one_float_past(x):
+    """x copied to an address one float past a 16-byte boundary (test_conv1x1_fused_kernel_unaligned_input)"""
+    big = torch.empty(x.numel() + 4, device=x.device, dtype=x.dtype)
+    at = 1 + (-(big.data_ptr() // 4)) % 4
+    xo = big[at:at + x.numel()].view(x.shape)
+    xo.copy_(x)
+    assert xo.data_ptr() % 16 == 4 and xo.is_contiguous()
+    return xo
+
+
+@pytest.mark.parametrize("which", ["dma", "dma_odd", "regs", "regs_rows"])
+def test_conv1x1(hip, which):
+    """csrc/conv1x1.hip past its cap of 256 passes, in both staging variants with one and three k-steps.  The DMA cases
+    are also run on a copy of x one float past a 16-byte boundary, which the launcher stages through registers: the two
+    variants feed the same fragments to the same instructions, so the results are the same bits (and the register
+    variant makes its three trips at 2 x 2 images too)."""
+    from vcnf_amd.nets.cnn import pack_conv1x1
+    case = gc.CASES["conv1x1.%s.f32" % which]
+    t0 = time.time()
+    c_in, c_out, h, w, b = case.shape["c_in"], case.shape["c_out"], case.shape["H"], case.shape["W"], case.B
+    g = seeded("grid caps conv1x1", which)
+    wgt = (torch.randn(c_out, c_in, generator=g) / c_in ** 0.5).cuda()
+    b_in, b_out = torch.randn(c_in, generator=g).cuda(), torch.randn(c_out, generator=g).cuda()
+    x = torch.randn(b, c_in, h, w, generator=g).cuda()
+    pack = pack_conv1x1(wgt)
+    # the launcher's choice: buffer_load ... lds for 16-byte aligned x with H W % 4 == 0, registers otherwise
+    assert x.data_ptr() % 16 == 0 and ((h * w) % 4 == 0) == case.shape["dma"]
+    call = lambda xs: (_lib.conv1x1_fused(xs, pack, c_out, in_bias=b_in, out_bias=b_out, in_slope=SLOPES[0], out_slope=SLOPES[1]),)
+    (got,) = call(x)
+    lrelu = torch.nn.functional.leaky_relu
+
+    def ref(dt):
+        t = lrelu(x.to(dt) + b_in.to(dt).view(1, -1, 1, 1), SLOPES[0])
+        return lrelu(torch.einsum("oc,bchw->bohw", wgt.to(dt), t) + b_out.to(dt).view(1, -1, 1, 1), SLOPES[1])
+    accept_matrix(case, "y", got, ref(F32), ref(F64), 2e-6)
+    rows_again(case, call, [(x, 0)], [(got, 0)])
+    if case.shape["dma"]:
+        assert torch.equal(call(one_float_past(x))[0], got), "register staging and DMA staging differ"
+    assert nf.check_saturation() == 0
+    print("GRIDCAP %-34s wall %.2f s" % (case.name, time.time() - t0))
+
+
+def conv31_weights(c_in, c_out, g):
+    """w1, w2, w3, b1, b2, b3 as test_conv3x3_1x1_fused_kernel and test_convnet3_fused_taps_and_col2im draw them"""
+    w1 = (torch.randn(256, c_in, 3, 3, generator=g) / (3.0 * c_in ** 0.5)).cuda()
+    w2 = (torch.randn(256, 256, generator=g) / 16).cuda()
+    w3 = (torch.randn(c_out, 256, 3, 3, generator=g) / 48).cuda()
+    return (w1, w2, w3) + tuple(torch.randn(n, generator=g).cuda() for n in (256, 256, c_out))
+
+
+def conv31_packs(w1, w2, w3, c_in, c_out):
+    from vcnf_amd.nets.cnn import pack_conv1x1
+    k1 = 9 * c_in
+    p1 = pack_conv1x1(torch.nn.functional.pad(w1.reshape(256, k1), (0, (-k1) % 16)))
+    p3 = pack_conv1x1(w3.permute(2, 3, 0, 1).reshape(9 * c_out, 256), row_blocks=(9 * c_out + 31) // 32)
+    return p1, pack_conv1x1(w2), p3
+
+
+def conv3x3_ref(x, w, b):
+    """torch.nn.functional.conv2d(x, w, b, padding=1) composed of nine matrix products, one per tap, over the shifted
+    zero-padded image, in the dtype of x.  The convolution library searches its kernels for seconds at every new shape
+    and type (measured at these shapes in fp32: 5.2 s for c_in 2 -> 256, 2.7 s for 256 -> 5); in fp64 on the host this sum and conv2d
+    differ by 4e-15 at entries of size 10."""
+    h, wd = x.shape[2:]
+    xp = torch.nn.functional.pad(x, (1, 1, 1, 1))
+    out = b.view(1, -1, 1, 1).expand(len(x), -1, h, wd).clone()
+    for dy in range(3):
+        for dx in range(3):
+            out += torch.einsum("oc,bchw->bohw", w[:, :, dy, dx], xp[:, :, dy:dy + h, dx:dx + wd])
+    return out
+
+
+def test_conv3x3_1x1(hip):
+    """csrc/conv3x3_1x1.hip (THIRD = false) past its cap: 2 x 3 images, every pixel on a border, every pass of 64
+    pixels across image boundaries."""
+    Fn = torch.nn.functional
+    case = gc.CASES["conv3x3_1x1.f32"]
+    t0 = time.time()
+    c_in, h, w, b = case.shape["c_in"], case.shape["H"], case.shape["W"], case.B
+    g = seeded("grid caps conv3x3_1x1")
+    w1, w2, w3, b1, b2, _ = conv31_weights(c_in, 1, g)
+    p1, p2, _ = conv31_packs(w1, w2, w3, c_in, 1)
+    x = torch.randn(b, c_in, h, w, generator=g).cuda()
+    call = lambda xs: (_lib.conv3x3_1x1_fused(xs, p1, p2, b1, b2, *SLOPES),)
+    (got,) = call(x)
+
+    def ref(dt):
+        t = Fn.leaky_relu(conv3x3_ref(x.to(dt), w1.to(dt), b1.to(dt)), SLOPES[0])
+        return Fn.leaky_relu(torch.einsum("oc,bchw->bohw", w2.to(dt), t) + b2.to(dt).view(1, -1, 1, 1), SLOPES[1])
+    accept_matrix(case, "y", got, ref(F32), ref(F64), 2e-6)
+    rows_again(case, call, [(x, 0)], [(got, 0)])
+    assert nf.check_saturation() == 0
+    print("GRIDCAP %-34s wall %.2f s" % (case.name, time.time() - t0))
+
+
+def test_convnet3(hip):
+    """The taps instance (THIRD = true) of csrc/conv3x3_1x1.hip past its cap and the col2im that follows it: the whole
+    conditioner against the fp64 composition, and the nine tap results z themselves in the windows."""
+    Fn = torch.nn.functional
+    case = gc.CASES["convnet3.f32"]
+    t0 = time.time()
+    c_in, c_out, h, w, b = case.shape["c_in"], case.shape["c_out"], case.shape["H"], case.shape["W"], case.B
+    g = seeded("grid caps convnet3")
+    w1, w2, w3, b1, b2, b3 = conv31_weights(c_in, c_out, g)
+    p1, p2, p3 = conv31_packs(w1, w2, w3, c_in, c_out)
+    x = torch.randn(b, c_in, h, w, generator=g).cuda()
+    call = lambda xs: (_lib.convnet3_fused(xs, p1, p2, p3, b1, b2, b3, c_out, *SLOPES),)
+    (got,) = call(x)
+
+    def ref(dt):
+        t = Fn.leaky_relu(conv3x3_ref(x.to(dt), w1.to(dt), b1.to(dt)), SLOPES[0])
+        t = Fn.leaky_relu(torch.einsum("oc,bchw->bohw", w2.to(dt), t) + b2.to(dt).view(1, -1, 1, 1), SLOPES[1])
+        return conv3x3_ref(t, w3.to(dt), b3.to(dt))
+    accept_matrix(case, "y", got, ref(F32), ref(F64), 2e-6)
+    rows_again(case, call, [(x, 0)], [(got, 0)])
+    assert nf.check_saturation() == 0
+    print("GRIDCAP %-34s wall %.2f s" % (case.name, time.time() - t0))
+
+
+@pytest.mark.parametrize("which", ["rows", "rows8", "image"])
+def test_channel_mix(hip, which):
+    """csrc/channel_mix.hip past its cap of 4096 workgroups: the ROWS instances on [B, C] matrices and the image
+    instance on 1 x 3 images.  The fp32 yardstick is torch's einsum (a matrix product): a batch of a million images is
+    not a shape to hand to the convolution library that test_channel_mix_kernel uses at b <= 257."""
+    case = gc.CASES["mix.%s.f32" % which]
+    t0 = time.time()
+    c, b = case.shape["C"], case.B
+    g = seeded("grid caps channel mix", which)
+    mat, vec = torch.randn(c, c, generator=g).cuda(), torch.randn(c, generator=g).cuda()
+    shape = (b, c) if case.shape["rows"] else (b, c, case.shape["H"], case.shape["W"])
+    x = torch.randn(*shape, generator=g).cuda()
+    call = lambda xs: (_lib.channel_mix(xs, mat, vec),)
+    (got,) = call(x)
+    assert got.data_ptr() % 16 == 0                                # what sends a [B, C] matrix to the ROWS instance
+    bias = (1, c) + (1,) * (len(shape) - 2)
+    ref = lambda dt: torch.einsum("oc,bc...->bo...", mat.to(dt), x.to(dt)) + vec.to(dt).view(bias)
+    accept_matrix(case, "y", got, ref(F32), ref(F64), 1e-6)
+    rows_again(case, call, [(x, 0)], [(got, 0)])
+    print("GRIDCAP %-34s wall %.2f s" % (case.name, time.time() - t0))
+
+
+@pytest.mark.parametrize("which", ["layer", "layer_odd"])
+def test_fused_affine_layer(hip, which):
+    """fused_affine_layer_kernel past its cap of 2048 workgroups, as test_fused_affine_layer_vs_three_step_path_and_oracle
+    builds and judges the block: both directions and the accumulate form against the oracle block in fp64 (the
+    three-step path is the fp32 yardstick of the GRIDCAP lines)."""
+    from oracle import layers as OL, nets as ON
+    from vcnf_amd import fused_affine
+    case = gc.CASES["faffine.%s.f32" % which]
+    t0 = time.time()
+    d, hidden, mode, sm, b = case.shape["D"], case.shape["hidden"], case.shape["mode"], case.shape["scale_map"], case.B
+    torch.manual_seed(d * 7 + hidden)
+    head = d - d // 2
+    cin, cout = (head, d - head) if mode == "channel" else (d - head, head)
+    blk = nf.flows.AffineCouplingBlock(nf.nets.MLP([cin, hidden, hidden, 2 * cout], leaky=0.1), scale=True, scale_map=sm, split_mode=mode)
+    with torch.no_grad():
+        blk.flows[1].param_map.net[4].weight.mul_(0.5)
+    sd64 = {k: v.detach().clone().double() for k, v in blk.state_dict().items()}
+    blk = blk.cuda()
+    x = torch.randn(b, d, generator=seeded("grid caps fused affine layer", which))
+    xg = x.cuda()
+    assert fused_affine.eligible(blk, xg)
+    ora = OL.AffineCouplingBlock(lambda z: ON.mlp(sd64, "flows.1.param_map.", z, 0.1), scale=True, scale_map=sm, split_mode=mode)
+    tol = dict(rtol=2e-5, atol=2e-5)
+    ld_tol = dict(rtol=2e-5, atol=2e-5 * max(1, cout))
+    with torch.no_grad():
+        for dirn in ("forward", "inverse"):
+            call = lambda xs: getattr(blk, dirn)(xs)
+            blk.fused = True
+            z1, ld1 = call(xg)
+            blk.fused = False
+            z2, ld2 = call(xg)
+            blk.fused = True
+            want_z, want_ld = getattr(ora, dirn)(x.double())
+            by_trip(case, dirn + " z", z1, z2, want_z)
+            by_trip(case, dirn + " log_det", ld1, ld2, want_ld)
+            assert_close(z1, want_z, what="%s z %s" % (case.name, dirn), **tol)
+            assert_close(ld1, want_ld, what="%s log_det %s" % (case.name, dirn), **ld_tol)
+            rows_again(case, call, [(xg, 0)], [(z1, 0), (ld1, 0)])
+        # accumulate-into form used by NormalizingFlow (want_z, want_ld: the inverse direction's)
+        def into(xs):
+            acc = torch.full((len(xs),), 0.25, device="cuda")
+            return blk.inverse_into(xs, acc), acc
+        z3, lq = into(xg)
+        assert torch.equal(z3, z1) and torch.allclose(lq, 0.25 + ld1, rtol=1e-6, atol=1e-6)
+        by_trip(case, "inverse_into log_q", lq, 0.25 + ld2, 0.25 + want_ld)
+        assert_close(lq, 0.25 + want_ld, what="%s inverse_into log_q" % case.name, **ld_tol)
+        rows_again(case, into, [(xg, 0)], [(z3, 0), (lq, 0)])
+    print("GRIDCAP %-34s wall %.2f s" % (case.name, time.time() - t0))
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp16x3"])
+def test_fused_affine_stack(hip, precision):
+    """fused_affine_stack_kernel past its cap in both forms, on config C1's stack (D = 2, MLP [1, 32, 32, 2], four
+    [coupling, swap] pairs): density and sampling passes against helpers.oracle_affine_stack in fp64 with the tolerances
+    of test_affine_stacks_c1_c2.  test_c2_full_size_round_trip crosses the cap too, but compares the kernel with itself.
+    The weights are torch's default initialisation, as test_affine_stack_split_half_matrix_path draws them for this
+    stack.  The golden fixture's weights (g10_c1_two_moons, final layer x 6) suit its own 64 rows only: among 262 177
+    standard-normal rows the fp64 oracle itself samples |z| up to 9e111 with them (measured), where no fp32 result
+    exists.  The per-layer path is the fp32 yardstick of the GRIDCAP lines."""
+    from helpers import oracle_affine_stack
+    from test_gpu_parity import LP, TOL
+    from vcnf_amd import fused_affine
+    case = gc.CASES["faffine.stack.f32"]
+    t0 = time.time()
+    d, widths, layers, b = case.shape["D"], list(case.shape["widths"]), case.shape["layers"], case.B
+    torch.manual_seed(77 + d)
+    flows = []
+    for _ in range(layers):
+        flows += [nf.flows.AffineCouplingBlock(nf.nets.MLP(widths, init_zeros=False)), nf.flows.Permute(d, mode="swap")]
+    model = nf.NormalizingFlow(nf.distributions.DiagGaussian(d), flows)
+    sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    model = model.cuda().eval()
+    for f in model.flows:
+        f.fused_precision = precision
+    g = seeded("grid caps fused affine stack")
+    x, eps = torch.randn(b, d, generator=g), torch.randn(b, d, generator=g)
+    xg, eg = x.cuda(), eps.cuda()
+    with torch.no_grad():                                          # as the passes below: no autograd, so the blocks are fusable
+        plan = fused_affine.plan_stack(list(model.flows), 0, xg, False)
+    assert plan is not None and len(plan[1]) == layers and model.fuse_affine_stacks      # one launch for the four blocks
+    assert fused_affine.h3_ok(model.flows[0]) == (precision == "fp16x3")
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    oracle = oracle_affine_stack(sd64, layers, d)
+    want_lp = oracle.log_prob(x.double())
+    want_z, want_lq = oracle.sample_from(eps.double())
+    density = lambda xs: (model.log_prob(xs),)
+    sampling = lambda es: tuple(model.sample_from(es))
+    nf.range_redo_count()
+    with torch.no_grad():
+        (lp,), (z, lq) = density(xg), sampling(eg)
+        model.fuse_affine_stacks = False
+        (lp0,), (z0, lq0) = density(xg), sampling(eg)
+        model.fuse_affine_stacks = True
+        assert all(bool(torch.isfinite(t).all()) for t in (want_lp, want_z, want_lq))
+        by_trip(case, precision + " log_prob", lp, lp0, want_lp)
+        by_trip(case, precision + " sample z", z, z0, want_z)
+        by_trip(case, precision + " sample log_q", lq, lq0, want_lq)
+        assert_close(lp, want_lp, what="%s log_prob" % precision, **LP)
+        assert_close(z, want_z, what="%s sample z" % precision, **TOL)
+        assert_close(lq, want_lq, what="%s sample log_q" % precision, **LP)
+        rows_again(case, density, [(xg, 0)], [(lp, 0)])
+        rows_again(case, sampling, [(eg, 0)], [(z, 0), (lq, 0)])
+    assert nf.range_redo_count() == 0, "a wave took the fp32 fallback: the rows are no longer independent of their tile"
     print("GRIDCAP %-34s wall %.2f s" % (case.name, time.time() - t0))

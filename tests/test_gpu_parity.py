@@ -1268,6 +1268,35 @@ def test_channel_mix_kernel(hip, c, h, w):
         _lib.channel_mix(torch.randn(2, 6, 2, 2, device="cuda"), torch.eye(6, device="cuda"), torch.zeros(6, device="cuda"))
 
 
+@pytest.mark.parametrize("c", range(4, 65, 4))
+def test_channel_mix_every_instance(hip, c):
+    """Every (row blocks, k-steps) instance of csrc/channel_mix.hip, C = 4 ... 64, under the rule of
+    test_channel_mix_kernel: as an image (3 x 5, b = 3: the tiles of 16 pixels cross images), as a [B, C] matrix
+    (b = 131: ROWS instance, five tiles of 32 rows with a ragged one) and on an output that is not 16-byte aligned.
+    _lib.channel_mix allocates its output itself (always aligned), so the last call goes to the entry point as the
+    wrapper does, with an output view one float past a 16-byte boundary: the launcher then takes the image instance at
+    inner = 1 (scalar stores).  [B, C], [B, C, 1, 1] and the unaligned call give the same bits."""
+    g = torch.Generator().manual_seed(c * 100 + 3)
+    mat = torch.randn(c, c, generator=g).cuda()
+    vec = torch.randn(c, generator=g).cuda()
+    for shape in ((3, c, 3, 5), (131, c)):
+        x = torch.randn(*shape, generator=g).cuda()
+        got = _lib.channel_mix(x, mat, vec)
+        x4 = x.view(shape[0], c, *(shape[2:] or (1, 1)))
+        ref64 = (torch.einsum("oc,bchw->bohw", mat.double(), x4.double()) + vec.double().view(1, c, 1, 1)).view(shape)
+        ref32 = torch.nn.functional.conv2d(x4, mat.view(c, c, 1, 1), vec).view(shape)
+        scale = float(ref64.abs().max())
+        e_got, e_ref = float((got.double() - ref64).abs().max()), float((ref32.double() - ref64).abs().max())
+        assert got.shape == x.shape and e_got <= 2.0 * e_ref + 1e-6 * scale, (c, shape, e_got, e_ref)
+    assert got.data_ptr() % 16 == 0
+    assert torch.equal(_lib.channel_mix(x4, mat, vec).view(shape), got)
+    big = torch.empty(x.numel() + 1, device="cuda")
+    out = big[1:].view(shape)
+    assert out.data_ptr() % 16 == 4 and out.is_contiguous()
+    _lib._call("vcnf_channel_mix_f32", x.device, x, out, mat, vec, shape[0], c, 1, tag="channel_mix")
+    assert torch.equal(out, got)
+
+
 @pytest.mark.parametrize("c_in,c_out,h,w", [(256, 256, 16, 16), (256, 256, 4, 4), (64, 48, 3, 5), (16, 7, 1, 1), (96, 256, 2, 2)])
 def test_conv1x1_fused_kernel(hip, c_in, c_out, h, w):
     """csrc/conv1x1.hip: y = leaky(W leaky(x + b_in) + b_out) in one pass on the fp16 split-half matrix path, against
@@ -1334,6 +1363,41 @@ def test_conv1x1_fused_kernel_unaligned_input(hip):
     assert nf.check_saturation() == 0
 
 
+@pytest.mark.parametrize("c_in", range(16, 257, 16))
+def test_conv1x1_every_k_step_count_in_both_stagings(hip, c_in):
+    """Every KS = c_in / 16 instance of csrc/conv1x1.hip in both staging variants (the DMA request loop treats an odd KS
+    specially: its last trip moves 16 channels with the waves 0 - 3 only).  2 x 2 images, b = 37: three passes, the last
+    one ragged; c_out = 33: a partial second row block.  The aligned x takes the DMA staging, the same x one float past
+    a 16-byte boundary the registers (test_conv1x1_fused_kernel_unaligned_input); same acceptance as
+    test_conv1x1_fused_kernel for each, and the two are the same bits."""
+    from vcnf_amd.nets.cnn import pack_conv1x1
+    c_out, h, w, b = 33, 2, 2, 37
+    g = torch.Generator().manual_seed(c_in + c_out + h)
+    wgt = (torch.randn(c_out, c_in, generator=g) / c_in ** 0.5).cuda()
+    b_in, b_out = torch.randn(c_in, generator=g).cuda(), torch.randn(c_out, generator=g).cuda()
+    pack = pack_conv1x1(wgt)
+    lrelu = torch.nn.functional.leaky_relu
+    x = torch.randn(b, c_in, h, w, generator=g).cuda()
+    big = torch.empty(x.numel() + 1, device="cuda")
+    xo = big[1:].view(x.shape)
+    xo.copy_(x)
+    assert x.data_ptr() % 16 == 0 and xo.data_ptr() % 16 == 4 and xo.is_contiguous()
+
+    def ref(dt):
+        t = lrelu(x.to(dt) + b_in.to(dt).view(1, -1, 1, 1), 0.1)
+        return lrelu(torch.einsum("oc,bchw->bohw", wgt.to(dt), t) + b_out.to(dt).view(1, -1, 1, 1), 0.2)
+    r64, r32 = ref(torch.float64), ref(torch.float32)
+    scale = float(r64.abs().max())
+    e_ref = float((r32.double() - r64).abs().max())
+    out = {}
+    for name, xs in (("dma", x), ("registers", xo)):
+        got = out[name] = _lib.conv1x1_fused(xs, pack, c_out, in_bias=b_in, out_bias=b_out, in_slope=0.1, out_slope=0.2)
+        e_got = float((got.double() - r64).abs().max())
+        assert got.shape == r64.shape and e_got <= 2.0 * e_ref + 2e-6 * scale, (c_in, name, e_got, e_ref)
+    assert torch.equal(out["dma"], out["registers"])
+    assert nf.check_saturation() == 0
+
+
 @pytest.mark.parametrize("c_in,h,w", [(6, 16, 16), (12, 8, 8), (24, 4, 4), (3, 5, 7), (1, 2, 2)])
 def test_conv3x3_1x1_fused_kernel(hip, c_in, h, w):
     """csrc/conv3x3_1x1.hip: y = leaky(W2 leaky(conv3x3(x, padding 1) + b1) + b2) in one launch (first two layers of the
@@ -1360,6 +1424,57 @@ def test_conv3x3_1x1_fused_kernel(hip, c_in, h, w):
         scale = float(r64.abs().max())
         e_got, e_ref = float((got.double() - r64).abs().max()), float((r32.double() - r64).abs().max())
         assert got.shape == r64.shape and e_got <= 2.0 * e_ref + 2e-6 * scale, (c_in, b, e_got, e_ref)
+    assert nf.check_saturation() == 0
+
+
+def _conv31_every_c_in(c_in, c_out):
+    """Weights, packs, x (3 x 5, b = 5: two passes, the second ragged) and the fp64 / fp32 hidden activation after the
+    1x1 convolution for the tests of every KS1 = ceil(9 c_in / 16) instance below; both LeakyReLUs on."""
+    import torch.nn.functional as F
+    from vcnf_amd.nets.cnn import pack_conv1x1
+    g = torch.Generator().manual_seed(31 * c_in + c_out)
+    w1 = (torch.randn(256, c_in, 3, 3, generator=g) / (3.0 * c_in ** 0.5)).cuda()
+    w2 = (torch.randn(256, 256, generator=g) / 16).cuda()
+    w3 = (torch.randn(c_out, 256, 3, 3, generator=g) / 48).cuda()
+    b1, b2, b3 = (torch.randn(n, generator=g).cuda() for n in (256, 256, c_out))
+    k1 = 9 * c_in
+    p1 = pack_conv1x1(F.pad(w1.reshape(256, k1), (0, (-k1) % 16)))
+    p3 = pack_conv1x1(w3.permute(2, 3, 0, 1).reshape(9 * c_out, 256), row_blocks=(9 * c_out + 31) // 32)
+    x = torch.randn(5, c_in, 3, 5, generator=g).cuda()
+
+    def hidden(dt):
+        t = F.leaky_relu(F.conv2d(x.to(dt), w1.to(dt), b1.to(dt), padding=1), 0.1)
+        return F.leaky_relu(torch.einsum("oc,bchw->bohw", w2.to(dt), t) + b2.to(dt).view(1, -1, 1, 1), 0.2)
+    return (w3, b1, b2, b3), (p1, pack_conv1x1(w2), p3), x, hidden
+
+
+@pytest.mark.parametrize("c_in", range(1, 25))
+def test_conv3x3_1x1_every_k_step_count(hip, c_in):
+    """Every KS1 instance of csrc/conv3x3_1x1.hip without the taps: c_in = 1 ... 24 reaches KS1 = 1 ... 14; at c_in = 16
+    the patch length 144 is a whole number of k-steps (no zero padding of k).  Acceptance of
+    test_conv3x3_1x1_fused_kernel."""
+    (_, b1, b2, _), (p1, p2, _), x, hidden = _conv31_every_c_in(c_in, 1)
+    assert p1.numel() == int(_lib.lib().vcnf_conv3x3_1x1_pack_floats(c_in)) and ((9 * c_in) % 16 == 0) == (c_in == 16)
+    got = _lib.conv3x3_1x1_fused(x, p1, p2, b1, b2, 0.1, 0.2)
+    r64, r32 = hidden(torch.float64), hidden(torch.float32)
+    scale = float(r64.abs().max())
+    e_got, e_ref = float((got.double() - r64).abs().max()), float((r32.double() - r64).abs().max())
+    assert got.shape == r64.shape and e_got <= 2.0 * e_ref + 2e-6 * scale, (c_in, e_got, e_ref)
+    assert nf.check_saturation() == 0
+
+
+@pytest.mark.parametrize("c_in,c_out", [(c, 5) for c in range(1, 25)] + [(16, 56)])
+def test_convnet3_every_k_step_count(hip, c_in, c_out):
+    """Every KS1 instance of the taps variant (THIRD) with its col2im; c_out = 56 is the limit: 504 tap rows, the last
+    of the 16 row blocks partial.  Acceptance of test_convnet3_fused_taps_and_col2im."""
+    import torch.nn.functional as F
+    (w3, b1, b2, b3), (p1, p2, p3), x, hidden = _conv31_every_c_in(c_in, c_out)
+    assert p3.numel() == int(_lib.lib().vcnf_convnet3_w3_pack_floats(c_out))
+    got = _lib.convnet3_fused(x, p1, p2, p3, b1, b2, b3, c_out, 0.1, 0.2)
+    r64, r32 = (F.conv2d(hidden(dt), w3.to(dt), b3.to(dt), padding=1) for dt in (torch.float64, torch.float32))
+    scale = float(r64.abs().max())
+    e_got, e_ref = float((got.double() - r64).abs().max()), float((r32.double() - r64).abs().max())
+    assert got.shape == r64.shape and e_got <= 2.0 * e_ref + 2e-6 * scale, (c_in, c_out, e_got, e_ref)
     assert nf.check_saturation() == 0
 
 

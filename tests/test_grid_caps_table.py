@@ -31,7 +31,9 @@ def test_the_caps_the_tests_were_written_for():
     want = {"affine.cap": 4096, "cc.cap": 4096, "target.cap": 2048, "stoch.cap": 2048, "tail.fwd_cap": 2048,
             "gmm.fwd_cap": 2048, "pr.fwd_cap": 4096, "pr.bwd_cap": 1024, "mvn.fwd_cap": 512, "mvn.bwd_cap": 256,
             "stoch.bwd_cap": 1024, "rqs.elem_cap": 4096, "rqs.bwd_cap": 4096, "rqs64.cap": 8192,
-            "rqs.shared_bwd_threads": 262144, "tail.bwd_hi": 2048, "gmm.bwd_hi": 4096}
+            "rqs.shared_bwd_threads": 262144, "tail.bwd_hi": 2048, "gmm.bwd_hi": 4096,
+            "conv1.cap": 256, "conv1.pix": 64, "conv31.cap": 256, "conv31.pix": 64, "mix.cap": 4096, "mix.pix": 128,
+            "mix.block": 256, "faffine.cap": 2048, "faffine.block": 256, "trunk.cap": 2048}
     assert {k: gc.constant(k) for k in want} == want
 
 
@@ -60,10 +62,13 @@ def test_case_crosses_its_cap(name):
     assert items % c.per_block != 0 or c.per_block == 1, c.describe()
     if c.per_block > 1:
         assert items % c.per_block == c.remainder or c.items_per_row > 1
+    assert c.kind in ("narrow", "wide", "tile"), c.describe()
     if c.kind == "narrow":
         assert c.B * c.items_per_row > 2 * c.cap * c.rule.worst
-    else:
+    elif c.kind == "wide":
         assert c.rule.lanes == 64, c.describe()
+    else:                                                   # a fixed tile per workgroup and trip: 2 x cap + 1 tiles exactly
+        assert c.rule.worst == c.per_block and c.tiles == 2 * c.cap + 1, c.describe()
     assert c.elements <= gc.MAX_ELEMENTS, c.describe()
     # the windows of the row-independence checks lie inside the batch and fit into a first trip and a ragged rest
     for lo, hi in c.windows():
@@ -80,6 +85,31 @@ def test_wide_and_narrow_cases_exist_for_the_lane_group_units():
     for t in ("f32", "f64"):
         k, d = gc.CASES["pr.bwd.ckpt." + t].shape["K"], gc.CASES["pr.bwd.ckpt." + t].shape["D"]
         assert (k - 1) // gc.pr_checkpoint_every(d) >= 1            # a checkpoint row exists
+    # the matrix kernels: both staging variants of conv1x1, each with an even and an odd count of k-steps (the DMA
+    # request loop treats odd counts specially) and a partial row block; the ROWS instance of channel_mix and the image one
+    conv1 = [gc.CASES["conv1x1.%s.f32" % n] for n in ("dma", "dma_odd", "regs", "regs_rows")]
+    for dma in (True, False):
+        mine = [c for c in conv1 if c.shape["dma"] == dma]
+        assert all((c.items_per_row % 4 == 0) == dma for c in mine)             # what the launcher decides on (aligned x)
+        assert {c.shape["c_in"] // 16 for c in mine} == {1, 3} and any(c.shape["c_out"] % 32 for c in mine)
+    assert {gc.CASES["mix.%s.f32" % n].shape["rows"] for n in ("rows", "rows8", "image")} == {True, False}
+    assert all(gc.CASES["mix.%s.f32" % n].items_per_row == 1 for n in ("rows", "rows8"))
+    assert gc.CASES["faffine.layer_odd.f32"].shape["D"] % 4 and not gc.CASES["faffine.layer.f32"].shape["D"] % 4
+
+
+def test_matrix_kernel_batches():
+    """The batches of the "tile" cases as they were sized (a changed cap moves them: look at the times again)."""
+    want = {"conv1x1.dma": 8201, "conv1x1.dma_odd": 8201, "conv1x1.regs": 10934, "conv1x1.regs_rows": 32801,
+            "conv3x3_1x1": 5467, "convnet3": 5467, "mix.rows": 1048641, "mix.rows8": 1048641, "mix.image": 349547,
+            "faffine.layer": 262177, "faffine.layer_odd": 262177, "faffine.stack": 262177}
+    assert {k: gc.CASES[k + ".f32"].B for k in want} == want
+    assert sorted(k[:-4] for k, c in gc.CASES.items() if c.kind == "tile") == sorted(want)
+    # the launch loops the rules restate
+    assert "for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x)" in gc.source("conv1x1.hip")
+    assert "for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x)" in gc.source("conv3x3_1x1.hip")
+    assert "t = (long long)blockIdx.x * (kMixBlock / 64) + wave; t < ntiles; t += stride" in gc.source("channel_mix.hip")
+    assert gc.source("fused_affine.hip").count("wt = blockIdx.x + (long long)gridDim.x * wave; wt < nwt; wt += wstride") == 2
+    assert "#define VCNF_FA_NCB 1" in gc.source("fused_affine.hip")
 
 
 def test_looping_files_are_the_covered_and_the_excluded():
