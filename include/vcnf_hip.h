@@ -883,6 +883,51 @@ int vcnf_vae_bernoulli_log_prob_f64(const double* x, const double* score, double
 int vcnf_vae_bernoulli_log_prob_bwd_f64(const double* x, const double* score, const double* g_lp, double* d_score,
                                         int64_t rows, int32_t x_div, int32_t features, void* stream);
 
+/* ---- Circular flows: the periodic maps of normflow 1.2's flows/periodic.py (PeriodicWrap, PeriodicShift) and the
+ * UniformGaussian base of its distributions/base.py (csrc/periodic.hip).  Rows of `features` = D contiguous columns.
+ *   periodic (z, out [n_rows, D]; half [D]; shift [D] or NULL = no shift): a column with half[j] == 0 is copied; on
+ *              the others, with bound = half[j] > 0 and s = sign * shift[j], in the element type and in this order
+ *                a = (z + s) + bound;  r = fmod(a, 2 * bound);  if (r != 0 && r < 0) r += 2 * bound;  out = r - bound
+ *              No step is contracted or reordered, so out has the bits of torch.remainder(z + s + bound, 2 * bound) -
+ *              bound.  sign is +1 for PeriodicShift.forward and -1 for its inverse.  out == z is allowed (in place).
+ *              Both maps have derivative 1 and log-det 0: there is nothing else to compute.
+ *   uniform_gaussian_log_prob (z [batch, D], inv_scale_g [D]):
+ *              logp[b] = const_term - 0.5 * sum_j (z[b, j] * inv_scale_g[j])^2
+ *              inv_scale_g is 1 / scale on a Gaussian column and 0 on a uniform one (the uniform part does not test
+ *              its range); const_term = -sum_j log scale_j - 0.5 * (number of Gaussian columns) * log(2 pi), which the
+ *              caller evaluates in fp64.  ld_mode: VCNF_LD_STORE or VCNF_LD_ACCUM (logp[b] += ...)
+ *   uniform_gaussian_sample (eps [batch, D] in the order drawn, src [D] int32, offset, scale, inv_scale_g [D]):
+ *              z[b, j] = scale[j] * (eps[b, src[j]] - offset[j])  (offset 0.5 where src[j] is a uniform draw, else 0)
+ *              and logp[b] of that z as above, in the same launch.  A src[j] outside [0, D) gives NaN, never a read
+ *              outside the row
+ *   uniform_gaussian_log_prob_bwd (cotangent g [batch]):  d_z[b, j] = -g[b] * z[b, j] * inv_scale_g[j]^2
+ * A lane group per row, the row in chunks of 16 bytes' worth of columns strided over the group, a lane's columns added
+ * in ascending order and the group by the ascending butterfly; 16-byte (8-byte) accesses when features % V == 0 and
+ * the row buffers and tables are aligned to them, scalar otherwise, with the same bits either way.  Any number of
+ * features.  No kernel loops over the grid: a shape that needs more than 2^31 - 1 workgroups -> VCNF_ERR_SHAPE.
+ * Checked in this order: NULL required pointer -> VCNF_ERR_NULL; features < 1, a negative count, or work beyond a grid
+ * -> VCNF_ERR_SHAPE; unknown ld_mode -> VCNF_ERR_UNSUPPORTED; n_rows == 0 / batch == 0 -> VCNF_OK without a launch; a
+ * pointer not aligned to its element size -> VCNF_ERR_ALIGN.  No atomics, no allocation, no host synchronisation:
+ * every call is bitwise reproducible and capturable. */
+int vcnf_periodic_f32(const float* z, const float* half, const float* shift, float* out, int64_t n_rows,
+                      int32_t features, float sign, void* stream);
+int vcnf_uniform_gaussian_log_prob_f32(const float* z, const float* inv_scale_g, float const_term, float* logp,
+                                       int64_t batch, int32_t features, int ld_mode, void* stream);
+int vcnf_uniform_gaussian_sample_f32(const float* eps, const int32_t* src, const float* offset, const float* scale,
+                                     float const_term, const float* inv_scale_g, float* z, float* logp, int64_t batch,
+                                     int32_t features, void* stream);
+int vcnf_uniform_gaussian_log_prob_bwd_f32(const float* z, const float* inv_scale_g, const float* g, float* d_z,
+                                           int64_t batch, int32_t features, void* stream);
+int vcnf_periodic_f64(const double* z, const double* half, const double* shift, double* out, int64_t n_rows,
+                      int32_t features, double sign, void* stream);
+int vcnf_uniform_gaussian_log_prob_f64(const double* z, const double* inv_scale_g, double const_term, double* logp,
+                                       int64_t batch, int32_t features, int ld_mode, void* stream);
+int vcnf_uniform_gaussian_sample_f64(const double* eps, const int32_t* src, const double* offset, const double* scale,
+                                     double const_term, const double* inv_scale_g, double* z, double* logp,
+                                     int64_t batch, int32_t features, void* stream);
+int vcnf_uniform_gaussian_log_prob_bwd_f64(const double* z, const double* inv_scale_g, const double* g, double* d_z,
+                                           int64_t batch, int32_t features, void* stream);
+
 /* ---- Full-covariance base distributions: the multivariate Gaussian and the multivariate Student-t over D = features
  * <= 128.  z / eps [B, D] contiguous, gamma [B], loc [D]; tri [D, D] row-major is a lower-triangular matrix of which
  * only the lower triangle including the diagonal is ever read: the scale L for sampling, its inverse M = L^-1 for the

@@ -1448,6 +1448,58 @@ def vae_bernoulli_log_prob_bwd(x, score, g, x_div=1):
     return d_score.view(score.shape)
 
 
+def periodic(z, half, shift, sign, out=None):
+    """vcnf_periodic_*: z [..., D] contiguous with the columns where half [D] is non-zero wrapped into [-half, half) after
+    adding sign * shift [D] (None: no shift); ``out``: write there (``out is z``: in place)."""
+    name = "vcnf_periodic" + _sfx(z)
+    dev = require_device(z, half, shift, out, f64=True)
+    d = half.numel()
+    if z.dim() < 1 or z.shape[-1] != d or not z.is_contiguous():
+        raise VcnfError("%s: inputs %s are not contiguous rows of %d columns" % (name, tuple(z.shape), d))
+    if any(t is not None and (t.dtype != z.dtype or t.numel() != d or not t.is_contiguous()) for t in (half, shift)):
+        raise VcnfError(name + ": the tables must be contiguous [features] tensors of the input's dtype")
+    if out is None:
+        out = torch.empty_like(z)
+    elif out is not z and (out.shape != z.shape or out.dtype != z.dtype or not out.is_contiguous()):
+        raise VcnfError(name + ": out must be a contiguous tensor of the input's shape and dtype")
+    _call(name, dev, z, half, shift, out, z.numel() // d, d, float(sign))
+    return out
+
+
+def uniform_gaussian_log_prob(z, inv_scale_g, const_term, logp=None):
+    """vcnf_uniform_gaussian_log_prob_*: const_term - sum((z inv_scale_g)^2) / 2 per row of z [B, D]; ``logp``: accumulate
+    into it."""
+    name = "vcnf_uniform_gaussian_log_prob" + _sfx(z)
+    dev, z2, (inv,), b, d = _tail_operands(z, (inv_scale_g,), name)
+    logp, mode = _ld_out(logp, b, z.dtype, dev, name)
+    _call(name, dev, z2, inv, float(const_term), logp, b, d, mode)
+    return logp
+
+
+def uniform_gaussian_sample(eps, src, offset, scale, const_term, inv_scale_g):
+    """vcnf_uniform_gaussian_sample_*: (z [B, D], log p(z) [B]) with z[:, j] = scale[j] (eps[:, src[j]] - offset[j])."""
+    name = "vcnf_uniform_gaussian_sample" + _sfx(eps)
+    dev, e2, (offset, scale, inv), b, d = _tail_operands(eps, (offset, scale, inv_scale_g), name)
+    require_device(src)
+    if src.dtype != torch.int32 or src.numel() != d or not src.is_contiguous():
+        raise VcnfError(name + ": src must be a contiguous int32 tensor [features]")
+    z = torch.empty_like(e2)
+    logp = torch.empty(b, dtype=eps.dtype, device=dev)
+    _call(name, dev, e2, src, offset, scale, float(const_term), inv, z, logp, b, d)
+    return z, logp
+
+
+def uniform_gaussian_log_prob_bwd(z, inv_scale_g, g):
+    """vcnf_uniform_gaussian_log_prob_bwd_*: d_z like z for the cotangent g [B] of the log density."""
+    name = "vcnf_uniform_gaussian_log_prob_bwd" + _sfx(z)
+    dev, z2, (inv,), b, d = _tail_operands(z, (inv_scale_g,), name)
+    require_device(g, f64=True)
+    g = _batch_vector(g, b, z.dtype, name, "g")
+    dz = torch.empty_like(z2)
+    _call(name, dev, z2, inv, g, dz, b, d)
+    return dz.view(z.shape)
+
+
 def _mvn_operands(x, loc, tri, consts, what):
     """Checked operands of the full-covariance base entry points: x [B, D], loc [D] (or None), tri [D, D], consts [2],
     one dtype.  Returns (device, x, loc, tri, consts contiguous, B, D)."""

@@ -559,6 +559,39 @@ class VaeBernoulliLogProbFn(torch.autograd.Function):
         return None, _lib.vae_bernoulli_log_prob_bwd(x, score, g, ctx.x_div), None
 
 
+class PeriodicFn(torch.autograd.Function):
+    """vcnf_periodic_*: a PeriodicWrap / PeriodicShift direction as ONE node.  The map is a translation by a multiple of
+    the period on every column, so its derivative is 1: backward hands the incoming gradient on, without a launch."""
+
+    @staticmethod
+    def forward(ctx, z, half, shift, sign):
+        with torch.no_grad():
+            return _lib.periodic(z, half, shift, sign)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None, None, None
+
+
+class UniformGaussianLogProbFn(torch.autograd.Function):
+    """vcnf_uniform_gaussian_log_prob_*: log density [B] of z [B, D] under UniformGaussian as ONE node that saves only
+    its inputs; backward is vcnf_uniform_gaussian_log_prob_bwd_*, one launch.  The scale is a buffer and gets no
+    gradient.  Not double-differentiable."""
+
+    @staticmethod
+    def forward(ctx, z, inv_scale_g, const_term):
+        with torch.no_grad():
+            lp = _lib.uniform_gaussian_log_prob(z, inv_scale_g, const_term)
+        ctx.save_for_backward(z, inv_scale_g)
+        return lp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        z, inv_scale_g = ctx.saved_tensors
+        return _lib.uniform_gaussian_log_prob_bwd(z, inv_scale_g, g), None, None
+
+
 class PlanarRadialStackFn(torch.autograd.Function):
     """vcnf_planar_radial_stack_*: (out, log|det| [B]) of a run of Planar / Radial layers from its effective operands va,
     vb [K, D] and sc [K, 2] (vcnf_amd.fused_planar.operands) as ONE node.  Forward launches the kernel with the trace

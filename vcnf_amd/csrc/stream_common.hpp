@@ -22,6 +22,37 @@ struct alignas(sizeof(T) * V) Pack {
   T v[V];
 };
 
+// A row cut into chunks of 16 bytes' worth of columns (vae_ends.hip, periodic.hip): which lane owns which chunk is fixed
+// by the shape, and only how a chunk is moved - one pack of 16 bytes, two of 8, or scalars - follows the alignment.
+template <typename T>
+constexpr int chunk_width() { return 16 / (int)sizeof(T); }
+
+// the first cnt columns of the chunk at src (cnt a multiple of V) in packs of V
+template <typename T, int V>
+__device__ __forceinline__ void load_chunk(T* d, const T* __restrict__ src, int cnt) {
+  constexpr int W = chunk_width<T>();
+#pragma unroll
+  for (int k = 0; k < W / V; ++k)
+    if (k * V < cnt) {
+      const Pack<T, V> q = *reinterpret_cast<const Pack<T, V>*>(src + k * V);
+#pragma unroll
+      for (int j = 0; j < V; ++j) d[k * V + j] = q.v[j];
+    }
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void store_chunk(T* __restrict__ dst, const T* s, int cnt) {
+  constexpr int W = chunk_width<T>();
+#pragma unroll
+  for (int k = 0; k < W / V; ++k)
+    if (k * V < cnt) {
+      Pack<T, V> q;
+#pragma unroll
+      for (int j = 0; j < V; ++j) q.v[j] = s[k * V + j];
+      *reinterpret_cast<Pack<T, V>*>(dst + k * V) = q;
+    }
+}
+
 __device__ __forceinline__ float exp_(float v) { return expf(v); }
 __device__ __forceinline__ double exp_(double v) { return exp(v); }
 __device__ __forceinline__ float log_(float v) { return logf(v); }

@@ -30,36 +30,6 @@ constexpr double kLog2Pi = 1.8378770664093454835606594728112353;
 
 enum { ENCODE = 0, GAUSS = 1, BERNOULLI = 2 };
 
-// columns of a chunk: what 16 bytes hold
-template <typename T>
-constexpr int chunk_width() { return 16 / (int)sizeof(T); }
-
-// the first cnt columns of the chunk at src (cnt a multiple of V) in packs of V
-template <typename T, int V>
-__device__ __forceinline__ void load_chunk(T* d, const T* __restrict__ src, int cnt) {
-  constexpr int W = chunk_width<T>();
-#pragma unroll
-  for (int k = 0; k < W / V; ++k)
-    if (k * V < cnt) {
-      const Pack<T, V> q = *reinterpret_cast<const Pack<T, V>*>(src + k * V);
-#pragma unroll
-      for (int j = 0; j < V; ++j) d[k * V + j] = q.v[j];
-    }
-}
-
-template <typename T, int V>
-__device__ __forceinline__ void store_chunk(T* __restrict__ dst, const T* s, int cnt) {
-  constexpr int W = chunk_width<T>();
-#pragma unroll
-  for (int k = 0; k < W / V; ++k)
-    if (k * V < cnt) {
-      Pack<T, V> q;
-#pragma unroll
-      for (int j = 0; j < V; ++j) q.v[j] = s[k * V + j];
-      *reinterpret_cast<Pack<T, V>*>(dst + k * V) = q;
-    }
-}
-
 // ------------------------------------------------------------------ forward
 // ENCODE:    a = eps [N, D] (a_div 1),  h [N / h_div, 2 D],  z [N, D],  out = logq
 // GAUSS:     a = v [N / a_div, D],      h [N / h_div, 2 D],             out = logp

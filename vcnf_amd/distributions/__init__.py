@@ -5,7 +5,7 @@ from . import mh_proposal                                      # noqa: F401
 from . import linear_interpolation                             # noqa: F401
 from . import encoder                                          # noqa: F401
 from . import decoder                                          # noqa: F401
-from .base import BaseDistribution, DiagGaussian, ClassCondDiagGaussian, GlowBase, GaussianMixture, StudentT, GeneralizedGaussian, MultivariateGaussian, MultivariateStudentT    # noqa: F401
+from .base import BaseDistribution, DiagGaussian, ClassCondDiagGaussian, GlowBase, GaussianMixture, StudentT, GeneralizedGaussian, MultivariateGaussian, MultivariateStudentT, UniformGaussian    # noqa: F401
 from .target import Target, TwoMoons, CircularGaussianMixture, RingMixture    # noqa: F401
 from .prior import PriorDistribution, TwoModes, Sinusoidal, Sinusoidal_gap, Sinusoidal_split, Smiley    # noqa: F401
 from .mh_proposal import MHProposal, DiagGaussianProposal    # noqa: F401

@@ -6,7 +6,8 @@ product Student-t (its T) and the generalised Gaussian (its GGD) are StudentT an
 GeneralizedGaussian here, with one trainable tail parameter per feature, and its
 full-covariance bases (its MultivariateGaussian and TMV) are MultivariateGaussian and
 MultivariateStudentT, parametrised by a lower-triangular scale factor; its other
-research distributions (GenNormal, ...) are out of scope."""
+research distributions (GenNormal, ...) are out of scope.  UniformGaussian is the base
+of normflow 1.2's circular models: uniform on the angles, Gaussian on the rest."""
 import math
 
 import numpy as np
@@ -14,6 +15,7 @@ import torch
 from torch import nn
 
 from .. import _lib, autograd
+from ..derived import memo, tensor_key
 
 
 class BaseDistribution(nn.Module):
@@ -501,3 +503,93 @@ class MultivariateStudentT(_FullCovarianceBase):
     def from_noise(self, eps, gamma=None):
         """``forward`` with the standard-normal draw eps [B, D] supplied, and optionally the gamma draw [B]."""
         return self._from_noise(eps, gamma)
+
+
+class UniformGaussian(BaseDistribution):
+    """Uniform on the columns ``ind`` and Gaussian on the others (normflow 1.2 base.py UniformGaussian): the base of a
+    flow whose coordinates ``ind`` are angles.  ``scale`` [ndim] (ones when None) is the width of the uniform columns -
+    for an angle the whole period, 2 bound - and the standard deviation of the Gaussian ones; it is a buffer, as are
+    ``ind``, ``ind_`` (the other indices, ascending) and ``inv_perm`` (the inverse of cat(ind, ind_)), all int64.
+    log p = -sum log scale - (ndim - len(ind)) / 2 log 2 pi - sum over ind_ of (z / scale)^2 / 2; the uniform part does not
+    test its range, so a point outside it gets no -inf.
+
+    Density, sampling and the gradient of the density run on the vcnf_uniform_gaussian_* kernels (csrc/periodic.hip),
+    one launch each, from per-column tables that are derived buffers; the constant of the density is evaluated on the
+    host in fp64.  The draws are torch's, in the reference's order (the uniform columns, then the Gaussian ones).  CPU
+    tensors, half precision, inputs that are not [B, ndim] of the scale's dtype and a draw that requires grad evaluate
+    the reference's composition in torch."""
+
+    def __init__(self, ndim, ind, scale=None):
+        super().__init__()
+        self.ndim = ndim
+        if isinstance(ind, int):
+            ind = [ind]
+        self.register_buffer("ind", ind.to(torch.long) if torch.is_tensor(ind) else torch.tensor(ind, dtype=torch.long))
+        taken = set(self.ind.tolist())
+        self.register_buffer("ind_", torch.tensor([i for i in range(ndim) if i not in taken], dtype=torch.long))
+        perm = torch.cat((self.ind, self.ind_))
+        inv_perm = torch.zeros_like(perm)
+        inv_perm[perm] = torch.arange(ndim)
+        self.register_buffer("inv_perm", inv_perm)
+        self.register_buffer("scale", torch.ones(ndim) if scale is None else scale)
+
+    def _build_tables(self):
+        """(inv_scale_g, scale, src, offset, const_term): 1 / scale on the Gaussian columns and 0 on the uniform ones,
+        the scale, the source column of each output column as int32, 0.5 where that source is a uniform draw, and the
+        density's constant as a Python float from fp64 arithmetic."""
+        scale, device, dtype = self.scale, self.scale.device, self.scale.dtype
+        s64 = scale.detach().double().cpu().reshape(-1)
+        inv = torch.zeros(self.ndim, dtype=torch.float64)
+        gauss = self.ind_.cpu()
+        inv[gauss] = 1.0 / s64[gauss]
+        const_term = float(-torch.log(s64).sum()) - 0.5 * len(gauss) * math.log(2.0 * math.pi)
+        src = self.inv_perm.cpu()
+        offset = torch.where(src < len(self.ind), 0.5, 0.0)
+        return (inv.to(device=device, dtype=dtype), scale.detach().reshape(-1).contiguous(),
+                src.to(device=device, dtype=torch.int32), offset.to(device=device, dtype=dtype), const_term)
+
+    def _tables(self):
+        key = tensor_key((self.scale, self.ind, self.ind_, self.inv_perm)) + (self.scale.dtype,)
+        return memo(self, 'uniform_gaussian_tables', key, UniformGaussian._build_tables, 4)
+
+    def _on_kernels(self, z):
+        return z.is_cuda and z.dtype in (torch.float32, torch.float64) and z.dtype == self.scale.dtype and \
+            z.device == self.scale.device and z.dim() == 2 and z.shape[1] == self.ndim and self.ndim >= 1
+
+    def forward(self, num_samples=1):
+        """The two draws in the reference's order, joined, then one kernel for z and log p."""
+        like = dict(dtype=self.scale.dtype, device=self.scale.device)
+        eps = torch.cat((torch.rand((num_samples, len(self.ind)), **like),
+                         torch.randn((num_samples, len(self.ind_)), **like)), -1)
+        return self.from_noise(eps)
+
+    def sample(self, num_samples=1):
+        return self.forward(num_samples)[0]
+
+    def from_noise(self, eps):
+        """``forward`` with the draws eps [B, ndim] supplied in the order drawn: the first len(ind) columns uniform on
+        [0, 1), the rest standard normal."""
+        if self._on_kernels(eps) and not autograd.needs_grad(eps):
+            inv, scale, src, offset, const_term = self._tables()
+            return _lib.uniform_gaussian_sample(eps, src, offset, scale, const_term, inv)
+        k = len(self.ind)
+        z = self.scale * torch.cat((eps[..., :k] - 0.5, eps[..., k:]), -1)[..., self.inv_perm]
+        return z, self._torch_log_prob(z)
+
+    def log_prob(self, z, out=None):
+        """``out`` [B]: accumulate into it instead of allocating."""
+        if not self._on_kernels(z):
+            lp = self._torch_log_prob(z)
+            return lp if out is None else out.add_(lp)
+        inv, _, _, _, const_term = self._tables()
+        if autograd.needs_grad(z, out):
+            lp = autograd.UniformGaussianLogProbFn.apply(z, inv, const_term)
+            return lp if out is None else out.add_(lp)
+        return _lib.uniform_gaussian_log_prob(z, inv, const_term, logp=out)
+
+    def _torch_log_prob(self, z):
+        """The density as the reference composes it."""
+        log_p_u = torch.broadcast_to(-torch.log(self.scale[self.ind]), (len(z), -1))
+        log_p_g = -0.5 * np.log(2 * np.pi) - torch.log(self.scale[self.ind_]) \
+            - 0.5 * torch.pow(z[..., self.ind_] / self.scale[self.ind_], 2)
+        return torch.sum(log_p_u, -1) + torch.sum(log_p_g, -1)

@@ -5,6 +5,7 @@ from .normalization import ActNorm                                              
 from .planar import Planar                                                        # noqa: F401
 from .radial import Radial                                                        # noqa: F401
 from .stochastic import MetropolisHastings, HamiltonianMonteCarlo                 # noqa: F401
+from .periodic import PeriodicWrap, PeriodicShift                                 # noqa: F401
 from .affine import (AffineConstFlow, AffineCoupling, MaskedAffineFlow,           # noqa: F401
                      AffineCouplingBlock)
 from .affine.glow import GlowBlock                                                # noqa: F401

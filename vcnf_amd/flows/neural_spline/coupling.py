@@ -89,6 +89,13 @@ class PiecewiseRationalQuadraticCDF(Flow):
             if grad:
                 y, ld = autograd.rqs_shared(*args, cfg, inverse=inverse)
                 out = out.index_copy(1, ix, y)
+            elif inputs.dtype == torch.float64:
+                # fp64 models: the elementwise fp64 spline on the group's logit rows expanded over the batch, as in _spline
+                x, *rows = args
+                y, le = _lib.rqs_elementwise(x, *[t.unsqueeze(0).expand((x.shape[0],) + tuple(t.shape)) for t in rows],
+                                             cfg, inverse)
+                ld = le.sum(1)
+                out.index_copy_(1, ix, y)
             else:
                 y, le = _lib.rqs_elementwise_shared(*args, cfg, inverse)
                 ld = le.sum(1)
