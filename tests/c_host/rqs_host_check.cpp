@@ -1,6 +1,6 @@
-// Host-only check of csrc/rqs_host.hpp (g++ -std=c++17, no HIP): the bin-count dispatcher over its three lists, the
-// spline constants of one configuration against the expressions the units carried before the header existed, and
-// the number of derivative logits.
+// Host-only check of csrc/rqs_host.hpp (g++ -std=c++17, no HIP): the bin-count dispatcher over its three lists,
+// host_common.hpp's with_flags, the spline constants of one configuration against the expressions the units carried
+// before the header existed, and the number of derivative logits.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,12 +41,44 @@ static void check_list(BinList<Ks...> list, const char* name) {
   }
 }
 
+// with_flags over N flags: each of the 2^N combinations reaches f once, with the constants of its booleans in their
+// order, and f's status comes back
+static int flag_bits() { return 0; }
+template <class B, class... Bs>
+static int flag_bits(B b, Bs... rest) {
+  static_assert(std::is_same<B, std::true_type>::value || std::is_same<B, std::false_type>::value, "a bool_constant");
+  return (B::value ? 1 << sizeof...(Bs) : 0) | flag_bits(rest...);
+}
+
+template <class... Bools>
+static void check_flags_at(int want, Bools... flags) {
+  int got = -1, calls = 0;
+  const int status = with_flags([&](auto... c) { got = flag_bits(c...); ++calls; return 100 + got; }, flags...);
+  if (got != want || calls != 1 || status != 100 + want) {
+    printf("FAILED with_flags, %d flags, combination %d: constants %d in %d calls, status %d\n", (int)sizeof...(Bools),
+           want, got, calls, status);
+    ++failures;
+  }
+}
+
+static void check_flags() {
+  check_flags_at(0);
+  for (int a = 0; a < 2; ++a) {
+    check_flags_at(a, a != 0);
+    for (int b = 0; b < 2; ++b) {
+      check_flags_at(a << 1 | b, a != 0, b != 0);
+      for (int c = 0; c < 2; ++c) check_flags_at(a << 2 | b << 1 | c, a != 0, b != 0, c != 0);
+    }
+  }
+}
+
 static bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof a) == 0; }
 
 int main() {
   check_list(kBins, "kBins");
   check_list(kBins64, "kBins64");
   check_list(kBinsIdHalf, "kBinsIdHalf");
+  check_flags();
 
   // 8 bins, linear tails, bound 3, the default floors
   vcnf_rqs_cfg cfg_v;

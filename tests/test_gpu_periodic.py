@@ -25,9 +25,11 @@ PI = math.pi
 # ---------------------------------------------------------------- the periodic layers
 # (features, ind, bound, shift, input shapes).  3: the scalar path with one wrapped column; 5: per-index tensors; 8: the
 # pack path (16-byte packs of fp32, 8-byte pairs of fp64), also with the index on the last axis of a 3-D input; 7: a
-# negative index on the scalar path, one row and more than one workgroup (257 rows of one lane each)
+# negative index on the scalar path, one row and more than one workgroup (257 rows of one lane each); 6: 8-byte pairs of
+# fp32 as well
 LAYER_CASES = {
     "d3": (3, [1], PI, 0.7, [(257, 3)]),
+    "d6_pairs": (6, [1, 4], 2.0, 0.7, [(257, 6)]),
     "d5_tensors": (5, torch.tensor([0, 3, 4]), torch.tensor([1.0, PI, 2.5]), torch.tensor([0.3, -4.0, 1.0]), [(257, 5)]),
     "d8_pack": (8, [0, 2, 5, 7], 2.0, -1.3, [(257, 8), (5, 7, 8)]),
     "d7_negative": (7, [-1], 1.0, 0.25, [(1, 7), (257, 7)]),

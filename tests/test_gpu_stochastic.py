@@ -124,7 +124,7 @@ def test_hmc_unusual_rows(hip, tgt, dtype):
     r = sref.hmc_reference(family, n, steps, step, b, 1)
     layers = layers_of(target, r["params"], steps, dtype)
     z, noise, unif = (r[name].to(dtype).cuda() for name in ("z", "noise", "unif"))
-    out, ld, _, accept = hmc_kernel(target, layers, z, noise, unif, steps)
+    out, ld, trace, accept = hmc_kernel(target, layers, z, noise, unif, steps)
     # unif = 0: every row whose probability is not 0 is accepted, and log_det is the module's own log p(z) - log p(z_out)
     out0, ld0, _, accept0 = hmc_kernel(target, layers, z, noise, torch.zeros_like(unif), steps)
     positive = r[torch.float64][3][0] > 1e-30
@@ -152,6 +152,16 @@ def test_hmc_unusual_rows(hip, tgt, dtype):
     assert shifted.data_ptr() % (2 * z.element_size()) == z.element_size()
     outs, lds, _, accs = hmc_kernel(target, layers, shifted, noise, unif, steps)
     assert torch.equal(outs, out) and torch.equal(lds, ld) and torch.equal(accs, accept)
+    # likewise the VJP (its trace one element off) and the Metropolis-Hastings walk (its z), on the draws at hand
+    buf[1:] = trace.reshape(-1)
+    table, scale = target._operands(z)
+    with torch.no_grad():
+        step_, mass, sqm = fused_stochastic.operands(layers)
+        vjp = lambda t: _lib.hmc_stack_bwd(t, accept, noise, step_, mass, sqm, steps, target._family, table, scale, g_out=noise[0], g_ld=unif[0])
+        assert all(torch.equal(x, y) for x, y in zip(vjp(buf[1:].view(1, b, 2)), vjp(trace)))
+        buf[1:] = z.reshape(-1)
+        walk = lambda x: _lib.mh_walk(x, noise, unif, step_[0], target._family, table, scale, want_accept=True)
+        assert all(torch.equal(x, y) for x, y in zip(walk(shifted), walk(z)))
 
 
 def test_bad_inputs_raise(hip):

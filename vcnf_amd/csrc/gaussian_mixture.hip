@@ -407,20 +407,14 @@ static int forward(const T* in, const int32_t* mode, const T* loc, const T* ls, 
   if (!in || !loc || !ls || !logw || !logp || (sample && (!z || !mode))) return VCNF_ERR_NULL;
   if (!all_aligned({in, loc, ls, logw, logp, z}, sizeof(T)) || !aligned(mode, 4)) return VCNF_ERR_ALIGN;
   FwdArgs<T> a{make_tables(loc, ls, logw, D, M), in, mode, z, logp, batch, 1, ld_mode, sample, sign};
-  const int V = pick_pack<T>(D, {in, z});
-  const int nv = D / V;
-  a.G = pick_lanes(nv);
-  const bool reg = nv <= kRegPacks * a.G;
-  const dim3 grid = grid_for(batch, a.G, kFwdBlock, kMaxFwdBlocks);
   const size_t lds = table_bytes(a.t);
-  hipStream_t st = (hipStream_t)stream;
-#define VCNF_GMM_FWD(VV) (reg ? launch_fwd<T, VV, true>(a, grid, lds, st) : launch_fwd<T, VV, false>(a, grid, lds, st))
-  if constexpr (sizeof(T) == 4) {
-    if (V == 4) return VCNF_GMM_FWD(4);
-  }
-  if (V == 2) return VCNF_GMM_FWD(2);
-  return VCNF_GMM_FWD(1);
-#undef VCNF_GMM_FWD
+  return with_pack<T>(D, {in, z}, [&](auto V) {
+    const int nv = D / V();
+    a.G = pick_lanes(nv);
+    const dim3 grid = grid_for(batch, a.G, kFwdBlock, kMaxFwdBlocks);
+    return with_flags([&](auto REG) { return launch_fwd<T, V(), REG()>(a, grid, lds, (hipStream_t)stream); },
+                      nv <= kRegPacks * a.G);
+  });
 }
 
 template <typename T>
@@ -431,25 +425,18 @@ static int backward(const T* z, const T* loc, const T* ls, const T* logw, const 
   if (!z || !loc || !ls || !logw || !lse || !g || !dz) return VCNF_ERR_NULL;
   if (!all_aligned({z, loc, ls, logw, lse, g, gz_in, dz, partials}, sizeof(T))) return VCNF_ERR_ALIGN;
   BwdArgs<T> a{make_tables(loc, ls, logw, D, M), z, lse, g, gz_in, dz, partials, batch, 1};
-  const int V = pick_pack<T>(D, {z, gz_in, dz});
-  const int nv = D / V;
-  a.G = pick_lanes(nv);
-  const bool reg = nv <= kRegPacks * a.G;
   size_t lds = table_bytes(a.t);
   const size_t acc = (size_t)M * (2 * D + 1) * sizeof(T);
   const bool acc_lds = partials && lds + acc <= kLdsBytes;
   if (acc_lds) lds += acc;
   const dim3 grid((unsigned)bwd_groups(batch, D, M));
-  hipStream_t st = (hipStream_t)stream;
-#define VCNF_GMM_BWD(VV)                                                                          \
-  (reg ? (acc_lds ? launch_bwd<T, VV, true, true>(a, grid, lds, st) : launch_bwd<T, VV, true, false>(a, grid, lds, st)) \
-       : (acc_lds ? launch_bwd<T, VV, false, true>(a, grid, lds, st) : launch_bwd<T, VV, false, false>(a, grid, lds, st)))
-  if constexpr (sizeof(T) == 4) {
-    if (V == 4) return VCNF_GMM_BWD(4);
-  }
-  if (V == 2) return VCNF_GMM_BWD(2);
-  return VCNF_GMM_BWD(1);
-#undef VCNF_GMM_BWD
+  return with_pack<T>(D, {z, gz_in, dz}, [&](auto V) {
+    const int nv = D / V();
+    a.G = pick_lanes(nv);
+    return with_flags(
+        [&](auto REG, auto ACC_LDS) { return launch_bwd<T, V(), REG(), ACC_LDS()>(a, grid, lds, (hipStream_t)stream); },
+        nv <= kRegPacks * a.G, acc_lds);
+  });
 }
 
 template <typename T>

@@ -314,7 +314,8 @@ struct RowsDest {
 };
 
 // ------------------------------------------------------------------ host side
-static inline bool ok_family(int f) { return f == VCNF_TAIL_STUDENT_T || f == VCNF_TAIL_GEN_GAUSSIAN; }
+constexpr IntList<VCNF_TAIL_STUDENT_T, VCNF_TAIL_GEN_GAUSSIAN> kFamilies{};
+static inline bool ok_family(int f) { return in_list(kFamilies, f); }
 
 static int check_shape(int64_t batch, int32_t D) { return batch < 0 || D < 1 ? VCNF_ERR_SHAPE : VCNF_OK; }
 
@@ -324,22 +325,6 @@ static long long bwd_groups(int64_t batch, int32_t D) {
   cap = cap < 128 ? 128 : cap > 2048 ? 2048 : cap;
   const long long n = (batch + 15) / 16;
   return n < 1 ? 1 : n > cap ? cap : n;
-}
-
-template <typename T, int V, int F>
-static int launch_fwd(const FwdArgs<T>& a, bool reg, bool sample, dim3 grid, hipStream_t st) {
-  if (reg) {
-    if (sample)
-      hipLaunchKernelGGL((tail_fwd_kernel<T, V, F, true, true>), grid, dim3(kBlock), 0, st, a);
-    else
-      hipLaunchKernelGGL((tail_fwd_kernel<T, V, F, true, false>), grid, dim3(kBlock), 0, st, a);
-  } else {
-    if (sample)
-      hipLaunchKernelGGL((tail_fwd_kernel<T, V, F, false, true>), grid, dim3(kBlock), 0, st, a);
-    else
-      hipLaunchKernelGGL((tail_fwd_kernel<T, V, F, false, false>), grid, dim3(kBlock), 0, st, a);
-  }
-  return launched();
 }
 
 template <typename T, int V, int F, int OP>
@@ -356,15 +341,13 @@ static int launch_bwd(BwdArgs<T> a, hipStream_t st) {
   return launched();
 }
 
-// V and family to template arguments
-#define VCNF_TAIL_DISPATCH(CALL)                                             \
-  do {                                                                       \
-    if constexpr (sizeof(T) == 4) {                                          \
-      if (V == 4) return family == VCNF_TAIL_STUDENT_T ? CALL(4, 0) : CALL(4, 1); \
-    }                                                                        \
-    if (V == 2) return family == VCNF_TAIL_STUDENT_T ? CALL(2, 0) : CALL(2, 1);   \
-    return family == VCNF_TAIL_STUDENT_T ? CALL(1, 0) : CALL(1, 1);          \
-  } while (0)
+// launch(V, F): the pack width of the streamed buffers and the family as constants
+template <typename T, typename L>
+static int with_pack_family(int32_t D, std::initializer_list<const void*> bufs, int family, L&& launch) {
+  return with_pack<T>(D, bufs, [&](auto V) {
+    return launch_listed(kFamilies, family, [&](auto F) { return launch(V, F); });
+  });
+}
 
 template <typename T>
 static int forward(const T* in, const T* gamma, const T* loc, const T* ls, const T* shape, const T* cst, T* z, T* logp,
@@ -375,15 +358,16 @@ static int forward(const T* in, const T* gamma, const T* loc, const T* ls, const
   if (!in || !loc || !ls || !shape || !cst || !logp || (sample && (!gamma || !z))) return VCNF_ERR_NULL;
   if (!all_aligned({in, gamma, loc, ls, shape, cst, z, logp}, sizeof(T))) return VCNF_ERR_ALIGN;
   FwdArgs<T> a{Rows<T>{loc, ls, shape, cst, D}, in, gamma, z, logp, batch, 1, ld_mode, sign};
-  const int V = pick_pack<T>(D, {in, gamma, z});
-  const int nv = D / V;
-  const bool reg = nv <= kRegPacks * 64;
-  a.G = reg ? pick_lanes((nv + kRegPacks - 1) / kRegPacks) : 64;
-  const dim3 grid = grid_for(batch, a.G, kBlock, kMaxFwdBlocks);
-  hipStream_t st = (hipStream_t)stream;
-#define VCNF_TAIL_FWD(VV, FF) launch_fwd<T, VV, FF>(a, reg, sample, grid, st)
-  VCNF_TAIL_DISPATCH(VCNF_TAIL_FWD);
-#undef VCNF_TAIL_FWD
+  return with_pack_family<T>(D, {in, gamma, z}, family, [&](auto V, auto F) {
+    const int nv = D / V();
+    const bool reg = nv <= kRegPacks * 64;
+    a.G = reg ? pick_lanes((nv + kRegPacks - 1) / kRegPacks) : 64;
+    const dim3 grid = grid_for(batch, a.G, kBlock, kMaxFwdBlocks);
+    return with_flags([&](auto REG, auto SAMPLE) {
+      hipLaunchKernelGGL((tail_fwd_kernel<T, V(), F(), REG(), SAMPLE()>), grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+      return launched();
+    }, reg, sample);
+  });
 }
 
 template <typename T>
@@ -395,11 +379,8 @@ static int log_prob_bwd(const T* z, const T* loc, const T* ls, const T* shape, c
   if (!z || !loc || !ls || !shape || !g || !dz) return VCNF_ERR_NULL;
   if (!all_aligned({z, loc, ls, shape, g, gz_in, dz, partials}, sizeof(T))) return VCNF_ERR_ALIGN;
   const BwdArgs<T> a{Rows<T>{loc, ls, shape, nullptr, D}, z, gz_in, g, nullptr, dz, nullptr, partials, batch, 1};
-  const int V = pick_pack<T>(D, {z, gz_in, dz});
-  hipStream_t st = (hipStream_t)stream;
-#define VCNF_TAIL_BWD(VV, FF) launch_bwd<T, VV, FF, 0>(a, st)
-  VCNF_TAIL_DISPATCH(VCNF_TAIL_BWD);
-#undef VCNF_TAIL_BWD
+  return with_pack_family<T>(D, {z, gz_in, dz}, family,
+                             [&](auto V, auto F) { return launch_bwd<T, V(), F(), 0>(a, (hipStream_t)stream); });
 }
 
 template <typename T>
@@ -411,11 +392,8 @@ static int sample_bwd(const T* eps, const T* gamma, const T* loc, const T* ls, c
   if (!eps || !gamma || !loc || !ls || !shape || !dgamma) return VCNF_ERR_NULL;
   if (!all_aligned({eps, gamma, loc, ls, shape, g_z, g_lp, deps, dgamma, partials}, sizeof(T))) return VCNF_ERR_ALIGN;
   const BwdArgs<T> a{Rows<T>{loc, ls, shape, nullptr, D}, eps, gamma, g_lp, g_z, deps, dgamma, partials, batch, 1};
-  const int V = pick_pack<T>(D, {eps, gamma, g_z, deps, dgamma});
-  hipStream_t st = (hipStream_t)stream;
-#define VCNF_TAIL_BWD(VV, FF) launch_bwd<T, VV, FF, 1>(a, st)
-  VCNF_TAIL_DISPATCH(VCNF_TAIL_BWD);
-#undef VCNF_TAIL_BWD
+  return with_pack_family<T>(D, {eps, gamma, g_z, deps, dgamma}, family,
+                             [&](auto V, auto F) { return launch_bwd<T, V(), F(), 1>(a, (hipStream_t)stream); });
 }
 
 template <typename T>

@@ -1,5 +1,6 @@
-// Host idioms of the entry points, each defined once: the dispatch from a run-time count to a kernel instance, the
-// status after a launch, pointer alignment, the log-det mode, the dynamic-LDS limit of a kernel.  The first part is
+// Host idioms of the entry points, each defined once: the dispatch from a run-time count or code (with_listed_only,
+// launch_listed) and from run-time booleans (with_flags) to a kernel instance, the status after a launch, pointer
+// alignment, the log-det mode, the dynamic-LDS limit of a kernel.  The first part is
 // plain C++17 (rqs_host.hpp includes it and is compiled without HIP by tests/c_host/); the rest needs the HIP runtime.
 #pragma once
 
@@ -32,6 +33,17 @@ inline bool in_list(IntList<Ns...>, int n) {
 template <int... Ns, class F>
 inline bool with_listed_only(IntList<Ns...>, int n, F&& f) {
   return ((n == Ns && (f(std::integral_constant<int, Ns>{}), true)) || ...);
+}
+
+// f(std::bool_constant<b>{}...) for the run-time booleans b..., in their order, and what f returns (a status)
+template <class F>
+inline auto with_flags(F&& f) {
+  return f();
+}
+template <class F, class... Bools>
+inline auto with_flags(F&& f, bool b, Bools... rest) {
+  if (b) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+  return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
 
 }  // namespace vcnf

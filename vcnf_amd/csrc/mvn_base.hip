@@ -462,16 +462,6 @@ static int launch(dim3 grid, size_t lds, size_t max_lds, const Args<T>& a, hipSt
   return launched();
 }
 
-// the pack width to a template argument
-#define VCNF_MVN_DISPATCH(CALL)            \
-  do {                                     \
-    if constexpr (sizeof(T) == 4) {        \
-      if (V == 4) return CALL(4);          \
-    }                                      \
-    if (V == 2) return CALL(2);            \
-    return CALL(1);                        \
-  } while (0)
-
 template <typename T>
 static int forward(const T* in, const T* gamma, const T* loc, const T* tri, const T* consts, T* z, T* logp, int64_t batch,
                    int32_t D, int family, int ld_mode, T sign, bool sample, void* stream) {
@@ -481,25 +471,23 @@ static int forward(const T* in, const T* gamma, const T* loc, const T* tri, cons
   if (!in || !loc || !tri || !consts || !logp || (sample && (!z || (family == VCNF_MVN_STUDENT_T && !gamma)))) return VCNF_ERR_NULL;
   if (!all_aligned({in, gamma, loc, tri, consts, z, logp}, sizeof(T))) return VCNF_ERR_ALIGN;
   Args<T> a{in, gamma, loc, tri, consts, nullptr, nullptr, z, logp, nullptr, nullptr, batch, D, family, ld_mode, sign};
-  const int V = pick_pack<T>(D, {in, z});
   constexpr int TS = tile_rows<T>();
   long long tiles = (batch + TS - 1) / TS;
   const dim3 grid((unsigned)(tiles > kMaxFwdBlocks ? kMaxFwdBlocks : tiles));
-  hipStream_t st = (hipStream_t)stream;
-#define VCNF_MVN_FWD(VV)                                                                                          \
-  (sample ? launch<mvn_fwd_kernel<T, VV, true>>(grid, bytes<T>(D, true), bytes<T>(kMaxD, true), a, st)            \
-          : launch<mvn_fwd_kernel<T, VV, false>>(grid, bytes<T>(D, false), bytes<T>(kMaxD, false), a, st))
-  VCNF_MVN_DISPATCH(VCNF_MVN_FWD);
-#undef VCNF_MVN_FWD
+  return with_pack<T>(D, {in, z}, [&](auto V) {
+    return with_flags([&](auto SAMPLE) {
+      return launch<mvn_fwd_kernel<T, V(), SAMPLE()>>(grid, bytes<T>(D, SAMPLE()), bytes<T>(kMaxD, SAMPLE()), a,
+                                                      (hipStream_t)stream);
+    }, sample);
+  });
 }
 
 template <typename T, int OP>
 static int backward(Args<T> a, std::initializer_list<const void*> streamed, hipStream_t st) {
-  const int V = pick_pack<T>(a.D, streamed);
   const dim3 grid((unsigned)bwd_groups(a.B, a.D));
-#define VCNF_MVN_BWD(VV) launch<mvn_bwd_kernel<T, VV, OP>>(grid, bytes<T>(a.D, true), bytes<T>(kMaxD, true), a, st)
-  VCNF_MVN_DISPATCH(VCNF_MVN_BWD);
-#undef VCNF_MVN_BWD
+  return with_pack<T>(a.D, streamed, [&](auto V) {
+    return launch<mvn_bwd_kernel<T, V(), OP>>(grid, bytes<T>(a.D, true), bytes<T>(kMaxD, true), a, st);
+  });
 }
 
 template <typename T>

@@ -165,23 +165,6 @@ static inline bool plan(int64_t rows, int32_t D, int& lg, long long& blocks) {
   return blocks <= kMaxGrid;
 }
 
-// launch(V) with the widest pack the row length and the buffers allow
-template <typename T, typename F>
-static inline int with_pack(int32_t D, std::initializer_list<const void*> bufs, F&& launch) {
-  const int V = pick_pack<T>(D, bufs);
-  if constexpr (sizeof(T) == 4) {
-    if (V == 4) {
-      launch(std::integral_constant<int, 4>{});
-      return launched();
-    }
-  }
-  if (V >= 2)
-    launch(std::integral_constant<int, 2>{});
-  else
-    launch(std::integral_constant<int, 1>{});
-  return launched();
-}
-
 template <typename T>
 static int periodic(const T* z, const T* half, const T* shift, T* out, int64_t rows, int32_t D, T sign, void* stream) {
   if (!z || !half || !out) return VCNF_ERR_NULL;
@@ -193,6 +176,7 @@ static int periodic(const T* z, const T* half, const T* shift, T* out, int64_t r
   return with_pack<T>(D, {z, half, shift, out}, [&](auto V) {
     hipLaunchKernelGGL((periodic_kernel<T, V()>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, z, half,
                        shift, out, (long long)rows, D, lg, sign);
+    return launched();
   });
 }
 
@@ -208,6 +192,7 @@ static int log_prob(const T* z, const T* inv, T cst, T* logp, int64_t rows, int3
   return with_pack<T>(D, {z, inv}, [&](auto V) {
     hipLaunchKernelGGL((ug_log_prob_kernel<T, V()>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, z, inv,
                        logp, (long long)rows, D, lg, cst, ld_mode);
+    return launched();
   });
 }
 
@@ -223,6 +208,7 @@ static int sample(const T* eps, const int32_t* src, const T* offset, const T* sc
   return with_pack<T>(D, {offset, scale, inv, z}, [&](auto V) {
     hipLaunchKernelGGL((ug_sample_kernel<T, V()>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, eps, src,
                        offset, scale, inv, z, logp, (long long)rows, D, lg, cst);
+    return launched();
   });
 }
 
@@ -237,6 +223,7 @@ static int log_prob_bwd(const T* z, const T* inv, const T* g, T* d_z, int64_t ro
   return with_pack<T>(D, {z, inv, d_z}, [&](auto V) {
     hipLaunchKernelGGL((ug_log_prob_bwd_kernel<T, V()>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, z,
                        inv, g, d_z, (long long)rows, D, lg);
+    return launched();
   });
 }
 

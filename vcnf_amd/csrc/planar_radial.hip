@@ -380,32 +380,6 @@ static long long bwd_groups(int64_t batch, int32_t D, int32_t K) {
   return n < 1 ? 1 : n > cap ? cap : n;
 }
 
-template <typename T, int V>
-static int launch_fwd(const FwdArgs<T>& a, bool inverse, hipStream_t st) {
-  const dim3 grid = grid_for(a.B, a.G, kBlock, kMaxFwdBlocks);
-  if (inverse)
-    hipLaunchKernelGGL((pr_fwd_kernel<T, V, true>), grid, dim3(kBlock), 0, st, a);
-  else
-    hipLaunchKernelGGL((pr_fwd_kernel<T, V, false>), grid, dim3(kBlock), 0, st, a);
-  return launched();
-}
-
-template <typename T, int V>
-static int launch_bwd(const BwdArgs<T>& a, hipStream_t st) {
-  hipLaunchKernelGGL((pr_bwd_kernel<T, V>), dim3((unsigned)bwd_groups(a.B, a.D, a.K)), dim3(kBlock), 0, st, a);
-  return launched();
-}
-
-// V to a template argument
-#define VCNF_PR_DISPATCH(CALL)             \
-  do {                                     \
-    if constexpr (sizeof(T) == 4) {        \
-      if (V == 4) return CALL(4);          \
-    }                                      \
-    if (V == 2) return CALL(2);            \
-    return CALL(1);                        \
-  } while (0)
-
 template <typename T>
 static int forward(const T* z, T* out, T* logdet, T* trace, T* ckpt, const int32_t* kind, const int32_t* kind_dev, const T* va,
                    const T* vb, const T* sc, int64_t batch, int32_t D, int32_t K, int inverse, int ld_mode, T sign,
@@ -420,11 +394,13 @@ static int forward(const T* z, T* out, T* logdet, T* trace, T* ckpt, const int32
     return VCNF_ERR_ALIGN;
   const FwdArgs<T> a{Operands<T>{kind_dev, va, vb, sc}, z, out, logdet, trace, ckpt, batch, D, K, lanes_for(D),
                      checkpoint_every(D), ld_mode, sign};
-  const int V = pick_pack<T>(D, {z, out, ckpt, va, vb});
-  hipStream_t st = (hipStream_t)stream;
-#define VCNF_PR_FWD(VV) launch_fwd<T, VV>(a, inverse != 0, st)
-  VCNF_PR_DISPATCH(VCNF_PR_FWD);
-#undef VCNF_PR_FWD
+  const dim3 grid = grid_for(batch, a.G, kBlock, kMaxFwdBlocks);
+  return with_pack<T>(D, {z, out, ckpt, va, vb}, [&](auto V) {
+    return with_flags([&](auto INVERSE) {
+      hipLaunchKernelGGL((pr_fwd_kernel<T, V(), INVERSE()>), grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+      return launched();
+    }, inverse != 0);
+  });
 }
 
 template <typename T>
@@ -443,14 +419,12 @@ static int backward(const T* zout, const T* trace, const T* ckpt, const T* gout,
     return VCNF_ERR_ALIGN;
   const BwdArgs<T> a{Operands<T>{kind_dev, va, vb, sc}, zout, trace, ckpt, gout, gld, gin, workspace, batch,
                      sample_tiles(batch, D), D, K, lanes_for(D), checkpoint_every(D)};
-  const int V = pick_pack<T>(D, {zout, ckpt, gout, gin, va, vb});
-  hipStream_t st = (hipStream_t)stream;
-  auto kernel = [&]() -> int {
-#define VCNF_PR_BWD(VV) launch_bwd<T, VV>(a, st)
-    VCNF_PR_DISPATCH(VCNF_PR_BWD);
-#undef VCNF_PR_BWD
-  };
-  if (const int rc = kernel()) return rc;
+  const dim3 grid((unsigned)bwd_groups(batch, D, K));
+  const int rc = with_pack<T>(D, {zout, ckpt, gout, gin, va, vb}, [&](auto V) {
+    hipLaunchKernelGGL((pr_bwd_kernel<T, V()>), grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+    return launched();
+  });
+  if (rc) return rc;
   return launch_reduce_partials(workspace, bwd_groups(batch, D, K), (long long)K * (2LL * D + 2),
                                 LayerDest<T>{g_va, g_vb, g_sc, D}, stream);
 }

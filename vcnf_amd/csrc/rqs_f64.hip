@@ -296,9 +296,9 @@ __global__ __launch_bounds__(256) void rqs_elementwise_bwd_f64_kernel(const Rqs6
 template <bool STRIDED, bool LIM = false>
 static void launch_bwd64(const Rqs64BwdArgs& g, dim3 grid, hipStream_t st) {
   with_bins(kBins64, g.f.K, [&](auto kt) {
-    constexpr int KT = decltype(kt)::value;
-    if (g.f.inverse) hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<KT, true, STRIDED, LIM>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<KT, false, STRIDED, LIM>), grid, dim3(256), 0, st, g);
+    with_flags([&](auto INVERSE) {
+      hipLaunchKernelGGL((rqs_elementwise_bwd_f64_kernel<kt(), INVERSE(), STRIDED, LIM>), grid, dim3(256), 0, st, g);
+    }, g.f.inverse != 0);
   });
 }
 

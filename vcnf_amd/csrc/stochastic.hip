@@ -371,42 +371,11 @@ static int check_run(int64_t batch, int32_t n_layers, int32_t steps, int32_t n_c
 
 static long long sample_tiles(int64_t batch) { return (batch + kBlock - 1) / kBlock; }
 
-// family and row pack to template arguments
-#define VCNF_STOCH_LAUNCH(KERNEL, GRID, ST, ARGS)                                                  \
-  do {                                                                                             \
-    if (row)                                                                                       \
-      hipLaunchKernelGGL((KERNEL<T, F, true>), GRID, dim3(kBlock), 0, ST, ARGS);                   \
-    else                                                                                           \
-      hipLaunchKernelGGL((KERNEL<T, F, false>), GRID, dim3(kBlock), 0, ST, ARGS);                  \
-    return launched();                                                                             \
-  } while (0)
-
-#define VCNF_STOCH_FAMILY(FN, ...)                                                                 \
-  switch (family) {                                                                                \
-    case VCNF_TARGET_TWO_MOONS: return FN<T, VCNF_TARGET_TWO_MOONS>(__VA_ARGS__);                  \
-    case VCNF_TARGET_CIRCULAR_GMM: return FN<T, VCNF_TARGET_CIRCULAR_GMM>(__VA_ARGS__);            \
-    case VCNF_TARGET_RING_MIXTURE: return FN<T, VCNF_TARGET_RING_MIXTURE>(__VA_ARGS__);            \
-    case VCNF_TARGET_TWO_MODES: return FN<T, VCNF_TARGET_TWO_MODES>(__VA_ARGS__);                  \
-    case VCNF_TARGET_SINUSOIDAL: return FN<T, VCNF_TARGET_SINUSOIDAL>(__VA_ARGS__);                \
-    case VCNF_TARGET_SINUSOIDAL_GAP: return FN<T, VCNF_TARGET_SINUSOIDAL_GAP>(__VA_ARGS__);        \
-    case VCNF_TARGET_SINUSOIDAL_SPLIT: return FN<T, VCNF_TARGET_SINUSOIDAL_SPLIT>(__VA_ARGS__);    \
-    case VCNF_TARGET_SMILEY: return FN<T, VCNF_TARGET_SMILEY>(__VA_ARGS__);                        \
-    default: return VCNF_ERR_UNSUPPORTED; /* check_run has refused it */                           \
-  }
-
-template <typename T, int F, typename P>
-static int launch_hmc(const HmcArgs<T, P>& a, bool row, hipStream_t st) {
-  VCNF_STOCH_LAUNCH(hmc_fwd_kernel, grid_for(a.B, 1, kBlock, kMaxBlocks), st, a);
-}
-
-template <typename T, int F, typename P>
-static int launch_hmc_bwd(const HmcBwdArgs<T, P>& a, int32_t groups, bool row, hipStream_t st) {
-  VCNF_STOCH_LAUNCH(hmc_bwd_kernel, dim3((unsigned)groups), st, a);
-}
-
-template <typename T, int F>
-static int launch_mh(const MhArgs<T>& a, bool row, hipStream_t st) {
-  VCNF_STOCH_LAUNCH(mh_walk_kernel, grid_for(a.B, 1, kBlock, kMaxBlocks), st, a);
+// launch(F, ROW): the family and whether rows move as one pack, as constants
+template <typename L>
+static int with_family_row(int family, bool row, L&& launch) {
+  return launch_listed(vcnf_target::kFamilies, family,
+                       [&](auto F) { return with_flags([&](auto ROW) { return launch(F, ROW); }, row); });
 }
 
 template <typename T>
@@ -437,8 +406,11 @@ static int hmc_stack(const P& policy, const T* z, const T* noise, const T* unif,
   const HmcArgs<T, P> a{target_of(table, n_comp, family, scale), policy, z, noise, unif, step, mass, sqm, out, logdet, trace,
                         accept, batch, n_layers, steps};
   const bool row = all_aligned({z, noise, out, trace}, 2 * sizeof(T));
-  hipStream_t st = (hipStream_t)stream;
-  VCNF_STOCH_FAMILY(launch_hmc, a, row, st)
+  return with_family_row(family, row, [&](auto F, auto ROW) {
+    hipLaunchKernelGGL((hmc_fwd_kernel<T, F(), ROW()>), grid_for(batch, 1, kBlock, kMaxBlocks), dim3(kBlock), 0,
+                       (hipStream_t)stream, a);
+    return launched();
+  });
 }
 
 template <typename T, typename P>
@@ -459,9 +431,11 @@ static int hmc_stack_bwd(const P& policy, const T* trace, const byte_t* accept, 
   const HmcBwdArgs<T, P> a{target_of(table, n_comp, family, scale), policy, trace, noise, step, mass, sqm, gout, gld, accept, gin,
                         workspace, batch, sample_tiles(batch), n_layers, steps};
   const bool row = all_aligned({trace, noise, gout, gin}, 2 * sizeof(T));
-  hipStream_t st = (hipStream_t)stream;
-  auto kernel = [&]() -> int { VCNF_STOCH_FAMILY(launch_hmc_bwd, a, groups, row, st) };
-  if (const int rc = kernel()) return rc;
+  const int rc = with_family_row(family, row, [&](auto F, auto ROW) {
+    hipLaunchKernelGGL((hmc_bwd_kernel<T, F(), ROW()>), dim3((unsigned)groups), dim3(kBlock), 0, (hipStream_t)stream, a);
+    return launched();
+  });
+  if (rc) return rc;
   return launch_reduce_partials(workspace, (long long)groups, (long long)n_layers * kTerms, ParamDest<T>{g_step, g_mass, g_sqm},
                                 stream);
 }
@@ -475,8 +449,11 @@ static int mh_walk(const T* z, const T* eps, const T* w, const T* prop, const T*
   if (!all_aligned({z, eps, w, prop, table, out}, sizeof(T))) return VCNF_ERR_ALIGN;
   const MhArgs<T> a{target_of(table, n_comp, family, scale), z, eps, w, prop, out, accept, batch, steps};
   const bool row = all_aligned({z, eps, out}, 2 * sizeof(T));
-  hipStream_t st = (hipStream_t)stream;
-  VCNF_STOCH_FAMILY(launch_mh, a, row, st)
+  return with_family_row(family, row, [&](auto F, auto ROW) {
+    hipLaunchKernelGGL((mh_walk_kernel<T, F(), ROW()>), grid_for(batch, 1, kBlock, kMaxBlocks), dim3(kBlock), 0,
+                       (hipStream_t)stream, a);
+    return launched();
+  });
 }
 
 }  // namespace vcnf_stoch

@@ -1,7 +1,10 @@
-// What the stream kernels share (affine_kernels.hip, class_cond_gaussian.hip, gaussian_mixture.hip, heavy_tail.hip): a
-// group of G <= 64 lanes (a power of two) owns a sample, streams its row in packs of up to 16 bytes and sums with a
-// shuffle butterfly.  Each unit keeps its kernels, argument structs and tuning constants (block sizes, grid caps,
-// packs per lane) in its own namespace; this header holds the scaffolding around them, each piece defined once.
+// What the stream kernels share (affine_kernels.hip, class_cond_gaussian.hip, gaussian_mixture.hip, heavy_tail.hip,
+// mvn_base.hip, planar_radial.hip, target_density.hip, stochastic.hip, vae_ends.hip, periodic.hip): a group of G <= 64
+// lanes (a power of two) owns a sample, streams its row in packs of up to 16 bytes and sums with a shuffle butterfly.
+// Each unit keeps its kernels, argument structs and tuning constants (block sizes, grid caps, packs per lane) in its own
+// namespace; this header holds the scaffolding around them, each piece defined once.  On the host side that is the
+// choice of lanes, pack and grid, and the way from run-time values to a kernel instance: with_pack for the pack width,
+// host_common.hpp's with_flags for booleans and launch_listed for a family code.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -122,8 +125,12 @@ __global__ __launch_bounds__(kRedEl * kRedSl) void reduce_partials_kernel(const 
 // ------------------------------------------------------------------ host side
 using vcnf::aligned;          // host_common.hpp
 using vcnf::all_aligned;
+using vcnf::in_list;
+using vcnf::IntList;
+using vcnf::launch_listed;
 using vcnf::launched;
 using vcnf::ok_ld;
+using vcnf::with_flags;
 
 // lanes per group for n items (elements or packs)
 static inline int pick_lanes(long long n) {
@@ -138,6 +145,17 @@ static inline int pick_pack(int32_t D, std::initializer_list<const void*> bufs) 
   for (int V = 16 / (int)sizeof(T); V > 1; V >>= 1)
     if (D % V == 0 && all_aligned(bufs, V * sizeof(T))) return V;
   return 1;
+}
+
+// launch(std::integral_constant<int, V>{}) for that V, and its status; an 8-byte T has no instance with V = 4
+template <typename T, typename F>
+static inline int with_pack(int32_t D, std::initializer_list<const void*> bufs, F&& launch) {
+  const int V = pick_pack<T>(D, bufs);
+  if constexpr (sizeof(T) == 4) {
+    if (V == 4) return launch(std::integral_constant<int, 4>{});
+  }
+  if (V == 2) return launch(std::integral_constant<int, 2>{});
+  return launch(std::integral_constant<int, 1>{});
 }
 
 // one lane group per item, block / G groups per workgroup, between 1 and max_blocks workgroups

@@ -64,28 +64,6 @@ __global__ __launch_bounds__(kBlock) void target_log_prob_kernel(const T* __rest
 }
 
 // ------------------------------------------------------------------ host side
-template <typename T, int F>
-static int launch(const T* z, const T* table, T* logp, T* score, int64_t batch, int32_t n, T scale, hipStream_t st) {
-  const bool row = all_aligned({z, score}, 2 * sizeof(T));
-  const dim3 grid = grid_for(batch, 1, kBlock, kMaxBlocks);
-#define VCNF_TARGET_LAUNCH(SCORE, ROW)                                                                               \
-  hipLaunchKernelGGL((target_log_prob_kernel<T, F, SCORE, ROW>), grid, dim3(kBlock), 0, st, z, table, logp, score, \
-                     (long long)batch, (int)n, scale)
-  if (score) {
-    if (row)
-      VCNF_TARGET_LAUNCH(true, true);
-    else
-      VCNF_TARGET_LAUNCH(true, false);
-  } else {
-    if (row)
-      VCNF_TARGET_LAUNCH(false, true);
-    else
-      VCNF_TARGET_LAUNCH(false, false);
-  }
-#undef VCNF_TARGET_LAUNCH
-  return launched();
-}
-
 template <typename T>
 static int log_prob(const T* z, const T* table, T* logp, T* score, int64_t batch, int32_t n, int family, T scale,
                     void* stream) {
@@ -95,22 +73,15 @@ static int log_prob(const T* z, const T* table, T* logp, T* score, int64_t batch
   if (batch == 0) return VCNF_OK;
   if (!z || !logp || (has_table(family) && !table)) return VCNF_ERR_NULL;
   if (!all_aligned({z, table, logp, score}, sizeof(T))) return VCNF_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
   if (!has_table(family)) table = nullptr, n = 0;      // ignored by the family: never read
-#define VCNF_TARGET_CASE(F) \
-  case F: return launch<T, F>(z, table, logp, score, batch, n, scale, st)
-  switch (family) {
-    VCNF_TARGET_CASE(VCNF_TARGET_TWO_MOONS);
-    VCNF_TARGET_CASE(VCNF_TARGET_CIRCULAR_GMM);
-    VCNF_TARGET_CASE(VCNF_TARGET_RING_MIXTURE);
-    VCNF_TARGET_CASE(VCNF_TARGET_TWO_MODES);
-    VCNF_TARGET_CASE(VCNF_TARGET_SINUSOIDAL);
-    VCNF_TARGET_CASE(VCNF_TARGET_SINUSOIDAL_GAP);
-    VCNF_TARGET_CASE(VCNF_TARGET_SINUSOIDAL_SPLIT);
-    VCNF_TARGET_CASE(VCNF_TARGET_SMILEY);
-    default: return VCNF_ERR_UNSUPPORTED;              // is_family has refused it
-  }
-#undef VCNF_TARGET_CASE
+  const dim3 grid = grid_for(batch, 1, kBlock, kMaxBlocks);
+  return launch_listed(kFamilies, family, [&](auto F) {
+    return with_flags([&](auto SCORE, auto ROW) {
+      hipLaunchKernelGGL((target_log_prob_kernel<T, F(), SCORE(), ROW()>), grid, dim3(kBlock), 0, (hipStream_t)stream, z,
+                         table, logp, score, (long long)batch, (int)n, scale);
+      return launched();
+    }, score != nullptr, all_aligned({z, score}, 2 * sizeof(T)));
+  });
 }
 
 }  // namespace vcnf_target

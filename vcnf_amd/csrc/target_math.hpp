@@ -186,6 +186,12 @@ __device__ __forceinline__ T density(const T* __restrict__ table, int n, T scale
   }
 }
 
+// the families, stated once: what both units dispatch on, and what is_family knows
+constexpr IntList<VCNF_TARGET_TWO_MOONS, VCNF_TARGET_CIRCULAR_GMM, VCNF_TARGET_RING_MIXTURE, VCNF_TARGET_TWO_MODES,
+                  VCNF_TARGET_SINUSOIDAL, VCNF_TARGET_SINUSOIDAL_GAP, VCNF_TARGET_SINUSOIDAL_SPLIT, VCNF_TARGET_SMILEY>
+    kFamilies{};
+static inline bool is_family(int f) { return in_list(kFamilies, f); }
+
 // the least n_comp of a family - a mixture's components, an energy's constants in `table` - below which a call is a
 // shape error; 0: table and n_comp are ignored; -1: no such family
 static inline int table_min(int f) {
@@ -201,7 +207,6 @@ static inline int table_min(int f) {
     default: return -1;
   }
 }
-static inline bool is_family(int f) { return table_min(f) >= 0; }
 static inline bool has_table(int f) { return table_min(f) > 0; }
 
 }  // namespace vcnf_target

@@ -178,20 +178,10 @@ static int launch_fwd(FwdArgs<T> p, void* stream) {
   const long long blocks = blocks_for(p.N, kBlock / p.G);
   if (!blocks) return VCNF_ERR_SHAPE;
   p.cst = (T)(-0.5 * (double)p.D * kLog2Pi);
-  const int V = pick_pack<T>(p.D, {p.a, p.h, p.z});
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = (hipStream_t)stream;
-  if constexpr (sizeof(T) == 4) {
-    if (V == 4) {
-      hipLaunchKernelGGL((vae_fwd_kernel<T, 4, OP>), grid, block, 0, st, p);
-      return launched();
-    }
-  }
-  if (V == 2)
-    hipLaunchKernelGGL((vae_fwd_kernel<T, 2, OP>), grid, block, 0, st, p);
-  else
-    hipLaunchKernelGGL((vae_fwd_kernel<T, 1, OP>), grid, block, 0, st, p);
-  return launched();
+  return with_pack<T>(p.D, {p.a, p.h, p.z}, [&](auto V) {
+    hipLaunchKernelGGL((vae_fwd_kernel<T, V(), OP>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, p);
+    return launched();
+  });
 }
 
 static inline bool ok_rows(int64_t B, int32_t S, int32_t D) { return B >= 0 && S >= 1 && D >= 1 && B <= INT64_MAX / S; }
@@ -245,12 +235,11 @@ static int gauss_log_prob_bwd(const T* v, const T* h, const T* g, T* d_v, T* d_h
   if (!blocks) return VCNF_ERR_SHAPE;
   if (!all_aligned({v, h, g, d_v, d_h}, sizeof(T))) return VCNF_ERR_ALIGN;
   if (S > VCNF_VAE_MAX_SAMPLES) return VCNF_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  if (v_div > 1)
-    hipLaunchKernelGGL((vae_gauss_bwd_kernel<T, true>), grid, block, 0, (hipStream_t)stream, v, h, g, d_v, d_h, B, S, D);
-  else
-    hipLaunchKernelGGL((vae_gauss_bwd_kernel<T, false>), grid, block, 0, (hipStream_t)stream, v, h, g, d_v, d_h, B, S, D);
-  return launched();
+  return with_flags([&](auto SHARED_V) {
+    hipLaunchKernelGGL((vae_gauss_bwd_kernel<T, SHARED_V()>), dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       v, h, g, d_v, d_h, B, S, D);
+    return launched();
+  }, v_div > 1);
 }
 
 template <typename T>
