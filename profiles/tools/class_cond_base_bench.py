@@ -4,35 +4,22 @@ shapes, and, alternated with them in the same process, of vcnf_diag_gaussian_log
 flattened [B, d] problem of the same size (the yardstick: it reads the same z bytes; the class-conditional kernel reads
 4 B of label per sample more and 2 * 10 * C parameters instead of 2 * d).
 
-Timing: a window is `calls` back-to-back launches between two device events, sized by a calibration pass so that it
-lasts at least --window seconds; time per call = window / calls.  After warm-up the variants of one (shape, dtype) are
-alternated for --reps windows each; the table gives the median, the spread (max - min) / median, the algorithmic bytes
-(what the kernel must move once, from the shapes), GB/s and that as a share of the HBM peak (8.0 TB/s specified; a
-float4 copy measures 6.29 TB/s on this part).  Successive calls rotate over enough input / output buffers to exceed
-the 256 MiB Infinity Cache, so the bytes come from HBM.
+Timing: the protocol of bench_windows.py, the variants of one (shape, dtype) alternated.  Beside the median and the spread
+the table gives the algorithmic bytes (what the kernel must move once, from the shapes), GB/s and that as a share of the
+HBM peak (8.0 TB/s specified; a float4 copy measures 6.29 TB/s on this part).  Successive calls rotate over enough
+input / output buffers to exceed twice the 256 MiB Infinity Cache, so the bytes come from HBM.
 
     python profiles/tools/class_cond_base_bench.py [--batch 16384] [--window 0.3] [--reps 5] [--out FILE]
 """
-import argparse
-import os
-import statistics
-import sys
-
 import torch
 
-sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]
-from vcnf_amd import _lib  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+from vcnf_amd import _lib
 
 _ptr = _lib._ptr
 SHAPES = [(48, 4, 4), (12, 8, 8), (6, 16, 16)]
 NUM_CLASSES = 10
-HBM_PEAK = 8.0e12
-CACHE_BYTES = 512 << 20           # rotate over at least this much input: twice the Infinity Cache
-
-
-def _check(st, what):
-    if st != 0:
-        raise RuntimeError("%s returned status %d" % (what, st))
+_check = bw.checked               # module-level names, as the calls below always had: a launch-bound row is host time
 
 
 def _variants(b, shape, dtype, g):
@@ -41,7 +28,7 @@ def _variants(b, shape, dtype, g):
     d = c * p
     es = 8 if dtype == torch.float64 else 4
     sfx = "_f64" if es == 8 else "_f32"
-    sets = max(2, -(-CACHE_BYTES // (b * d * es)))
+    sets = bw.rotation_sets(b * d * es)
     rnd = lambda *s: torch.randn(*s, device="cuda", dtype=dtype, generator=g)
     zs = [rnd(b, d) for _ in range(sets)]
     outs = [torch.empty(b, d, device="cuda", dtype=dtype) for _ in range(sets)]
@@ -85,16 +72,6 @@ def _variants(b, shape, dtype, g):
     return out
 
 
-def _window(launch, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        launch(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(batch, window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| shape | dtype | kernel | us per call | spread | bytes | GB/s | share of 8.0 TB/s |",
@@ -103,36 +80,24 @@ def run(batch, window, reps, out):
     for shape in SHAPES:
         for dtype in (torch.float32, torch.float64):
             variants = _variants(batch, shape, dtype, g)
-            calls = {}
-            for name, (launch, _) in variants.items():      # warm-up, then size the window
-                _window(launch, 20)
-                calls[name] = max(20, int(window / _window(launch, 200)) + 1)
-            times = {name: [] for name in variants}
-            for _ in range(reps):
-                for name, (launch, _) in variants.items():
-                    times[name].append(_window(launch, calls[name]))
+            results, failed = bw.measure({name: v[0] for name, v in variants.items()}, window, reps)
             for name, (_, nbytes) in variants.items():
-                med = statistics.median(times[name])
-                spread = (max(times[name]) - min(times[name])) / med
-                lines.append("| %s | %s | %s | %.2f | %.3f | %d | %.0f | %.1f %% |" % (
-                    "x".join(map(str, shape)), "fp64" if dtype == torch.float64 else "fp32", name, med * 1e6, spread,
-                    nbytes, nbytes / med / 1e9, 100.0 * nbytes / med / HBM_PEAK))
+                lead = "| %s | %s | %s |" % ("x".join(map(str, shape)), bw.dtype_name(dtype), name)
+                if name in failed:
+                    lines.append("%s failed: %s | | | | |" % (lead, failed[name]))
+                else:
+                    med, spread, _ = results[name]
+                    lines.append("%s %.2f | %.3f | %d | %.0f | %.1f %% |" % (
+                        lead, med * 1e6, spread, nbytes, nbytes / med / 1e9, 100.0 * nbytes / med / bw.HBM_PEAK))
                 print(lines[-1], flush=True)
             del variants
             torch.cuda.empty_cache()
-    text = "B = %d, hard labels, %d classes, windows of >= %.2f s, %d alternated windows per kernel\n\n%s\n" % (
-        batch, NUM_CLASSES, window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out, "B = %d, hard labels, %d classes, windows of >= %.2f s, %d alternated windows "
+                     "per kernel" % (batch, NUM_CLASSES, window, reps))
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.3)
     ap.add_argument("--batch", type=int, default=16384)
-    ap.add_argument("--window", type=float, default=0.3)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     run(a.batch, a.window, a.reps, a.out)

@@ -14,22 +14,18 @@ Smiley(0.2) in fp32:
       launch, the same layers one by one (one launch each), and the layers' torch composition against the restatement.
   (d) HAIS.sample(1024) at 10 betas: the sampler on the module, and on the restatement with a plain-torch walk.
 
-Timing as in target_density_bench.py, whose windows these are.
+Timing: the protocol of bench_windows.py, the variants of one row group alternated; the row forms are
+target_density_bench.py's.
 
     python profiles/tools/energy_targets_bench.py [--window 0.2] [--reps 5] [--out FILE]
 """
-import argparse
-import os
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.dirname(os.path.abspath(__file__))]
-import energy_ref as eref  # noqa: E402
-import target_density_bench as tdb  # noqa: E402
-import vcnf_amd as nf  # noqa: E402
-from vcnf_amd import _lib, fused_stochastic  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import energy_ref as eref
+import target_density_bench as tdb
+import vcnf_amd as nf
+from vcnf_amd import _lib, fused_stochastic
 
 CASES = eref.FAMILIES
 BATCHES = (1024, 1 << 20)
@@ -50,18 +46,7 @@ def part_a(window, reps, lines):
               "| density | B | score | us per call | spread | GB/s | of 8 TB/s |", "|---|---|---|---|---|---|---|"]
     for case in CASES:
         for b in BATCHES:
-            calls = kernel_calls(case, b)
-            res = tdb._measure({("with" if w else "without"): c for w, c in calls.items()}, window, reps)
-            for name, (t, spread) in res.items():
-                rate = b * (20 if name == "with" else 12) / t
-                lines.append("| %s | %d | %s | %.1f | %.3f | %.1f | %.3f |" % (eref.case_id(case), b, name, t * 1e6, spread, rate * 1e-9, rate / tdb.PEAK))
-                print(lines[-1], flush=True)
-
-
-def _rows(res, base, case, lines):
-    for name, (t, spread) in res.items():
-        lines.append("| %s | %s | %.1f | %.3f | %.2f |" % (eref.case_id(case), name, t * 1e6, spread, t / res[base][0]))
-        print(lines[-1], flush=True)
+            tdb.kernel_rows(eref.case_id(case), b, kernel_calls(case, b), window, reps, lines)
 
 
 def part_b(window, reps, lines):
@@ -74,9 +59,9 @@ def part_b(window, reps, lines):
                 x = z.detach().requires_grad_(True)
                 torch.autograd.grad(p.log_prob(x).sum(), x)
             return call
-        res = tdb._measure({"module (one launch + one multiply)": fwd_bwd(eref.prior_of(case)),
-                            "torch restatement": fwd_bwd(eref.PlainEnergy(case))}, window, reps)
-        _rows(res, "module (one launch + one multiply)", case, lines)
+        tdb.ratio_rows(eref.case_id(case), {"module (one launch + one multiply)": fwd_bwd(eref.prior_of(case)),
+                                            "torch restatement": fwd_bwd(eref.PlainEnergy(case))},
+                       "module (one launch + one multiply)", window, reps, lines)
 
 
 def hmc_flows(target):
@@ -107,9 +92,8 @@ def part_c(window, reps, lines):
                             (out.sum() + ld.sum()).backward()
                 return call
             kernel, plain = hmc_flows(eref.prior_of(case)), hmc_flows(eref.PlainEnergy(case))
-            res = tdb._measure({"one launch": walk(kernel, True), "layer by layer": walk(kernel, False),
-                                "torch composition": walk(plain, False)}, window, reps)
-            _rows(res, "one launch", case, lines)
+            tdb.ratio_rows(eref.case_id(case), {"one launch": walk(kernel, True), "layer by layer": walk(kernel, False),
+                                                "torch composition": walk(plain, False)}, "one launch", window, reps, lines)
 
 
 def part_d(window, reps, lines):
@@ -126,9 +110,8 @@ def part_d(window, reps, lines):
                 with torch.no_grad():
                     s.sample(1024)
             return call
-        res = tdb._measure({"one launch": sampler(eref.prior_of(case)), "layer by layer": sampler(eref.prior_of(case), False),
-                            "torch composition": sampler(eref.PlainEnergy(case))}, window, reps)
-        _rows(res, "one launch", case, lines)
+        tdb.ratio_rows(eref.case_id(case), {"one launch": sampler(eref.prior_of(case)), "layer by layer": sampler(eref.prior_of(case), False),
+                                            "torch composition": sampler(eref.PlainEnergy(case))}, "one launch", window, reps, lines)
 
 
 def launches(count=200):
@@ -144,21 +127,14 @@ def launches(count=200):
 def run(window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     torch.manual_seed(17)
-    lines = ["windows of >= %.2f s, %d alternated windows per variant" % (window, reps)]
+    lines = []
     for part in (part_a, part_b, part_c, part_d):
         part(window, reps, lines)
-    text = "\n".join(lines) + "\n"
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines[1:], window, reps, out)         # every part leads with a blank line; the header brings its own
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--window", type=float, default=0.2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
+    ap = bw.parser(0.2)
     ap.add_argument("--launches", action="store_true", help="only launch the kernels (to be traced)")
     ap.add_argument("--parse-trace", default=None, metavar="DIR")
     a = ap.parse_args()

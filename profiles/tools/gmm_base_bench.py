@@ -4,33 +4,23 @@ the same process, of the plain-torch form (the only other way the library could 
 (modes, features) = (1, 64), (8, 2), (16, 64), (64, 30) and B = 16 384 and 1 048 576.  For one mode the existing
 vcnf_diag_gaussian_log_prob_f32 on the same rows is a second yardstick.
 
-Timing: a window is `calls` back-to-back calls between two device events, sized by a calibration pass so that it lasts
-at least --window seconds; time per call = window / calls (launches included).  After warm-up the variants of one
-(batch, shape, dtype) are alternated for --reps windows each; the table gives the median, the spread (max - min) /
-median, the algorithmic bytes of the kernels (what must move once, from the shapes) and GB/s.  Successive calls rotate
-over enough input / output buffers to exceed 512 MiB (twice the Infinity Cache), so the rows come from HBM.
+Timing: the protocol of bench_windows.py, the variants of one (batch, shape, dtype) alternated.  Beside the median and
+the spread the table gives the algorithmic bytes of the kernels (what must move once, from the shapes) and GB/s.
+Successive calls rotate over enough input / output buffers to exceed 512 MiB (twice the Infinity Cache), so the rows
+come from HBM.
 
     python profiles/tools/gmm_base_bench.py [--batches 16384,1048576] [--window 0.2] [--reps 5] [--out FILE]
 """
-import argparse
 import math
-import os
-import statistics
-import sys
 
 import torch
 
-sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]
-from vcnf_amd import _lib  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+from vcnf_amd import _lib
 
 _ptr = _lib._ptr
 SHAPES = [(1, 64), (8, 2), (16, 64), (64, 30)]
-CACHE_BYTES = 512 << 20           # rotate over at least this much input: twice the Infinity Cache
-
-
-def _check(st, what):
-    if st != 0:
-        raise RuntimeError("%s returned status %d" % (what, st))
+_check = bw.checked               # module-level names, as the calls below always had: a launch-bound row is host time
 
 
 def eager_log_prob(z, loc, ls, ws):
@@ -44,7 +34,7 @@ def _variants(b, m, d, dtype, g):
     """name -> (call(i), algorithmic bytes or None); call(i) uses buffer set i % sets."""
     es = 8 if dtype == torch.float64 else 4
     sfx = "_f64" if es == 8 else "_f32"
-    sets = max(2, -(-CACHE_BYTES // (b * d * es)))
+    sets = bw.rotation_sets(b * d * es)
     rnd = lambda *s: torch.randn(*s, device="cuda", dtype=dtype, generator=g)
     loc, ls, ws = 2.0 * rnd(1, m, d), 0.3 * rnd(1, m, d), rnd(1, m)
     log_w = torch.log_softmax(ws, 1)[0].contiguous()
@@ -120,16 +110,6 @@ def _variants(b, m, d, dtype, g):
     return out
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(batches, window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| B | (M, D) | dtype | variant | us per call | spread | bytes | GB/s |", "|---|---|---|---|---|---|---|---|"]
@@ -138,45 +118,24 @@ def run(batches, window, reps, out):
         for m, d in SHAPES:
             for dtype in (torch.float32, torch.float64):
                 variants = _variants(b, m, d, dtype, g)
-                calls, times = {}, {}
-                for name, (call, _) in list(variants.items()):      # warm-up, then size the window
-                    try:
-                        _window(call, 3)
-                        t = _window(call, 5)
-                        if t * 50 < window:
-                            t = _window(call, 50)
-                        calls[name] = max(3, int(window / t) + 1)
-                        times[name] = []
-                    except torch.cuda.OutOfMemoryError:
-                        del variants[name]
-                        torch.cuda.empty_cache()
-                        lines.append("| %d | (%d, %d) | %s | %s | out of memory | | | |" % (
-                            b, m, d, "fp64" if dtype == torch.float64 else "fp32", name))
-                        print(lines[-1], flush=True)
-                for _ in range(reps):
-                    for name, (call, _) in variants.items():
-                        times[name].append(_window(call, calls[name]))
+                results, failed = bw.measure({name: v[0] for name, v in variants.items()}, window, reps)
                 for name, (_, nbytes) in variants.items():
-                    med = statistics.median(times[name])
-                    spread = (max(times[name]) - min(times[name])) / med
-                    lines.append("| %d | (%d, %d) | %s | %s | %.2f | %.3f | %s | %s |" % (
-                        b, m, d, "fp64" if dtype == torch.float64 else "fp32", name, med * 1e6, spread,
-                        "" if nbytes is None else "%d" % nbytes, "" if nbytes is None else "%.0f" % (nbytes / med / 1e9)))
+                    lead = "| %d | (%d, %d) | %s | %s |" % (b, m, d, bw.dtype_name(dtype), name)
+                    if name in failed:
+                        lines.append("%s failed: %s | | | |" % (lead, failed[name]))
+                    else:
+                        med, spread, _ = results[name]
+                        lines.append("%s %.2f | %.3f | %s | %s |" % (
+                            lead, med * 1e6, spread, "" if nbytes is None else "%d" % nbytes,
+                            "" if nbytes is None else "%.0f" % (nbytes / med / 1e9)))
                     print(lines[-1], flush=True)
                 del variants
                 torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.2)
     ap.add_argument("--batches", default="16384,1048576")
-    ap.add_argument("--window", type=float, default=0.2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     run([int(v) for v in a.batches.split(",")], a.window, a.reps, a.out)

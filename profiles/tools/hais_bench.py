@@ -7,25 +7,16 @@ layer, and one of csrc/target_density.hip for the last term) and the torch compo
 ``reverse_kld`` step of a NormalizingFlow whose flows are the chain's layers (the run is one autograd node), against the
 same model with ``fuse_stochastic_stacks = False`` and on the torch composition.
 
-Timing: a window is `calls` back-to-back calls between two device events, sized by a calibration pass so that it lasts
-at least --window seconds; time per call = window / calls (launches included).  After warm-up the variants of one
-(shape, dtype, target) are alternated for --reps windows each; the table gives the median and the spread (max - min) /
-median.
+Timing: the protocol of bench_windows.py, the variants of one (shape, dtype, target) alternated.
 
     python profiles/tools/hais_bench.py [--shapes 1024x10,1024x100,16384x20] [--targets two_moons] [--window 0.15] [--reps 5] [--out FILE]
 """
-import argparse
-import os
-import statistics
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import vcnf_amd as nf  # noqa: E402
-import stochastic_ref as sref  # noqa: E402
-from vcnf_amd import fused_stochastic  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import stochastic_ref as sref
+import vcnf_amd as nf
+from vcnf_amd import fused_stochastic
 
 TARGETS = {"two_moons": (lambda: nf.distributions.TwoMoons(), 0), "circular": (lambda: nf.distributions.CircularGaussianMixture(8), 8),
            "ring": (lambda: nf.distributions.RingMixture(2), 2)}
@@ -79,16 +70,6 @@ def _variants(num, m, name, dtype):
     return out
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(shapes, targets, window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| N | M | dtype | target | variant | us per call | spread | x one launch per chain |", "|---|---|---|---|---|---|---|---|"]
@@ -97,37 +78,24 @@ def run(shapes, targets, window, reps, out):
         for dtype in (torch.float32, torch.float64):
             for name in targets:
                 variants = _variants(num, m, name, dtype)
-                calls, times = {}, {}
-                for v, call in variants.items():                # warm-up, then size the window
-                    _window(call, 1)
-                    t = _window(call, 2)
-                    calls[v] = max(2, int(window / t) + 1)
-                    times[v] = []
-                for _ in range(reps):
-                    for v, call in variants.items():
-                        times[v].append(_window(call, calls[v]))
-                med = {v: statistics.median(times[v]) for v in variants}
+                results, failed = bw.measure(variants, window, reps)
                 for v in variants:
-                    base = med[v.split(",")[0] + ", one launch per chain"]
-                    spread = (max(times[v]) - min(times[v])) / med[v]
-                    lines.append("| %d | %d | %s | %s | %s | %.1f | %.3f | %.2f |" % (
-                        num, m, "fp64" if dtype == torch.float64 else "fp32", name, v, med[v] * 1e6, spread, med[v] / base))
+                    lead = "| %d | %d | %s | %s | %s |" % (num, m, bw.dtype_name(dtype), name, v)
+                    base = results.get(v.split(",")[0] + ", one launch per chain")
+                    if v in failed:
+                        lines.append("%s failed: %s | | |" % (lead, failed[v]))
+                    else:
+                        med, spread, _ = results[v]
+                        lines.append("%s %.1f | %.3f | %s |" % (lead, med * 1e6, spread, "%.2f" % (med / base.median) if base else ""))
                     print(lines[-1], flush=True)
                 del variants
                 torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.15)
     ap.add_argument("--shapes", default="1024x10,1024x100,16384x20")
     ap.add_argument("--targets", default="two_moons")
-    ap.add_argument("--window", type=float, default=0.15)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     run([tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")], a.targets.split(","), a.window, a.reps, a.out)

@@ -5,44 +5,29 @@ from_noise with both draws given, and log_prob forward plus backward (loss = sum
 parameters).  The module-level calls are what a training loop pays, Python included; the vcnf_tail_* entry points are
 also called directly, and those rows carry the algorithmic bytes (what must move once, from the shapes) and GB/s.
 
-Timing: a window is `calls` back-to-back calls between two device events, sized by a calibration pass so that it lasts
-at least --window seconds; time per call = window / calls (launches included).  After warm-up the variants of one
-(batch, dtype, family) are alternated for --reps windows each; the table gives the median and the spread (max - min) /
-median.  Successive calls rotate over enough input / output buffers to exceed 512 MiB (twice the Infinity Cache), so
-the rows come from HBM.
+Timing: the protocol of bench_windows.py, the variants of one (batch, dtype, family) alternated.  Successive calls rotate
+over enough input / output buffers to exceed 512 MiB (twice the Infinity Cache), so the rows come from HBM.
 
     python profiles/tools/heavy_tail_bench.py [--batches 2048,1048576] [--window 0.2] [--reps 5] [--out FILE]
 """
-import argparse
-import os
-import statistics
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import heavy_tail_ref as ref  # noqa: E402
-import vcnf_amd as nf  # noqa: E402
-from vcnf_amd import _lib  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import heavy_tail_ref as ref
+import vcnf_amd as nf
+from vcnf_amd import _lib
 
 _ptr = _lib._ptr
 D = 64
-CACHE_BYTES = 512 << 20           # rotate over at least this much input: twice the Infinity Cache
 CLASSES = {"student_t": "StudentT", "gen_gaussian": "GeneralizedGaussian"}
-HBM_PEAK = 8e12
-
-
-def _check(st, what):
-    if st != 0:
-        raise RuntimeError("%s returned status %d" % (what, st))
+_check = bw.checked               # module-level names, as the calls below always had: a launch-bound row is host time
 
 
 def _variants(b, family, dtype, g):
     """name -> (call(i), algorithmic bytes or None); call(i) uses buffer set i % sets."""
     es = 8 if dtype == torch.float64 else 4
     sfx = "_f64" if es == 8 else "_f32"
-    sets = max(2, -(-CACHE_BYTES // (b * D * es)))
+    sets = bw.rotation_sets(b * D * es)
     rnd = lambda *s: torch.randn(*s, device="cuda", dtype=dtype, generator=g)
     q = getattr(nf.distributions, CLASSES[family])(D).to(dtype).cuda()
     with torch.no_grad():
@@ -138,16 +123,6 @@ def _variants(b, family, dtype, g):
             "DiagGaussian log_prob forward + backward": (module_fwd_bwd(dg), None)}
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(batches, window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| B | dtype | family | variant | us per call | spread | bytes | GB/s | of 8 TB/s |", "|---|---|---|---|---|---|---|---|---|"]
@@ -157,39 +132,25 @@ def run(batches, window, reps, out):
         for dtype in (torch.float32, torch.float64):
             for family in ref.FAMILIES:
                 variants = _variants(b, family, dtype, g)
-                calls, times = {}, {}
-                for name, (call, _) in variants.items():             # warm-up, then size the window
-                    _window(call, 3)
-                    t = _window(call, 5)
-                    if t * 50 < window:
-                        t = _window(call, 50)
-                    calls[name] = max(3, int(window / t) + 1)
-                    times[name] = []
-                for _ in range(reps):
-                    for name, (call, _) in variants.items():
-                        times[name].append(_window(call, calls[name]))
+                results, failed = bw.measure({name: v[0] for name, v in variants.items()}, window, reps)
                 for name, (_, nbytes) in variants.items():
-                    med = statistics.median(times[name])
-                    spread = (max(times[name]) - min(times[name])) / med
-                    lines.append("| %d | %s | %s | %s | %.2f | %.3f | %s | %s | %s |" % (
-                        b, "fp64" if dtype == torch.float64 else "fp32", family, name, med * 1e6, spread,
-                        "" if nbytes is None else "%d" % nbytes, "" if nbytes is None else "%.0f" % (nbytes / med / 1e9),
-                        "" if nbytes is None else "%.2f" % (nbytes / med / HBM_PEAK)))
+                    lead = "| %d | %s | %s | %s |" % (b, bw.dtype_name(dtype), family, name)
+                    if name in failed:
+                        lines.append("%s failed: %s | | | | |" % (lead, failed[name]))
+                    else:
+                        med, spread, _ = results[name]
+                        lines.append("%s %.2f | %.3f | %s | %s | %s |" % (
+                            lead, med * 1e6, spread, "" if nbytes is None else "%d" % nbytes,
+                            "" if nbytes is None else "%.0f" % (nbytes / med / 1e9),
+                            "" if nbytes is None else "%.2f" % (nbytes / med / bw.HBM_PEAK)))
                     print(lines[-1], flush=True)
                 del variants
                 torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.2)
     ap.add_argument("--batches", default="2048,1048576")
-    ap.add_argument("--window", type=float, default=0.2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     run([int(v) for v in a.batches.split(",")], a.window, a.reps, a.out)

@@ -7,43 +7,29 @@ module-level calls are what a training loop pays, Python and the D x D solve inc
 also called directly, and those rows carry the algorithmic bytes (what must move once, from the shapes), GB/s, and the
 multiply-adds of the triangular products (D (D + 1) / 2 per sample and product) as GFMA/s.
 
-Timing: a window is `calls` back-to-back calls between two device events, sized by a calibration pass so that it lasts
-at least --window seconds; time per call = window / calls (launches included).  After warm-up the variants of one
-(shape, dtype, family) are alternated for --reps windows each; the table gives the median and the spread (max - min) /
-median.  Successive calls rotate over enough input / output buffers to exceed 512 MiB (twice the Infinity Cache), so
-the rows come from HBM.
+Timing: the protocol of bench_windows.py, the variants of one (shape, dtype, family) alternated; a variant the libraries
+cannot run at a shape (the torch composition's solve at the largest) gets its `failed:` row.  Successive calls rotate
+over enough input / output buffers to exceed 512 MiB (twice the Infinity Cache), so the rows come from HBM.
 
     python profiles/tools/mvn_bench.py [--shapes 2048x16,1048576x64,1048576x128] [--window 0.2] [--reps 5] [--out FILE]
 """
-import argparse
-import os
-import statistics
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import mvn_ref as ref  # noqa: E402
-import vcnf_amd as nf  # noqa: E402
-from vcnf_amd import _lib  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import mvn_ref as ref
+import vcnf_amd as nf
+from vcnf_amd import _lib
 
 _ptr = _lib._ptr
-CACHE_BYTES = 512 << 20           # rotate over at least this much input: twice the Infinity Cache
 CLASSES = {"gaussian": "MultivariateGaussian", "student_t": "MultivariateStudentT"}
-HBM_PEAK = 8e12
-
-
-def _check(st, what):
-    if st != 0:
-        raise RuntimeError("%s returned status %d" % (what, st))
+_check = bw.checked               # module-level names, as the calls below always had: a launch-bound row is host time
 
 
 def _variants(b, d, family, dtype):
     """name -> (call(i), algorithmic bytes or None, triangular products per sample); call(i) uses buffer set i % sets."""
     es = 8 if dtype == torch.float64 else 4
     sfx = "_f64" if es == 8 else "_f32"
-    sets = max(2, -(-CACHE_BYTES // (b * d * es)))
+    sets = bw.rotation_sets(b * d * es)
     p = ref.cast(ref.inputs(family, d, 8)[0], dtype)
     q = getattr(nf.distributions, CLASSES[family])(d).to(dtype)
     q.load_state_dict(p)
@@ -125,16 +111,6 @@ def _variants(b, d, family, dtype):
             "torch composition log_prob forward + backward": (eager_fwd_bwd, None, 0)}
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(shapes, window, reps, out, dtypes=(torch.float32, torch.float64)):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| B | D | dtype | family | variant | us per call | spread | bytes | GB/s | of 8 TB/s | GFMA/s |",
@@ -144,52 +120,28 @@ def run(shapes, window, reps, out, dtypes=(torch.float32, torch.float64)):
         for dtype in dtypes:
             for family in ref.FAMILIES:
                 variants = _variants(b, d, family, dtype)
-                calls, times, failed = {}, {}, {}
-                for name, (call, _, _) in variants.items():          # warm-up, then size the window
-                    try:
-                        _window(call, 3)
-                        t = _window(call, 5)
-                        if t * 50 < window:
-                            t = _window(call, 50)
-                    except RuntimeError as e:                        # a variant the libraries cannot run at this shape
-                        failed[name] = str(e).splitlines()[0][:120]
-                        continue
-                    calls[name] = max(3, int(window / t) + 1)
-                    times[name] = []
-                for _ in range(reps):
-                    for name, (call, _, _) in variants.items():
-                        if name not in failed:
-                            times[name].append(_window(call, calls[name]))
+                results, failed = bw.measure({name: v[0] for name, v in variants.items()}, window, reps)
                 for name, (_, nbytes, products) in variants.items():
+                    lead = "| %d | %d | %s | %s | %s |" % (b, d, bw.dtype_name(dtype), family, name)
                     if name in failed:
-                        lines.append("| %d | %d | %s | %s | %s | failed: %s | | | | | |" % (
-                            b, d, "fp64" if dtype == torch.float64 else "fp32", family, name, failed[name]))
-                        print(lines[-1], flush=True)
-                        continue
-                    med = statistics.median(times[name])
-                    spread = (max(times[name]) - min(times[name])) / med
-                    lines.append("| %d | %d | %s | %s | %s | %.2f | %.3f | %s | %s | %s | %s |" % (
-                        b, d, "fp64" if dtype == torch.float64 else "fp32", family, name, med * 1e6, spread,
-                        "" if nbytes is None else "%d" % nbytes, "" if nbytes is None else "%.0f" % (nbytes / med / 1e9),
-                        "" if nbytes is None else "%.3f" % (nbytes / med / HBM_PEAK),
-                        "" if not products else "%.0f" % (products * b * d * (d + 1) / 2 / med / 1e9)))
+                        lines.append("%s failed: %s | | | | | |" % (lead, failed[name]))
+                    else:
+                        med, spread, _ = results[name]
+                        lines.append("%s %.2f | %.3f | %s | %s | %s | %s |" % (
+                            lead, med * 1e6, spread, "" if nbytes is None else "%d" % nbytes,
+                            "" if nbytes is None else "%.0f" % (nbytes / med / 1e9),
+                            "" if nbytes is None else "%.3f" % (nbytes / med / bw.HBM_PEAK),
+                            "" if not products else "%.0f" % (products * b * d * (d + 1) / 2 / med / 1e9)))
                     print(lines[-1], flush=True)
                 del variants
                 torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.2)
     ap.add_argument("--shapes", default="2048x16,1048576x64,1048576x128")
-    ap.add_argument("--window", type=float, default=0.2)
-    ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--dtypes", default="fp32,fp64")
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     kinds = {"fp32": torch.float32, "fp64": torch.float64}
     run([tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")], a.window, a.reps, a.out,

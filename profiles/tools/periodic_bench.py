@@ -12,27 +12,19 @@ tensors).  Per dtype:
   Its bytes (every element read once and written once; read once for the density) over that time are given as a share
   of the 8 TB/s peak.
 
-Everything is eager, Python included, under no_grad.  Timing: a window is `calls` back-to-back calls between two device
-events, sized by a calibration pass so that it lasts at least --window seconds; after warm-up the variants of one group
-are alternated for --reps windows each; the table gives the median and the spread (max - min) / median.
+Everything is eager, Python included, under no_grad.  Timing: the protocol of bench_windows.py, the variants of one
+group alternated.
 
     python profiles/tools/periodic_bench.py [--window 0.2] [--reps 5] [--out FILE]
 """
-import argparse
 import math
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import periodic_ref as ref  # noqa: E402
-import vcnf_amd as nf  # noqa: E402
-from vcnf_amd import _lib  # noqa: E402
-
-PEAK = 8e12             # bytes / s
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import periodic_ref as ref
+import vcnf_amd as nf
+from vcnf_amd import _lib
 
 
 def _layer_groups(b, d, dtype):
@@ -78,16 +70,6 @@ def _model_group(b, dtype):
                                                 "torch restatement": lambda i: other.log_prob(x)}, None)}
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| B | D | dtype | call | variant | us per call | spread | x the kernel path | share of 8 TB/s |", "|---|---|---|---|---|---|---|---|---|"]
@@ -97,36 +79,23 @@ def run(window, reps, out):
             for b, d in ((1024, 3), (1 << 20, 64), (1024, 0)):
                 groups = _layer_groups(b, d, dtype) if d else _model_group(b, dtype)
                 for group, (variants, nbytes) in groups.items():
-                    calls, times = {}, {}
-                    for name, call in variants.items():             # warm-up, then size the window
-                        _window(call, 3)
-                        t = _window(call, 5)
-                        calls[name] = max(3, int(window / t) + 1)
-                        times[name] = []
-                    for _ in range(reps):
-                        for name, call in variants.items():
-                            times[name].append(_window(call, calls[name]))
-                    med = {name: statistics.median(times[name]) for name in variants}
+                    results, failed = bw.measure(variants, window, reps)
                     for name in variants:
-                        spread = (max(times[name]) - min(times[name])) / med[name]
-                        share = "%.1f %%" % (100 * nbytes / med[name] / PEAK) if nbytes else ""
-                        lines.append("| %d | %d | %s | %s | %s | %.1f | %.3f | %.2f | %s |" % (
-                            b, d or 3, "fp64" if dtype == torch.float64 else "fp32", group, name, med[name] * 1e6, spread,
-                            med[name] / med["kernel"], share))
+                        lead = "| %d | %d | %s | %s | %s |" % (b, d or 3, bw.dtype_name(dtype), group, name)
+                        base = results.get("kernel")
+                        if name in failed:
+                            lines.append("%s failed: %s | | | |" % (lead, failed[name]))
+                        else:
+                            med, spread, _ = results[name]
+                            lines.append("%s %.1f | %.3f | %s | %s |" % (
+                                lead, med * 1e6, spread, "%.2f" % (med / base.median) if base else "",
+                                "%.1f %%" % (100 * nbytes / med / bw.HBM_PEAK) if nbytes else ""))
                         print(lines[-1], flush=True)
                 del groups
                 torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--window", type=float, default=0.2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = bw.parser(0.2).parse_args()
     run(a.window, a.reps, a.out)

@@ -6,24 +6,15 @@ plain-torch restatement of the same arithmetic (tests/planar_radial_ref.py, run 
 (the model's ``reverse_kld``; the restatement's loss at a draw of its own).  The calls are what a training loop pays,
 Python included.
 
-Timing: a window is `calls` back-to-back calls between two device events, sized by a calibration pass so that it lasts
-at least --window seconds; time per call = window / calls (launches included).  After warm-up the variants of one
-(shape, dtype, stack) are alternated for --reps windows each; the table gives the median and the spread (max - min) /
-median.
+Timing: the protocol of bench_windows.py, the variants of one (shape, dtype, stack) alternated.
 
     python profiles/tools/planar_radial_bench.py [--shapes 1024x2x32,2048x16x64] [--window 0.2] [--reps 5] [--out FILE]
 """
-import argparse
-import os
-import statistics
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import planar_radial_ref as ref  # noqa: E402
-import vcnf_amd as nf  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import planar_radial_ref as ref
+import vcnf_amd as nf
 
 
 def _model(layers, d, dtype):
@@ -81,16 +72,6 @@ def _variants(b, d, k, stack, dtype):
             "reverse_kld forward + backward, torch restatement": eager_reverse_kld}
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(shapes, window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| B | D | K | dtype | stack | variant | us per call | spread | x the run |", "|---|---|---|---|---|---|---|---|---|"]
@@ -99,36 +80,23 @@ def run(shapes, window, reps, out):
         for dtype in (torch.float32, torch.float64):
             for stack in ("tanh", "radial"):
                 variants = _variants(b, d, k, stack, dtype)
-                calls, times = {}, {}
-                for name, call in variants.items():             # warm-up, then size the window
-                    _window(call, 3)
-                    t = _window(call, 5)
-                    calls[name] = max(3, int(window / t) + 1)
-                    times[name] = []
-                for _ in range(reps):
-                    for name, call in variants.items():
-                        times[name].append(_window(call, calls[name]))
-                med = {name: statistics.median(times[name]) for name in variants}
+                results, failed = bw.measure(variants, window, reps)
                 for name in variants:
-                    base = med[[n for n in variants if n.split(",")[0].lower() == name.split(",")[0].lower()][0]]
-                    spread = (max(times[name]) - min(times[name])) / med[name]
-                    lines.append("| %d | %d | %d | %s | %s | %s | %.1f | %.3f | %.2f |" % (
-                        b, d, k, "fp64" if dtype == torch.float64 else "fp32", stack, name, med[name] * 1e6, spread, med[name] / base))
+                    lead = "| %d | %d | %d | %s | %s | %s |" % (b, d, k, bw.dtype_name(dtype), stack, name)
+                    base = results.get([n for n in variants if n.split(",")[0].lower() == name.split(",")[0].lower()][0])
+                    if name in failed:
+                        lines.append("%s failed: %s | | |" % (lead, failed[name]))
+                    else:
+                        med, spread, _ = results[name]
+                        lines.append("%s %.1f | %.3f | %s |" % (lead, med * 1e6, spread, "%.2f" % (med / base.median) if base else ""))
                     print(lines[-1], flush=True)
                 del variants
                 torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.2)
     ap.add_argument("--shapes", default="1024x2x32,2048x16x64")
-    ap.add_argument("--window", type=float, default=0.2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     run([tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")], a.window, a.reps, a.out)

@@ -7,25 +7,17 @@ score is an ``autograd.grad`` through one launch of csrc/target_density.hip.  Sh
 forward pass without autograd, and forward + backward of ``log_det.sum() + z.sum()``.  The calls are what a training loop
 pays, Python and the draws included.
 
-Timing: a window is `calls` back-to-back calls between two device events, sized by a calibration pass so that it lasts
-at least --window seconds; time per call = window / calls (launches included).  After warm-up the variants of one
-(shape, dtype, target) are alternated for --reps windows each; the table gives the median and the spread (max - min) /
-median.
+Timing: the protocol of bench_windows.py, the variants of one (shape, dtype, target) alternated.
 
     python profiles/tools/stochastic_bench.py [--shapes 1024x1x5,1024x8x5,2048x32x10] [--window 0.15] [--reps 5] [--out FILE]
 """
-import argparse
 import math
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT]
-import vcnf_amd as nf  # noqa: E402
-from vcnf_amd import fused_stochastic  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import vcnf_amd as nf
+from vcnf_amd import fused_stochastic
 
 TARGETS = {"TwoMoons": lambda: nf.distributions.TwoMoons(), "CircularGaussianMixture": lambda: nf.distributions.CircularGaussianMixture(),
            "RingMixture": lambda: nf.distributions.RingMixture()}
@@ -94,16 +86,6 @@ def _variants(b, k, steps, name, dtype):
             "forward + backward, torch path": both(one_by_one(torch_path), torch_path)}
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def run(shapes, window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     lines = ["| B | K | steps | dtype | target | variant | us per call | spread | x the run |", "|---|---|---|---|---|---|---|---|---|"]
@@ -115,36 +97,23 @@ def run(shapes, window, reps, out):
                 continue
             for name in TARGETS:
                 variants = _variants(b, k, steps, name, dtype)
-                calls, times = {}, {}
-                for v, call in variants.items():                # warm-up, then size the window
-                    _window(call, 2)
-                    t = _window(call, 3)
-                    calls[v] = max(2, int(window / t) + 1)
-                    times[v] = []
-                for _ in range(reps):
-                    for v, call in variants.items():
-                        times[v].append(_window(call, calls[v]))
-                med = {v: statistics.median(times[v]) for v in variants}
+                results, failed = bw.measure(variants, window, reps)
                 for v in variants:
-                    base = med[v.split(",")[0] + ", one launch per run"]
-                    spread = (max(times[v]) - min(times[v])) / med[v]
-                    lines.append("| %d | %d | %d | %s | %s | %s | %.1f | %.3f | %.2f |" % (
-                        b, k, steps, "fp64" if dtype == torch.float64 else "fp32", name, v, med[v] * 1e6, spread, med[v] / base))
+                    lead = "| %d | %d | %d | %s | %s | %s |" % (b, k, steps, bw.dtype_name(dtype), name, v)
+                    base = results.get(v.split(",")[0] + ", one launch per run")
+                    if v in failed:
+                        lines.append("%s failed: %s | | |" % (lead, failed[v]))
+                    else:
+                        med, spread, _ = results[v]
+                        lines.append("%s %.1f | %.3f | %s |" % (lead, med * 1e6, spread, "%.2f" % (med / base.median) if base else ""))
                     print(lines[-1], flush=True)
                 del variants
                 torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.15)
     ap.add_argument("--shapes", default="1024x1x5,1024x8x5,2048x32x10")
-    ap.add_argument("--window", type=float, default=0.15)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     run([tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")], a.window, a.reps, a.out)

@@ -13,31 +13,25 @@ same process.  TwoMoons, CircularGaussianMixture(8) and RingMixture(2) in fp32:
   (c) reverse_kld(1024) forward + backward of the 32-layer tanh Planar model of profiles/planar_radial.md with the module
       as p, against the same model with the restatement as p.
 
-Timing as in planar_radial_bench.py: a window is `calls` back-to-back calls between two device events, sized by a
-calibration pass to last at least --window seconds; the variants of one row are alternated for --reps windows each; the
-tables give the median and the spread (max - min) / median.
+Timing: the protocol of bench_windows.py, the variants of one row group alternated.
 
     python profiles/tools/target_density_bench.py [--window 0.2] [--reps 5] [--out FILE]
 """
-import argparse
 import csv
 import glob
 import os
 import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
-import planar_radial_ref as pr_ref  # noqa: E402
-import target_ref as ref  # noqa: E402
-import vcnf_amd as nf  # noqa: E402
-from vcnf_amd import _lib  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import planar_radial_ref as pr_ref
+import target_ref as ref
+import vcnf_amd as nf
+from vcnf_amd import _lib
 
 TARGETS = [("two_moons", 0), ("circular", 8), ("ring", 2)]
 BATCHES = (1024, 1 << 20)
-PEAK = 8e12                      # B/s
 
 
 def module_of(family, n):
@@ -62,28 +56,31 @@ class Restatement(torch.nn.Module):
         return ref.log_prob(self.family, self.n, z, self.scale)
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
+def kernel_rows(label, b, calls, window, reps, lines):
+    """Part (a) for one density and batch: the kernel wrapper without and with the score, 12 B and 20 B per sample."""
+    variants = {("with" if w else "without"): c for w, c in calls.items()}
+    results, failed = bw.measure(variants, window, reps)
+    for name in variants:
+        if name in failed:
+            lines.append("| %s | %d | %s | failed: %s | | | |" % (label, b, name, failed[name]))
+        else:
+            t, spread, _ = results[name]
+            rate = b * (20 if name == "with" else 12) / t
+            lines.append("| %s | %d | %s | %.1f | %.3f | %.1f | %.3f |" % (label, b, name, t * 1e6, spread, rate * 1e-9, rate / bw.HBM_PEAK))
+        print(lines[-1], flush=True)
 
 
-def _measure(variants, window, reps):
-    """{name: (median seconds per call, spread)} with the variants alternated."""
-    calls, times = {}, {}
-    for name, call in variants.items():                 # warm-up, then size the window
-        _window(call, 3)
-        t = _window(call, 5)
-        calls[name] = max(3, int(window / t) + 1)
-        times[name] = []
-    for _ in range(reps):
-        for name, call in variants.items():
-            times[name].append(_window(call, calls[name]))
-    return {name: (statistics.median(ts), (max(ts) - min(ts)) / statistics.median(ts)) for name, ts in times.items()}
+def ratio_rows(label, variants, base, window, reps, lines):
+    """Parts (b) and on: the variants of one density, each with its time as a multiple of ``base``'s."""
+    results, failed = bw.measure(variants, window, reps)
+    for name in variants:
+        if name in failed:
+            lines.append("| %s | %s | failed: %s | | |" % (label, name, failed[name]))
+        else:
+            t, spread, _ = results[name]
+            lines.append("| %s | %s | %.1f | %.3f | %s |" % (
+                label, name, t * 1e6, spread, "%.2f" % (t / results[base].median) if base in results else ""))
+        print(lines[-1], flush=True)
 
 
 def _z(b):
@@ -105,12 +102,7 @@ def part_a(window, reps, lines):
               "| target | B | score | us per call | spread | GB/s | of 8 TB/s |", "|---|---|---|---|---|---|---|"]
     for family, n in TARGETS:
         for b in BATCHES:
-            calls = kernel_calls(family, n, b)
-            res = _measure({("with" if w else "without"): c for w, c in calls.items()}, window, reps)
-            for name, (t, spread) in res.items():
-                rate = b * (20 if name == "with" else 12) / t
-                lines.append("| %s %d | %d | %s | %.1f | %.3f | %.1f | %.3f |" % (family, n, b, name, t * 1e6, spread, rate * 1e-9, rate / PEAK))
-                print(lines[-1], flush=True)
+            kernel_rows("%s %d" % (family, n), b, kernel_calls(family, n, b), window, reps, lines)
 
 
 def part_b(window, reps, lines):
@@ -123,12 +115,9 @@ def part_b(window, reps, lines):
                 x = z.detach().requires_grad_(True)
                 torch.autograd.grad(p.log_prob(x).sum(), x)
             return call
-        res = _measure({"module (one launch + one multiply)": fwd_bwd(module_of(family, n)),
-                        "torch restatement": fwd_bwd(Restatement(family, n).cuda())}, window, reps)
-        base = res["module (one launch + one multiply)"][0]
-        for name, (t, spread) in res.items():
-            lines.append("| %s %d | %s | %.1f | %.3f | %.2f |" % (family, n, name, t * 1e6, spread, t / base))
-            print(lines[-1], flush=True)
+        ratio_rows("%s %d" % (family, n), {"module (one launch + one multiply)": fwd_bwd(module_of(family, n)),
+                                           "torch restatement": fwd_bwd(Restatement(family, n).cuda())},
+                   "module (one launch + one multiply)", window, reps, lines)
 
 
 def part_c(window, reps, lines):
@@ -144,12 +133,8 @@ def part_c(window, reps, lines):
                 model.zero_grad(set_to_none=True)
                 model.reverse_kld(1024).backward()
             return call
-        res = _measure({"module": model_with(module_of(family, n)), "torch restatement": model_with(Restatement(family, n))},
-                       window, reps)
-        base = res["module"][0]
-        for name, (t, spread) in res.items():
-            lines.append("| %s %d | %s | %.1f | %.3f | %.2f |" % (family, n, name, t * 1e6, spread, t / base))
-            print(lines[-1], flush=True)
+        ratio_rows("%s %d" % (family, n), {"module": model_with(module_of(family, n)),
+                                           "torch restatement": model_with(Restatement(family, n))}, "module", window, reps, lines)
 
 
 def launches(count=200):
@@ -182,22 +167,15 @@ def parse_trace(directory):
 def run(window, reps, out):
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     torch.manual_seed(17)
-    lines = ["windows of >= %.2f s, %d alternated windows per variant" % (window, reps)]
+    lines = []
     part_a(window, reps, lines)
     part_b(window, reps, lines)
     part_c(window, reps, lines)
-    text = "\n".join(lines) + "\n"
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines[1:], window, reps, out)         # every part leads with a blank line; the header brings its own
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--window", type=float, default=0.2)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
+    ap = bw.parser(0.2)
     ap.add_argument("--launches", action="store_true", help="only launch the kernels (to be traced)")
     ap.add_argument("--parse-trace", default=None, metavar="DIR")
     a = ap.parse_args()

@@ -4,24 +4,16 @@ DiagGaussian prior; loss = mean(log_q) - mean(log_p).  Variants, on the same GPU
 weights: "kernels" (fuse=True on both ends, fuse_planar_stacks = True) and "torch ends, layer by layer" (fuse=False on
 both ends, fuse_planar_stacks = False).  The calls are what a training loop pays, Python and the dense layers included.
 
-Timing: a window is `calls` back-to-back calls between two device events, sized by a calibration pass so that it lasts
-at least --window seconds; time per call = window / calls.  After warm-up the two variants of a (B, S, dtype) are
-alternated for --reps windows each; the table gives the median and the spread (max - min) / median.
+Timing: the protocol of bench_windows.py, the two variants of a (B, S, dtype) alternated.
 
     python profiles/tools/vae_bench.py [--shapes 256x1,64x16,4096x1] [--window 0.3] [--reps 5] [--out FILE]
     python profiles/tools/vae_bench.py --trace     # five steps per shape of the kernel variant, for a kernel trace
 """
-import argparse
-import os
-import statistics
-import sys
-
 import torch
 from torch import nn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT]
-import vcnf_amd as nf  # noqa: E402
+import bench_windows as bw         # first: it puts the repository root and tests/ on sys.path
+import vcnf_amd as nf
 
 LATENT, LAYERS = 40, 10
 
@@ -46,16 +38,6 @@ def step(m, x, s):
     return call
 
 
-def _window(call, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(calls):
-        call(i)
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / calls          # seconds per call
-
-
 def data(b, dtype):
     return torch.rand(b, 784, generator=torch.Generator().manual_seed(1)).round().to(dtype).cuda()
 
@@ -67,27 +49,19 @@ def run(shapes, window, reps, out):
         for dtype in (torch.float32, torch.float64):
             x = data(b, dtype)
             variants = {"kernels": step(model(dtype, True), x, s), "torch ends, layer by layer": step(model(dtype, False), x, s)}
-            calls, times = {}, {}
-            for name, call in variants.items():
-                _window(call, 3)
-                calls[name] = max(3, int(window / _window(call, 5)) + 1)
-                times[name] = []
-            for _ in range(reps):
-                for name, call in variants.items():
-                    times[name].append(_window(call, calls[name]))
-            med = {name: statistics.median(times[name]) for name in variants}
+            results, failed = bw.measure(variants, window, reps)
             for name in variants:
-                lines.append("| %d | %d | %s | %s | %.1f | %.3f | %.2f |" % (
-                    b, s, "fp64" if dtype == torch.float64 else "fp32", name, med[name] * 1e6,
-                    (max(times[name]) - min(times[name])) / med[name], med[name] / med["kernels"]))
+                lead = "| %d | %d | %s | %s |" % (b, s, bw.dtype_name(dtype), name)
+                base = results.get("kernels")
+                if name in failed:
+                    lines.append("%s failed: %s | | |" % (lead, failed[name]))
+                else:
+                    med, spread, _ = results[name]
+                    lines.append("%s %.1f | %.3f | %s |" % (lead, med * 1e6, spread, "%.2f" % (med / base.median) if base else ""))
                 print(lines[-1], flush=True)
             del variants
             torch.cuda.empty_cache()
-    text = "windows of >= %.2f s, %d alternated windows per variant\n\n%s\n" % (window, reps, "\n".join(lines))
-    if out:
-        with open(out, "w") as f:
-            f.write(text)
-    return text
+    return bw.finish(lines, window, reps, out)
 
 
 def trace(shapes):
@@ -100,11 +74,8 @@ def trace(shapes):
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
+    ap = bw.parser(0.3)
     ap.add_argument("--shapes", default="256x1,64x16,4096x1")
-    ap.add_argument("--window", type=float, default=0.3)
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=None)
     ap.add_argument("--trace", action="store_true")
     a = ap.parse_args()
     shapes = [tuple(int(v) for v in s.split("x")) for s in a.shapes.split(",")]
