@@ -290,12 +290,25 @@ int vcnf_linear_wgrad_f32(const float* x, const float* dy, float* dw, float* db,
 /* The same gradients with the partial products on the fp16 split-half matrix path (v_mfma_f32_32x32x16_f16, both
  * operands split in registers, fp32 accumulation; arithmetic of VCNF_PREC_F16X3): the exact-fp32 kernel is bound by
  * its matrix instructions, this one runs the 736-row last layer of config C3 in a third of the time.  Same workspace,
- * same deterministic slice order.  relu_input: the layer's input is relu(x) (applied on load).  Values beyond +-65504
- * are clamped and counted in sat_count (may be NULL). */
+ * same deterministic slice order.  relu_input: the layer's input is relu(x) (applied on load).  dy_amax (may be NULL):
+ * [out_features] device floats, the largest |dy[:, o]| of every column (col_amax of vcnf_abs_max_rows_cols_f32) -
+ * column o of dy is then multiplied by the power of two that puts that value in [2^14, 2^15) as it is read and row o
+ * of dW and db[o] by its inverse as they are written (both exact: 2^-k dy gives 2^-k dW bit for bit), so a cotangent
+ * of any magnitude keeps full precision for 2^29 below the largest entry of its column and is not clamped; NULL, or 0
+ * or a non-finite value for a column: no scaling (of that column).  Values beyond +-65504 (after the scaling) are
+ * clamped and counted in sat_count (may be NULL). */
 int vcnf_linear_wgrad_f16x3_f32(const float* x, const float* dy, float* dw, float* db, float* workspace,
                                 int64_t workspace_floats, int64_t batch, int32_t in_features,
-                                int32_t out_features, int accumulate, int relu_input, int32_t* sat_count,
-                                void* stream);
+                                int32_t out_features, int accumulate, int relu_input, const float* dy_amax,
+                                int32_t* sat_count, void* stream);
+/* Largest |value| of every row (row_amax [rows]) and of every column (col_amax [cols]) of x [rows, cols], left on the
+ * device for the x_amax / dy_amax arguments of the split-half training kernels (one launch, one read of x, no host
+ * read; graph-capturable); a NaN in a row / column gives NaN there.  cols <= 8192.  scratch: at least
+ * vcnf_abs_max_rows_cols_scratch_floats(rows, cols) floats (0: shape not supported), owned by one stream; its first word
+ * is zero when first used and left zero by every launch. */
+int64_t vcnf_abs_max_rows_cols_scratch_floats(int64_t rows, int32_t cols);
+int vcnf_abs_max_rows_cols_f32(const float* x, int64_t rows, int32_t cols, float* row_amax, float* col_amax,
+                               float* scratch, int64_t scratch_floats, void* stream);
 
 /* First two layers of the Glow conditioner in one launch (nets/cnn.py:20-52): y = act2(W2 act1(conv3x3(x; W1, padding 1)
  * + b1) + b2) with x [batch, c_in, height, width], 256 hidden and 256 output channels, act = LeakyReLU(slope); the
@@ -452,12 +465,16 @@ int vcnf_masked_affine_stack_bwd_f64(const double* z_out, const double* g_out, c
  * is read / to y before it is stored (the residual block's activations, nets/resnet.py:42, :46, without their own
  * passes over memory); mask / addend [batch, n] (16-byte aligned, may be NULL): y = addend + y * (mask > 0) - a ReLU's
  * backward pass and the skip connection's gradient applied to an input gradient as it is stored (autograd of
- * nets/resnet.py:42-57).  Values beyond +-65504 (or NaN inputs) are clamped and counted in sat_count (device int32,
- * may be NULL) once per 64-sample tile. */
+ * nets/resnet.py:42-57).  x_amax (may be NULL; input-gradient form only: bias == NULL and ldk != 1, else
+ * VCNF_ERR_UNSUPPORTED): [batch] device floats, the largest |x[b, :]| of every row (row_amax of
+ * vcnf_abs_max_rows_cols_f32): the pre-scale of vcnf_linear_wgrad_f16x3_f32's dy_amax applied to the rows of x as they
+ * are staged and taken out of the rows of y before mask and addend.  Values beyond +-65504 after that scaling
+ * (or NaN inputs) are clamped and counted in sat_count (device int32, may be NULL) once per 64-sample tile. */
 int vcnf_linear_f16x3_supported(int32_t k, int32_t n);
 int vcnf_linear_f16x3_f32(const float* x, const float* w, const float* bias, float* y, int64_t batch,
                           int32_t k, int32_t n, int64_t ldn, int64_t ldk, int relu_input, int relu_output,
-                          const float* mask, const float* addend, int32_t* sat_count, void* stream);
+                          const float* mask, const float* addend, const float* x_amax, int32_t* sat_count,
+                          void* stream);
 
 /* A run of n_layers (<= vcnf_rqs_stack_fused_max_layers() = 16) RQS coupling layers of ONE shape and one spline
  * configuration in a single launch: the body of NormalizingFlow.log_prob / sample over consecutive

@@ -252,6 +252,35 @@ def test_validation_status_codes_of_the_round2_entry_points():
     assert s == 512 and L.vcnf_linear_wgrad_slices(1000, 128, 128) == 4 and L.vcnf_linear_wgrad_slices(131072, 128, 736) == 85
     assert L.vcnf_linear_wgrad_f32(fake, fake, fake, fake, fake, s * (128 * 128 + 128) - 1, 131072, 128, 128, 0, None) == 2
     assert L.vcnf_linear_wgrad_f32(fake, fake, None, fake, fake, s * (128 * 128 + 128), 131072, 128, 128, 0, None) == 1
+    # split-half form with the cotangent's pre-scale slot: same validation with the slot given or NULL
+    for slot in (None, fake):
+        assert L.vcnf_linear_wgrad_f16x3_f32(fake, fake, fake, fake, fake, s * (128 * 128 + 128) - 1, 131072, 128, 128, 0, 0, slot, None, None) == 2
+        assert L.vcnf_linear_wgrad_f16x3_f32(fake, None, fake, fake, fake, s * (128 * 128 + 128), 131072, 128, 128, 0, 0, slot, None, None) == 1
+        assert L.vcnf_linear_wgrad_f16x3_f32(fake, fake, fake, fake, fake, s * (100 * 128 + 128), 131072, 100, 128, 0, 0, slot, None, None) == 5
+    # the maxima's reduction: NULL, empty shapes, more columns than its LDS holds, an address that is not a float's
+    for missing in range(4):
+        ptrs = [fake] * 4
+        ptrs[missing] = None
+        assert L.vcnf_abs_max_rows_cols_f32(ptrs[0], 8, 8, ptrs[1], ptrs[2], ptrs[3], 9, None) == 1
+    assert L.vcnf_abs_max_rows_cols_f32(fake, 0, 8, fake, fake, fake, 9, None) == 2
+    assert L.vcnf_abs_max_rows_cols_f32(fake, 8, 0, fake, fake, fake, 9, None) == 2
+    assert L.vcnf_abs_max_rows_cols_f32(fake, 8, 8193, fake, fake, fake, 9, None) == 5
+    assert L.vcnf_abs_max_rows_cols_f32(ctypes.c_void_p(0x1002), 8, 8, fake, fake, fake, 9, None) == 3
+    # its scratch: one ticket word and a row of columns per workgroup (256 of them until their rows outgrow the LDS table)
+    sf = L.vcnf_abs_max_rows_cols_scratch_floats
+    assert sf(8, 8) == 1 + 8 * 8 and sf(131072, 128) == 1 + 256 * 128 and sf(131072, 736) == 1 + 256 * 736
+    assert sf(4 << 20, 128) == 1 + 1024 * 128 and sf(8, 8193) == 0 and sf(0, 8) == 0
+    assert L.vcnf_abs_max_rows_cols_f32(fake, 131072, 128, fake, fake, fake, 256 * 128, None) == 2
+    # dense layer on the split-half path: shapes; the pre-scale slot goes with the input-gradient form only (no bias,
+    # strided weight rows); an empty batch launches nothing
+    assert L.vcnf_linear_f16x3_supported(128, 736) == 1 and L.vcnf_linear_f16x3_supported(736, 128) == 1
+    assert L.vcnf_linear_f16x3_supported(736, 132) == 0 and L.vcnf_linear_f16x3_supported(24, 128) == 0
+    assert L.vcnf_linear_f16x3_f32(fake, fake, None, fake, 0, 128, 128, 1, 128, 0, 0, None, None, fake, None, None) == 0
+    assert L.vcnf_linear_f16x3_f32(fake, fake, fake, fake, 0, 128, 128, 1, 128, 0, 0, None, None, fake, None, None) == 5
+    assert L.vcnf_linear_f16x3_f32(fake, fake, None, fake, 0, 128, 128, 128, 1, 0, 0, None, None, fake, None, None) == 5
+    assert L.vcnf_linear_f16x3_f32(fake, fake, fake, fake, 0, 128, 128, 128, 1, 0, 0, None, None, None, None, None) == 0
+    assert L.vcnf_linear_f16x3_f32(fake, None, None, fake, 4, 128, 128, 1, 128, 0, 0, None, None, fake, None, None) == 1
+    assert L.vcnf_linear_f16x3_f32(fake, fake, None, fake, 4, 128, 128, 1, 128, 0, 0, ctypes.c_void_p(0x1004), None, fake, None, None) == 3
     # residual-block maps: op 0-3, op 1 needs the second output
     assert L.vcnf_resblock_elementwise_f32(4, fake, fake, fake, fake, None, 8, None) == 5
     assert L.vcnf_resblock_elementwise_f32(1, fake, fake, fake, fake, None, 8, None) == 1

@@ -883,15 +883,58 @@ def masked_affine_stack_bwd(z_out, g_out, g_ld, table, goff, n_layers, n_grad, i
     return g_in, grads
 
 
-def linear_f16x3(x, weight, bias=None, input_grad=False, relu_in=False, relu_out=False, mask=None, addend=None):
+def _stream_key(dev):
+    return (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+
+
+_AMAX_SCRATCH = {}    # per (device, stream), like _WGRAD_WS: the reduction's scratch.  Its first word must be zero
+                      # between launches (the kernel leaves it so); a larger shape REPLACES the tensor, so a captured
+                      # graph must have seen its largest cotangent during warm-up, as for _WGRAD_WS
+
+
+def abs_max(t):
+    """(row_amax [B], col_amax [N]): the largest |value| of every row and column of the fp32 matrix ``t`` [B, N], on the
+    device (csrc/linear_wgrad.hip::abs_max_rows_cols_kernel; one launch, no host read).  The pair is what the ``amax``
+    argument of linear_f16x3 (which takes the rows) and linear_wgrad (the columns) is."""
+    dev = require_device(t, allow_grad=True)
+    t = t.detach().contiguous()
+    b, n = t.shape
+    key = _stream_key(dev)
+    scratch = _AMAX_SCRATCH.get(key)
+    need = int(lib().vcnf_abs_max_rows_cols_scratch_floats(b, n))
+    if need < 1:
+        raise VcnfError("abs_max: unsupported shape %d x %d" % (b, n))
+    if scratch is None or scratch.numel() < need:
+        scratch = _AMAX_SCRATCH[key] = torch.zeros(need, dtype=torch.float32, device=dev)
+    rows = torch.empty(b, dtype=torch.float32, device=dev)
+    cols = torch.empty(n, dtype=torch.float32, device=dev)
+    _call("vcnf_abs_max_rows_cols_f32", dev, t, b, n, rows, cols, scratch, scratch.numel(), tag="abs_max")
+    return rows, cols
+
+
+def _amax_or_none(t):
+    """abs_max(t), or None for a shape the reduction does not take (more than 8192 columns): the kernels then run
+    without the pre-scale, clamp and count."""
+    return abs_max(t) if lib().vcnf_abs_max_rows_cols_scratch_floats(t.shape[0], t.shape[1]) > 0 else None
+
+
+def linear_f16x3(x, weight, bias=None, input_grad=False, relu_in=False, relu_out=False, mask=None, addend=None,
+                 prescale=None, amax=None):
     """nn.Linear on the fp16 split-half matrix path at training batch sizes (csrc/linear_f16x3.hip): ``x @ weight.T +
     bias`` for weight [out, in], or with ``input_grad`` the layer's input gradient ``x @ weight`` (x = the upstream
     gradient [B, out]).  The weight is read in place (no packed copy); ``relu_in`` / ``relu_out`` apply ReLU to x as it is
     read / to the result before it is stored; ``mask`` / ``addend`` [B, n]: result = addend + result * (mask > 0) (a ReLU's
     backward and a skip connection's gradient on the way out).  Clamped values are counted in saturation_counter
-    (nf.check_saturation())."""
+    (nf.check_saturation()).  ``prescale`` (default: with ``input_grad``, where x is a cotangent of any magnitude): every
+    row of x travels times the power of two that puts its largest |value| in [2^14, 2^15), taken out of that row of the
+    result exactly - nothing is clamped and 2^-k x gives 2^-k times the result bit for bit; ``amax``: ``abs_max(x)`` when
+    the caller already has it (computed here otherwise)."""
     dev = require_device(x, weight, bias, allow_grad=True)
     x, weight = x.detach().contiguous(), weight.detach().contiguous()
+    if input_grad if prescale is None else prescale:
+        amax = _amax_or_none(x) if amax is None else amax
+    else:
+        amax = None
     b, k = x.shape
     n_out, n_in = weight.shape
     if input_grad:
@@ -908,7 +951,7 @@ def linear_f16x3(x, weight, bias=None, input_grad=False, relu_in=False, relu_out
     if addend is not None:
         addend = addend.detach().contiguous()
     _call("vcnf_linear_f16x3_f32", dev, x, weight, bias, y, b, k, n, ldn, ldk, bool(relu_in), bool(relu_out), mask,
-          addend, saturation_counter(dev), tag="linear_f16x3")
+          addend, amax[0] if amax is not None else None, saturation_counter(dev), tag="linear_f16x3")
     return y
 
 
@@ -916,10 +959,11 @@ _WGRAD_WS = {}        # workspace of the partial results per (device, stream): c
                       # different streams (two models' backward passes, side streams) must not share it
 
 
-def linear_wgrad(x, dy, want_bias=True, f16x3=False, relu_x=False):
+def linear_wgrad(x, dy, want_bias=True, f16x3=False, relu_x=False, prescale=True, amax=None):
     """(dW [out, in], db [out] or None) of y = x W^T + b from x [B, in] and dy [B, out] (csrc/linear_wgrad.hip: the batch
     reduction split over the chip, deterministic; exact fp32 matrix instructions, or with ``f16x3`` the fp16 split-half
-    matrix path - clamped values are counted in saturation_counter)."""
+    matrix path - clamped values are counted in saturation_counter; there ``prescale`` / ``amax`` apply to the columns
+    of dy as to the rows of x in linear_f16x3: a cotangent of any magnitude keeps its precision and is never clamped)."""
     dev = require_device(x, dy, allow_grad=True)
     x, dy = x.detach().contiguous(), dy.detach().contiguous()
     if relu_x and not f16x3:
@@ -930,8 +974,7 @@ def linear_wgrad(x, dy, want_bias=True, f16x3=False, relu_x=False):
     if slices < 1:
         raise VcnfError("linear_wgrad: unsupported layer shape %d -> %d" % (n_in, n_out))
     need = slices * (n_out * n_in + n_out)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream(dev).cuda_stream)
+    key = _stream_key(dev)
     ws = _WGRAD_WS.get(key)
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, dtype=torch.float32, device=dev)
@@ -940,7 +983,10 @@ def linear_wgrad(x, dy, want_bias=True, f16x3=False, relu_x=False):
     db = torch.empty(n_out, dtype=torch.float32, device=dev) if want_bias else None
     args = (x, dy, dw, db, ws, ws.numel(), b, n_in, n_out, 0)
     if f16x3:
-        _call("vcnf_linear_wgrad_f16x3_f32", dev, *args, bool(relu_x), saturation_counter(dev), tag="linear_wgrad")
+        if prescale:
+            amax = _amax_or_none(dy) if amax is None else amax
+        _call("vcnf_linear_wgrad_f16x3_f32", dev, *args, bool(relu_x), amax[1] if prescale and amax is not None else None, saturation_counter(dev),
+              tag="linear_wgrad")
     else:
         _call("vcnf_linear_wgrad_f32", dev, *args, tag="linear_wgrad")
     return dw, db

@@ -760,10 +760,32 @@ class MultivariateSampleFn(torch.autograd.Function):
 
 # Matrix path of the conditioner's dense layers on the training path at large batches: 'fp16x3' - forward products, the
 # 128 -> 128 layers' input gradients (csrc/linear_f16x3.hip) and the weight gradients (csrc/linear_wgrad.hip, split-half
-# form) on fp16 split-half operands with fp32 accumulation (error against fp64 below the library's fp32 GEMM on every
-# layer shape; values beyond +-65504 are clamped and counted: nf.check_saturation()) - or 'fp32': the library's fp32
-# GEMMs and the exact-fp32 weight-gradient kernel.
+# form) on fp16 split-half operands with fp32 accumulation - or 'fp32': the library's fp32 GEMMs and the exact-fp32
+# weight-gradient kernel.  What holds on 'fp16x3' (tests/test_gpu_gemm_error.py, tests/test_gpu_grad_range.py): every
+# entry within 4 * 2^-24 * sum |a b| of the fp64 product and mean / p99.9 error not above the library's fp32 GEMM, for
+# activations and weights of unit scale and for cotangents of ANY scale - a cotangent (1/B under a mean loss: 2^-17 at
+# the benchmark's batch, below fp16's smallest normal) travels times a power of two taken from its largest
+# |value| (_cot_amax; split_half.hpp::pre_scale) - per row of the cotangent in an input gradient, per column in a weight
+# gradient -, exact on the way in and out, so it is never clamped and keeps full precision for 2^29 below the largest
+# entry of its row / column.  Activations and weights are NOT scaled: beyond +-65504 they are clamped
+# and counted (nf.check_saturation()), and below 2^-14 they lose bits as a bare fp16 split does.
 TRAIN_MATRIX_PATH = 'fp16x3'
+
+
+def _cot_amax(g, n_in, wgrad=True, dgrad=True):
+    """Largest |g| per row and per column for the split-half kernels that take the cotangent ``g`` [B, n_out] of a layer
+    with ``n_in`` inputs (one reduction shared by its weight-gradient and input-gradient launches), or None when neither
+    launch will run: off the 'fp16x3' path, below WGRAD_MIN_BATCH, or a shape that goes to the library in both
+    (``wgrad`` / ``dgrad``: whether the caller wants that product at all)."""
+    if not (TRAIN_MATRIX_PATH == 'fp16x3' and g.is_cuda and g.dtype == torch.float32 and g.dim() == 2
+            and g.is_contiguous() and g.shape[0] >= WGRAD_MIN_BATCH):
+        return None
+    n_out = g.shape[1]
+    takes_w = wgrad and bool(_lib.lib().vcnf_linear_wgrad_supported(n_in, n_out))
+    takes_d = dgrad and n_in == n_out and bool(_lib.lib().vcnf_linear_f16x3_supported(n_out, n_in))
+    if not (takes_w or takes_d) or not _lib.lib().vcnf_abs_max_rows_cols_scratch_floats(g.shape[0], n_out):
+        return None
+    return _lib.abs_max(g)
 
 
 def _f16x3_ok(x, n_in, n_out):
@@ -778,11 +800,11 @@ def _fwd(x, weight, bias):
     return torch.addmm(bias, x, weight.t()) if bias is not None else x @ weight.t()
 
 
-def _dgrad(gy, weight):
+def _dgrad(gy, weight, amax=None):
     """gy W: split-half kernel for the square hidden layers (40 against 52 us at 131 072 x 128 x 128), library for the
     narrow / very deep ones, where its tiling is as fast."""
     if weight.shape[0] == weight.shape[1] and _f16x3_ok(gy, weight.shape[0], weight.shape[1]):
-        return _lib.linear_f16x3(gy, weight, None, input_grad=True)
+        return _lib.linear_f16x3(gy, weight, None, input_grad=True, amax=amax)
     return gy @ weight
 
 
@@ -802,11 +824,14 @@ class LinearFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         gx = gw = gb = None
+        gy = gy.contiguous()
+        want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        amax = _cot_amax(gy, weight.shape[1], wgrad=want_w, dgrad=ctx.needs_input_grad[0])
         if ctx.needs_input_grad[0]:
-            gx = _dgrad(gy.contiguous(), weight)
+            gx = _dgrad(gy, weight, amax)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             gw, gb = _lib.linear_wgrad(x, gy, want_bias=ctx.has_bias and ctx.needs_input_grad[2],
-                                       f16x3=TRAIN_MATRIX_PATH == 'fp16x3')
+                                       f16x3=TRAIN_MATRIX_PATH == 'fp16x3', amax=amax)
             if not ctx.needs_input_grad[1]:
                 gw = None
         return gx, gw, gb
@@ -824,9 +849,9 @@ def linear(mod, x):
         return LinearFn.apply(x, mod.weight, mod.bias)
     return mod(x)
 
-def _wgrad_or_torch(x, gy, want_bias=True):
+def _wgrad_or_torch(x, gy, want_bias=True, amax=None):
     if x.shape[0] >= WGRAD_MIN_BATCH and _lib.lib().vcnf_linear_wgrad_supported(x.shape[1], gy.shape[1]):
-        return _lib.linear_wgrad(x, gy, want_bias=want_bias, f16x3=TRAIN_MATRIX_PATH == 'fp16x3')
+        return _lib.linear_wgrad(x, gy, want_bias=want_bias, f16x3=TRAIN_MATRIX_PATH == 'fp16x3', amax=amax)
     return gy.t() @ x, (gy.sum(0) if want_bias else None)
 
 
@@ -870,22 +895,26 @@ class ResBlockFn(torch.autograd.Function):
             t0, t1, w0, w1 = ctx.saved_tensors
             g_c, g_gate = g.contiguous(), None
         need = ctx.needs_input_grad
-        gw1, gb1 = _wgrad_or_torch(t1, g_c) if (need[4] or need[5]) else (None, None)
+        # one reduction per cotangent: its weight-gradient and input-gradient launches share it
+        am_c = _cot_amax(g_c, w1.shape[1], wgrad=need[4] or need[5])
+        gw1, gb1 = _wgrad_or_torch(t1, g_c, amax=am_c) if (need[4] or need[5]) else (None, None)
         sq1 = w1.shape[0] == w1.shape[1] and _f16x3_ok(g_c, w1.shape[0], w1.shape[1])
         # square layers: the ReLU's backward (and, below, the skip connection's gradient) applied as the split-half kernel
         # stores the input gradient - no elementwise pass of their own
-        g_a = _lib.linear_f16x3(g_c, w1, None, input_grad=True, mask=t1) if sq1 else _lib.resblock_op(2, _dgrad(g_c, w1), t1)
+        g_a = (_lib.linear_f16x3(g_c, w1, None, input_grad=True, mask=t1, amax=am_c) if sq1
+               else _lib.resblock_op(2, _dgrad(g_c, w1, am_c), t1))
+        am_a = _cot_amax(g_a, w0.shape[1], wgrad=need[2] or need[3], dgrad=need[0])
         if ctx.fused_relu:          # t0 is the block input h: relu on load
-            gw0, gb0 = _lib.linear_wgrad(t0, g_a, f16x3=TRAIN_MATRIX_PATH == 'fp16x3', relu_x=True) if (need[2] or need[3]) else (None, None)
+            gw0, gb0 = _lib.linear_wgrad(t0, g_a, f16x3=TRAIN_MATRIX_PATH == 'fp16x3', relu_x=True, amax=am_a) if (need[2] or need[3]) else (None, None)
         else:
-            gw0, gb0 = _wgrad_or_torch(t0, g_a) if (need[2] or need[3]) else (None, None)
+            gw0, gb0 = _wgrad_or_torch(t0, g_a, amax=am_a) if (need[2] or need[3]) else (None, None)
         sq0 = w0.shape[0] == w0.shape[1] and _f16x3_ok(g_a, w0.shape[0], w0.shape[1])
         if not need[0]:
             g_h = None
         elif sq0:
-            g_h = _lib.linear_f16x3(g_a, w0, None, input_grad=True, mask=t0, addend=g)
+            g_h = _lib.linear_f16x3(g_a, w0, None, input_grad=True, mask=t0, addend=g, amax=am_a)
         else:
-            g_h = _lib.resblock_op(3, _dgrad(g_a, w0), t0, g)
+            g_h = _lib.resblock_op(3, _dgrad(g_a, w0, am_a), t0, g)
         return g_h, (g_gate if ctx.gated and need[1] else None), gw0, gb0, gw1, gb1
 
 

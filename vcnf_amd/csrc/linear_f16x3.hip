@@ -36,6 +36,7 @@ struct ShLinearArgs {
   const float* mask;       // [B, N] or NULL: y *= (mask > 0)   - the ReLU's backward on an input gradient
   const float* addend;     // [B, N] or NULL: y += addend        - the skip connection's gradient (after the mask)
   int32_t* sat;
+  const float* amax;       // largest |x[b, :]| per row [B] or NULL: pre-scale of x's rows, split_half.hpp::pre_scale
 };
 
 constexpr int kShTile = 64;
@@ -52,6 +53,7 @@ __global__ __launch_bounds__(256, (!LOLO && !WROWS) ? 3 : 2) void linear_f16x3_k
   // three workgroups per compute unit forced, 67 -> 74 us per forward launch of the C3 training step, 59 -> 54 us per
   // input-gradient launch)
   constexpr bool EPI = !WROWS;
+  // the pre-scale of x's rows (the cotangent) exists in the input-gradient forms only: the forward forms keep their code
   constexpr int NCB = kShTile / 32;
   constexpr int NT = kShChunk / 16;
   extern __shared__ __align__(16) float smem[];
@@ -100,6 +102,11 @@ __global__ __launch_bounds__(256, (!LOLO && !WROWS) ? 3 : 2) void linear_f16x3_k
         const int r = i / (nt * 2), j = i - r * (nt * 2);
         const float4 p = xp[u], q = xq[u];
         float v8[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
+        if (EPI) {
+          const float sc = pre_scale(a.amax && r < rows ? a.amax + b0 + r : nullptr).scale;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v8[e] *= sc;
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) satm = fmaxf(satm, v8[e] == v8[e] ? 0.f : __builtin_inff());   // NaN inputs count
         half8 h8, l8;
@@ -155,14 +162,21 @@ __global__ __launch_bounds__(256, (!LOLO && !WROWS) ? 3 : 2) void linear_f16x3_k
         // through the wave's strip [sample][36] so that a store instruction writes whole rows of 32 floats
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
+          // (this lane's accumulator column is sample cb * 32 + c32: that row's power of two comes out here)
+          const float unscale = EPI ? pre_scale(a.amax && cb * 32 + c32 < rows ? a.amax + b0 + cb * 32 + c32 : nullptr).unscale : 1.f;
+          const float lo_unscale = kLoUnscale * unscale;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             floatx4 v;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const int r = 4 * j + q;
-              v[q] = LOLO ? fmaf(fmaf(corr2[cb][r], kLoUnscale, corr[cb][r]), kLoUnscale, mainv[cb][r])
-                          : fmaf(corr[cb][r], kLoUnscale, mainv[cb][r]);
+              if (EPI)
+                v[q] = LOLO ? fmaf(fmaf(corr2[cb][r], kLoUnscale, corr[cb][r]), lo_unscale, mainv[cb][r] * unscale)
+                            : fmaf(corr[cb][r], lo_unscale, mainv[cb][r] * unscale);
+              else
+                v[q] = LOLO ? fmaf(fmaf(corr2[cb][r], kLoUnscale, corr[cb][r]), kLoUnscale, mainv[cb][r])
+                            : fmaf(corr[cb][r], kLoUnscale, mainv[cb][r]);
               if (a.relu_out) v[q] = fmaxf(v[q], 0.f);
             }
             *reinterpret_cast<floatx4*>(mystrip + c32 * 36 + 8 * j + 4 * kg) = v;
@@ -232,15 +246,18 @@ extern "C" int vcnf_linear_f16x3_supported(int32_t k, int32_t n) {
 
 extern "C" int vcnf_linear_f16x3_f32(const float* x, const float* w, const float* bias, float* y, int64_t batch,
                                      int32_t k, int32_t n, int64_t ldn, int64_t ldk, int relu_input, int relu_output,
-                                     const float* mask, const float* addend, int32_t* sat_count, void* stream) {
+                                     const float* mask, const float* addend, const float* x_amax,
+                                     int32_t* sat_count, void* stream) {
   if (!x || !w || !y) return VCNF_ERR_NULL;
   if (batch < 0) return VCNF_ERR_SHAPE;
   if (!vcnf_linear_f16x3_supported(k, n)) return VCNF_ERR_UNSUPPORTED;
+  // the pre-scale is taken out of the whole accumulator: no bias under it, and only the input-gradient forms carry it
+  if (x_amax && (bias || ldk == 1)) return VCNF_ERR_UNSUPPORTED;
   if (batch == 0) return VCNF_OK;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return VCNF_ERR_ALIGN;
   if ((reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(addend)) & 15) return VCNF_ERR_ALIGN;
   ShLinearArgs a{x, w, bias, y, (long long)batch, k, n, (long long)ldn, (long long)ldk, relu_input ? 1 : 0,
-                 relu_output ? 1 : 0, mask, addend, sat_count};
+                 relu_output ? 1 : 0, mask, addend, sat_count, x_amax};
   const size_t lds = (size_t)2 * (kShChunk / 16) * (kShTile / 32) * 64 * 16 + 4 * 32 * 36 * 4;
   dim3 grid((unsigned)((batch + kShTile - 1) / kShTile));
   hipStream_t st = (hipStream_t)stream;

@@ -30,6 +30,7 @@ struct WgradArgs {
   int col_tiles;      // split-half form: workgroups per row tile (64 input columns each)
   int relu_x;         // split-half form: the layer's input is relu(x) (x = the residual stream, nets/resnet.py:42)
   int32_t* sat;       // split-half form: tiles that clamped a value at +-65504 (or NULL)
+  const float* amax;  // split-half form: largest |dy[:, o]| per output row o [OUT] or NULL: split_half.hpp::pre_scale
 };
 
 constexpr int kWgBlock = 256;
@@ -126,6 +127,9 @@ __global__ __launch_bounds__(kWgBlock, 2) void linear_wgrad_f16x3_kernel(const W
   for (int kb = 0; kb < KB; ++kb) { mainv[kb] = floatx16{}; corr[kb] = floatx16{}; }
   float bsum = 0.f, satm = 0.f;
   const bool rok = o0 + c32 < a.OUT;
+  // column o of dy travels as dy * 2^e(o) (this lane's A values are all of column o0 + c32); row o of dW and db[o]
+  // leave as sums * 2^-e(o)
+  const PreScale ps = pre_scale(a.amax && rok ? a.amax + o0 + c32 : nullptr);
   bool cok[KB];
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) cok[kb] = i0 + 32 * kb + c32 < a.IN;
@@ -161,6 +165,7 @@ __global__ __launch_bounds__(kWgBlock, 2) void linear_wgrad_f16x3_kernel(const W
 #define VCNF_WG_COMPUTE(BUF)                                                              \
   _Pragma("unroll") for (int u = 0; u < U; ++u) {                                         \
     _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                       \
+      av[BUF][u][i] *= ps.scale;                                                          \
       bsum += av[BUF][u][i];                                                              \
       satm = fmaxf(satm, av[BUF][u][i] == av[BUF][u][i] ? 0.f : __builtin_inff());        \
     }                                                                                     \
@@ -198,15 +203,17 @@ __global__ __launch_bounds__(kWgBlock, 2) void linear_wgrad_f16x3_kernel(const W
   for (int r = 0; r < 16; ++r) {
     const int row = o0 + 8 * (r >> 2) + 4 * kg + (r & 3);
     if (row < a.OUT) {
+      const float unscale = pre_scale(a.amax ? a.amax + row : nullptr).unscale;
+      const float lo_unscale = kLoUnscale * unscale;
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb)
-        if (cok[kb]) pw[(long long)row * a.IN + i0 + 32 * kb + c32] = fmaf(corr[kb][r], kLoUnscale, mainv[kb][r]);
+        if (cok[kb]) pw[(long long)row * a.IN + i0 + 32 * kb + c32] = fmaf(corr[kb][r], lo_unscale, mainv[kb][r] * unscale);
     }
   }
   if (a.part_b && ct == 0) {
     float t = bsum;
     t += __shfl_xor(t, 32, 64);
-    if (kg == 0 && rok) a.part_b[(long long)s * a.OUT + o0 + c32] = t;
+    if (kg == 0 && rok) a.part_b[(long long)s * a.OUT + o0 + c32] = t * ps.unscale;
   }
   if (a.sat && satm > 65504.f) atomicAdd(a.sat, 1);
 }
@@ -254,6 +261,157 @@ __global__ __launch_bounds__(kWgBlock) void wgrad_reduce_kernel(const WreduceArg
   }
 }
 
+// Largest |value| of every row and of every column of a cotangent g [B, N], left on the device for the split-half
+// kernels' pre-scale (split_half.hpp::pre_scale; no host read): the input gradient g W scales row b of g by its own
+// power of two (row b of the result depends on no other row), the weight gradient g^T x column o (row o of dW depends
+// on no other column) - so an entry is carried with full precision as long as it is within 2^29 of the largest one in
+// ITS row / column, whatever the rest of the tensor holds.  One launch, one read of g: a workgroup owns a set of
+// rows, folds |values| (as bit patterns: an unsigned orders like the value, a NaN above infinity) into LDS
+// maxima per row and per column, writes its rows, stores its columns as scratch[1 + workgroup * N + c] and takes a
+// ticket from scratch[0]; the last workgroup folds the stored columns, publishes them and puts the ticket word back
+// to zero.  (Folding with one global atomic per workgroup and column cost 130 us a launch: the 128 words of a
+// [B, 128] cotangent's columns lie in four cache lines, and atomics on one line are served one after the other.)
+// Which rows: in the fast form (whole 16-byte packs, rows of at most 4096 columns) a workgroup takes passes of
+// kAmaxLoads * RP rows, pass p = workgroup + trip * workgroups, so that at any moment the workgroups read one stretch
+// of memory side by side (a contiguous block of rows each - 256 KB apart for [131 072, 128] - reached 0.6 TB/s; the
+// later trips are run by tests/test_gpu_grad_range.py::test_abs_max_rows_and_columns); the plain forms keep a
+// contiguous block.
+constexpr int kAmaxThreads = 1024;
+constexpr int kAmaxBlocks = 256;            // one per compute unit: 16 waves, four loads in flight per thread
+constexpr int kAmaxCols = 8192;            // LDS words for the column maxima
+constexpr int kAmaxRows = 4096;            // ... and for a workgroup's rows
+constexpr int kAmaxLoads = 4;              // 16-byte loads in flight per thread
+struct AmaxArgs {
+  const float* x;
+  long long B;
+  int N, rows_per_block, nblocks, vec, fast, pass_rows;
+  float* row_amax;
+  float* col_amax;
+  unsigned* scratch;
+};
+__global__ __launch_bounds__(kAmaxThreads) void abs_max_rows_cols_kernel(const AmaxArgs a) {
+  __shared__ unsigned colm[kAmaxCols];
+  __shared__ unsigned rowm[kAmaxRows];
+  __shared__ int last;
+  const int tid = threadIdx.x, N = a.N;
+  const long long r0 = (long long)blockIdx.x * a.rows_per_block;
+  const int rows = a.fast ? a.rows_per_block : (int)min((long long)a.rows_per_block, a.B - r0);
+  for (int i = tid; i < N; i += kAmaxThreads) colm[i] = 0u;
+  for (int i = tid; i < rows; i += kAmaxThreads) rowm[i] = 0u;
+  __syncthreads();
+  const float* xb = a.x + r0 * N;
+  const int total = rows * N;                                  // <= kAmaxRows * kAmaxCols: fits an int
+  bool rows_written = false;
+  if (a.fast) {
+    // N % 4 == 0, x 16-byte aligned, a row is at most one 16-byte pack per thread: thread = (pack column pc, row lane
+    // rl) keeps its four columns' maxima in registers while it walks down the rows; a row's maximum is folded across
+    // the PT lanes that share the row (PT <= 64: inside the wave, the row is written at once; else per wave into LDS)
+    const int P = N / 4;
+    int PT = 1;
+    while (PT < P) PT <<= 1;
+    const int pc = tid & (PT - 1), rl = tid / PT, RP = kAmaxThreads / PT;
+    const int RPP = kAmaxLoads * RP;                           // rows of a pass
+    const uint4* xv = reinterpret_cast<const uint4*>(a.x);
+    unsigned c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u;
+    rows_written = PT <= 64;
+    for (int rb = 0; rb < rows; rb += RPP) {                   // (uniform trip count: every lane reaches the shuffles)
+      const long long g0 = ((long long)(rb / RPP) * a.nblocks + blockIdx.x) * RPP;   // first row of this pass
+      uint4 v[kAmaxLoads];
+#pragma unroll
+      for (int u = 0; u < kAmaxLoads; ++u) {
+        const long long gr = g0 + u * RP + rl;
+        v[u] = (pc < P && gr < a.B) ? xv[gr * P + pc] : uint4{0u, 0u, 0u, 0u};
+      }
+#pragma unroll
+      for (int u = 0; u < kAmaxLoads; ++u) {
+        const long long gr = g0 + u * RP + rl;
+        const int r = rb + u * RP + rl;                        // place in this workgroup's LDS table
+        const unsigned e0 = v[u].x & 0x7FFFFFFFu, e1 = v[u].y & 0x7FFFFFFFu, e2 = v[u].z & 0x7FFFFFFFu, e3 = v[u].w & 0x7FFFFFFFu;
+        c0 = max(c0, e0); c1 = max(c1, e1); c2 = max(c2, e2); c3 = max(c3, e3);
+        unsigned m = max(max(e0, e1), max(e2, e3));
+        if (PT <= 64) {
+          for (int o = PT >> 1; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+          if (pc == 0 && gr < a.B) a.row_amax[gr] = __builtin_bit_cast(float, m);
+        } else {                                               // PT is a multiple of 64: a wave lies in one row
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+          if ((tid & 63) == 0 && gr < a.B) atomicMax(&rowm[r], m);
+        }
+      }
+    }
+    if (pc < P) {
+      atomicMax(&colm[4 * pc], c0);
+      atomicMax(&colm[4 * pc + 1], c1);
+      atomicMax(&colm[4 * pc + 2], c2);
+      atomicMax(&colm[4 * pc + 3], c3);
+    }
+  } else if (a.vec) {                                          // wider rows: flat walk, LDS maxima per pack
+    const int nv = total / 4;
+    for (int i = tid; i < nv; i += kAmaxLoads * kAmaxThreads) {
+      uint4 v[kAmaxLoads];
+#pragma unroll
+      for (int u = 0; u < kAmaxLoads; ++u) {
+        const int j = i + u * kAmaxThreads;
+        v[u] = j < nv ? reinterpret_cast<const uint4*>(xb)[j] : uint4{0u, 0u, 0u, 0u};
+      }
+#pragma unroll
+      for (int u = 0; u < kAmaxLoads; ++u) {
+        const int j = i + u * kAmaxThreads;
+        if (j < nv) {
+          const int r = (4 * j) / N, c = 4 * j - r * N;
+          const unsigned e0 = v[u].x & 0x7FFFFFFFu, e1 = v[u].y & 0x7FFFFFFFu, e2 = v[u].z & 0x7FFFFFFFu, e3 = v[u].w & 0x7FFFFFFFu;
+          atomicMax(&rowm[r], max(max(e0, e1), max(e2, e3)));
+          atomicMax(&colm[c], e0);
+          atomicMax(&colm[c + 1], e1);
+          atomicMax(&colm[c + 2], e2);
+          atomicMax(&colm[c + 3], e3);
+        }
+      }
+    }
+  } else {
+    for (int i = tid; i < total; i += kAmaxThreads) {
+      const unsigned e = __builtin_bit_cast(unsigned, xb[i]) & 0x7FFFFFFFu;
+      const int r = i / N;
+      atomicMax(&rowm[r], e);
+      atomicMax(&colm[i - r * N], e);
+    }
+  }
+  __syncthreads();
+  if (!rows_written)
+    for (int i = tid; i < rows; i += kAmaxThreads) {
+      long long gr = r0 + i;
+      if (a.fast) gr = ((long long)(i / a.pass_rows) * a.nblocks + blockIdx.x) * a.pass_rows + i % a.pass_rows;
+      if (gr < a.B) a.row_amax[gr] = __builtin_bit_cast(float, rowm[i]);
+    }
+  unsigned* part = a.scratch + 1 + (long long)blockIdx.x * N;
+  for (int i = tid; i < N; i += kAmaxThreads) part[i] = colm[i];
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) last = atomicAdd(a.scratch, 1u) == (unsigned)(a.nblocks - 1);
+  __syncthreads();
+  if (last) {                                                  // every other workgroup's columns are in scratch by now
+    __threadfence();
+    const int stored = a.nblocks * N;                          // (fits an int: the launcher checks)
+    // (eight requests in flight: this workgroup is alone on the device by now, one load at a time is all latency)
+    for (int i0 = tid; i0 < stored; i0 += 8 * kAmaxThreads) {
+      unsigned v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * kAmaxThreads;
+        v[u] = i < stored ? __hip_atomic_load(a.scratch + 1 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * kAmaxThreads;
+        if (i < stored && v[u] > colm[i % N]) atomicMax(&colm[i % N], v[u]);
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < N; i += kAmaxThreads) a.col_amax[i] = __builtin_bit_cast(float, colm[i]);
+    if (tid == 0) atomicExch(a.scratch, 0u);
+  }
+}
+
 template <int NB>
 static void launch_wgrad(const WgradArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((linear_wgrad_kernel<NB>), dim3((unsigned)(a.row_tiles * a.S)), dim3(kWgBlock), 0, st, a);
@@ -278,27 +436,88 @@ extern "C" int64_t vcnf_linear_wgrad_slices(int64_t batch, int32_t in_features, 
   return s < 1 ? 1 : s;
 }
 
+/* rows a workgroup takes and the workgroups that makes: kAmaxBlocks of them while their rows fit the LDS table.
+ * fast: the form for whole 16-byte packs (rows taken in passes of *pass_rows, interleaved over the workgroups) */
+static long long amax_blocks(int64_t rows, int32_t cols, bool fast, long long* rows_per_block, int* pass_rows) {
+  if (fast) {
+    int pt = 1;
+    while (pt < cols / 4) pt <<= 1;
+    const long long rpp = (long long)kAmaxLoads * (kAmaxThreads / pt);
+    const long long passes = (rows + rpp - 1) / rpp;
+    long long blocks = passes < kAmaxBlocks ? passes : kAmaxBlocks;
+    long long trips = (passes + blocks - 1) / blocks;
+    if (trips * rpp > kAmaxRows) {
+      trips = kAmaxRows / rpp;
+      blocks = (passes + trips - 1) / trips;
+    }
+    *rows_per_block = trips * rpp;
+    *pass_rows = (int)rpp;
+    return blocks;
+  }
+  long long rpb = (rows + kAmaxBlocks - 1) / kAmaxBlocks;
+  const long long fit = (long long)kAmaxRows * kAmaxCols / 4 / cols;      // rows * cols of a workgroup stays an int
+  if (rpb > fit) rpb = fit;
+  if (rpb > kAmaxRows) rpb = kAmaxRows;
+  *rows_per_block = rpb;
+  *pass_rows = 0;
+  return (rows + rpb - 1) / rpb;
+}
+static bool amax_fast_shape(int32_t cols) { return cols % 4 == 0 && cols <= 4 * kAmaxThreads; }
+
+extern "C" int64_t vcnf_abs_max_rows_cols_scratch_floats(int64_t rows, int32_t cols) {
+  long long rpb;
+  int pr;
+  if (rows < 1 || cols < 1 || cols > kAmaxCols) return 0;
+  long long blocks = amax_blocks(rows, cols, false, &rpb, &pr);          // (which form runs depends on x's alignment too)
+  if (amax_fast_shape(cols)) {
+    const long long other = amax_blocks(rows, cols, true, &rpb, &pr);
+    if (other > blocks) blocks = other;
+  }
+  return 1 + blocks * cols;
+}
+
+extern "C" int vcnf_abs_max_rows_cols_f32(const float* x, int64_t rows, int32_t cols, float* row_amax, float* col_amax,
+                                          float* scratch, int64_t scratch_floats, void* stream) {
+  if (!x || !row_amax || !col_amax || !scratch) return VCNF_ERR_NULL;
+  if (rows < 1 || cols < 1) return VCNF_ERR_SHAPE;
+  if (cols > kAmaxCols) return VCNF_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(x) & 3) return VCNF_ERR_ALIGN;
+  AmaxArgs a;
+  a.x = x; a.B = rows; a.N = cols; a.row_amax = row_amax; a.col_amax = col_amax;
+  a.scratch = reinterpret_cast<unsigned*>(scratch);
+  long long rpb;
+  a.vec = (cols % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) ? 1 : 0;
+  a.fast = (a.vec && amax_fast_shape(cols)) ? 1 : 0;
+  const long long blocks = amax_blocks(rows, cols, a.fast != 0, &rpb, &a.pass_rows);
+  if (blocks * cols > 0x7FFFFFFF) return VCNF_ERR_UNSUPPORTED;           // (the last workgroup indexes the stored columns with an int)
+  if (scratch_floats < 1 + blocks * cols) return VCNF_ERR_SHAPE;
+  a.rows_per_block = (int)rpb;
+  a.nblocks = (int)blocks;
+  hipLaunchKernelGGL(abs_max_rows_cols_kernel, dim3((unsigned)blocks), dim3(kAmaxThreads), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
+}
+
 static int wgrad_run(const float* x, const float* dy, float* dw, float* db, float* workspace, int64_t workspace_floats,
                      int64_t batch, int32_t in_features, int32_t out_features, int accumulate, int f16x3,
-                     int32_t* sat_count, void* stream);
+                     const float* dy_amax, int32_t* sat_count, void* stream);
 
 extern "C" int vcnf_linear_wgrad_f32(const float* x, const float* dy, float* dw, float* db, float* workspace,
                                      int64_t workspace_floats, int64_t batch, int32_t in_features,
                                      int32_t out_features, int accumulate, void* stream) {
-  return wgrad_run(x, dy, dw, db, workspace, workspace_floats, batch, in_features, out_features, accumulate, 0, nullptr, stream);
+  return wgrad_run(x, dy, dw, db, workspace, workspace_floats, batch, in_features, out_features, accumulate, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int vcnf_linear_wgrad_f16x3_f32(const float* x, const float* dy, float* dw, float* db, float* workspace,
                                            int64_t workspace_floats, int64_t batch, int32_t in_features,
                                            int32_t out_features, int accumulate, int relu_input,
-                                           int32_t* sat_count, void* stream) {
+                                           const float* dy_amax, int32_t* sat_count, void* stream) {
   return wgrad_run(x, dy, dw, db, workspace, workspace_floats, batch, in_features, out_features, accumulate,
-                   relu_input ? 2 : 1, sat_count, stream);
+                   relu_input ? 2 : 1, dy_amax, sat_count, stream);
 }
 
 static int wgrad_run(const float* x, const float* dy, float* dw, float* db, float* workspace, int64_t workspace_floats,
                      int64_t batch, int32_t in_features, int32_t out_features, int accumulate, int f16x3,
-                     int32_t* sat_count, void* stream) {
+                     const float* dy_amax, int32_t* sat_count, void* stream) {
   if (!vcnf_linear_wgrad_supported(in_features, out_features)) return VCNF_ERR_UNSUPPORTED;
   if (batch < 1) return VCNF_ERR_SHAPE;
   if (!x || !dy || !dw || !workspace) return VCNF_ERR_NULL;
@@ -307,6 +526,7 @@ static int wgrad_run(const float* x, const float* dy, float* dw, float* db, floa
   if (workspace_floats < S * per) return VCNF_ERR_SHAPE;
   WgradArgs a;
   a.sat = sat_count;
+  a.amax = dy_amax;
   a.col_tiles = 1;
   a.relu_x = f16x3 == 2 ? 1 : 0;              // f16x3: 0 exact fp32 kernel, 1 split-half, 2 split-half on relu(x)
   a.x = x; a.dy = dy; a.part_w = workspace;

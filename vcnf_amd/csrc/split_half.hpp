@@ -68,4 +68,29 @@ __device__ __forceinline__ void split8(const float (&v)[8], half8& hi, half8& lo
   }
 }
 
+// Pre-scale of ONE operand of a split-half product (the cotangent of the training path's backward GEMMs: a mean loss
+// over B samples puts it at 1/B, below fp16's smallest normal 2^-14 from B = 32 768 on, where hi and lo are subnormal
+// and keep few bits), per vector of that operand that meets only its own outputs: a row of g in g W, a column of dy
+// in dy^T x.  ``amax`` points at the device float holding that vector's largest |value|
+// (vcnf_abs_max_rows_cols_f32); the vector is multiplied by 2^e as it is read, e = 14 - floor(log2 amax) - the largest
+// |value| lands in [2^14, 2^15), 2^29 of full-precision range below it - and its outputs by 2^-e in the epilogue.
+// Both are exact in fp32, so a launch on 2^-k times the operand gives 2^-k times the result bit for bit.  e is kept in [-113, 100] (2^e,
+// 2^-e and 2^-e * 2^-11 stay normal fp32).  amax NULL, 0 or not finite: e = 0, the plain clamp-and-count behaviour.
+struct PreScale {
+  float scale, unscale;
+};
+__device__ __forceinline__ PreScale pre_scale(const float* amax) {
+  PreScale p{1.f, 1.f};
+  if (amax) {
+    const float m = *amax;
+    if (m > 0.f && m < __builtin_inff()) {
+      int e = 14 + 127 - (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255u);   // (a subnormal amax reads as 2^-127)
+      e = e > 100 ? 100 : (e < -113 ? -113 : e);
+      p.scale = __builtin_bit_cast(float, (unsigned)(127 + e) << 23);
+      p.unscale = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
+    }
+  }
+  return p;
+}
+
 }  // namespace vcnf
