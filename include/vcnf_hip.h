@@ -487,7 +487,11 @@ int vcnf_linear_f16x3_f32(const float* x, const float* w, const float* bias, flo
  * the last (meant for the small batches at which one launch per layer is launch-bound: the reference's drivers use
  * 1024 - 2048 samples, /root/reference/run.py:45-47); a tile in which ANY layer met a value the fp16 halves cannot
  * carry is left unwritten and flagged in redo_tiles, and the same call with VCNF_PREC_F32 and the F32 packings
- * evaluates exactly the flagged rows through all layers on exact fp32 matrix instructions. */
+ * evaluates exactly the flagged rows through all layers on exact fp32 matrix instructions.  The one exception to
+ * the 32-sample tiles: n_layers == 2 at a batch above vcnf_rqs_layer_fused_small_batch_rows() where
+ * vcnf_rqs_pair_fused_supported() says 1 - the 128-sample-tile kernel then walks both layers per tile visit and adds
+ * their log|det| one after the other: y AND logdet are bitwise those of two vcnf_rqs_layer_fused_f32 calls (the
+ * fp32 re-evaluation of a flagged tile still adds the sum). */
 typedef struct vcnf_rqs_stack_layer {
   const int32_t* transform_idx;
   const int32_t* identity_idx;
@@ -497,6 +501,10 @@ typedef struct vcnf_rqs_stack_layer {
   const float* shared_d;
 } vcnf_rqs_stack_layer;
 int32_t vcnf_rqs_stack_fused_max_layers(void);
+/* 1 if a run of exactly TWO layers of this shape on the fp16 split-half path, at a batch above
+ * vcnf_rqs_layer_fused_small_batch_rows(), is evaluated two layers per tile visit by the 128-sample-tile kernel (both
+ * layers' tables fit its LDS), else 0.  y and logdet of such a run are bitwise those of two one-layer calls. */
+int vcnf_rqs_pair_fused_supported(int32_t d_id, int32_t d_t, int32_t ctx_dim, int32_t hidden, int32_t num_blocks);
 int vcnf_rqs_stack_fused_f32(const float* x, const float* context, float* y, float* logdet,
                              int64_t batch, const vcnf_rqs_stack_layer* layers, int32_t n_layers,
                              int32_t d_t, int32_t d_id, int32_t ctx_dim, int32_t hidden,

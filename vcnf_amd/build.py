@@ -16,12 +16,13 @@ SOURCES = ["rqs_kernels.hip", "affine_kernels.hip", "fused_layer.hip",
            "rqs_backward.hip", "gemm_probe.hip", "rqs_f64.hip", "linear_f16x3.hip", "masked_affine_stack.hip", "class_cond_gaussian.hip",
            "gaussian_mixture.hip", "heavy_tail.hip", "mvn_base.hip", "planar_radial.hip", "target_density.hip", "stochastic.hip",
            "vae_ends.hip", "periodic.hip"]
-# (source, extra flags, object name): fused_layer_v6.hip is compiled once per number of residual blocks.  The two
-# kernels whose spline code runs beside matrix instructions are built without SLP vectorisation: packed-f32 vector
+# (source, extra flags, object name): fused_layer_v6.hip, its two-layer form fused_layer_v6_pair.hip and fused_layer_v6s.hip
+# are compiled once per number of residual blocks.  The kernels whose spline code runs beside matrix instructions are built without SLP vectorisation: packed-f32 vector
 # instructions starve beside the partner wave's matrix instructions (profiles/r02_spline_eval_microbench.md)
 NO_SLP = ["-fno-slp-vectorize"]
 UNITS = [(s, NO_SLP if s == "fused_final.hip" else [], os.path.splitext(s)[0]) for s in SOURCES if s != "fused_layer_v6.hip"] + \
         [("fused_layer_v6.hip", ["-DVCNF_V6_NBLK=%d" % n] + NO_SLP, "fused_layer_v6_b%d" % n) for n in (2, 3, 1)] + \
+        [("fused_layer_v6_pair.hip", ["-DVCNF_V6_NBLK=%d" % n] + NO_SLP, "fused_layer_v6_pair_b%d" % n) for n in (2, 3, 1)] + \
         [("fused_layer_v6s.hip", ["-DVCNF_V6_NBLK=%d" % n] + NO_SLP, "fused_layer_v6s_b%d" % n) for n in (2, 3, 1)] + \
         [("fused_layer.hip", ["-DVCNF_F32_NBLK=%d" % n], "fused_layer_f32_b%d" % n) for n in (3, 1)]
 HEADERS = ["rqs_math.hpp", "rqs_vjp.hpp", "rqs_lean.hpp", "fused_common.hpp", "fused_lds.hpp", "split_half.hpp", "stream_common.hpp", "mvn_lds.hpp", "target_math.hpp",
@@ -32,7 +33,7 @@ def stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + ["fused_layer_v6s.hip"] + HEADERS)
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + ["fused_layer_v6s.hip", "fused_layer_v6_pair.hip"] + HEADERS)
 
 
 def build(force=False, verbose=False):

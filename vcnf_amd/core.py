@@ -57,7 +57,7 @@ class _FlowWalks:
 
     def _init_stack_switches(self):
         self.fuse_affine_stacks = True           # runs of one-kernel affine layers in a single launch (fused_affine.run_stack)
-        self.fuse_rqs_stacks = True              # runs of one-kernel RQS layers in a single launch at small batches (fused.run_stack)
+        self.fuse_rqs_stacks = True              # runs of one-kernel RQS layers in a single launch: long runs at small batches, pairs above (fused.run_stack)
         self.fuse_masked_stacks = True           # runs of MaskedAffineFlow (+ MLP conditioners) / ActNorm layers in a single launch
         self.fuse_planar_stacks = True           # runs of Planar / Radial layers in a single launch (fused_planar.run)
         self.fuse_stochastic_stacks = True       # runs of HamiltonianMonteCarlo layers in a single launch (fused_stochastic.run)

@@ -193,6 +193,11 @@ int launch_fused_v6_b1(const FusedArgs& a, int d_id, int ctx_dim, int inverse, h
 int launch_fused_v6_b2(const FusedArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);
 int launch_fused_v6_b3(const FusedArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);
 
+// defined in fused_layer_v6_pair.hip (two layers per tile visit; VCNF_ERR_UNSUPPORTED where LdsV6Pair does not fit)
+int launch_fused_v6_pair_b1(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);
+int launch_fused_v6_pair_b2(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);
+int launch_fused_v6_pair_b3(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);
+
 // defined in fused_layer_v6s.hip (32-sample tiles: small batches)
 int launch_fused_v6s_b1(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);
 int launch_fused_v6s_b2(const FusedStackArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st);

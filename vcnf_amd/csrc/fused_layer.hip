@@ -410,9 +410,29 @@ extern "C" int64_t vcnf_rqs_layer_fused_small_batch_rows(int64_t rows) {
   return prev;
 }
 
-// sa.n_layers == 1: one layer; > 1: a run of layers in one launch (small-batch kernel on the split-half path: the
-// 128-sample kernel has no layer loop)
+// 1 if the 128-sample-tile kernel has its two-layer form at this shape (two table sets fit the LDS: LdsV6Pair), else 0
+extern "C" int vcnf_rqs_pair_fused_supported(int32_t d_id, int32_t d_t, int32_t ctx_dim, int32_t hidden,
+                                             int32_t num_blocks) {
+  if (hidden != 128 || vcnf_rqs_layer_fused_pack_floats(d_id, d_t, ctx_dim, num_blocks) <= 0) return 0;
+  int fits = 0;
+  with_listed_only(IntRange<1, 3>{}, num_blocks, [&](auto NBLK) {
+    fits = with_fused_shape(d_id, ctx_dim, [](auto DI, auto C) -> int {
+      return LdsV6Pair<DI(), DI(), C(), 128, decltype(NBLK)::value, 8>::FITS ? 1 : 0;
+    });
+  });
+  return fits;
+}
+
+// sa.n_layers == 1: one layer; 2 above the small-batch threshold where the shape has the pair form: both layers per
+// tile visit of the 128-sample kernel (fused_layer_v6_pair.hip); any other run of layers: the small-batch kernel (the
+// 128-sample kernel has no longer layer loop)
 static int launch_f16x3(const FusedStackArgs& sa, int d_id, int ctx_dim, int num_blocks, int inverse, hipStream_t st) {
+  if (sa.n_layers == 2 && sa.a.B > g_small_batch_rows &&
+      vcnf_rqs_pair_fused_supported(d_id, d_id, ctx_dim, 128, num_blocks)) {
+    if (num_blocks == 1) return launch_fused_v6_pair_b1(sa, d_id, ctx_dim, inverse, st);
+    if (num_blocks == 2) return launch_fused_v6_pair_b2(sa, d_id, ctx_dim, inverse, st);
+    return launch_fused_v6_pair_b3(sa, d_id, ctx_dim, inverse, st);
+  }
   if (sa.n_layers > 1 || sa.a.B <= g_small_batch_rows) {
     if (num_blocks == 1) return launch_fused_v6s_b1(sa, d_id, ctx_dim, inverse, st);
     if (num_blocks == 2) return launch_fused_v6s_b2(sa, d_id, ctx_dim, inverse, st);

@@ -61,6 +61,14 @@
 #ifndef VCNF_AHEAD
 #define VCNF_AHEAD 1
 #endif
+// -DVCNF_V6_PAIR=1 (fused_layer_v6_pair.hip): this body compiled as fused_rqs_layer_v6_pair_kernel, which applies TWO
+// consecutive layers of one shape to every tile it visits: rows and context enter LDS once, layer 1's identity phase
+// reads layer 0's output from xt where it lies, the tail runs once.  Per layer: a weight descriptor and a table set in
+// LDS (LdsV6Pair, kSet floats apart), both sets filled in the launch prologue.  The log-density keeps the per-layer
+// launches' association, (old + o0) + o1, so that a pair gives bitwise what two launches give.
+#ifndef VCNF_V6_PAIR
+#define VCNF_V6_PAIR 0
+#endif
 #if VCNF_TIME
 #define VCNF_T(I) { const long long t_ = clock64(); tacc[I] += t_ - tlast; tlast = t_; }
 #define VCNF_TIME_PARAM , float* tstamps
@@ -91,14 +99,40 @@ static float* time_buffer() {
   return buf;
 }
 // stamps of the last launch (any shape, either direction): [wave 0 | wave 4][kTimeSlots]
+#if VCNF_V6_PAIR
+extern "C" int vcnf_v6_pair_phase_stamps(float* out) {
+#else
 extern "C" int vcnf_v6_phase_stamps(float* out) {
+#endif
   if (!time_buffer() || hipDeviceSynchronize() != hipSuccess) return VCNF_ERR_LAUNCH;
   return hipMemcpy(out, time_buffer(), 2 * kTimeSlots * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess ? VCNF_OK : VCNF_ERR_LAUNCH;
 }
 #endif
 
+#if VCNF_V6_PAIR
+#define VCNF_V6_LDS LdsV6Pair
+#define VCNF_LAYER(L_) sa.lay[L_]
+// The thread index as a value the compiler cannot trace back: the addresses a phase makes from it are made in the phase
+// (a few instructions per tile) and not before the tile loop, where each would hold a register through the whole tile.
+// The one-layer kernels have those registers to spare; with a second layer's state live the pair kernels do not.
+#define VCNF_PHASE_TID(N) int N = tid; asm volatile("" : "+v"(N));
+// the layers of a visit: a run-time loop (one copy of the code) here, a plain block in the one-layer kernels
+#define VCNF_FOR_LAYERS(L_) _Pragma("nounroll") for (int L_ = 0; L_ < 2; ++L_)
+#else
+#define VCNF_V6_LDS LdsV6
+#define VCNF_LAYER(L_) a                    // FusedArgs carries the fields of FusedLayerDesc under the same names
+#define VCNF_PHASE_TID(N) const int N = tid;
+#define VCNF_FOR_LAYERS(L_) constexpr int L_ = 0;
+#endif
+
 template <int DI, int DT, int C, int H, int NBLK, int K, bool INV>
+#if VCNF_V6_PAIR
+__global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_pair_kernel(const FusedStackArgs sa VCNF_TIME_PARAM) {
+  const FusedArgs& a = sa.a;
+#else
 __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedArgs a VCNF_TIME_PARAM) {
+#endif
+  constexpr int NL = VCNF_V6_PAIR ? 2 : 1;  // layers per tile visit
   static_assert(H == 128 && K == 8, "4 row blocks of 32 over 4 waves; 3 K - 1 = 23 logits: two features per 48 rows");
   static_assert((DI == 16 || DI == 32) && DT == DI && (C == 0 || C == 16), "shape family");
   constexpr int kBlock = 512;
@@ -119,7 +153,12 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   constexpr int RING = VCNF_AHEAD + 1;
 
   extern __shared__ __align__(16) float smem[];
-  using S = LdsV6<DI, DT, C, H, NBLK, K>;                   // the regions, their offsets and the launch's byte count
+  using S = VCNF_V6_LDS<DI, DT, C, H, NBLK, K>;             // the regions, their offsets and the launch's byte count
+#if VCNF_V6_PAIR
+  constexpr int kSet = S::SET;                              // layer l's tables: l * kSet floats behind layer 0's
+#else
+  constexpr int kSet = 0;
+#endif
   static_assert(S::TILE == kTile && S::FRAG_N == 2 * GFRAG * 4 && S::XT_N == kTile * XS && S::TAB_N >= DI * TABW, "layout");
   // fragment region first (LDS offset 0: every fragment address is a per-lane base + 16-bit immediate).
   // Trunk: activation fragments [t][cb][lane] of 16 bytes, hi (32 KB) then lo (32 KB); last layer: the weight
@@ -158,28 +197,34 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   // the second-dispatched wave group loses the issue arbitration on every step (MI355X_MICROARCH.md, two waves per
   // SIMD, item 4): one static priority for it, no per-step flips (+0.5 %)
   if (ch == 1) __builtin_amdgcn_s_setprio(1);
-  for (int i = tid; i < NG * 96; i += kBlock) {            // packed [group][lane half][48]
-    const int g = i / 96, hf = i % 96 / 48;
-    biasf[hf * BPL + g * 48 + i % 48] = a.wpack[L::BF + i];
-  }
-  for (int i = tid; i < NBT * H; i += kBlock) {             // packed [row block][lane half][16] per vector
-    const int v = i / H, blk = (v - 1) / NBV, sel = (v - 1) % NBV, r = i % H;
-    const int off = v == 0 ? L::B0 : L::BLK0 + blk * L::BLK + (sel == 0 ? L::BA : sel == 1 ? L::BB : L::BC);
-    biasf[(r >> 4 & 1) * BPL + NG * 48 + v * (H / 2) + (r >> 5) * 16 + (r & 15)] = a.wpack[off + r];
-  }
-  for (int i = tid; i < DT; i += kBlock) tfi[i] = a.tf_idx[i];
-  for (int i = tid; i < DI; i += kBlock) idi[i] = a.id_idx[i];
-  if (shared) {
-    // knot tables of the identity half: one thread per (feature, column: x knots | y knots | derivatives)
-    for (int i = tid; i < 3 * DI; i += kBlock) {
-      const int f = i % DI;
-      SplitLogits p{a.sh_w + f * K, a.sh_h + f * K, a.sh_d + f * (K - 1), K, 1.f, c.edge_logit, c.tails};
-      rqs_build_table_part_k<K>(p, c, tab + f * TABW, 1, i / DI);
+  VCNF_FOR_LAYERS(l) {                                      // the table set of every layer of the visit, once per launch
+    const auto& d = VCNF_LAYER(l);
+    const int lo = l * kSet;
+    for (int i = tid; i < NG * 96; i += kBlock) {            // packed [group][lane half][48]
+      const int g = i / 96, hf = i % 96 / 48;
+      biasf[lo + hf * BPL + g * 48 + i % 48] = d.wpack[L::BF + i];
+    }
+    for (int i = tid; i < NBT * H; i += kBlock) {             // packed [row block][lane half][16] per vector
+      const int v = i / H, blk = (v - 1) / NBV, sel = (v - 1) % NBV, r = i % H;
+      const int off = v == 0 ? L::B0 : L::BLK0 + blk * L::BLK + (sel == 0 ? L::BA : sel == 1 ? L::BB : L::BC);
+      biasf[lo + (r >> 4 & 1) * BPL + NG * 48 + v * (H / 2) + (r >> 5) * 16 + (r & 15)] = d.wpack[off + r];
+    }
+    for (int i = tid; i < DT; i += kBlock) tfi[lo + i] = d.tf_idx[i];
+    for (int i = tid; i < DI; i += kBlock) idi[lo + i] = d.id_idx[i];
+    if (shared) {
+      // knot tables of the identity half: one thread per (feature, column: x knots | y knots | derivatives)
+      for (int i = tid; i < 3 * DI; i += kBlock) {
+        const int f = i % DI;
+        SplitLogits p{d.sh_w + f * K, d.sh_h + f * K, d.sh_d + f * (K - 1), K, 1.f, c.edge_logit, c.tails};
+        rqs_build_table_part_k<K>(p, c, tab + lo + f * TABW, 1, i / DI);
+      }
     }
   }
 
+#if !VCNF_V6_PAIR
   const __amdgpu_buffer_rsrc_t wr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wpack), 0, a.wpack_bytes, 0x00020000);
+#endif
   const int voff = lane * 16;
   const float* bplane = biasf + kg * BPL;                   // bias tables of this lane half
 
@@ -196,17 +241,18 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   static_assert(kTile * (D / 4) % kBlock == 0 && (C == 0 || kTile * (C / 4) == kBlock), "rows per thread");
 #define VCNF_PREFETCH_ROWS(TILE)                                                          \
   {                                                                                       \
+    VCNF_PHASE_TID(tidp)                                                                  \
     const long long pb0 = min((TILE) * kTile, a.B);                                       \
     const long long left = (a.B - pb0) * (D * 4);                                         \
     const __amdgpu_buffer_rsrc_t xr_ = __builtin_amdgcn_make_buffer_rsrc(                 \
         const_cast<float*>(a.x) + pb0 * D, 0, (int)min(left, (long long)(kTile * D * 4)), 0x00020000); \
     _Pragma("unroll") for (int k = 0; k < kTile * (D / 4) / kBlock; ++k)                  \
-      xpre[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr_, (tid + kBlock * k) * 16, 0, 0)); \
+      xpre[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr_, (tidp + kBlock * k) * 16, 0, 0)); \
     if (C > 0) {                                                                          \
       const long long leftc = (a.B - pb0) * (C * 4);                                      \
       const __amdgpu_buffer_rsrc_t cr_ = __builtin_amdgcn_make_buffer_rsrc(               \
           const_cast<float*>(a.ctx) + pb0 * C, 0, (int)min(leftc, (long long)(kTile * C * 4)), 0x00020000); \
-      cpre[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cr_, tid * 16, 0, 0)); \
+      cpre[0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(cr_, tidp * 16, 0, 0)); \
     }                                                                                     \
   }
   // the compiler waits for the prefetched rows where their registers are first touched
@@ -232,16 +278,17 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     { VCNF_T(0) VCNF_SYNC(); VCNF_T(15) }
     {   // ---- x rows -> LDS tile; context row quarter -> half of a B fragment (hi | lo)
       constexpr int D4 = D / 4;
+      VCNF_PHASE_TID(tidp)
       if (tid == 0) *tflag = 0;
 #pragma unroll
       for (int k = 0; k < kTile * D4 / kBlock; ++k) {
-        const int i = tid + kBlock * k;
+        const int i = tidp + kBlock * k;
         const int r = i / D4, o = i - r * D4;
         *reinterpret_cast<float4*>(xt + r * XS + 4 * o) = xpre[k];
       }
       if (C > 0) {
         // thread holds context columns 4 (tid & 3) .. + 3 of row tid >> 2: k-slots (kg', 4 half .. + 3)
-        const int r = tid >> 2, part = tid & 3;
+        const int r = tidp >> 2, part = tidp & 3;
         half4 h4, l4;
         const float cv[4] = {cpre[0].x, cpre[0].y, cpre[0].z, cpre[0].w};
         // raw inputs: a NaN counts as out of range too (fmaxf drops NaNs; the reference propagates them)
@@ -264,6 +311,27 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     }
     { VCNF_T(1) VCNF_SYNC(); VCNF_T(15) }
 
+    // ---- the layers of the visit, a run-time loop (one copy of the code).  Between two layers nothing but the groups'
+    // re-alignment barrier behind the round loop: behind it xt holds the layer's whole output, and the weight window,
+    // which shares LDS with the activation fragments the next identity phase writes, is no longer read.
+    float ld_acc = 0.f, ld_first = 0.f;      // transformed-half log|det| shares of the last layer and of the one before
+   VCNF_FOR_LAYERS(l) {
+#if VCNF_V6_PAIR
+    // one scalar, opaque to the optimiser, added where a table address is formed: left to itself the compiler keeps
+    // an address per table and lane that steps from layer to layer, some twenty registers live through the whole tile
+    int lo = l * kSet;
+    asm volatile("" : "+s"(lo));
+    const __amdgpu_buffer_rsrc_t wr =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sa.lay[l].wpack), 0, a.wpack_bytes, 0x00020000);
+#else
+    constexpr int lo = 0;
+#endif
+    const float* tab_l = tab + lo;
+    float* ldt_l = ldt + lo;
+    const int* tfi_l = tfi + lo;
+    const int* idi_l = idi + lo;
+    const float* bpl = bplane + lo;          // bias tables of this lane half and layer
+
     // ---- identity half through the unconditional spline: 4 lanes per sample, each lane a run of DI/4
     // features (branch-free: points outside the interval are evaluated at the left end and selected to the
     // identity afterwards).  The same thread holds exactly one (half) B fragment of the first layer's input:
@@ -271,13 +339,14 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     // (:110-114) - split to hi | lo and stored in the activation region.
     {
       constexpr int UNR = DI / 4;
-      const int mi = tid >> 2, part = tid & 3;
+      VCNF_PHASE_TID(tidp)
+      const int mi = tidp >> 2, part = tidp & 3;
       float lsum = 0.f;
       float xv[UNR], fv[UNR];
       float* px[UNR];
 #pragma unroll
       for (int k = 0; k < UNR; ++k) {
-        px[k] = xt + mi * XS + idi[part * UNR + k];
+        px[k] = xt + mi * XS + idi_l[part * UNR + k];
         xv[k] = *px[k];
         fv[k] = xv[k];
       }
@@ -288,7 +357,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
         for (int k = 0; k < UNR; ++k) {
           in_[k] = (xv[k] >= c.lo_x) && (xv[k] <= c.hi_x);
           bool bad1 = false;
-          rqs_point_table_inside<INV, K>(in_[k] ? xv[k] : c.lo_x, tab + (part * UNR + k) * TABW, yv[k], lad[k], bad1);
+          rqs_point_table_inside<INV, K>(in_[k] ? xv[k] : c.lo_x, tab_l + (part * UNR + k) * TABW, yv[k], lad[k], bad1);
           bad = bad || (bad1 && in_[k]);
         }
 #pragma unroll
@@ -305,7 +374,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       // tile it was spilled to scratch and reloaded behind an s_waitcnt vmcnt(0) in the sampling direction
       int tid_ = tid;
       asm volatile("" : "+v"(tid_));
-      if (part == 0) ldt[tid_ >> 2] = lsum;
+      if (part == 0) ldt_l[tid_ >> 2] = lsum;
       // raw inputs of the conditioner: NaN / Inf count as out of range (fmaxf in the splits drops NaNs)
 #pragma unroll
       for (int k = 0; k < UNR; ++k) satm = fmaxf(satm, fv[k] == fv[k] ? 0.f : __builtin_inff());
@@ -345,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     floatx16 abias;
 #define VCNF_LOAD_BIAS16(DST, VEC)                                                        \
   _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                      \
-    const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bplane + NG * 48 + (VEC) * (H / 2) + 16 * rp + 4 * i_); \
+    const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bpl + NG * 48 + (VEC) * (H / 2) + 16 * rp + 4 * i_); \
     DST[4 * i_ + 0] = b4_[0]; DST[4 * i_ + 1] = b4_[1]; DST[4 * i_ + 2] = b4_[2]; DST[4 * i_ + 3] = b4_[3]; \
   }
 #define VCNF_LOAD_HIDDEN(WOFF, BVEC)                                                      \
@@ -517,7 +586,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       fhi[t] = __builtin_bit_cast(half8, act_hi[(t * NCB + rp) * 64 + lane]);
       flo[t] = __builtin_bit_cast(half8, act_lo[(t * NCB + rp) * 64 + lane]);
     }
-    float ld_acc = 0.f;
+    ld_acc = 0.f;
     uint4* win = act + ch * GFRAG;           // this group's half of the window: one feature group, 48 KB
     const int gtid = tid & 255;              // thread index inside the group
     constexpr int NSTG = GFRAG / 256;        // 16-byte fragments a thread moves per staged group (12)
@@ -531,7 +600,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
 #define VCNF_LOAD_BIASF(G)                                                                \
   _Pragma("unroll") for (int b = 0; b < 3; ++b) {                                         \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                    \
-      const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bplane + (G) * 48 + 16 * b + 4 * i_); \
+      const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bpl + (G) * 48 + 16 * b + 4 * i_); \
       pa[b][4 * i_ + 0] = b4_[0]; pa[b][4 * i_ + 1] = b4_[1]; pa[b][4 * i_ + 2] = b4_[2]; pa[b][4 * i_ + 3] = b4_[3]; \
     }                                                                                     \
   }
@@ -541,22 +610,38 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     // accumulate mode: the values this tile adds onto travel beside the first window straight into LDS
     // (buffer_load_dword ... lds, no register; rows past the batch read 0) and are covered by the same wait; the
     // tail reads them from LDS
-    if (ch == 0 && rp < 2 && a.ld_mode) {
+    if (ch == 0 && rp < 2 && a.ld_mode && l == 0) {
       const __amdgpu_buffer_rsrc_t or_ = __builtin_amdgcn_make_buffer_rsrc(a.logdet + b0, 0, rows * 4, 0x00020000);
+      VCNF_PHASE_TID(tidp)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(or_, (__attribute__((address_space(3))) void*)(ldold + rp * 64), 4,
-                                               lane * 4, rp * 256, 0, 0);
+                                               (tidp & 63) * 4, rp * 256, 0, 0);
     }
     wait_vector_memory();
     { VCNF_T(9) VCNF_SYNC(); VCNF_T(15) }
     if (ch == 1) { VCNF_T(14) VCNF_SYNC(); VCNF_T(18) }            // ---- group B one step behind again
     for (int rnd = 0; rnd < (VCNF_ABL == 3 ? 0 : NR); ++rnd) {
       const int g = 2 * rnd + ch;
+#if VCNF_V6_PAIR
+      // The prefetch registers hold nothing from the tile top to the last round of the last layer: say so in every
+      // round (an output-only operand, no instruction), or the loops carry the dead values through both layers.
+#pragma unroll
+      for (int k = 0; k < kTile * (D / 4) / kBlock; ++k) {
+        floatx4 v_;
+        asm volatile("" : "=v"(v_));
+        xpre[k] = __builtin_bit_cast(float4, v_);
+      }
+      if (C > 0) {
+        floatx4 v_;
+        asm volatile("" : "=v"(v_));
+        cpre[0] = __builtin_bit_cast(float4, v_);
+      }
+#endif
       // the two elements this lane transforms (features 4 g + 2 kg + {0, 1} of sample c32)
       float* px[2];
       float xin[2];
 #pragma unroll
       for (int f2 = 0; f2 < 2; ++f2) {
-        px[f2] = xt + (rp * 32 + c32) * XS + tfi[4 * g + 2 * kg + f2];
+        px[f2] = xt + (rp * 32 + c32) * XS + tfi_l[4 * g + 2 * kg + f2];
         xin[f2] = *px[f2];
       }
       {
@@ -600,7 +685,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       {
         // ---- step V: two spline evaluations per lane; the group's next window and bias travel meanwhile
         const bool more = rnd + 1 < NR;
-        if (!more) {                           // last vector step of the tile: the next tile's rows are requested
+        if (!more && l + 1 == NL) {            // last vector step of the tile: the next tile's rows are requested
           VCNF_PREFETCH_ROWS(tile + gridDim.x)
         }
         if (more && VCNF_ABL != 2) {
@@ -635,7 +720,12 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     // ---- per-sample log|det|: this wave covered one group parity of its samples; the partner
     // wave (other parity) adds its share through LDS (ldt already holds the identity half)
     ld_acc += __shfl_xor(ld_acc, 32, 64);
-    if (ch == 1 && kg == 0) ldt[rp * 32 + c32] += ld_acc;
+    {
+      VCNF_PHASE_TID(tidp)
+      if (ch == 1 && kg == 0) ldt_l[rp * 32 + (tidp & 31)] += ld_acc;
+    }
+    if (l + 1 < NL) ld_first = ld_acc;
+   }   // layers
     if (satm > 65504.f) *tflag = 1;
     { VCNF_T(12) VCNF_SYNC(); VCNF_T(15) }
     // The next tile's rows are waited for HERE, in front of the tail's stores: they were requested a whole vector step
@@ -663,8 +753,11 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     if (ch == 0 && (tid_ & 32) == 0) {
       const int mrow = (tid_ >> 6) * 32 + (tid_ & 31);         // ch == 0: tid >> 6 is the column block
       const __amdgpu_buffer_rsrc_t lr = __builtin_amdgcn_make_buffer_rsrc(a.logdet + b0, 0, rows * 4, 0x00020000);
-      const float o = a.ld_sign * (ld_acc + ldt[mrow]);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a.ld_mode ? ldold[mrow] + o : o), lr, mrow * 4, 0, 0);
+      // one add per layer, in the layers' order: what a launch per layer leaves in the log-density, bit for bit
+      const float o0 = a.ld_sign * ((NL > 1 ? ld_first : ld_acc) + ldt[mrow]);
+      float o = a.ld_mode ? ldold[mrow] + o0 : o0;
+      if (NL > 1) o += a.ld_sign * (ld_acc + ldt[(NL - 1) * kSet + mrow]);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), lr, mrow * 4, 0, 0);
     }
     {
       constexpr int D4 = D / 4;
@@ -694,6 +787,43 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   if (INV && a.bad && bad) atomicAdd(a.bad, 1);
 }
 
+#if VCNF_V6_PAIR
+// two layers per tile visit (sa.n_layers == 2); VCNF_ERR_UNSUPPORTED where two table sets do not fit the LDS
+// (LdsV6Pair::FITS, the answer of vcnf_rqs_pair_fused_supported: fused_layer.hip asks before it comes here)
+template <int DI, int DT, int C, int H, int NBLK, int K>
+static int launch_v6_pair(const FusedStackArgs& sa, int inverse, hipStream_t st) {
+  using S = LdsV6Pair<DI, DT, C, H, NBLK, K>;
+  if constexpr (!S::FITS) {
+    return VCNF_ERR_UNSUPPORTED;
+  } else {
+    constexpr int TILE = 128;
+    constexpr size_t lds = S::BYTES;
+    if (sa.n_layers != 2) return VCNF_ERR_SHAPE;
+    const bool set = inverse ? lds_limit_once<&fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, true>>(lds)
+                             : lds_limit_once<&fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, false>>(lds);
+    if (!set) return VCNF_ERR_LAUNCH;
+    const long long ntiles = (sa.a.B + TILE - 1) / TILE;
+    dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
+    if (inverse)
+      hipLaunchKernelGGL((fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, sa VCNF_TIME_ARG);
+    else
+      hipLaunchKernelGGL((fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, sa VCNF_TIME_ARG);
+    return launched();
+  }
+}
+
+template <int NBLK>
+static int launch_v6_pair_family(const FusedStackArgs& sa, int d_id, int ctx_dim, int inverse, hipStream_t st) {
+  return with_fused_shape(d_id, ctx_dim,
+                          [&](auto DI, auto C) { return launch_v6_pair<DI(), DI(), C(), 128, NBLK, 8>(sa, inverse, st); });
+}
+
+// One translation unit per number of residual blocks (-DVCNF_V6_NBLK=1|2|3).
+#ifndef VCNF_V6_NBLK
+#define VCNF_V6_NBLK 2
+#endif
+VCNF_BLOCKS_ENTRY(launch_fused_v6_pair_b, VCNF_V6_NBLK, FusedStackArgs, launch_v6_pair_family)
+#else
 template <int DI, int DT, int C, int H, int NBLK, int K>
 static int launch_v6(const FusedArgs& a, int inverse, hipStream_t st) {
   constexpr int TILE = 128;
@@ -726,5 +856,7 @@ static int launch_v6_family(const FusedArgs& a, int d_id, int ctx_dim, int inver
 #define VCNF_V6_NBLK 2
 #endif
 VCNF_BLOCKS_ENTRY(launch_fused_v6_b, VCNF_V6_NBLK, FusedArgs, launch_v6_family)
+
+#endif  // VCNF_V6_PAIR
 
 }  // namespace vcnf

@@ -1,7 +1,8 @@
-// Dynamic-LDS layouts of the three fused RQS layer kernels, each stated once: the kernel takes its pointers from the
-// offsets, its launcher takes BYTES.  Offsets and sizes are in floats (4 bytes), BYTES in bytes; a region named X has
-// X (offset) and X_N (floats).  Plain C++17 without a HIP include, so that a host program can compile and test it on
-// its own (tests/c_host/fused_lds_check.cpp).  Template parameters as the kernels': DI identity features, DT
+// Dynamic-LDS layouts of the three fused RQS layer kernels and of the 128-sample kernel's two-layer form, each stated
+// once: the kernel takes its pointers from the offsets, its launcher takes BYTES.  Offsets and sizes are in floats (4
+// bytes), BYTES in bytes; a region named X has X (offset) and X_N (floats).  Plain C++17 without a HIP include, so that a
+// host program can compile and test it on its own (tests/c_host/fused_lds_check.cpp, fused_lds_pair_check.cpp).
+// Template parameters as the kernels': DI identity features, DT
 // transformed features, C context features, H hidden units, NBLK residual blocks, K bins.
 #pragma once
 
@@ -36,6 +37,34 @@ struct LdsV6 {
                     LDOLD + LDOLD_N <= TFLAG && (size_t)(TFLAG + TFLAG_N) * 4 <= BYTES,
                 "regions in order, none overlaps the next, the last ends within BYTES");
   static_assert(XT % 4 == 0 && CTXF % 4 == 0 && TAB % 4 == 0, "16-byte aligned rows and fragments");
+};
+
+// fused_rqs_layer_v6_pair_kernel (fused_layer_v6_pair.hip): LdsV6 with the per-layer tables (knot tables, identity-half
+// log|det|, index vectors, bias planes) twice, SET floats apart: layer l of the pair adds l * SET to every table
+// address.  Where BYTES exceeds kLdsMaxBytes the pair kernel does not exist (FITS).
+constexpr size_t kLdsMaxBytes = 160 * 1024;
+template <int DI, int DT, int C, int H, int NBLK, int K>
+struct LdsV6Pair {
+  using One = LdsV6<DI, DT, C, H, NBLK, K>;
+  static constexpr int TILE = One::TILE, D = One::D, NG = One::NG, NBT = One::NBT, BPL = One::BPL;
+  static constexpr int FRAG = One::FRAG, FRAG_N = One::FRAG_N, XT = One::XT, XT_N = One::XT_N;
+  static constexpr int CTXF = One::CTXF, CTXF_N = One::CTXF_N;
+  static constexpr int TAB = One::TAB, TAB_N = One::TAB_N, LDT = One::LDT, LDT_N = One::LDT_N;      // set 0, as LdsV6
+  static constexpr int TFI = One::TFI, TFI_N = One::TFI_N, IDI = One::IDI, IDI_N = One::IDI_N;
+  static constexpr int BIAS = One::BIAS, BIAS_N = One::BIAS_N;
+  static constexpr int SET = BIAS + BIAS_N - TAB;                               // tab | ldt | tfi | idi | bias planes
+  static constexpr int SET1 = TAB + SET;                                        // set 1: the same five, SET further
+  static constexpr int LDOLD = SET1 + SET, LDOLD_N = TILE;
+  static constexpr int TFLAG = LDOLD + LDOLD_N, TFLAG_N = 1;
+  static constexpr int END = TFLAG + TFLAG_N;
+  static constexpr size_t SLACK_BYTES = One::SLACK_BYTES;
+  static constexpr size_t BYTES = (size_t)END * 4 + SLACK_BYTES;
+  static constexpr bool FITS = BYTES <= kLdsMaxBytes;
+  static_assert(SET == TAB_N + LDT_N + TFI_N + IDI_N + BIAS_N && TAB + TAB_N <= LDT && LDT + LDT_N <= TFI &&
+                    TFI + TFI_N <= IDI && IDI + IDI_N <= BIAS && CTXF + CTXF_N <= TAB && TAB + SET <= SET1 &&
+                    SET1 + SET <= LDOLD && LDOLD + LDOLD_N <= TFLAG && (size_t)(TFLAG + TFLAG_N) * 4 <= BYTES,
+                "regions in order, a set is its five regions and nothing else, none overlaps the next, the last ends within BYTES");
+  static_assert(SET % 4 == 0 && SET1 % 4 == 0, "16-byte aligned tables in both sets");
 };
 
 // fused_rqs_layer_v6s_kernel (fused_layer_v6s.hip): 32-sample tiles, two sets of per-layer tables

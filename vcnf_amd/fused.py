@@ -272,7 +272,7 @@ def run(coupling, inputs, context, sampling, log_q=None, sign=1.0):
                                 wpack_f32=packed_weights(coupling, PREC_F32, key) if safe else None)
 
 
-# ---------------------------------------------------------------- runs of layers in one launch (small batches)
+# ---------------------------------------------------------------- runs of layers in one launch
 def _stack_sig(coupling, context):
     """What must agree between the layers of one launch: shape, conditioner structure, spline configuration, matrix
     path, range policy; None for a layer the fused kernels do not cover."""
@@ -286,15 +286,24 @@ def _stack_sig(coupling, context):
             tuple(getattr(cfg, f) for f, _ in cfg._fields_))
 
 
+def _pair_form(sig):
+    """Above the small-batch threshold: the 128-sample-tile kernel takes a run of exactly two layers per tile visit, on
+    the split-half matrix path, where both layers' tables fit its LDS (csrc/fused_layer_v6_pair.hip)."""
+    d_id, d_t, ctx_dim, hidden, blocks, prec = sig[:6]
+    return prec == PREC_F16X3 and bool(_lib.lib().vcnf_rqs_pair_fused_supported(d_id, d_t, ctx_dim, hidden, blocks))
+
+
 def plan_stack(order, start, z, context):
-    """Longest run order[start:end] (at least two, at most the kernel's limit) of CoupledRationalQuadraticSpline layers
-    that one launch of vcnf_rqs_stack_fused_f32 evaluates, or None: 2-D fp32 inputs on the device, no gradient
-    required, a batch small enough for the 32-sample-tile kernel, every layer fused-eligible with ONE shape, spline
-    configuration and matrix path.  Returns (end, couplings, signature)."""
+    """Run order[start:end] of CoupledRationalQuadraticSpline layers that one launch of vcnf_rqs_stack_fused_f32
+    evaluates, or None: 2-D fp32 inputs on the device, no gradient required, every layer fused-eligible with ONE shape,
+    spline configuration and matrix path.  Up to the small-batch threshold the longest such run (at least two, at most
+    the kernel's limit) on the 32-sample-tile kernel; above it exactly two layers where the shape has the pair form
+    (an odd layer at the end takes the one-layer launch).  Returns (end, couplings, signature)."""
     from .flows.neural_spline.wrapper import CoupledRationalQuadraticSpline
-    if z.dim() != 2 or z.dtype != torch.float32 or not z.is_cuda or z.shape[0] > _lib.small_batch_rows():
+    if z.dim() != 2 or z.dtype != torch.float32 or not z.is_cuda:
         return None
-    lim = int(_lib.lib().vcnf_rqs_stack_fused_max_layers())
+    large = z.shape[0] > _lib.small_batch_rows()
+    lim = 2 if large else int(_lib.lib().vcnf_rqs_stack_fused_max_layers())
     run, sig = [], None
     for flow in order[start:start + lim]:
         if type(flow) is not CoupledRationalQuadraticSpline:
@@ -307,7 +316,7 @@ def plan_stack(order, start, z, context):
             break
         sig = s
         run.append(cp)
-    if len(run) < 2:
+    if len(run) < 2 or (large and not _pair_form(sig)):
         return None
     return start + len(run), run, sig
 
