@@ -23,19 +23,18 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]
-from vcnf_amd.build import UNITS as BUILD_UNITS   # (source, extra flags, object name): the build's own list
+from vcnf_amd.build import FLAGS as BUILD_FLAGS, UNITS as BUILD_UNITS   # the build's own flags and (source, extra flags, name)s
 
 # the units that include rqs_host.hpp, host_common.hpp, fused_common.hpp or split_half.hpp, directly or through
 # rqs_math.hpp / stream_common.hpp, and the units that take a limit or a code from include/vcnf_hip.h
 # (profiles/abi_single_source.md section 3)
 CHECKED = ("rqs_kernels.hip", "rqs_backward.hip", "rqs_f64.hip", "fused_layer.hip", "fused_final.hip",
-           "fused_layer_v6.hip", "fused_layer_v6s.hip", "affine_kernels.hip", "class_cond_gaussian.hip",
-           "gaussian_mixture.hip", "heavy_tail.hip", "conv1x1.hip", "conv3x3_1x1.hip", "linear_f16x3.hip",
+           "fused_layer_v6.hip", "fused_layer_v6_pair.hip", "fused_layer_v6s.hip", "affine_kernels.hip",
+           "class_cond_gaussian.hip", "gaussian_mixture.hip", "heavy_tail.hip", "conv1x1.hip", "conv3x3_1x1.hip", "linear_f16x3.hip",
            "linear_wgrad.hip", "resnet_trunk.hip", "fused_affine.hip", "gemm_probe.hip", "channel_mix.hip",
            "mvn_base.hip", "planar_radial.hip", "stochastic.hip", "target_density.hip", "vae_ends.hip", "periodic.hip")
 UNITS = sorted(((s, e) for s, e, _ in BUILD_UNITS if s in CHECKED), key=lambda u: CHECKED.index(u[0]))
-# the flags of every unit as vcnf_amd/build.py build() sets them (a local of that function: keep the two alike)
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S"]
+FLAGS = BUILD_FLAGS + ["--cuda-device-only", "-S"]
 
 
 def kernels(path):

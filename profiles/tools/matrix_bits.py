@@ -1,5 +1,5 @@
 """Result bits of the matrix units (csrc/conv1x1.hip, conv3x3_1x1.hip and the fused RQS layer kernels fused_layer_v6.hip,
-fused_layer_v6s.hip, fused_layer.hip) and of the composed RQS coupling around them, for comparing two builds or two
+fused_layer_v6_pair.hip, fused_layer_v6s.hip, fused_layer.hip) and of the composed RQS coupling around them, for comparing two builds or two
 checkouts (VCNF_ROOT), modelled on stream_bits.py.
 
     python profiles/tools/matrix_bits.py --out DIR          # on a GPU: every output's raw bytes, one file each
@@ -129,6 +129,24 @@ def fused_rqs(L):
             assert sig is not None and sig == fused._stack_sig(run[1], c)
             for sampling in (False, True):
                 save("rqs_stack2_%s_%s" % (prec, "inv" if sampling else "fwd"), *fused.run_stack(run, sig, x, c, sampling, None, 1.0))
+        # two layers above the small-batch threshold on the split-half path, one full 128-sample tile + 1 row: both layers
+        # per tile visit (fused_layer_v6_pair.hip) where the shape has the pair form, else one launch per layer - what
+        # fused.plan_stack decides
+        L.small_batch_rows(0)
+        for d, ctx, blocks, pair in ((32, 0, 1, True), (64, 0, 3, True), (64, 16, 2, True), (64, 16, 3, False)):
+            run = [_coupling(d, ctx, blocks, 5000 + 1000 * d + 10 * ctx + blocks + s) for s in (0, 100)]
+            for cp in run:
+                cp.fused_precision = 'fp16x3'
+            x, c = rnd(129, d), (rnd(129, ctx) if ctx else None)
+            sig = fused._stack_sig(run[0], c)
+            assert sig is not None and sig == fused._stack_sig(run[1], c) and fused._pair_form(sig) == pair
+            for sampling in (False, True):
+                if pair:
+                    out = fused.run_stack(run, sig, x, c, sampling, None, 1.0)
+                else:
+                    y, ld = fused.run(run[0], x, c, sampling)
+                    out = fused.run(run[1], y, c, sampling, log_q=ld)
+                save("rqs_pair_d%d_c%d_n%d_%s" % (d, ctx, blocks, "inv" if sampling else "fwd"), *out)
     finally:
         L.small_batch_rows(prev)
 

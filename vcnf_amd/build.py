@@ -25,6 +25,8 @@ UNITS = [(s, NO_SLP if s == "fused_final.hip" else [], os.path.splitext(s)[0]) f
         [("fused_layer_v6_pair.hip", ["-DVCNF_V6_NBLK=%d" % n] + NO_SLP, "fused_layer_v6_pair_b%d" % n) for n in (2, 3, 1)] + \
         [("fused_layer_v6s.hip", ["-DVCNF_V6_NBLK=%d" % n] + NO_SLP, "fused_layer_v6s_b%d" % n) for n in (2, 3, 1)] + \
         [("fused_layer.hip", ["-DVCNF_F32_NBLK=%d" % n], "fused_layer_f32_b%d" % n) for n in (3, 1)]
+# what every unit is compiled with (profiles/tools/isa_kernel_diff.py compiles with the same)
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 HEADERS = ["rqs_math.hpp", "rqs_vjp.hpp", "rqs_lean.hpp", "fused_common.hpp", "fused_lds.hpp", "split_half.hpp", "stream_common.hpp", "mvn_lds.hpp", "target_math.hpp",
            "rqs_host.hpp", "host_common.hpp", os.path.join("..", "..", "include", "vcnf_hip.h")]
 
@@ -33,7 +35,7 @@ def stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + ["fused_layer_v6s.hip", "fused_layer_v6_pair.hip"] + HEADERS)
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in sorted({s for s, _, _ in UNITS}) + HEADERS)
 
 
 def build(force=False, verbose=False):
@@ -42,7 +44,6 @@ def build(force=False, verbose=False):
     if not force and not stale():
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
     jobs = max(1, min(len(UNITS), int(os.environ.get("VCNF_BUILD_JOBS", os.cpu_count() or 1))))
     keep = os.environ.get("VCNF_OBJ_DIR")            # keep the object files (variant links of one unit)
     if keep:
@@ -53,7 +54,7 @@ def build(force=False, verbose=False):
         def compile_one(unit):
             src, extra, name = unit
             obj = os.path.join(tmp, name + ".o")
-            cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
+            cmd = [hipcc] + FLAGS + extra + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, cwd=CSRC, check=True)

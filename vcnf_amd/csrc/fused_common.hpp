@@ -1,8 +1,9 @@
 // Shared pieces of the fused RQS-layer kernels (fused_layer.hip: exact fp32 matrix path; fused_layer_v6.hip,
 // fused_layer_v6s.hip: fp16x3 split-half matrix path): argument structs, packed-weight layouts, LDS layouts
-// (fused_lds.hpp), the shape-family dispatch and the per-block-count entry points.  Its vector types, kLoScale, split4,
-// wload and dma16_to_lds also serve fused_final.hip, resnet_trunk.hip and channel_mix.hip, and - beside split_half.hpp -
-// fused_affine.hip, linear_f16x3.hip, linear_wgrad.hip, gemm_probe.hip, conv1x1.hip and conv3x3_1x1.hip.
+// (fused_lds.hpp), the shape-family dispatch, the per-block-count entry points and the split-half kernels' barrier
+// (VCNF_SYNC).  Its vector types, kLoScale, split4, wload and dma16_to_lds also serve fused_final.hip, resnet_trunk.hip
+// and channel_mix.hip, and - beside split_half.hpp - fused_affine.hip, linear_f16x3.hip, linear_wgrad.hip,
+// gemm_probe.hip, conv1x1.hip and conv3x3_1x1.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,6 +80,17 @@ __device__ __forceinline__ void dma16_to_lds(__amdgpu_buffer_rsrc_t rsrc, void* 
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voff, soff, 0, 0);
 }
 __device__ __forceinline__ void wait_vector_memory() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // vmcnt(0)
+
+// Workgroup barrier of the split-half layer kernels (fused_layer_v6.hip, fused_layer_v6s.hip).  Not __syncthreads():
+// its release fence drains EVERY outstanding vector-memory operation (s_waitcnt vmcnt(0)) in front of every barrier -
+// the next layer's weights requested in this step, the next tile's rows - and puts their latency into every step.
+// What the steps exchange through the barrier is LDS data only: the wave's LDS operations are complete (lgkmcnt(0)),
+// window pieces written by buffer_load ... lds are waited for explicitly by the wave that requested them
+// (wait_vector_memory).  The inline assembly is opaque to the compiler (memory clobber: no access moves across it) and
+// fenced for the instruction scheduler (matrix instructions are no memory operations and were otherwise sunk below the
+// barrier that ends their step, into the vector step, where the next layer's weights are already being loaded: both
+// weight sets live, spills).
+#define VCNF_SYNC() { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
 
 // Packed weight buffer of one layer, in floats (host side: vcnf_amd/fused.py::pack_layer):
 //   W0 [NB][NS0/4][64][4] | b0 [H] | per block: WA [NB][NSH/4][64][4] | ba [H] |

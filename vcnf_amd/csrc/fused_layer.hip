@@ -338,22 +338,16 @@ __global__ __launch_bounds__(kFBlock, 2) void fused_rqs_layer_kernel(const Fused
 
 template <int DI, int DT, int C, int H, int NBLK, int K, int kCB>
 static int launch_fused(const FusedStackArgs& sa, int inverse, hipStream_t st) {
-  const FusedArgs& a = sa.a;
   constexpr int kTile = 4 * kCB * 16;
   constexpr size_t lds = LdsF32<DI, DT, C, H, NBLK, K, kCB>::BYTES;  // below 64 KB: no limit to raise
-  const long long ntiles = (a.B + kTile - 1) / kTile;
   const long long resident = 256 * 2;   // workgroups the chip holds at once
-  dim3 grid((unsigned)(ntiles < resident ? ntiles : resident));
-  if (sa.n_layers > 1) {
-    if (inverse)
-      hipLaunchKernelGGL((fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, true, kCB, true>), grid, dim3(kFBlock), lds, st, sa);
-    else
-      hipLaunchKernelGGL((fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, false, kCB, true>), grid, dim3(kFBlock), lds, st, sa);
-  } else if (inverse)
-    hipLaunchKernelGGL((fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, true, kCB, false>), grid, dim3(kFBlock), lds, st, sa);
-  else
-    hipLaunchKernelGGL((fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, false, kCB, false>), grid, dim3(kFBlock), lds, st, sa);
-  return launched();
+  if (sa.n_layers > 1)                  // the instances with the layer loop
+    return launch_tiled<&fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, true, kCB, true>,
+                        &fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, false, kCB, true>, kTile, kFBlock, lds>(
+        inverse, sa.a.B, resident, st, sa);
+  return launch_tiled<&fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, true, kCB, false>,
+                      &fused_rqs_layer_kernel<DI, DT, C, H, NBLK, K, false, kCB, false>, kTile, kFBlock, lds>(
+      inverse, sa.a.B, resident, st, sa);
 }
 
 // Shape family of the exact fp32 kernel: (d_id = d_t, ctx) with H = 128, 8 bins, NBLK residual blocks.
@@ -423,24 +417,22 @@ extern "C" int vcnf_rqs_pair_fused_supported(int32_t d_id, int32_t d_t, int32_t 
   return fits;
 }
 
+// The per-block-count entry (VCNF_BLOCKS_ENTRY) of a run-time block count; the entry points have validated 1 .. 3.
+template <class Entry>
+static Entry* by_blocks(int num_blocks, Entry* b1, Entry* b2, Entry* b3) {
+  return num_blocks == 1 ? b1 : num_blocks == 2 ? b2 : b3;
+}
+
 // sa.n_layers == 1: one layer; 2 above the small-batch threshold where the shape has the pair form: both layers per
 // tile visit of the 128-sample kernel (fused_layer_v6_pair.hip); any other run of layers: the small-batch kernel (the
 // 128-sample kernel has no longer layer loop)
 static int launch_f16x3(const FusedStackArgs& sa, int d_id, int ctx_dim, int num_blocks, int inverse, hipStream_t st) {
   if (sa.n_layers == 2 && sa.a.B > g_small_batch_rows &&
-      vcnf_rqs_pair_fused_supported(d_id, d_id, ctx_dim, 128, num_blocks)) {
-    if (num_blocks == 1) return launch_fused_v6_pair_b1(sa, d_id, ctx_dim, inverse, st);
-    if (num_blocks == 2) return launch_fused_v6_pair_b2(sa, d_id, ctx_dim, inverse, st);
-    return launch_fused_v6_pair_b3(sa, d_id, ctx_dim, inverse, st);
-  }
-  if (sa.n_layers > 1 || sa.a.B <= g_small_batch_rows) {
-    if (num_blocks == 1) return launch_fused_v6s_b1(sa, d_id, ctx_dim, inverse, st);
-    if (num_blocks == 2) return launch_fused_v6s_b2(sa, d_id, ctx_dim, inverse, st);
-    return launch_fused_v6s_b3(sa, d_id, ctx_dim, inverse, st);
-  }
-  if (num_blocks == 1) return launch_fused_v6_b1(sa.a, d_id, ctx_dim, inverse, st);
-  if (num_blocks == 2) return launch_fused_v6_b2(sa.a, d_id, ctx_dim, inverse, st);
-  return launch_fused_v6_b3(sa.a, d_id, ctx_dim, inverse, st);
+      vcnf_rqs_pair_fused_supported(d_id, d_id, ctx_dim, 128, num_blocks))
+    return by_blocks(num_blocks, launch_fused_v6_pair_b1, launch_fused_v6_pair_b2, launch_fused_v6_pair_b3)(sa, d_id, ctx_dim, inverse, st);
+  if (sa.n_layers > 1 || sa.a.B <= g_small_batch_rows)
+    return by_blocks(num_blocks, launch_fused_v6s_b1, launch_fused_v6s_b2, launch_fused_v6s_b3)(sa, d_id, ctx_dim, inverse, st);
+  return by_blocks(num_blocks, launch_fused_v6_b1, launch_fused_v6_b2, launch_fused_v6_b3)(sa.a, d_id, ctx_dim, inverse, st);
 }
 
 static int run_stack(const float* x, const float* context, float* y, float* logdet, int64_t batch,
@@ -485,9 +477,7 @@ static int run_stack(const float* x, const float* context, float* y, float* logd
   }
   hipStream_t st = (hipStream_t)stream;
   if (precision == VCNF_PREC_F16X3) return launch_f16x3(sa, d_id, ctx_dim, num_blocks, inverse, st);
-  if (num_blocks == 1) return launch_fused_f32_b1(sa, d_id, ctx_dim, inverse, st);
-  if (num_blocks == 3) return launch_fused_f32_b3(sa, d_id, ctx_dim, inverse, st);
-  return launch_fused_f32_family<2>(sa, d_id, ctx_dim, inverse, st);
+  return by_blocks(num_blocks, launch_fused_f32_b1, launch_fused_f32_family<2>, launch_fused_f32_b3)(sa, d_id, ctx_dim, inverse, st);
 }
 
 extern "C" int32_t vcnf_rqs_stack_fused_max_layers(void) { return kMaxStackLayers; }

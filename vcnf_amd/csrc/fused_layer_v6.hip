@@ -47,19 +47,12 @@
 #include "rqs_lean.hpp"
 #include "split_half.hpp"
 
-#ifndef VCNF_ABL
-#define VCNF_ABL 0
-#endif
 // -DVCNF_TIME=1: s_memtime stamps at every barrier; waves 0 (group A) and 4 (group B) of workgroup 0 leave their
 // per-phase sums in a buffer of the timing build's own (kTimeSlots floats per wave; results are untouched), read
 // through vcnf_v6_phase_stamps by profiles/tools/v6_phase_timing.py.  Slots: 0-13 the steps in program order, 15 all
 // barriers between steps, 16-19 the four waits that shift group B one step behind group A and re-align them.
 #ifndef VCNF_TIME
 #define VCNF_TIME 0
-#endif
-// operand fragments are requested VCNF_AHEAD steps (of three matrix instructions) before their use
-#ifndef VCNF_AHEAD
-#define VCNF_AHEAD 1
 #endif
 // -DVCNF_V6_PAIR=1 (fused_layer_v6_pair.hip): this body compiled as fused_rqs_layer_v6_pair_kernel, which applies TWO
 // consecutive layers of one shape to every tile it visits: rows and context enter LDS once, layer 1's identity phase
@@ -78,16 +71,6 @@
 #define VCNF_TIME_PARAM
 #define VCNF_TIME_ARG
 #endif
-
-// Workgroup barrier.  Not __syncthreads(): its release fence drains EVERY outstanding vector-memory operation
-// (s_waitcnt vmcnt(0)) in front of every barrier - the next layer's weights requested in this step, the next
-// tile's rows - and puts their latency into every step.  What the steps exchange through the barrier is LDS data
-// only: the wave's LDS operations are complete (lgkmcnt(0)), window pieces written by buffer_load ... lds are
-// waited for explicitly by the wave that requested them (wait_vector_memory).  The inline assembly is opaque to
-// the compiler (memory clobber: no access moves across it) and fenced for the instruction scheduler (matrix
-// instructions are no memory operations and were otherwise sunk below the barrier that ends their step, into the
-// vector step, where the next layer's weights are already being loaded: both weight sets live, spills).
-#define VCNF_SYNC() { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
 
 namespace vcnf {
 
@@ -150,7 +133,8 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   constexpr int TABW = 3 * (K + 1);
   using L = PackLayout6<DI, DT, C, H, NBLK, K>;
   constexpr int GFRAG = 3 * NTH * 2 * 64;   // 16-byte fragments of one feature group (48 KB)
-  constexpr int RING = VCNF_AHEAD + 1;
+  constexpr int AHEAD = 1;                  // operand fragments are requested AHEAD steps (of 3 matrix instructions) early
+  constexpr int RING = AHEAD + 1;
 
   extern __shared__ __align__(16) float smem[];
   using S = VCNF_V6_LDS<DI, DT, C, H, NBLK, K>;             // the regions, their offsets and the launch's byte count
@@ -291,17 +275,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
         const int r = tidp >> 2, part = tidp & 3;
         half4 h4, l4;
         const float cv[4] = {cpre[0].x, cpre[0].y, cpre[0].z, cpre[0].w};
-        // raw inputs: a NaN counts as out of range too (fmaxf drops NaNs; the reference propagates them)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) satm = fmaxf(satm, cv[i] == cv[i] ? __builtin_fabsf(cv[i]) : __builtin_inff());
-        asm volatile("" : "+v"(satm));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float x = __builtin_amdgcn_fmed3f(cv[i], -65504.f, 65504.f);
-          const _Float16 hv = (_Float16)x;
-          h4[i] = hv;
-          l4[i] = (_Float16)((x - (float)hv) * kLoScale);
-        }
+        split4_raw(cv, h4, l4, satm);
         const int at = (((r >> 5) * 2) * 64 + (r & 31) + 32 * (part >> 1));          // uint4 index of the hi fragment entry
         uint2* dh = reinterpret_cast<uint2*>(ctxf + at) + (part & 1);
         uint2* dl = reinterpret_cast<uint2*>(ctxf + at + 64) + (part & 1);
@@ -395,6 +369,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
         satm = fmaxf(fmaxf(satm, __builtin_fabsf(fv[0])), __builtin_fabsf(fv[1]));
         satm = fmaxf(fmaxf(satm, __builtin_fabsf(fv[2 < UNR ? 2 : 0])), __builtin_fabsf(fv[3 < UNR ? 3 : 0]));
         asm volatile("" : "+v"(satm));
+        // (the plain splits of split4_raw, written out: through a function the two-layer kernels come out on other registers)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float x = __builtin_amdgcn_fmed3f(fv[i < UNR ? i : 0], -65504.f, 65504.f);
@@ -413,10 +388,8 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     half8 ahi[NTH], alo[NTH];
     floatx16 abias;
 #define VCNF_LOAD_BIAS16(DST, VEC)                                                        \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                      \
-    const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bpl + NG * 48 + (VEC) * (H / 2) + 16 * rp + 4 * i_); \
-    DST[4 * i_ + 0] = b4_[0]; DST[4 * i_ + 1] = b4_[1]; DST[4 * i_ + 2] = b4_[2]; DST[4 * i_ + 3] = b4_[3]; \
-  }
+  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                        \
+    set_quad(DST, i_, *reinterpret_cast<const floatx4*>(bpl + NG * 48 + (VEC) * (H / 2) + 16 * rp + 4 * i_));
 #define VCNF_LOAD_HIDDEN(WOFF, BVEC)                                                      \
   {                                                                                       \
     _Pragma("unroll") for (int t = 0; t < NTH; ++t) {                                     \
@@ -445,11 +418,9 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
         for (int t = 0; t < NT0; ++t) {
           const half8 bh = __builtin_bit_cast(half8, t < NTX ? act_hi[(t * NCB + cb) * 64 + lane] : ctxf[(cb * 2 + 0) * 64 + lane]);
           const half8 bl = __builtin_bit_cast(half8, t < NTX ? act_lo[(t * NCB + cb) * 64 + lane] : ctxf[(cb * 2 + 1) * 64 + lane]);
-          mainv = mfma32h(w0h[t], bh, mainv);
-          corr = mfma32h(w0h[t], bl, corr);
-          corr = mfma32h(w0l[t], bh, corr);
-          corr2 = mfma32h(w0l[t], bl, corr2);
+          mfma32h_x4(w0h[t], w0l[t], bh, bl, mainv, corr, corr2);
         }
+        // (not fold_x4: through it the two-block kernels come out on other registers, profiles/fused_leaf_blocks.md)
 #pragma unroll
         for (int r = 0; r < 16; ++r) h[j][r] = fmaf(fmaf(corr2[r], kLoUnscale, corr[r]), kLoUnscale, mainv[r]);
       }
@@ -484,13 +455,13 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
   {                                                                                       \
     half8 rh[RING], rl[RING];                /* ring: step st = 8 j + t uses slot st % RING */ \
     floatx16 corr;                                                                        \
-    _Pragma("unroll") for (int st_ = 0; st_ < VCNF_AHEAD; ++st_) {                        \
+    _Pragma("unroll") for (int st_ = 0; st_ < AHEAD; ++st_) {                             \
       VCNF_READ_B(st_)                                                                    \
     }                                                                                     \
     _Pragma("unroll") for (int st_ = 0; st_ < 2 * NTH; ++st_) {                           \
       const int j = st_ >> 3, tk_ = st_ & 7;                                              \
-      if (st_ + VCNF_AHEAD < 2 * NTH) {                                                   \
-        VCNF_READ_B(st_ + VCNF_AHEAD)                                                     \
+      if (st_ + AHEAD < 2 * NTH) {                                                        \
+        VCNF_READ_B(st_ + AHEAD)                                                          \
       }                                                                                   \
       if (tk_ == 0) {                                                                       \
         OUT[j] = abias;                                                                   \
@@ -500,19 +471,19 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       corr = mfma32h(ahi[tk_], rl[st_ % RING], corr);                                          \
       corr = mfma32h(alo[tk_], rh[st_ % RING], corr);                                          \
       if (tk_ == NTH - 1) {                                                                 \
-        _Pragma("unroll") for (int r = 0; r < 16; ++r) OUT[j][r] = fmaf(corr[r], kLoUnscale, OUT[j][r]); \
+        OUT[j] = fold_x3(OUT[j], corr);                                                   \
       }                                                                                   \
     }                                                                                     \
-    __builtin_amdgcn_sched_group_barrier(0x100, 2 * VCNF_AHEAD, 0);                       \
-    _Pragma("unroll") for (int st_ = 0; st_ + VCNF_AHEAD < 2 * NTH; ++st_) {              \
+    __builtin_amdgcn_sched_group_barrier(0x100, 2 * AHEAD, 0);                            \
+    _Pragma("unroll") for (int st_ = 0; st_ + AHEAD < 2 * NTH; ++st_) {                   \
       __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                                  \
       __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                                  \
     }                                                                                     \
-    __builtin_amdgcn_sched_group_barrier(0x008, 3 * VCNF_AHEAD, 0);                       \
+    __builtin_amdgcn_sched_group_barrier(0x008, 3 * AHEAD, 0);                            \
   }
 
 #pragma unroll
-    for (int blk = 0; blk < (VCNF_ABL == 5 ? 0 : NBLK); ++blk) {
+    for (int blk = 0; blk < NBLK; ++blk) {
       const int base = L::BLK0 + blk * L::BLK;
       floatx16 t[2];
       // ---- step M: first layer of the block                                          resnet.py:42-43
@@ -531,37 +502,26 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       { VCNF_T(6) VCNF_SYNC(); VCNF_T(15) }
       // ---- step M: second layer of the block (:48) and the gate pre-activations (:53)
       VCNF_HIDDEN_COMPUTE(t)
-      if (C > 0 && VCNF_ABL != 6) {
+      if (C > 0) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const half8 bh = __builtin_bit_cast(half8, ctxf[((2 * ch + j) * 2 + 0) * 64 + lane]);
           const half8 bl = __builtin_bit_cast(half8, ctxf[((2 * ch + j) * 2 + 1) * 64 + lane]);
-          // 16-deep layer: the accumulator rounds once, so the operands' 22 bits are what is left of the error -
-          // the lo*lo term is kept like in the first layer (tests/test_gpu_gemm_error.py)
+          // 16-deep layer: the lo*lo term is kept like in the first layer
           floatx16 corr = {}, corr2 = {};
-          gate[j] = mfma32h(wch, bh, gbias);
-          corr = mfma32h(wch, bl, corr);
-          corr = mfma32h(wcl, bh, corr);
-          corr2 = mfma32h(wcl, bl, corr2);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) gate[j][r] = fmaf(fmaf(corr2[r], kLoUnscale, corr[r]), kLoUnscale, gate[j][r]);
+          gate[j] = gbias;
+          mfma32h_x4(wch, wcl, bh, bl, gate[j], corr, corr2);
+          gate[j] = fold_x4(gate[j], corr, corr2);
         }
       }
       { VCNF_T(5) VCNF_SYNC(); VCNF_T(15) }
-      // ---- step V: GLU gate (the packed gate weights carry log2 e: sigmoid(g) = 1 / (1 + 2^-g')),
-      // residual update, publish                                                       :49-57
+      // ---- step V: GLU gate, residual update, publish                                :49-57
       if (blk + 1 < NBLK) {
         VCNF_LOAD_HIDDEN(base + L::BLK + L::WA, 1 + (blk + 1) * NBV)
       }
-      if (C > 0 && VCNF_ABL != 6) {
+      if (C > 0) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float sg = hw_rcp(1.f + hw_exp2(-gate[j][r]));
-            h[j][r] = fmaf(t[j][r], sg, h[j][r]);
-          }
-        }
+        for (int j = 0; j < 2; ++j) h[j] = glu_update(h[j], t[j], gate[j]);
       } else {
 #pragma unroll
         for (int j = 0; j < 2; ++j) h[j] += t[j];
@@ -599,10 +559,8 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     floatx16 pa[3];
 #define VCNF_LOAD_BIASF(G)                                                                \
   _Pragma("unroll") for (int b = 0; b < 3; ++b) {                                         \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                    \
-      const floatx4 b4_ = *reinterpret_cast<const floatx4*>(bpl + (G) * 48 + 16 * b + 4 * i_); \
-      pa[b][4 * i_ + 0] = b4_[0]; pa[b][4 * i_ + 1] = b4_[1]; pa[b][4 * i_ + 2] = b4_[2]; pa[b][4 * i_ + 3] = b4_[3]; \
-    }                                                                                     \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                      \
+      set_quad(pa[b], i_, *reinterpret_cast<const floatx4*>(bpl + (G) * 48 + 16 * b + 4 * i_)); \
   }
     VCNF_LOAD_BIASF(ch)
     { VCNF_T(8) VCNF_SYNC(); VCNF_T(15) }                         // every wave has its operand fragments: the window may be written
@@ -619,7 +577,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     wait_vector_memory();
     { VCNF_T(9) VCNF_SYNC(); VCNF_T(15) }
     if (ch == 1) { VCNF_T(14) VCNF_SYNC(); VCNF_T(18) }            // ---- group B one step behind again
-    for (int rnd = 0; rnd < (VCNF_ABL == 3 ? 0 : NR); ++rnd) {
+    for (int rnd = 0; rnd < NR; ++rnd) {
       const int g = 2 * rnd + ch;
 #if VCNF_V6_PAIR
       // The prefetch registers hold nothing from the tile top to the last round of the last layer: say so in every
@@ -654,31 +612,28 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
     wl[(T) % RING] = __builtin_bit_cast(half8, win[((T) * 2 + 1) * 64 + lane]);           \
   }
 #pragma unroll
-        for (int u = 0; u < VCNF_AHEAD; ++u) {
+        for (int u = 0; u < AHEAD; ++u) {
           VCNF_READ_W(u)
         }
 #pragma unroll
         for (int u = 0; u < 3 * NTH; ++u) {
           const int b = u >> 3, t = u & 7;
-          if (u + VCNF_AHEAD < 3 * NTH) {
-            VCNF_READ_W(u + VCNF_AHEAD)
+          if (u + AHEAD < 3 * NTH) {
+            VCNF_READ_W(u + AHEAD)
           }
           if (t == 0) corr = floatx16{};
           pa[b] = mfma32h(wh[u % RING], fhi[t], pa[b]);
           corr = mfma32h(wh[u % RING], flo[t], corr);
           corr = mfma32h(wl[u % RING], fhi[t], corr);
-          if (t == NTH - 1) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) pa[b][r] = fmaf(corr[r], kLoUnscale, pa[b][r]);
-          }
+          if (t == NTH - 1) pa[b] = fold_x3(pa[b], corr);
         }
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * VCNF_AHEAD, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * AHEAD, 0);
 #pragma unroll
-        for (int u = 0; u + VCNF_AHEAD < 3 * NTH; ++u) {
+        for (int u = 0; u + AHEAD < 3 * NTH; ++u) {
           __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
           __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
         }
-        __builtin_amdgcn_sched_group_barrier(0x008, 3 * VCNF_AHEAD, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 3 * AHEAD, 0);
 #undef VCNF_READ_W
       }
       { VCNF_T(10) VCNF_SYNC(); VCNF_T(15) }
@@ -688,16 +643,14 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
         if (!more && l + 1 == NL) {            // last vector step of the tile: the next tile's rows are requested
           VCNF_PREFETCH_ROWS(tile + gridDim.x)
         }
-        if (more && VCNF_ABL != 2) {
+        if (more) {
           VCNF_STAGE_DMA(g + 2)
         }
         float yv[2], lad[2];
 #pragma unroll
         for (int f2 = 0; f2 < 2; ++f2) {
-          // logits of feature f2: accumulator entries 24 f2 + 0 .. 22 (entry v = register v % 16 of block v / 16)
           float lg[P];
-#pragma unroll
-          for (int tl = 0; tl < P; ++tl) lg[tl] = pa[(24 * f2 + tl) >> 4][(24 * f2 + tl) & 15];
+          acc_logits(pa, f2, lg);
           rqs_lean_eval<8, INV>(xin[f2], lg, lc, yv[f2], lad[f2], bad);
         }
         *px[0] = yv[0];
@@ -709,7 +662,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6_kernel(const FusedA
       }
       // this wave's part of the window must have landed before the other waves of the group read it
       // (vmcnt(0); the loads were requested a whole vector step ago)
-      if (rnd + 1 < NR && VCNF_ABL != 2) wait_vector_memory();
+      if (rnd + 1 < NR) wait_vector_memory();
       { VCNF_T(11) VCNF_SYNC(); VCNF_T(15) }
     }
     if (ch == 0) { VCNF_T(14) VCNF_SYNC(); VCNF_T(19) }            // ---- groups re-aligned: every spline of the tile is done
@@ -796,19 +749,10 @@ static int launch_v6_pair(const FusedStackArgs& sa, int inverse, hipStream_t st)
   if constexpr (!S::FITS) {
     return VCNF_ERR_UNSUPPORTED;
   } else {
-    constexpr int TILE = 128;
-    constexpr size_t lds = S::BYTES;
     if (sa.n_layers != 2) return VCNF_ERR_SHAPE;
-    const bool set = inverse ? lds_limit_once<&fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, true>>(lds)
-                             : lds_limit_once<&fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, false>>(lds);
-    if (!set) return VCNF_ERR_LAUNCH;
-    const long long ntiles = (sa.a.B + TILE - 1) / TILE;
-    dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
-    if (inverse)
-      hipLaunchKernelGGL((fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, sa VCNF_TIME_ARG);
-    else
-      hipLaunchKernelGGL((fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, sa VCNF_TIME_ARG);
-    return launched();
+    return launch_tiled<&fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, true>,
+                        &fused_rqs_layer_v6_pair_kernel<DI, DT, C, H, NBLK, K, false>, 128, 512, S::BYTES>(
+        inverse, sa.a.B, 256, st, sa VCNF_TIME_ARG);
   }
 }
 
@@ -826,29 +770,16 @@ VCNF_BLOCKS_ENTRY(launch_fused_v6_pair_b, VCNF_V6_NBLK, FusedStackArgs, launch_v
 #else
 template <int DI, int DT, int C, int H, int NBLK, int K>
 static int launch_v6(const FusedArgs& a, int inverse, hipStream_t st) {
-  constexpr int TILE = 128;
-  constexpr size_t lds = LdsV6<DI, DT, C, H, NBLK, K>::BYTES;
-  const bool set = inverse ? lds_limit_once<&fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>>(lds)
-                           : lds_limit_once<&fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>>(lds);
-  if (!set) return VCNF_ERR_LAUNCH;
-  const long long ntiles = (a.B + TILE - 1) / TILE;
-  dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
-  if (inverse)
-    hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, a VCNF_TIME_ARG);
-  else
-    hipLaunchKernelGGL((fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, a VCNF_TIME_ARG);
-  return launched();
+  return launch_tiled<&fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, true>,
+                      &fused_rqs_layer_v6_kernel<DI, DT, C, H, NBLK, K, false>, 128, 512,
+                      LdsV6<DI, DT, C, H, NBLK, K>::BYTES>(inverse, a.B, 256, st, a VCNF_TIME_ARG);
 }
 
 // Shape family of the fused fp16 split-half kernel: (d_id = d_t, ctx, residual blocks) with H = 128, 8 bins.
 template <int NBLK>
 static int launch_v6_family(const FusedArgs& a, int d_id, int ctx_dim, int inverse, hipStream_t st) {
-#ifdef VCNF_DEV_ONLY
-  return launch_v6<32, 32, 16, 128, NBLK, 8>(a, inverse, st);
-#else
   return with_fused_shape(d_id, ctx_dim,
                           [&](auto DI, auto C) { return launch_v6<DI(), DI(), C(), 128, NBLK, 8>(a, inverse, st); });
-#endif
 }
 
 // One translation unit per number of residual blocks (-DVCNF_V6_NBLK=1|2|3).

@@ -27,9 +27,6 @@
 #include "rqs_lean.hpp"
 #include "split_half.hpp"
 
-// workgroup barrier that waits for LDS traffic only (see fused_layer_v6.hip)
-#define VCNF_SYNC() { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
-
 // -DVCNF_TIME=1 (timing builds only, profiles/tools/v6s_phase_timing.py): waves 0 and 4 of workgroup 0 stamp the
 // 100 MHz wall clock and the shader clock at every phase boundary and leave them in the first output rows
 #ifndef VCNF_TIME
@@ -42,14 +39,6 @@
 #endif
 
 namespace vcnf {
-
-// hi / lo halves of one value, the arithmetic of split8 (split_half.hpp)
-template <bool RELU>
-__device__ __forceinline__ void split1(float v, _Float16& hi, _Float16& lo) {
-  const float x = __builtin_amdgcn_fmed3f(v, RELU ? 0.f : -65504.f, 65504.f);
-  hi = (_Float16)x;
-  lo = (_Float16)__builtin_fmaf((float)hi, -kLoScale, x * kLoScale);
-}
 
 template <int DI, int DT, int C, int H, int NBLK, int K, bool INV>
 __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const FusedStackArgs sa) {
@@ -216,17 +205,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
         const int r = tid >> 2, part = tid & 3;
         half4 h4, l4;
         const float cv[4] = {cpre.x, cpre.y, cpre.z, cpre.w};
-        // raw inputs: a NaN counts as out of range too (fmaxf drops NaNs; the reference propagates them)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) satm = fmaxf(satm, cv[i] == cv[i] ? __builtin_fabsf(cv[i]) : __builtin_inff());
-        asm volatile("" : "+v"(satm));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float x = __builtin_amdgcn_fmed3f(cv[i], -65504.f, 65504.f);
-          const _Float16 hv = (_Float16)x;
-          h4[i] = hv;
-          l4[i] = (_Float16)((x - (float)hv) * kLoScale);
-        }
+        split4_raw(cv, h4, l4, satm);
         const int at = r + 32 * (part >> 1);                  // uint4 index of the hi fragment entry
         uint2* dh = reinterpret_cast<uint2*>(ctxf + at) + (part & 1);
         uint2* dl = reinterpret_cast<uint2*>(ctxf + at + 64) + (part & 1);
@@ -311,10 +290,8 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
 #pragma unroll
       for (int b = 0; b < 3; ++b) {
 #pragma unroll
-        for (int i_ = 0; i_ < 4; ++i_) {
-          const floatx4 b4_ = *reinterpret_cast<const floatx4*>(biasf + g * 96 + kg * 48 + 16 * b + 4 * i_);
-          pa[b][4 * i_ + 0] = b4_[0]; pa[b][4 * i_ + 1] = b4_[1]; pa[b][4 * i_ + 2] = b4_[2]; pa[b][4 * i_ + 3] = b4_[3];
-        }
+        for (int i_ = 0; i_ < 4; ++i_)
+          set_quad(pa[b], i_, *reinterpret_cast<const floatx4*>(biasf + g * 96 + kg * 48 + 16 * b + 4 * i_));
       }
       // the two elements this lane transforms (features 4 g + 2 kg + {0, 1} of sample c32)
       float* px[2];
@@ -333,10 +310,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
           pa[b] = mfma32h(wh[u % RING], fhi[t], pa[b]);
           corr = mfma32h(wh[u % RING], flo[t], corr);
           corr = mfma32h(wl[u % RING], fhi[t], corr);
-          if (t == NTH - 1) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) pa[b][r] = fmaf(corr[r], kLoUnscale, pa[b][r]);
-          }
+          if (t == NTH - 1) pa[b] = fold_x3(pa[b], corr);
           // keep the written order: a fragment pair is requested RING steps (of 3 matrix instructions) before its
           // use - left alone the scheduler sinks every request to just above its use (two in flight, L2 latency
           // per step)
@@ -351,10 +325,8 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
       float yv[2], lad[2];
 #pragma unroll
       for (int f2 = 0; f2 < 2; ++f2) {
-        // logits of feature f2: accumulator entries 24 f2 + 0 .. 22 (entry v = register v % 16 of block v / 16)
         float lg[P];
-#pragma unroll
-        for (int tl = 0; tl < P; ++tl) lg[tl] = pa[(24 * f2 + tl) >> 4][(24 * f2 + tl) & 15];
+        acc_logits(pa, f2, lg);
         rqs_lean_eval<8, INV>(xin[f2], lg, lc, yv[f2], lad[f2], bad);
       }
       *px[0] = yv[0];
@@ -371,10 +343,7 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
     half8 ahi[2][NTH], alo[2][NTH];
     floatx16 abias;
 #define VCNF_LOAD_BIAS16(DST, FOFF)                                                       \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                      \
-    const floatx4 b4_ = wload(wr, boff, 4 * ((FOFF) + 32 * rp) + 16 * i_);                \
-    DST[4 * i_ + 0] = b4_[0]; DST[4 * i_ + 1] = b4_[1]; DST[4 * i_ + 2] = b4_[2]; DST[4 * i_ + 3] = b4_[3]; \
-  }
+  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) set_quad(DST, i_, wload(wr, boff, 4 * ((FOFF) + 32 * rp) + 16 * i_));
 #define VCNF_LOAD_HIDDEN(SET, WOFF)                                                       \
   {                                                                                       \
     _Pragma("unroll") for (int t = 0; t < NTH; ++t) {                                     \
@@ -393,7 +362,8 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
     VCNF_ACT_HI(BUF)[(2 * rp + hh) * 64 + lane] = __builtin_bit_cast(uint4, h8_);         \
     VCNF_ACT_LO(BUF)[(2 * rp + hh) * 64 + lane] = __builtin_bit_cast(uint4, l8_);         \
   }
-    // OUT = bias + W_slice(register set SET) * operand(buffer BUF)
+    // OUT = bias + W_slice(register set SET) * operand(buffer BUF).  (Its fold is fold_x3 written out: through the
+    // function half of the kernels come out on other registers, profiles/fused_leaf_blocks.md.)
 #define VCNF_HIDDEN_COMPUTE(OUT, BUF, SET)                                                \
   {                                                                                       \
     /* operand fragments are read AHEAD k-steps before their use (ring, pinned with sched_group_barrier: left */ \
@@ -449,13 +419,9 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
         for (int t = 0; t < NT0; ++t) {
           const half8 bh = __builtin_bit_cast(half8, t < NTX ? VCNF_ACT_HI(0)[t * 64 + lane] : ctxf[lane]);
           const half8 bl = __builtin_bit_cast(half8, t < NTX ? VCNF_ACT_LO(0)[t * 64 + lane] : ctxf[64 + lane]);
-          mainv = mfma32h(w0h[t], bh, mainv);
-          corr = mfma32h(w0h[t], bl, corr);
-          corr = mfma32h(w0l[t], bh, corr);
-          corr2 = mfma32h(w0l[t], bl, corr2);
+          mfma32h_x4(w0h[t], w0l[t], bh, bl, mainv, corr, corr2);
         }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h[r] = fmaf(fmaf(corr2[r], kLoUnscale, corr[r]), kLoUnscale, mainv[r]);
+        h = fold_x4(mainv, corr, corr2);
         VCNF_PUBLISH(h, true, 1)
       }
       VCNF_TS(7)
@@ -490,18 +456,9 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
         if (C > 0) {
           const half8 bh = __builtin_bit_cast(half8, ctxf[lane]);
           const half8 bl = __builtin_bit_cast(half8, ctxf[64 + lane]);
-          floatx16 gate, corr = {}, corr2 = {};
-          gate = mfma32h(wch, bh, gbias);
-          corr = mfma32h(wch, bl, corr);
-          corr = mfma32h(wcl, bh, corr);
-          corr2 = mfma32h(wcl, bl, corr2);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) gate[r] = fmaf(fmaf(corr2[r], kLoUnscale, corr[r]), kLoUnscale, gate[r]);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float sg = hw_rcp(1.f + hw_exp2(-gate[r]));
-            h[r] = fmaf(t[r], sg, h[r]);
-          }
+          floatx16 gate = gbias, corr = {}, corr2 = {};
+          mfma32h_x4(wch, wcl, bh, bl, gate, corr, corr2);
+          h = glu_update(h, t, fold_x4(gate, corr, corr2));
         } else {
           h += t;
         }
@@ -598,16 +555,9 @@ __global__ __launch_bounds__(512, 2) void fused_rqs_layer_v6s_kernel(const Fused
 
 template <int DI, int DT, int C, int H, int NBLK, int K>
 static int launch_v6s(const FusedStackArgs& sa, int inverse, hipStream_t st) {
-  const FusedArgs& a = sa.a;
-  constexpr int TILE = kFusedFlagRows;
-  constexpr size_t lds = LdsV6s<DI, DT, C, H, NBLK, K>::BYTES;       // below 64 KB: no limit to raise
-  const long long ntiles = (a.B + TILE - 1) / TILE;
-  dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
-  if (inverse)
-    hipLaunchKernelGGL((fused_rqs_layer_v6s_kernel<DI, DT, C, H, NBLK, K, true>), grid, dim3(512), lds, st, sa);
-  else
-    hipLaunchKernelGGL((fused_rqs_layer_v6s_kernel<DI, DT, C, H, NBLK, K, false>), grid, dim3(512), lds, st, sa);
-  return launched();
+  return launch_tiled<&fused_rqs_layer_v6s_kernel<DI, DT, C, H, NBLK, K, true>,
+                      &fused_rqs_layer_v6s_kernel<DI, DT, C, H, NBLK, K, false>, kFusedFlagRows, 512,
+                      LdsV6s<DI, DT, C, H, NBLK, K>::BYTES>(inverse, sa.a.B, 256, st, sa);   // below 64 KB: no limit to raise
 }
 
 template <int NBLK>

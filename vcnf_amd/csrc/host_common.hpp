@@ -1,7 +1,8 @@
 // Host idioms of the entry points, each defined once: the dispatch from a run-time count or code (with_listed_only,
 // launch_listed) and from run-time booleans (with_flags) to a kernel instance, the status after a launch, pointer
-// alignment, the log-det mode, the dynamic-LDS limit of a kernel.  The first part is
-// plain C++17 (rqs_host.hpp includes it and is compiled without HIP by tests/c_host/); the rest needs the HIP runtime.
+// alignment, the log-det mode, the dynamic-LDS limit of a kernel, the launch end of a tiled kernel (launch_tiled).
+// The first part is plain C++17 (rqs_host.hpp includes it and is compiled without HIP by tests/c_host/); the rest needs
+// the HIP runtime.
 #pragma once
 
 #include <stdint.h>
@@ -81,6 +82,23 @@ inline bool lds_limit_once(size_t bytes) {
     done = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)bytes) == hipSuccess;
   return done;
+}
+
+// The launch end of a kernel that walks the batch in tiles of TILE samples and has an instance per direction: raises the
+// instance's dynamic-LDS limit once where LDS exceeds 64 KiB (VCNF_ERR_LAUNCH if the runtime refuses), one workgroup of
+// BLOCK threads per tile up to ``max_grid`` (what the chip holds at once), launches KInv or KFwd on ``args``.
+template <auto KInv, auto KFwd, int TILE, int BLOCK, size_t LDS, class... Args>
+inline int launch_tiled(int inverse, long long batch, long long max_grid, hipStream_t st, const Args&... args) {
+  if constexpr (LDS > 64 * 1024) {
+    if (!(inverse ? lds_limit_once<KInv>(LDS) : lds_limit_once<KFwd>(LDS))) return VCNF_ERR_LAUNCH;
+  }
+  const long long ntiles = (batch + TILE - 1) / TILE;
+  const dim3 grid((unsigned)(ntiles < max_grid ? ntiles : max_grid));
+  if (inverse)
+    hipLaunchKernelGGL(KInv, grid, dim3(BLOCK), LDS, st, args...);
+  else
+    hipLaunchKernelGGL(KFwd, grid, dim3(BLOCK), LDS, st, args...);
+  return launched();
 }
 
 }  // namespace vcnf
