@@ -953,6 +953,59 @@ int vcnf_uniform_gaussian_sample_f64(const double* eps, const int32_t* src, cons
 int vcnf_uniform_gaussian_log_prob_bwd_f64(const double* z, const double* inv_scale_g, const double* g, double* d_z,
                                            int64_t batch, int32_t features, void* stream);
 
+/* ---- Image data end caps: the Logit transform of normflow 1.2's transforms.py and the byte ingest in front of it
+ * (csrc/logit.hip).  Rows of `features` = D contiguous elements (all axes of an item but the first); alpha in [0, 0.5)
+ * and beta = 1 - 2 alpha are passed / formed in fp64 and rounded to the element type once, as torch rounds a Python
+ * scalar operand; every step below is rounded once in the element type and none is contracted into an fma.
+ *   logit_inverse (x, z [batch, D]; the density direction):
+ *              u = alpha + beta * x (a multiply, then an add);  z = log(u) - log(1 - u)
+ *              ld[b] = D log(beta) - sum_j log(u) - sum_j log(1 - u)
+ *              With alpha = 0, x = 0 gives z = -inf, x = 1 gives z = +inf and either gives ld = +inf, never NaN.
+ *   logit_forward (z, y [batch, D]; the sampling direction):  with s = sigmoid(z)
+ *              y = (s - alpha) / beta;  ld[b] = -D log(beta) + sum_j (-|z| - 2 log1p(exp(-|z|)))
+ *              the sum's term is logsigmoid(z) + logsigmoid(-z): finite for every finite z, -inf at +-inf
+ *   logit_inverse_u8 (bytes [batch, D] uint8, noise [batch, D] uniform on [0, 1) drawn by the caller):
+ *              x = ((T(byte) / 255) + noise * jitter) * scale, one rounded operation at a time, then logit_inverse of
+ *              that x in the same launch: one byte and one noise value are read per element, x is never stored
+ *   logdet[b] = ld_sign * ld[b] (VCNF_LD_STORE) or logdet[b] + ld_sign * ld[b] (VCNF_LD_ACCUM).  z == x / y == z is
+ *              allowed (in place).
+ *   logit_inverse_bwd (cotangents g_z [batch, D], g_ld [batch]; either may be NULL = zero), recomputing u from x:
+ *              d_x = beta / (u (1 - u)) * (g_z - g_ld[b] * (1 - 2 u))
+ *   logit_forward_bwd (cotangents g_y [batch, D], g_ld [batch]; either may be NULL = zero), recomputing s from z:
+ *              d_z = g_y * (s (1 - s) / beta) + g_ld[b] * (1 - 2 s)
+ * A lane group per row, the row in chunks of 16 bytes' worth of elements strided over the group (at features = 3072 a
+ * row is 12 trips of a 64-lane group, at features = 1 a lane owns a row), a lane's elements added in ascending order and
+ * the group by the ascending butterfly; 16-byte (8-byte) accesses when features % V == 0 and the row buffers are aligned
+ * to them, scalar otherwise, with the same bits either way.  Any number of features.  The grid is NOT capped and no
+ * kernel loops over it, as in csrc/periodic.hip (the row-sum kernels of csrc/affine_kernels.hip cap theirs and loop): a
+ * shape that needs more than 2^31 - 1 workgroups -> VCNF_ERR_SHAPE.
+ * Checked in this order: NULL required pointer -> VCNF_ERR_NULL; features < 1, a negative count, or work beyond a grid
+ * -> VCNF_ERR_SHAPE; unknown ld_mode -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch; a pointer not
+ * aligned to its element size -> VCNF_ERR_ALIGN.  No atomics, no allocation, no host synchronisation: every call is
+ * bitwise reproducible and capturable. */
+int vcnf_logit_inverse_f32(const float* x, double alpha, float* z, float* logdet, int64_t batch, int32_t features,
+                           int ld_mode, float ld_sign, void* stream);
+int vcnf_logit_forward_f32(const float* z, double alpha, float* y, float* logdet, int64_t batch, int32_t features,
+                           int ld_mode, float ld_sign, void* stream);
+int vcnf_logit_inverse_bwd_f32(const float* x, double alpha, const float* g_z, const float* g_ld, float* d_x,
+                               int64_t batch, int32_t features, void* stream);
+int vcnf_logit_forward_bwd_f32(const float* z, double alpha, const float* g_y, const float* g_ld, float* d_z,
+                               int64_t batch, int32_t features, void* stream);
+int vcnf_logit_inverse_u8_f32(const uint8_t* bytes, const float* noise, double jitter, double scale, double alpha,
+                              float* z, float* logdet, int64_t batch, int32_t features, int ld_mode, float ld_sign,
+                              void* stream);
+int vcnf_logit_inverse_f64(const double* x, double alpha, double* z, double* logdet, int64_t batch, int32_t features,
+                           int ld_mode, double ld_sign, void* stream);
+int vcnf_logit_forward_f64(const double* z, double alpha, double* y, double* logdet, int64_t batch, int32_t features,
+                           int ld_mode, double ld_sign, void* stream);
+int vcnf_logit_inverse_bwd_f64(const double* x, double alpha, const double* g_z, const double* g_ld, double* d_x,
+                               int64_t batch, int32_t features, void* stream);
+int vcnf_logit_forward_bwd_f64(const double* z, double alpha, const double* g_y, const double* g_ld, double* d_z,
+                               int64_t batch, int32_t features, void* stream);
+int vcnf_logit_inverse_u8_f64(const uint8_t* bytes, const double* noise, double jitter, double scale, double alpha,
+                              double* z, double* logdet, int64_t batch, int32_t features, int ld_mode, double ld_sign,
+                              void* stream);
+
 /* ---- Full-covariance base distributions: the multivariate Gaussian and the multivariate Student-t over D = features
  * <= 128.  z / eps [B, D] contiguous, gamma [B], loc [D]; tri [D, D] row-major is a lower-triangular matrix of which
  * only the lower triangle including the diagonal is ever read: the scale L for sampling, its inverse M = L^-1 for the

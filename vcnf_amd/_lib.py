@@ -1546,6 +1546,61 @@ def uniform_gaussian_log_prob_bwd(z, inv_scale_g, g):
     return dz.view(z.shape)
 
 
+def _logit_rows(name, x, *like):
+    """Checked operands of the vcnf_logit_* entry points: x [B, ...] contiguous with D >= 1 elements per item, the
+    tensors ``like`` (None allowed) contiguous, of its shape, dtype and device.  Returns (device, B, D)."""
+    dev = require_device(x, *like, f64=True)
+    d = math.prod(x.shape[1:]) if x.dim() >= 1 else 0
+    if d < 1 or not x.is_contiguous():
+        raise VcnfError("%s: inputs %s are not contiguous [batch, ...] items of at least one element" % (name, tuple(x.shape)))
+    if any(t is not None and (t.shape != x.shape or t.dtype != x.dtype or not t.is_contiguous()) for t in like):
+        raise VcnfError(name + ": every operand must be a contiguous tensor of the input's shape and dtype")
+    return dev, len(x), d
+
+
+def logit(x, alpha, inverse, logdet=None, sign=1.0):
+    """vcnf_logit_inverse_* / vcnf_logit_forward_*: (out like x, log-det [B]) of the Logit transform in the density
+    direction (``inverse``) or the sampling direction; ``logdet``: add sign * log-det into it."""
+    name = ("vcnf_logit_inverse" if inverse else "vcnf_logit_forward") + _sfx(x)
+    dev, b, d = _logit_rows(name, x)
+    out = torch.empty_like(x)
+    logdet, mode = _ld_out(logdet, b, x.dtype, dev, name)
+    if b:                       # an empty tensor has no address: nothing to launch
+        _call(name, dev, x, float(alpha), out, logdet, b, d, mode, float(sign))
+    return out, logdet
+
+
+def logit_bwd(x, alpha, inverse, g_out=None, g_ld=None):
+    """vcnf_logit_inverse_bwd_* / vcnf_logit_forward_bwd_*: the gradient like x of a direction's input for the
+    cotangents g_out (like x) and g_ld [B] of its two outputs; None: zero."""
+    name = ("vcnf_logit_inverse_bwd" if inverse else "vcnf_logit_forward_bwd") + _sfx(x)
+    if g_out is not None:
+        g_out = g_out.contiguous()
+    dev, b, d = _logit_rows(name, x, g_out)
+    if g_ld is not None:
+        require_device(g_ld, f64=True)
+        g_ld = _batch_vector(g_ld, b, x.dtype, name, "g_ld")
+    d_x = torch.empty_like(x)
+    if b:
+        _call(name, dev, x, float(alpha), g_out, g_ld, d_x, b, d)
+    return d_x
+
+
+def logit_inverse_u8(x_u8, noise, jitter, scale, alpha, logdet=None, sign=1.0):
+    """vcnf_logit_inverse_u8_*: (z, log-det [B]) of the Logit density direction at ((byte / 255) + noise * jitter) *
+    scale for the bytes x_u8 [B, ...] and the uniform draws ``noise`` of their shape, in the dtype of ``noise``."""
+    name = "vcnf_logit_inverse_u8" + _sfx(noise)
+    dev, b, d = _logit_rows(name, noise)
+    require_device(x_u8)
+    if x_u8.dtype != torch.uint8 or x_u8.shape != noise.shape or not x_u8.is_contiguous() or x_u8.device != dev:
+        raise VcnfError(name + ": the bytes must be a contiguous uint8 tensor of the noise's shape on its device")
+    z = torch.empty_like(noise)
+    logdet, mode = _ld_out(logdet, b, noise.dtype, dev, name)
+    if b:
+        _call(name, dev, x_u8, noise, float(jitter), float(scale), float(alpha), z, logdet, b, d, mode, float(sign))
+    return z, logdet
+
+
 def _mvn_operands(x, loc, tri, consts, what):
     """Checked operands of the full-covariance base entry points: x [B, D], loc [D] (or None), tri [D, D], consts [2],
     one dtype.  Returns (device, x, loc, tri, consts contiguous, B, D)."""

@@ -592,6 +592,28 @@ class UniformGaussianLogProbFn(torch.autograd.Function):
         return _lib.uniform_gaussian_log_prob_bwd(z, inv_scale_g, g), None, None
 
 
+class LogitFn(torch.autograd.Function):
+    """vcnf_logit_inverse_* / vcnf_logit_forward_*: (out, log-det [B]) of a Logit direction as ONE node that saves only
+    its input; backward is vcnf_logit_*_bwd_*, one launch that recomputes from it.  Not double-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, alpha, inverse):
+        with torch.no_grad():
+            out, ld = _lib.logit(x, alpha, inverse)
+        ctx.save_for_backward(x)
+        ctx.args = (alpha, inverse)
+        ctx.set_materialize_grads(False)
+        return out, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_ld):
+        x, = ctx.saved_tensors
+        if g_out is None and g_ld is None:
+            return None, None, None
+        return _lib.logit_bwd(x, *ctx.args, g_out=g_out, g_ld=g_ld), None, None
+
+
 class PlanarRadialStackFn(torch.autograd.Function):
     """vcnf_planar_radial_stack_*: (out, log|det| [B]) of a run of Planar / Radial layers from its effective operands va,
     vb [K, D] and sc [K, 2] (vcnf_amd.fused_planar.operands) as ONE node.  Forward launches the kernel with the trace

@@ -25,6 +25,7 @@ from .flows.planar import Planar
 from .flows.radial import Radial
 from .flows.stochastic import HamiltonianMonteCarlo
 from .stacks import refresh_packed
+from .transforms import Logit
 
 # The single-launch families, tried in this order at every position of a pass: (the model's switch, the flow types a
 # run can start with, the family's planner - the contract is the docstring of vcnf_amd.stacks)
@@ -338,10 +339,19 @@ class MultiscaleFlow(_PackedWeightsMixin, nn.Module):
 
     def log_prob(self, x, y=None):
         """core.py:348-367: optional input transform, then per level (finest last) the
-        flows inverted, the split-off half scored by that level's base."""
+        flows inverted, the split-off half scored by that level's base.  ``x`` may be a ``torch.uint8`` batch of image
+        bytes when the transform is a ``transforms.Logit``: it is dequantised with fresh uniform noise, scaled and
+        transformed in one launch, in the dtype of the first base's ``loc``."""
         log_q = 0
         z = x
-        if self.transform is not None:
+        if x.dtype == torch.uint8:
+            # image bytes: dequantisation noise, scaling and the transform in one launch (transforms.Logit.inverse_u8)
+            if not isinstance(self.transform, Logit):
+                raise TypeError("byte input needs transform=vcnf_amd.transforms.Logit(...) to dequantise it; this "
+                                "model's transform is %r" % (self.transform,))
+            z, log_det = self.transform.inverse_u8(x, dtype=self.q0[0].loc.dtype)
+            log_q = log_q + log_det
+        elif self.transform is not None:
             z, log_det = self.transform.inverse(z)
             log_q = log_q + log_det
         for i in range(self.num_levels - 1, -1, -1):

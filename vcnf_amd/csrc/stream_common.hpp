@@ -1,6 +1,7 @@
 // What the stream kernels share (affine_kernels.hip, class_cond_gaussian.hip, gaussian_mixture.hip, heavy_tail.hip,
-// mvn_base.hip, planar_radial.hip, target_density.hip, stochastic.hip, vae_ends.hip, periodic.hip): a group of G <= 64
-// lanes (a power of two) owns a sample, streams its row in packs of up to 16 bytes and sums with a shuffle butterfly.
+// mvn_base.hip, planar_radial.hip, target_density.hip, stochastic.hip, vae_ends.hip, periodic.hip, logit.hip): a group of
+// G <= 64 lanes (a power of two) owns a sample, streams its row in packs of up to 16 bytes and sums with a shuffle
+// butterfly.
 // Each unit keeps its kernels, argument structs and tuning constants (block sizes, grid caps, packs per lane) in its own
 // namespace; this header holds the scaffolding around them, each piece defined once.  On the host side that is the
 // choice of lanes, pack and grid, and the way from run-time values to a kernel instance: with_pack for the pack width,
