@@ -1006,6 +1006,68 @@ int vcnf_logit_inverse_u8_f64(const uint8_t* bytes, const double* noise, double 
                               double* z, double* logdet, int64_t batch, int32_t features, int ld_mode, double ld_sign,
                               void* stream);
 
+/* ---- Categorical columns: uniform and variational dequantisation (Ho et al. 2019) per column and the reverse map to
+ * integer codes (csrc/dequant.hip).  Rows x / z / out [batch, D] contiguous, D = features; C = n_cat <= D of the columns
+ * are categorical.  slot [D] int32 (device) holds -1 for a continuous column and otherwise the column's index c into the
+ * [batch, C] operands (u, v, ctx, w, d_w); levels [C] int32 (device) holds K_c >= 1.  A categorical column holds the
+ * integer codes 0 .. K_c - 1 as floating values k.  a = alpha in [0, 1) crosses in fp64; a/2, 1 - a and log(1 - a) are
+ * formed in fp64 and rounded to the element type once, as torch rounds a Python scalar operand; K = K_c converted to the
+ * element type; every step below is rounded once in the element type and none is contracted into an fma.
+ *   dequant_prepare (u [batch, C] uniform on [0, 1) drawn by the caller -> v, ctx [batch, C]):
+ *              s = a/2 + (1 - a) u;  v = log(s) - log(1 - s);  ctx = 2 k / (K - 1) - 1, and 0 where K = 1
+ *              ld[b] = sum_c ((log(1 - a) - log(s)) - log(1 - s))
+ *   dequant_merge (w [batch, C] -> out [batch, D]; the density direction):
+ *              noise_is_logit != 0:  n = 1 / (1 + exp(-w)),  ld_n = sum_c (-|w| - 2 log1p(exp(-|w|)))
+ *                                    (the term is logsigmoid(w) + logsigmoid(-w))
+ *              noise_is_logit == 0:  n = w,  ld_n = 0
+ *              y = (k + n) / K;  s = a/2 + (1 - a) y;  out[:, col_c] = log(s) - log(1 - s);  a continuous column of out is
+ *              that column of x, bit for bit
+ *              ld[b] = ld_n + sum_c (((log(1 - a) - log(K)) - log(s)) - log(1 - s))
+ *   dequant_merge_bwd (cotangents g_out [batch, D], g_ld [batch]; either may be NULL = zero), recomputing n and s from x
+ *              and w:  d_n = ((1 - a) / K) / (s (1 - s)) * (g_out[:, col_c] - g_ld[b] (1 - 2 s))
+ *              noise_is_logit != 0:  d_w = d_n (n (1 - n)) + g_ld[b] (1 - 2 n);   else d_w = d_n
+ *              d_x [batch, D] (may be NULL: not written) = g_out on a continuous column, 0 on a categorical one
+ *   quantize (z -> out [batch, D]; the sampling direction):  t = z[:, col_c],  sg = 1 / (1 + exp(-t))
+ *              y = (sg - a/2) / (1 - a);  out[:, col_c] = min(max(floor(y K), 0), K - 1);  other columns copied
+ *              ld[b] = sum_c (((-|t| - 2 log1p(exp(-|t|))) - log(1 - a)) + log(K)),  the log-det of t -> y K
+ *   logdet[b] = ld_sign * ld[b] (VCNF_LD_STORE) or logdet[b] + ld_sign * ld[b] (VCNF_LD_ACCUM).  out must not overlap x / z.
+ * The kernels do not test that a code is integral or in range: an out-of-range or fractional code gives the formula's
+ * value.  A level < 1 cannot be seen on the host and is the caller's business, as is a slot outside -1 .. C - 1.
+ * A lane group per row, the row in chunks of 16 bytes' worth of columns strided over the group (at features = 14 in fp32
+ * four lanes share a row, at features <= 4 a lane owns one), a lane's terms added in ascending column order and the
+ * group by the ascending butterfly: two calls give the same bits.  The [batch, D] buffers move in 16-byte (8-byte)
+ * accesses when features % V == 0 and they are aligned to them, scalar otherwise, with the same bits either way; the
+ * [batch, C] operands move one element at a time.  At most 4096 workgroups; a lane group walks further rows one grid
+ * of rows apart.  Any number of features, any n_cat <= features.
+ * Checked in this order: NULL required pointer -> VCNF_ERR_NULL; features < 1, n_cat < 0, n_cat > features, a negative
+ * batch or batch * features beyond int64 -> VCNF_ERR_SHAPE; a pointer not aligned to its element size ->
+ * VCNF_ERR_ALIGN; unknown ld_mode -> VCNF_ERR_UNSUPPORTED; batch == 0 -> VCNF_OK without a launch.  No atomics, no
+ * random numbers, no allocation, no host synchronisation: every call is bitwise reproducible and capturable. */
+int vcnf_dequant_prepare_f32(const float* x, const int32_t* slot, const int32_t* levels, const float* u, double alpha,
+                             float* v, float* ctx, float* logdet, int64_t batch, int32_t features, int32_t n_cat,
+                             int ld_mode, float ld_sign, void* stream);
+int vcnf_dequant_merge_f32(const float* x, const int32_t* slot, const int32_t* levels, const float* w,
+                           int noise_is_logit, double alpha, float* out, float* logdet, int64_t batch, int32_t features,
+                           int32_t n_cat, int ld_mode, float ld_sign, void* stream);
+int vcnf_dequant_merge_bwd_f32(const float* x, const int32_t* slot, const int32_t* levels, const float* w,
+                               int noise_is_logit, double alpha, const float* g_out, const float* g_ld, float* d_w,
+                               float* d_x, int64_t batch, int32_t features, int32_t n_cat, void* stream);
+int vcnf_quantize_f32(const float* z, const int32_t* slot, const int32_t* levels, double alpha, float* out,
+                      float* logdet, int64_t batch, int32_t features, int32_t n_cat, int ld_mode, float ld_sign,
+                      void* stream);
+int vcnf_dequant_prepare_f64(const double* x, const int32_t* slot, const int32_t* levels, const double* u, double alpha,
+                             double* v, double* ctx, double* logdet, int64_t batch, int32_t features, int32_t n_cat,
+                             int ld_mode, double ld_sign, void* stream);
+int vcnf_dequant_merge_f64(const double* x, const int32_t* slot, const int32_t* levels, const double* w,
+                           int noise_is_logit, double alpha, double* out, double* logdet, int64_t batch,
+                           int32_t features, int32_t n_cat, int ld_mode, double ld_sign, void* stream);
+int vcnf_dequant_merge_bwd_f64(const double* x, const int32_t* slot, const int32_t* levels, const double* w,
+                               int noise_is_logit, double alpha, const double* g_out, const double* g_ld, double* d_w,
+                               double* d_x, int64_t batch, int32_t features, int32_t n_cat, void* stream);
+int vcnf_quantize_f64(const double* z, const int32_t* slot, const int32_t* levels, double alpha, double* out,
+                      double* logdet, int64_t batch, int32_t features, int32_t n_cat, int ld_mode, double ld_sign,
+                      void* stream);
+
 /* ---- Full-covariance base distributions: the multivariate Gaussian and the multivariate Student-t over D = features
  * <= 128.  z / eps [B, D] contiguous, gamma [B], loc [D]; tri [D, D] row-major is a lower-triangular matrix of which
  * only the lower triangle including the diagonal is ever read: the scale L for sampling, its inverse M = L^-1 for the

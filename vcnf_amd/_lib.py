@@ -1601,6 +1601,102 @@ def logit_inverse_u8(x_u8, noise, jitter, scale, alpha, logdet=None, sign=1.0):
     return z, logdet
 
 
+_COLUMN_TABLES = {}
+
+
+def column_tables(columns, levels, features, device):
+    """(slot [D] int32, levels [C] int32) on ``device`` for the categorical ``columns`` of rows of D = ``features``: slot
+    holds -1 for a continuous column and otherwise the column's index into the [B, C] operands of the vcnf_dequant_*
+    entry points.  Built once per (columns, levels, D, device) and kept."""
+    key = (tuple(columns), tuple(levels), int(features), torch.device(device))
+    if key not in _COLUMN_TABLES:
+        if len(key[0]) != len(key[1]) or len(set(key[0])) != len(key[0]) or any(not 0 <= c < features for c in key[0]) \
+                or any(k < 1 for k in key[1]):
+            raise VcnfError("categorical columns %s with levels %s do not fit rows of %d features" % (key[0], key[1], features))
+        slot = [-1] * int(features)
+        for i, c in enumerate(key[0]):
+            slot[c] = i
+        _COLUMN_TABLES[key] = (torch.tensor(slot, dtype=torch.int32, device=device),
+                               torch.tensor(key[1], dtype=torch.int32, device=device).reshape(len(key[1])))
+    return _COLUMN_TABLES[key]
+
+
+def _dequant_rows(name, x, slot, levels, *per_column, like=()):
+    """Checked operands of the vcnf_dequant_* / vcnf_quantize_* entry points: rows x [B, D] contiguous, the tables of
+    ``column_tables`` for D, the tensors ``per_column`` [B, C] and ``like`` [B, D] (None allowed) contiguous, of its
+    dtype and device.  Returns (device, B, D, C)."""
+    dev = require_device(x, *per_column, *like, f64=True)
+    require_device(slot, levels)
+    if x.dim() != 2 or x.shape[1] < 1 or not x.is_contiguous():
+        raise VcnfError("%s: inputs %s are not contiguous [batch, features] rows" % (name, tuple(x.shape)))
+    b, d = x.shape
+    c = len(levels)
+    if slot.dtype != torch.int32 or levels.dtype != torch.int32 or tuple(slot.shape) != (d,) or levels.dim() != 1 \
+            or c > d or slot.device != dev or levels.device != dev:
+        raise VcnfError(name + ": slot [features] and levels [n_cat <= features] must be int32 tensors on the rows' device")
+    for t, shape in [(t, (b, c)) for t in per_column] + [(t, (b, d)) for t in like]:
+        if t is not None and (tuple(t.shape) != shape or t.dtype != x.dtype or not t.is_contiguous()):
+            raise VcnfError("%s: every operand must be a contiguous %s tensor of the rows' dtype" % (name, list(shape)))
+    return dev, b, d, c
+
+
+def dequant_prepare(x, slot, levels, u, alpha, logdet=None, sign=1.0):
+    """vcnf_dequant_prepare_*: (v, ctx, log-det [B]) for the rows x [B, D] and the uniform draws u [B, C]: the logit of
+    the draws, the rows' categories scaled to [-1, 1] and the log-det of u -> v; ``logdet``: add sign * log-det into it."""
+    name = "vcnf_dequant_prepare" + _sfx(x)
+    dev, b, d, c = _dequant_rows(name, x, slot, levels, u)
+    v, ctx = torch.empty_like(u), torch.empty_like(u)
+    logdet, mode = _ld_out(logdet, b, x.dtype, dev, name)
+    if b and c:
+        _call(name, dev, x, slot, levels, u, float(alpha), v, ctx, logdet, b, d, c, mode, float(sign))
+    elif mode == LD_STORE:
+        logdet.zero_()
+    return v, ctx, logdet
+
+
+def dequant_merge(x, slot, levels, w, noise_is_logit, alpha, logdet=None, sign=1.0):
+    """vcnf_dequant_merge_*: (out [B, D], log-det [B]) of the rows x with the noise w [B, C] merged into their categorical
+    columns; ``noise_is_logit``: w is the logit of the noise (variational) and not the noise itself."""
+    name = "vcnf_dequant_merge" + _sfx(x)
+    dev, b, d, c = _dequant_rows(name, x, slot, levels, w)
+    out = torch.empty_like(x)
+    logdet, mode = _ld_out(logdet, b, x.dtype, dev, name)
+    if b:                       # an empty tensor has no address: nothing to launch
+        _call(name, dev, x, slot, levels, w if c else x, int(bool(noise_is_logit)), float(alpha), out, logdet, b, d, c, mode,
+              float(sign))
+    return out, logdet
+
+
+def dequant_merge_bwd(x, slot, levels, w, noise_is_logit, alpha, g_out=None, g_ld=None, want_x=False):
+    """vcnf_dequant_merge_bwd_*: (d_w [B, C], d_x [B, D] or None) for the cotangents g_out [B, D] and g_ld [B] of
+    ``dequant_merge``'s two outputs; None: zero."""
+    name = "vcnf_dequant_merge_bwd" + _sfx(x)
+    if g_out is not None:
+        g_out = g_out.contiguous()
+    dev, b, d, c = _dequant_rows(name, x, slot, levels, w, like=(g_out,))
+    if g_ld is not None:
+        require_device(g_ld, f64=True)
+        g_ld = _batch_vector(g_ld, b, x.dtype, name, "g_ld")
+    d_w = torch.empty_like(w)
+    d_x = torch.empty_like(x) if want_x else None
+    if b:
+        _call(name, dev, x, slot, levels, w if c else x, int(bool(noise_is_logit)), float(alpha), g_out, g_ld,
+              d_w if c else x, d_x, b, d, c)
+    return d_w, d_x
+
+
+def quantize(z, slot, levels, alpha, logdet=None, sign=1.0):
+    """vcnf_quantize_*: (out [B, D], log-det [B]): the categorical columns of z mapped back to integer codes, the others
+    copied, and the log-det of the continuous map in front of the floor."""
+    name = "vcnf_quantize" + _sfx(z)
+    dev, b, d, c = _dequant_rows(name, z, slot, levels)
+    out = torch.empty_like(z)
+    logdet, mode = _ld_out(logdet, b, z.dtype, dev, name)
+    if b:
+        _call(name, dev, z, slot, levels, float(alpha), out, logdet, b, d, c, mode, float(sign))
+    return out, logdet
+
+
 def _mvn_operands(x, loc, tri, consts, what):
     """Checked operands of the full-covariance base entry points: x [B, D], loc [D] (or None), tri [D, D], consts [2],
     one dtype.  Returns (device, x, loc, tri, consts contiguous, B, D)."""

@@ -614,6 +614,32 @@ class LogitFn(torch.autograd.Function):
         return _lib.logit_bwd(x, *ctx.args, g_out=g_out, g_ld=g_ld), None, None
 
 
+class DequantMergeFn(torch.autograd.Function):
+    """vcnf_dequant_merge_*: (out, log-det [B]) of the noise w [B, C] merged into the categorical columns of the rows x as
+    ONE node that saves x and w; backward is vcnf_dequant_merge_bwd_*, one launch that recomputes from them.  The rows
+    get a gradient only where they ask for one (continuous columns hand the cotangent through, categorical ones are
+    constants).  Not double-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, w, slot, levels, noise_is_logit, alpha):
+        with torch.no_grad():
+            out, ld = _lib.dequant_merge(x, slot, levels, w, noise_is_logit, alpha)
+        ctx.save_for_backward(x, w, slot, levels)
+        ctx.args = (noise_is_logit, alpha)
+        ctx.set_materialize_grads(False)
+        return out, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, g_ld):
+        x, w, slot, levels = ctx.saved_tensors
+        if g_out is None and g_ld is None:
+            return None, None, None, None, None, None
+        d_w, d_x = _lib.dequant_merge_bwd(x, slot, levels, w, *ctx.args, g_out=g_out, g_ld=g_ld,
+                                          want_x=ctx.needs_input_grad[0])
+        return d_x, (d_w if ctx.needs_input_grad[1] else None), None, None, None, None
+
+
 class PlanarRadialStackFn(torch.autograd.Function):
     """vcnf_planar_radial_stack_*: (out, log|det| [B]) of a run of Planar / Radial layers from its effective operands va,
     vb [K, D] and sc [K, 2] (vcnf_amd.fused_planar.operands) as ONE node.  Forward launches the kernel with the trace

@@ -8,10 +8,13 @@ for the whole stack, no per-layer allocation or add); every other Flow goes
 through the plain ``(z, log_det)`` contract.
 
 Training objectives (forward_kld / reverse_kld / reverse_alpha_div) differentiate through
-vcnf_amd.autograd (the spline VJP kernel).  The reference's
-categorical-dequantisation branch is out of scope; ``categoricals`` is always
-defined (None) so ``sample`` follows core.py:150-155 instead of failing with
-the AttributeError the reference has at this HEAD.
+vcnf_amd.autograd (the spline VJP kernel).  The fork's
+categorical-dequantisation branch (core.py:13-30, :42-54, :157-165) is the
+published algorithm per column (vcnf_amd/nets/varquant.py): the fork's file is
+not available, so no parity with it is claimed.  ``categoricals`` is always
+defined (None without categorical columns) so ``sample`` follows core.py:150-155
+instead of failing with the AttributeError the reference has at this HEAD
+(SURVEY 8b).
 """
 import torch
 from torch import nn
@@ -140,23 +143,97 @@ class _FlowWalks:
         return z, log_q
 
 
+def _int_list(values, name, lowest, distinct=False):
+    """``values`` as a list of ints >= ``lowest`` (``distinct``: no value twice), or a ValueError naming the argument."""
+    try:
+        listed = list(values)
+    except TypeError:
+        raise ValueError("%s must be a sequence of ints, got %r" % (name, values)) from None
+    if any(isinstance(v, bool) or not isinstance(v, int) or v < lowest for v in listed):
+        raise ValueError("%s must hold ints >= %d, got %r" % (name, lowest, listed))
+    if distinct and len(set(listed)) != len(listed):
+        raise ValueError("%s must hold distinct columns, got %r" % (name, listed))
+    return listed
+
+
 class NormalizingFlow(_PackedWeightsMixin, _FlowWalks, nn.Module):
+    """The model container (core.py:13-30).  With ``categoricals`` (column indices of the rows [B, D]) and ``catlevels``
+    (their numbers of levels) those columns hold integer codes: ``log_prob`` and ``forward_kld`` dequantise them first and
+    add the log-dets, ``sample`` and ``sample_from`` quantise last, both through the ONE dequantiser module ``catvdeqs``
+    that covers all categorical columns (None: ``nets.Dequantization()``, uniform noise; ``nets.VariationalDequantization``
+    learns the noise - vcnf_amd/nets/varquant.py).  ``reverse_kld`` and ``reverse_alpha_div`` stay on the continuous rows.
+    Without categoricals ``categoricals`` is None, there is no ``catvdeqs`` and no pass changes."""
+
     def __init__(self, q0, flows, p=None, categoricals=None, catlevels=None, catvdeqs=None):
         super().__init__()
         self._install_pack_hooks()
-        if categoricals is not None:
-            raise NotImplementedError("variational dequantisation of categorical columns is out of scope")
         self.q0 = q0
         self.flows = nn.ModuleList(flows)
         self.p = p
         self.categoricals = None
+        self.catlevels = None
         self._init_stack_switches()
+        if categoricals is not None or catlevels is not None or catvdeqs is not None:
+            self._init_categoricals(categoricals, catlevels, catvdeqs)
+
+    def _init_categoricals(self, categoricals, catlevels, catvdeqs):
+        from .nets.varquant import Dequantization
+        if categoricals is None:
+            raise ValueError("categoricals must be given together with catlevels" if catlevels is not None else
+                             "categoricals and catlevels must be given with catvdeqs")
+        if catlevels is None:
+            raise ValueError("catlevels must be given together with categoricals")
+        columns = _int_list(categoricals, "categoricals", 0, distinct=True)
+        levels = _int_list(catlevels, "catlevels", 1)
+        if len(columns) != len(levels):
+            raise ValueError("categoricals and catlevels must have equal lengths, got %d and %d" % (len(columns), len(levels)))
+        if isinstance(catvdeqs, (list, tuple)):
+            raise TypeError("catvdeqs must be ONE dequantiser module (nets.Dequantization or nets.VariationalDequantization): "
+                            "one module covers all categorical columns; the fork's per-column list cannot be restated "
+                            "without its source")
+        if catvdeqs is None:
+            catvdeqs = Dequantization()
+        if not (isinstance(catvdeqs, nn.Module) and callable(getattr(catvdeqs, 'dequantize', None))
+                and callable(getattr(catvdeqs, 'quantize', None))):
+            raise TypeError("catvdeqs must be a module with dequantize and quantize, got %r" % (catvdeqs,))
+        self.categoricals, self.catlevels = columns, levels
+        self.catvdeqs = catvdeqs
+
+    # ------------------------------------------------------------ categorical columns
+    def _need_categoricals(self):
+        if self.categoricals is None:
+            raise RuntimeError("this model has no categorical columns (categoricals=, catlevels=)")
+
+    def dequantize(self, x, noise=None, log_q=None):
+        """(xt, ld): the rows with their categorical columns made continuous, and the log-det that goes with
+        ``log q(xt)``.  ``noise``: the uniform draws [B, C]; None draws them.  ``log_q``: add ld into it in place."""
+        self._need_categoricals()
+        return self.catvdeqs.dequantize(x, self.categoricals, self.catlevels, noise=noise, log_q=log_q)
+
+    def quantize(self, z):
+        """(x, ld): continuous rows with their categorical columns turned into integer codes, and the log-det of the
+        continuous map in front of the floor (a sampling pass subtracts it)."""
+        self._need_categoricals()
+        return self.catvdeqs.quantize(z, self.categoricals, self.catlevels)
+
+    def _quantized(self, z, log_q):
+        z, log_det = self.catvdeqs.quantize(z, self.categoricals, self.catlevels)
+        return z, (log_q - log_det if log_q.requires_grad else log_q.sub_(log_det))
 
     # ------------------------------------------------------------ density
-    def log_prob(self, x, context=None):
+    def log_prob(self, x, context=None, noise=None):
         """log q(x) [B]: flows inverted last to first, log-dets added, base
-        log-density at the end (core.py:176-183)."""
-        z, log_q = self._walk(x, torch.zeros(len(x), dtype=x.dtype, device=x.device), context, True)
+        log-density at the end (core.py:176-183).
+
+        With categorical columns this is ONE draw of the variational bound
+        ``log P(x) >= E_u[log q(xt) + ld_merge + ld_prepare + ld_varflows]`` and not the log-probability of the codes: a
+        stochastic lower bound, different from call to call unless the draws ``noise`` [B, C] are given."""
+        log_q = torch.zeros(len(x), dtype=x.dtype, device=x.device)
+        if self.categoricals is not None:
+            x, log_q = self.catvdeqs.dequantize(x, self.categoricals, self.catlevels, noise=noise, log_q=log_q)
+        elif noise is not None:
+            self._need_categoricals()
+        z, log_q = self._walk(x, log_q, context, True)
         if hasattr(self.q0, 'from_noise'):
             self.q0.log_prob(z, out=log_q)
         else:
@@ -165,14 +242,17 @@ class NormalizingFlow(_PackedWeightsMixin, _FlowWalks, nn.Module):
 
     # ------------------------------------------------------------ sampling
     def sample(self, num_samples=1, context=None):
-        """(z, log q(z)) for fresh base draws (core.py:150-155, :168)."""
+        """(z, log q(z)) for fresh base draws (core.py:150-155, :168).  With categorical columns z holds integer codes
+        there and log q is the density of the continuous point in [0, K_c) in front of the floor."""
         z, log_q = self.q0(num_samples)
-        return self._walk(z, log_q, context, False)
+        z, log_q = self._walk(z, log_q, context, False)
+        return (z, log_q) if self.categoricals is None else self._quantized(z, log_q)
 
     def sample_from(self, eps, context=None):
         """Same as ``sample`` with the standard-normal base draw given."""
         z, log_q = self.q0.from_noise(eps)
-        return self._walk(z, log_q, context, False)
+        z, log_q = self._walk(z, log_q, context, False)
+        return (z, log_q) if self.categoricals is None else self._quantized(z, log_q)
 
     # ------------------------------------------------------------ objectives
     def _pull(self, z, context=None, trace=None):
@@ -182,13 +262,18 @@ class NormalizingFlow(_PackedWeightsMixin, _FlowWalks, nn.Module):
         z, log_q = self._plain_walk(z, log_q, context, True, trace)
         return log_q + self.q0.log_prob(z)
 
-    def forward_kld(self, x, extended=False, context=None):
+    def forward_kld(self, x, extended=False, context=None, noise=None):
         """-mean log q(x) (core.py:30-65).  ``extended``: also the per-layer latents and
-        log-dets as numpy arrays and the per-sample log q."""
+        log-dets as numpy arrays and the per-sample log q; with categorical columns the lists start after the
+        dequantisation.  ``noise``: as for ``log_prob``."""
         if not extended:
-            return -torch.mean(self.log_prob(x, context))
+            return -torch.mean(self.log_prob(x, context, noise))
         trace = ([], [])
-        log_q = self._pull(x, context, trace)
+        if self.categoricals is not None:
+            x, log_det = self.dequantize(x, noise)
+            log_q = self._pull(x, context, trace) + log_det
+        else:
+            log_q = self._pull(x, context, trace)
         return -torch.mean(log_q), trace[0], trace[1], log_q
 
     def _frozen_log_q(self, z, context):
