@@ -1354,6 +1354,67 @@ int vcnf_mh_walk_f64(const double* z, const double* eps, const double* w, const 
                      double* z_out, uint8_t* accept, int64_t batch, int32_t steps, int32_t n_comp, int family,
                      double scale, void* stream);
 
+/* ---- The sampling direction of the autoregressive flows in one launch (csrc/made_sample.hip):
+ * MaskedAffineAutoregressive.inverse and MaskedPiecewiseRationalQuadraticAutoregressive.inverse
+ * (normflow/flows/affine/autoregressive.py:29-36, the loop of D = features MADE passes, over nets/made.py:215-300 with
+ * residual blocks and ReLU).  With the reference's sequential degrees a hidden unit of degree m depends on inputs and
+ * hidden units of degree <= m only, so once the variable of degree m is known every unit of degree m in every layer is
+ * final: the loop is one masked MADE pass ordered by degree with one inversion between stages.
+ *   x / y [B, D] contiguous, D = features, H = hidden, nb = num_blocks >= 0, P = params_per_feature.
+ *   tables int32 [2 D] on the device: order[i] = the column holding the variable of degree i + 1; count[i] = the number
+ *     of hidden units of degree <= i.  Hidden units are stored in ascending degree, in the same order in every layer.
+ *     The kernel clamps order to 0 .. D - 1 and count to a non-decreasing sequence in 0 .. H: a wrong table gives wrong
+ *     values, never an access out of bounds.
+ *   wpack, vcnf_made_sample_pack_elems(D, H, nb, P) elements, the masked weights W * mask one after the other:
+ *     Wi [H, D] (columns in the order of `order`), bi [H];  per block  W0 [H, H], b0 [H], W1 [H, H], b1 [H];
+ *     Wf [D P, H] (the P rows of the variable of degree i + 1 at rows i P ..), bf [D P].
+ *   ctx_add [B, H]: the MADE's context_layer(context);  ctx_gate [nb, B, H]: the blocks' context_layer(context) before
+ *     the sigmoid; units in the stored order.  Both NULL without context; with nb = 0 ctx_gate is NULL.
+ * Per sample, for i = 0 .. D - 1 (count[-1] = 0):
+ *   1. for the units u in [count[i - 1], count[i]), layer by layer:
+ *        h_0[u]     = bi[u] + sum_{j < i} Wi[u, j] y[j] + ctx_add[u]
+ *        t_k[u]     = b0_k[u] + sum_{v < count[i]} W0_k[u, v] relu(h_k[v])
+ *        h_{k+1}[u] = h_k[u] + (b1_k[u] + sum_{v < count[i]} W1_k[u, v] relu(t_k[v])) gate_k[u]
+ *        gate_k[u]  = sigmoid(ctx_gate[k, b, u]), or 1
+ *   2. q[p] = bf[i P + p] + sum_{v < count[i]} Wf[i P + p, v] h_nb[v],  p < P
+ *   3. cfg == NULL (P = 2, the MAF): scale = sigmoid(q[0] + 2) + 1e-3, y[i] = (x[order[i]] - q[1]) / scale,
+ *        ld -= log(scale)  (vcnf_maf_affine, inverse);
+ *      cfg != NULL (P = 2 K + the derivative logits of cfg->tails): (y[i], lad) = the inverse spline of
+ *        vcnf_rqs_elementwise (wh_scale included) at x[order[i]] with the logits q = [K widths | K heights | derivatives],
+ *        ld += lad; bad_disc (may be NULL) as there
+ *   4. out[b, order[i]] = y[i]
+ * and logdet[b] = ld_sign ld, stored or accumulated (ld_mode).  features = 1 has count[0] = H and no input term; a
+ * degree that owns no unit has an empty range in step 1.
+ * Arithmetic: buffers and the activations kept between stages are float (_f32) or double (_f64); sums, the logits q
+ * and step 3 are evaluated in double in both (the _f32 entry point inverts with the spline of vcnf_rqs_elementwise_f64
+ * on cfg's values), and each activation, y and the log-det are rounded to the buffer's type once.
+ * vcnf_made_sample_supported answers from the kernel's budget: a sample keeps (1 + 2 nb) H + D values and P doubles in
+ * LDS and shares vcnf_made_sample_lanes(...) = 8 .. 64 lanes (the smallest group with which a workgroup of 256 threads
+ * stays under 48 KiB of LDS, at most the 64 KiB a launch gets without raising the limit; 0: unsupported); D <= 1024,
+ * H <= 4096, nb <= 16; splines have K in {8, 10, 16} (any other count would index the knot arrays in scratch).  A
+ * workgroup takes 256 / lanes samples per trip.
+ * batch < 0, an unsupported shape, wpack_elems or P not matching -> VCNF_ERR_SHAPE; unknown ld_mode or tails, or a
+ * bin count without an instance -> VCNF_ERR_UNSUPPORTED; an invalid cfg as for vcnf_rqs_elementwise; batch == 0 ->
+ * VCNF_OK without a launch; NULL required pointer, or one of ctx_add / ctx_gate without the other (nb > 0) ->
+ * VCNF_ERR_NULL; a pointer not aligned to its element size -> VCNF_ERR_ALIGN.  Dot products are summed in a fixed order
+ * (lane g of a group takes the terms g, g + lanes, ..., then the ascending butterfly): every call gives the same bits
+ * and a row's bits do not depend on the batch (of this entry point: a caller that chooses between it and another path
+ * by batch size, as vcnf_amd/made_sample.py does at 65 536 rows, changes the bits where it changes the path).  No scratch, no atomics besides bad_disc, no allocation, no host
+ * synchronisation: capturable. */
+int vcnf_made_sample_supported(int32_t features, int32_t hidden, int32_t num_blocks, int32_t params_per_feature,
+                               int32_t elem_size);
+int32_t vcnf_made_sample_lanes(int32_t features, int32_t hidden, int32_t num_blocks, int32_t params_per_feature,
+                               int32_t elem_size);
+int64_t vcnf_made_sample_pack_elems(int32_t features, int32_t hidden, int32_t num_blocks, int32_t params_per_feature);
+int vcnf_made_sample_f32(const float* x, float* y, float* logdet, const float* ctx_add, const float* ctx_gate,
+                         const float* wpack, int64_t wpack_elems, const int32_t* tables, int64_t batch,
+                         int32_t features, int32_t hidden, int32_t num_blocks, int32_t params_per_feature,
+                         const vcnf_rqs_cfg* cfg, int ld_mode, float ld_sign, int32_t* bad_disc, void* stream);
+int vcnf_made_sample_f64(const double* x, double* y, double* logdet, const double* ctx_add, const double* ctx_gate,
+                         const double* wpack, int64_t wpack_elems, const int32_t* tables, int64_t batch,
+                         int32_t features, int32_t hidden, int32_t num_blocks, int32_t params_per_feature,
+                         const vcnf_rqs_cfg_f64* cfg, int ld_mode, double ld_sign, int32_t* bad_disc, void* stream);
+
 /* Diagnostic, not on any product path: ONE dense layer y[B, N] = x[B, K] W[N, K]^T + b (nn.Linear,
  * nets/resnet.py:78-106) evaluated with the arithmetic of one of the fused RQS layer kernels' matrix paths, so that
  * the GEMM-level error of each path can be measured against an fp64 product (tests/test_gpu_gemm_error.py):

@@ -831,6 +831,37 @@ def maf_affine(x, params, inverse):
     return out, ld
 
 
+def made_sample_supported(features, hidden, num_blocks, params_per_feature, elem_size):
+    """vcnf_made_sample_supported: whether the one-launch sampling kernel of the autoregressive flows has room for a
+    MADE of this shape (its LDS budget; for splines, in both precisions, the bin counts with an instance: 8, 10, 16)."""
+    return bool(lib().vcnf_made_sample_supported(int(features), int(hidden), int(num_blocks), int(params_per_feature),
+                                                 int(elem_size)))
+
+
+def made_sample(x, wpack, tables, ctx_add, ctx_gate, hidden, num_blocks, params_per_feature, cfg=None, logdet=None,
+                sign=1.0):
+    """vcnf_made_sample_*: the sampling direction of an autoregressive flow over x [B, D] in one launch from the packed
+    operands of vcnf_amd.made_sample.pack (layouts: include/vcnf_hip.h).  ``cfg``: the spline constants, None for the
+    affine map of the MAF (params_per_feature = 2).  Returns (y, logdet) - logdet a fresh [B] tensor holding
+    sign * log|det|, or the caller's with that added.  fp32 or fp64, every floating tensor of x's dtype."""
+    name = "vcnf_made_sample" + _sfx(x)
+    dev = require_device(x, wpack, tables, ctx_add, ctx_gate, logdet, f64=True)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise VcnfError(name + ": expects contiguous [batch, features] inputs")
+    b, d = x.shape
+    h, nb = int(hidden), int(num_blocks)
+    if tables.dtype != torch.int32 or tuple(tables.shape) != (2 * d,) or not tables.is_contiguous():
+        raise VcnfError(name + ": tables must be a contiguous int32 tensor of 2 * features entries")
+    for what, t, shape in (("wpack", wpack, (wpack.numel(),)), ("ctx_add", ctx_add, (b, h)), ("ctx_gate", ctx_gate, (nb, b, h))):
+        if t is not None and (t.dtype != x.dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise VcnfError("%s: %s must be a contiguous %s tensor of shape %s" % (name, what, x.dtype, list(shape)))
+    out = torch.empty_like(x)
+    logdet, mode = _ld_out(logdet, b, x.dtype, dev, name)
+    _call(name, dev, x, out, logdet, ctx_add, ctx_gate, wpack, wpack.numel(), tables, b, d, h, nb, int(params_per_feature),
+          None if cfg is None else _cfg_of(cfg, x), mode, sign, None if cfg is None else bad_discriminant_counter(dev))
+    return out, logdet
+
+
 def affine_const(z, s, t, inverse):
     dev = require_device(z, s, t, f64=True)
     if any(u is not None and u.dtype != z.dtype for u in (s, t)):

@@ -15,7 +15,7 @@ SOURCES = ["rqs_kernels.hip", "affine_kernels.hip", "fused_layer.hip",
            "fused_layer_v6.hip", "fused_affine.hip", "fused_final.hip", "resnet_trunk.hip", "channel_mix.hip", "conv1x1.hip", "conv3x3_1x1.hip", "linear_wgrad.hip", "resblock_ops.hip",
            "rqs_backward.hip", "gemm_probe.hip", "rqs_f64.hip", "linear_f16x3.hip", "masked_affine_stack.hip", "class_cond_gaussian.hip",
            "gaussian_mixture.hip", "heavy_tail.hip", "mvn_base.hip", "planar_radial.hip", "target_density.hip", "stochastic.hip",
-           "vae_ends.hip", "periodic.hip", "logit.hip", "dequant.hip"]
+           "vae_ends.hip", "periodic.hip", "logit.hip", "dequant.hip", "made_sample.hip"]
 # (source, extra flags, object name): fused_layer_v6.hip, its two-layer form fused_layer_v6_pair.hip and fused_layer_v6s.hip
 # are compiled once per number of residual blocks.  The kernels whose spline code runs beside matrix instructions are built without SLP vectorisation: packed-f32 vector
 # instructions starve beside the partner wave's matrix instructions (profiles/r02_spline_eval_microbench.md)
@@ -27,7 +27,7 @@ UNITS = [(s, NO_SLP if s == "fused_final.hip" else [], os.path.splitext(s)[0]) f
         [("fused_layer.hip", ["-DVCNF_F32_NBLK=%d" % n], "fused_layer_f32_b%d" % n) for n in (3, 1)]
 # what every unit is compiled with (profiles/tools/isa_kernel_diff.py compiles with the same)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
-HEADERS = ["rqs_math.hpp", "rqs_vjp.hpp", "rqs_lean.hpp", "fused_common.hpp", "fused_lds.hpp", "split_half.hpp", "stream_common.hpp", "mvn_lds.hpp", "target_math.hpp",
+HEADERS = ["rqs_math.hpp", "rqs_math64.hpp", "rqs_vjp.hpp", "rqs_lean.hpp", "fused_common.hpp", "fused_lds.hpp", "split_half.hpp", "stream_common.hpp", "mvn_lds.hpp", "target_math.hpp",
            "rqs_host.hpp", "host_common.hpp", os.path.join("..", "..", "include", "vcnf_hip.h")]
 
 

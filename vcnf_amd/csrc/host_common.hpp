@@ -72,6 +72,10 @@ inline int launch_listed(IntList<Ns...> list, int n, F&& launch) {
   return rc;
 }
 
+// Dynamic LDS a kernel may be launched with before its limit has been raised; a unit that sizes its LDS at run time
+// (made_sample.hip) stays below it, so that it needs no per-instance flag.
+constexpr size_t kDynamicLdsDefault = 64 * 1024;
+
 // Raises Kernel's dynamic-LDS limit to ``bytes`` on its first launch (above 64 KiB the runtime wants to be told); the
 // flag is per kernel instance, so ``bytes`` must be a constant of the instance.  False if the runtime refuses: the
 // caller returns VCNF_ERR_LAUNCH.
@@ -89,7 +93,7 @@ inline bool lds_limit_once(size_t bytes) {
 // BLOCK threads per tile up to ``max_grid`` (what the chip holds at once), launches KInv or KFwd on ``args``.
 template <auto KInv, auto KFwd, int TILE, int BLOCK, size_t LDS, class... Args>
 inline int launch_tiled(int inverse, long long batch, long long max_grid, hipStream_t st, const Args&... args) {
-  if constexpr (LDS > 64 * 1024) {
+  if constexpr (LDS > kDynamicLdsDefault) {
     if (!(inverse ? lds_limit_once<KInv>(LDS) : lds_limit_once<KFwd>(LDS))) return VCNF_ERR_LAUNCH;
   }
   const long long ntiles = (batch + TILE - 1) / TILE;

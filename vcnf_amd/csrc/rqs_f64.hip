@@ -13,6 +13,7 @@
 #include "../../include/vcnf_hip.h"
 #include "host_common.hpp"
 #include "rqs_host.hpp"
+#include "rqs_math64.hpp"
 #include "rqs_vjp.hpp"
 
 namespace vcnf {
@@ -46,69 +47,9 @@ __device__ __forceinline__ Rows64 rows64(const Rqs64Args& a, long long i) {
   return Rows64{outer * a.ld_w + s, outer * a.ld_h + s, outer * a.ld_d + s, a.ks};
 }
 
-// Knot construction, bin search and derivative-logit padding are shared by the forward kernel and the VJP kernel
-// below, so that both select the same bin for every element.  KT > 0: compile-time bin count (the templated instances
-// of both kernels keep every array in registers); KT == 0: runtime K (their generic instances).
-
-// knots of one side: cum[0..K] from K logits lg[k * ks] (splines.py:109-119 / :123-133); ``prob`` (optional) receives
-// the softmax probabilities, ``frac`` (optional) the cumulative fractions of the knots (0 and 1 at the ends)
-template <int KT>
-__device__ __forceinline__ void partition64(const double* lg, long long ks, int Kr, double scale, double lo, double hi,
-                                            double floor_, double* cum, double* prob = nullptr,
-                                            double* frac = nullptr) {
-  const int K = KT > 0 ? KT : Kr;
-  double m = -INFINITY;
-  for (int k = 0; k < K; ++k) m = fmax(m, lg[k * ks] * scale);
-  double s = 0.0;
-  for (int k = 0; k < K; ++k) s += exp(lg[k * ks] * scale - m);
-  double run = 0.0;
-  cum[0] = lo;
-  for (int k = 0; k < K; ++k) {
-    if (prob) prob[k] = exp(lg[k * ks] * scale - m) / s;
-    const double p = floor_ + (1.0 - floor_ * K) * (exp(lg[k * ks] * scale - m) / s);
-    run += p;
-    cum[k + 1] = (hi - lo) * run + lo;
-    if (frac) frac[k + 1] = run;
-  }
-  cum[K] = hi;
-  if (frac) {
-    frac[0] = 0.0;
-    frac[K] = 1.0;
-  }
-}
-
-// bin: number of knots <= value, last knot bumped by eps (splines.py:12-17), clamped to [0, K-1]
-template <int KT>
-__device__ __forceinline__ int bin64(const double* kn, int Kr, double x) {
-  const int K = KT > 0 ? KT : Kr;
-  int bin = -1;
-  for (int k = 0; k <= K; ++k) bin += (x >= (k == K ? kn[k] + 1e-6 : kn[k])) ? 1 : 0;
-  return bin < 0 ? 0 : (bin > K - 1 ? K - 1 : bin);
-}
-
-// derivative logit of knot k (padding per tails mode, splines.py:36-49): its column in the ud row, or -1 for the
-// constant boundary logit of linear tails
-__device__ __forceinline__ int dlogit_col64(int k, int K, int tails) {
-  if (tails == VCNF_TAILS_LINEAR) return (k == 0 || k == K) ? -1 : k - 1;
-  if (tails == VCNF_TAILS_CIRCULAR) return k == K ? 0 : k;
-  return k;
-}
-
-__device__ __forceinline__ double softplus64(double v) { return v > 20.0 ? v : log1p(exp(v)); }   // F.softplus (threshold 20)
-
-// the knots bounding bin ``bin`` on both sides.  KT > 0: picked by comparison, so that the knot arrays stay in
-// registers; KT == 0: indexed.
-template <int KT>
-__device__ __forceinline__ void pick_bin64(const double* xk, const double* yk, int bin, int K, double& xl, double& xr,
-                                           double& yl, double& yr) {
-  if (KT > 0) {
-    xl = xk[0]; xr = xk[1]; yl = yk[0]; yr = yk[1];
-    for (int k = 1; k < K; ++k)
-      if (bin == k) { xl = xk[k]; xr = xk[k + 1]; yl = yk[k]; yr = yk[k + 1]; }
-  } else {
-    xl = xk[bin]; xr = xk[bin + 1]; yl = yk[bin]; yr = yk[bin + 1];
-  }
-}
+// Knot construction, bin search and derivative-logit padding (rqs_math64.hpp) are shared by the forward kernel and the
+// VJP kernel below, so that both select the same bin for every element.  KT > 0: compile-time bin count (the templated
+// instances of both kernels keep every array in registers); KT == 0: runtime K (their generic instances).
 
 // KT > 0: compile-time bin count, every array in registers (K = 8, 10, 16); KT == 0: any K up to 64 (runtime-indexed
 // arrays in scratch).  Both instances evaluate the same expressions in the same order.  LIM (dense rows, no tails): the

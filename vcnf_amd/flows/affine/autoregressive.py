@@ -1,20 +1,22 @@
 """Masked affine autoregressive flow (MAF): every variable is scaled and shifted by parameters a MADE network
 computes from the variables of lower degree.  ``forward`` is one MADE pass + one launch of the elementwise kernel
-(csrc/affine_kernels.hip::maf_affine_kernel reads the MADE output [B, D * 2] in place); ``inverse`` needs D
-sequential passes (variable i can only be inverted once its predecessors are), as in the reference.
+(csrc/affine_kernels.hip::maf_affine_kernel reads the MADE output [B, D * 2] in place); ``inverse`` is one launch of
+csrc/made_sample.hip, which completes the MADE's hidden units degree by degree and inverts one variable between stages
+(vcnf_amd/made_sample.py says which layers and calls take it); every other call runs the reference's loop of D passes.
 Reference: normflow/flows/affine/autoregressive.py:11-45 (Autoregressive), :48-103 (MaskedAffineAutoregressive)."""
 import numpy as np
 import torch
 from torch.nn import functional as F
 
-from ..base import Flow
-from ... import _lib, autograd
+from ..base import Flow, fold_log_det
+from ... import _lib, autograd, made_sample
 from ...nets.made import MADE
 
 
 class Autoregressive(Flow):
     """autoregressive.py:11-45: elementwise invertible map whose parameters come from ``autoregressive_net``."""
     takes_context = True
+    fuse_sampling = True        # ``inverse`` in one launch where vcnf_amd.made_sample.plan allows; False: always the loop
 
     def __init__(self, autoregressive_net):
         super().__init__()
@@ -23,12 +25,27 @@ class Autoregressive(Flow):
     def forward(self, inputs, context=None):
         return self._elementwise_forward(inputs, self.autoregressive_net(inputs, context))
 
-    def inverse(self, inputs, context=None):
+    def _fused_inverse(self, inputs, context, log_q, sign):
+        """(outputs, log_det) of ``inverse`` in one launch, or None: a subclass with such a kernel overrides this."""
+        return None
+
+    def _inverse_run(self, inputs, context, log_q, sign):
+        """(outputs, log_det) of ``inverse``, with ``sign * log_det`` added into ``log_q`` in place where one is given."""
+        fused = self._fused_inverse(inputs, context, log_q, sign)
+        if fused is not None:
+            return fused
         outputs = torch.zeros_like(inputs)
         logabsdet = None
         for _ in range(int(np.prod(inputs.shape[1:]))):
             outputs, logabsdet = self._elementwise_inverse(inputs, self.autoregressive_net(outputs, context))
-        return outputs, logabsdet
+        return fold_log_det(outputs, logabsdet, log_q, sign) if log_q is not None else (outputs, logabsdet)
+
+    def inverse(self, inputs, context=None):
+        return self._inverse_run(inputs, context, None, 1.0)
+
+    def inverse_into(self, z, log_q, context=None):
+        """``inverse`` with the log-det added into ``log_q`` (inside the kernel on the one-launch path)."""
+        return self._inverse_run(z, context, log_q, 1.0)[0]
 
     def _output_dim_multiplier(self):
         raise NotImplementedError()
@@ -52,6 +69,12 @@ class MaskedAffineAutoregressive(Autoregressive):
 
     def _output_dim_multiplier(self):
         return 2
+
+    def _fused_inverse(self, inputs, context, log_q, sign):
+        """One launch (csrc/made_sample.hip) for the layers and calls vcnf_amd.made_sample.plan accepts.  On its first
+        use a layer packs its weights and copies small tables to the device: call it once before a graph capture."""
+        packed = made_sample.plan(self, inputs, context, 2)
+        return None if packed is None else made_sample.run(self, packed, inputs, context, None, log_q, sign)
 
     def _elementwise(self, inputs, params, inverse):
         if inputs.dim() != 2 or inputs.shape[1] != self.features:

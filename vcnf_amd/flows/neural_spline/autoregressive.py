@@ -1,15 +1,17 @@
 """Autoregressive rational-quadratic spline flow: every variable gets its own spline whose logits a
 MADE network computes from the variables of lower degree.  The density direction is one MADE pass +
 one launch of the packed spline kernel (the MADE output [B, D*P] is read in place); the sampling
-direction needs D sequential passes (variable i can only be inverted once its predecessors are), as
-in the reference.  Per-feature tails / tensor bounds go through utils.splines' grouped evaluation.
+direction is one launch of csrc/made_sample.hip, which completes the MADE's hidden units degree by
+degree and inverts one variable between stages (vcnf_amd/made_sample.py says which layers and calls
+take it); every other call runs the reference's loop of D passes.  Per-feature tails / tensor bounds
+go through utils.splines' grouped evaluation.
 Reference: normflow/flows/neural_spline/autoregressive.py:18-136, flows/affine/autoregressive.py:11-45."""
 import numpy as np
 import torch
 from torch.nn import functional as F
 
-from ..base import Flow
-from ... import _lib, autograd
+from ..base import Flow, fold_log_det
+from ... import _lib, autograd, made_sample
 from ...nets.made import MADE
 from ...utils import splines
 from ...utils.nn import PeriodicFeatures
@@ -17,6 +19,7 @@ from ...utils.nn import PeriodicFeatures
 
 class MaskedPiecewiseRationalQuadraticAutoregressive(Flow):
     takes_context = True
+    fuse_sampling = True        # ``inverse`` in one launch where vcnf_amd.made_sample.plan allows; False: always the loop
 
     def __init__(self, features, hidden_features, context_features=None, num_bins=10, tails=None, tail_bound=1.,
                  num_blocks=2, use_residual_blocks=True, random_mask=False, permute_mask=False, activation=F.relu,
@@ -98,10 +101,29 @@ class MaskedPiecewiseRationalQuadraticAutoregressive(Flow):
         """Density direction: one pass (flows/affine/autoregressive.py:24-27)."""
         return self._elementwise(inputs, self.autoregressive_net(inputs, context), False)
 
-    def inverse(self, inputs, context=None):
-        """Sampling direction: D passes, each fixing one more variable (:29-36)."""
+    def _spline_cfg(self):
+        return _lib.make_cfg(self.num_bins, self.tails, tail_bound=self.tail_bound, min_bin_width=self.min_bin_width,
+                             min_bin_height=self.min_bin_height, min_derivative=self.min_derivative,
+                             wh_scale=self._logit_scale())
+
+    def _inverse_run(self, inputs, context, log_q, sign):
+        """(outputs, log_det): the sampling direction, with ``sign * log_det`` added into ``log_q`` in place where one
+        is given.  One launch (csrc/made_sample.hip) for the layers and calls vcnf_amd.made_sample.plan accepts - on its
+        first use a layer packs its weights and copies small tables to the device, so call it once before a graph
+        capture - and otherwise D passes, each fixing one more variable (:29-36)."""
+        packed = made_sample.plan(self, inputs, context, self._output_dim_multiplier())
+        if packed is not None:
+            return made_sample.run(self, packed, inputs, context, self._spline_cfg(), log_q, sign)
         outputs = torch.zeros_like(inputs)
         logabsdet = None
         for _ in range(int(np.prod(inputs.shape[1:]))):
             outputs, logabsdet = self._elementwise(inputs, self.autoregressive_net(outputs, context), True)
-        return outputs, logabsdet
+        return fold_log_det(outputs, logabsdet, log_q, sign) if log_q is not None else (outputs, logabsdet)
+
+    def inverse(self, inputs, context=None):
+        """Sampling direction (see ``_inverse_run``)."""
+        return self._inverse_run(inputs, context, None, 1.0)
+
+    def inverse_into(self, z, log_q, context=None):
+        """``inverse`` with the log-det added into ``log_q`` (inside the kernel on the one-launch path)."""
+        return self._inverse_run(z, context, log_q, 1.0)[0]

@@ -101,8 +101,9 @@ class CircularCoupledRationalQuadraticSpline(Flow):
 
 
 class AutoregressiveRationalQuadraticSpline(Flow):
-    """Autoregressive neural spline layer (wrapper.py:197-259): ``forward`` samples (D sequential
-    passes), ``inverse`` evaluates density (one pass)."""
+    """Autoregressive neural spline layer (wrapper.py:197-259): ``forward`` samples (one launch of
+    csrc/made_sample.hip where vcnf_amd.made_sample.plan allows, else D sequential passes), ``inverse``
+    evaluates density (one pass)."""
 
     def __init__(self, num_input_channels, num_blocks, num_hidden_channels, num_bins=8, tail_bound=3,
                  activation=nn.ReLU, dropout_probability=0., permute_mask=False, init_identity=True):
@@ -121,6 +122,10 @@ class AutoregressiveRationalQuadraticSpline(Flow):
     def inverse(self, z):
         z, log_det = self.mprqat(z)
         return z, log_det.view(-1)
+
+    # accumulate-into-log_q form used by NormalizingFlow.sample (core.py:153-155)
+    def forward_into(self, z, log_q):
+        return self.mprqat._inverse_run(z, None, log_q, -1.0)[0]
 
 
 class CircularAutoregressiveRationalQuadraticSpline(Flow):
