@@ -1,5 +1,5 @@
 """Device code of two source trees, kernel by kernel, without a GPU (profiles/stream_helpers.md section 1,
-profiles/rqs_host.md section 1, profiles/split_half_units.md section 1):
+profiles/rqs_host.md section 1, profiles/split_half_units.md section 1, profiles/rqs64_unit.md section 2):
 
     isa_kernel_diff.py PARENT_CSRC NEW_CSRC [--work DIR] [--jobs N] [--reuse] [--renamed OLD=NEW ...] [--mix]
 
@@ -32,7 +32,7 @@ CHECKED = ("rqs_kernels.hip", "rqs_backward.hip", "rqs_f64.hip", "fused_layer.hi
            "fused_layer_v6.hip", "fused_layer_v6_pair.hip", "fused_layer_v6s.hip", "affine_kernels.hip",
            "class_cond_gaussian.hip", "gaussian_mixture.hip", "heavy_tail.hip", "conv1x1.hip", "conv3x3_1x1.hip", "linear_f16x3.hip",
            "linear_wgrad.hip", "resnet_trunk.hip", "fused_affine.hip", "gemm_probe.hip", "channel_mix.hip",
-           "mvn_base.hip", "planar_radial.hip", "stochastic.hip", "target_density.hip", "vae_ends.hip", "periodic.hip", "logit.hip")
+           "mvn_base.hip", "planar_radial.hip", "stochastic.hip", "target_density.hip", "vae_ends.hip", "periodic.hip", "logit.hip", "made_sample.hip")
 UNITS = sorted(((s, e) for s, e, _ in BUILD_UNITS if s in CHECKED), key=lambda u: CHECKED.index(u[0]))
 FLAGS = BUILD_FLAGS + ["--cuda-device-only", "-S"]
 

@@ -1,6 +1,6 @@
 // Host-only check of csrc/rqs_host.hpp (g++ -std=c++17, no HIP): the bin-count dispatcher over its three lists,
 // host_common.hpp's with_flags, the spline constants of one configuration against the expressions the units carried
-// before the header existed, and the number of derivative logits.
+// before the header existed, the fp64 constants (rqs_fill_const64) field by field, and the number of derivative logits.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -73,6 +73,27 @@ static void check_flags() {
 }
 
 static bool same_bits(float a, float b) { return memcmp(&a, &b, sizeof a) == 0; }
+static bool same_bits(double a, double b) { return memcmp(&a, &b, sizeof a) == 0; }
+
+// rqs_fill_const64: every field is the configuration's own, the boundary logit its one expression
+static void check_const64(int tails, double bound, double min_w, double min_h, double min_d, double scale) {
+  vcnf_rqs_cfg_f64 cfg;
+  cfg.num_bins = 10; cfg.tails = tails;
+  cfg.left = -bound; cfg.right = bound; cfg.bottom = -0.5 * bound; cfg.top = 2.0 * bound;
+  cfg.min_bin_width = min_w; cfg.min_bin_height = min_h; cfg.min_derivative = min_d; cfg.wh_scale = scale;
+  const Rqs64Const c = rqs_fill_const64(cfg);
+  CHECK(c.K == cfg.num_bins);
+  CHECK(c.tails == cfg.tails);
+  CHECK(same_bits(c.left, cfg.left));
+  CHECK(same_bits(c.right, cfg.right));
+  CHECK(same_bits(c.bottom, cfg.bottom));
+  CHECK(same_bits(c.top, cfg.top));
+  CHECK(same_bits(c.min_w, cfg.min_bin_width));
+  CHECK(same_bits(c.min_h, cfg.min_bin_height));
+  CHECK(same_bits(c.min_d, cfg.min_derivative));
+  CHECK(same_bits(c.wh_scale, cfg.wh_scale));
+  CHECK(same_bits(c.edge, log(exp(1.0 - cfg.min_derivative) - 1.0)));
+}
 
 int main() {
   check_list(kBins, "kBins");
@@ -107,6 +128,13 @@ int main() {
   CHECK(same_bits(c.edge_logit, (float)log(exp(1.0 - (double)cfg->min_derivative) - 1.0)));
   CHECK(sizeof(RqsConst) == 15 * 4);               // 2 ints + 13 floats: part of every kernel's argument layout
   CHECK(rqs_check_cfg(cfg, 64) == VCNF_OK);
+
+  // the fp64 constants: the three tails modes at the default floors, and one other set of floors
+  check_const64(VCNF_TAILS_NONE, 1.0, 1e-3, 1e-3, 1e-3, 1.0);
+  check_const64(VCNF_TAILS_LINEAR, 3.0, 1e-3, 1e-3, 1e-3, 1.0);
+  check_const64(VCNF_TAILS_CIRCULAR, 3.141592653589793, 1e-3, 1e-3, 1e-3, 1.0);
+  check_const64(VCNF_TAILS_LINEAR, 5.0, 2e-2, 5e-3, 0.25, 0.125);
+  CHECK(sizeof(Rqs64Const) == 2 * 4 + 9 * 8);      // part of the fp64 kernels' argument layout
 
   CHECK(rqs_n_deriv(VCNF_TAILS_LINEAR, 8) == 7);
   CHECK(rqs_n_deriv(VCNF_TAILS_CIRCULAR, 8) == 8);

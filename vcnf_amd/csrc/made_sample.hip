@@ -257,9 +257,8 @@ static int launch(const Args<T>& a, size_t lds, hipStream_t st) {
 // the constants of either configuration, in double (a float configuration's values as they are)
 template <class Cfg>
 static void fill(const Cfg& cfg, vcnf::Rqs64Const& c) {
-  c = vcnf::Rqs64Const{cfg.num_bins, cfg.tails, cfg.left, cfg.right, cfg.bottom, cfg.top, cfg.min_bin_width,
-                       cfg.min_bin_height, cfg.min_derivative, cfg.wh_scale,
-                       log(exp(1.0 - (double)cfg.min_derivative) - 1.0)};
+  c = vcnf::rqs_fill_const64(vcnf_rqs_cfg_f64{cfg.num_bins, cfg.tails, cfg.left, cfg.right, cfg.bottom, cfg.top,
+                                              cfg.min_bin_width, cfg.min_bin_height, cfg.min_derivative, cfg.wh_scale});
 }
 
 template <typename T>

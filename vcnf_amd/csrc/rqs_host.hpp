@@ -48,6 +48,19 @@ inline void rqs_fill_const(const vcnf_rqs_cfg& cfg, RqsConst& c) {
   c.edge_logit = (float)log(exp(1.0 - (double)cfg.min_derivative) - 1.0);
 }
 
+// The constants of the fp64 spline unit (rqs_f64.hip and both instances of made_sample.hip, whose arithmetic is double):
+// the configuration as it is, and the boundary logit of linear tails.  Sits inside those kernels' argument structs.
+struct Rqs64Const {
+  int K, tails;
+  double left, right, bottom, top, min_w, min_h, min_d, wh_scale;
+  double edge;            // log(exp(1 - min_d) - 1), splines.py:38
+};
+
+inline Rqs64Const rqs_fill_const64(const vcnf_rqs_cfg_f64& cfg) {
+  return Rqs64Const{cfg.num_bins, cfg.tails, cfg.left, cfg.right, cfg.bottom, cfg.top, cfg.min_bin_width,
+                    cfg.min_bin_height, cfg.min_derivative, cfg.wh_scale, log(exp(1.0 - cfg.min_derivative) - 1.0)};
+}
+
 // Validation of a configuration (vcnf_rqs_cfg or vcnf_rqs_cfg_f64), in this order: cfg, bin count, tails, two bins
 // for linear tails, bin minima (splines.py:104-107).  The callers test their sizes after it.
 template <class Cfg>
